@@ -526,6 +526,27 @@ def timed_steps(D_, ctx, step, steps, warmup):
     return D_.max_over_ranks(time.perf_counter() - t0), last, trsm_ms / steps
 
 
+DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs: at most this much in all
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: write every (name, array) as out_dir/<name>.npy in float64.  An array that would take the total past
+    DUMP_LIMIT_BYTES is replaced by a fixed sample of its entries (RandomState(0), sorted indices), stored next to it as
+    <name>_index.npy, so two builds given the same arguments write the same entries."""
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES
+    for name, a in arrays:
+        a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+        if a.nbytes > budget:
+            keep = max(1, budget // 16)            # value + index per kept entry
+            idx = np.sort(np.random.RandomState(0).choice(a.size, keep, replace=False))
+            np.save(os.path.join(out_dir, name + "_index.npy"), idx.astype(np.float64))
+            a = a[idx]
+            budget -= idx.size * 8
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        budget -= a.nbytes
+
+
 def config_traffic(config, kernel):
     """PMC-measured HBM bytes per launch of `kernel` for one of the other configurations (profiles/trsm_traffic_<config>.json,
     written by tools/gpu_r03.sh pmcconf), or None"""
@@ -849,6 +870,16 @@ def run_headline(args, D_, _lib, sharding):
     elapsed, best, trsm_ms = timed_steps(D_, ctx, step, args.steps, args.warmup)
     ctx.set_phase_events(False)
     solve_kernel = cand.solve_kernel()
+    if args.dump_outputs:
+        # what the last timed step returned (global max and argmax), and the per-candidate values the same call hands a
+        # caller who asks for them: one more evaluation of the same fitted GP on the same resident candidates, untimed
+        if comm is not None:
+            vals = comm.acq_sharded(gp, args.acq, 0.0, eta, cand, offset, want_values=True)[0]
+        else:
+            vals = gp.acq(args.acq, 0.0, eta, cand, want_values=True)[0]
+        if rank == 0:
+            dump_outputs(args.dump_outputs, [("acq_max", [best[0]]), ("acq_argmax", [best[1]]),
+                                             ("acq_values_rank0", vals)])
     clock = clock_during_step(D_, ctx, step, elapsed / args.steps * 1e3)  # every rank: the step holds a collective
 
     # the OTHER scaling of the same job, in the same run (multi-rank runs only; every rank takes part): the driver's
@@ -1434,6 +1465,7 @@ def config_args(args, cfg, lean=False):
     a.steps = {"c2": 100, "c4": 50}.get(cfg, 5)
     a.warmup = 5 if cfg in ("c2", "c4") else 2
     a.scaling = "strong" if cfg == "c3" else "weak"
+    a.dump_outputs = None          # the dump is the run's own configuration's, not the side configurations'
     if lean:
         a.lean = True
         a.no_cpu_baseline = True
@@ -1465,9 +1497,19 @@ def main():
                                                     "may repeat: several contexts on it)")
     ap.add_argument("--lean", action="store_true",
                     help="the timed region and the fit only: no side measurements (phases, micro-benchmarks, small batches)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="headline / c2: after the timed steps write what the last one returned (acq_max, acq_argmax) and "
+                         "the per-candidate values of rank 0's candidates (acq_values_rank0) as DIR/<name>.npy, float64, "
+                         "at most 64 MB in all; the inputs are seeded, so equal arguments give equal inputs")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.dump_outputs and (args.launcher == "inproc" or args.config not in ("headline", "c2")):
+        ap.error("--dump-outputs: the headline and c2 runs only (one process per GPU)")
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)      # (rank processes may start elsewhere)
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is not None and int(env_world) != args.gpus:
         sys.stderr.write("bench.py: --gpus %d but the launcher started WORLD_SIZE=%s ranks; refusing to report a line "

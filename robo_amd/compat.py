@@ -11,7 +11,7 @@ the three front ends).  ``george`` is a module with one attribute, ``kernels`` (
 robo_amd/kernels.py: Matern-5/2, squared-exponential, the Fabolas product; with and without the amplitude factor).
 Anything else (``robo.models.random_forest``, ``george.GP`` ...) raises the ordinary ImportError / AttributeError.
 
-The reference's own unit tests run this way (tools/run_reference_tests.py, tests/test_reference_suite.py).  It is an
+The reference's own unit tests run this way (tools/run_reference_tests.py).  It is an
 import alias for callers, not a backend switch: with ``robo`` really installed, call ``install(force=True)`` to shadow it.
 """
 import importlib

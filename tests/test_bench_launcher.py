@@ -43,6 +43,19 @@ def test_single_rank_line(single):
     assert "exchange" in single
 
 
+def test_dump_outputs(single, tmp_path):
+    """--dump-outputs DIR: the last timed step's (max, argmax) and the per-candidate values as float64 .npy files; the inputs
+    are seeded, so a second run with the same arguments returns what the first one's line reported"""
+    import numpy as np
+    out = _line(_run(["--gpus", "1", "--dump-outputs", str(tmp_path)]))
+    assert out["steps"] == 2 and out["ms_per_step"] > 0
+    assert sorted(os.listdir(str(tmp_path))) == ["acq_argmax.npy", "acq_max.npy", "acq_values_rank0.npy"]
+    mx, am, vals = (np.load(str(tmp_path / (n + ".npy"))) for n in ("acq_max", "acq_argmax", "acq_values_rank0"))
+    assert mx.dtype == am.dtype == vals.dtype == np.float64 and vals.shape == (601,)
+    assert [mx[0], am[0]] == out["argmax"] == single["argmax"]
+    assert vals[int(am[0])] == mx[0] == vals.max()
+
+
 @pytest.mark.parametrize("world", [2, 3])
 def test_self_launch_strong(single, world):
     """SURVEY 8(d)'s strong-scaled headline: the SAME 601 candidates split over the ranks -> the single-rank argmax"""

@@ -1,14 +1,12 @@
-"""End-to-end drop-in: the REFERENCE's own BayesianOptimization + RandomSampling
-(robo/solver/bayesian_optimization.py, robo/maximizers/random_sampling.py, imported unchanged
-from /root/reference) drive
+"""End-to-end drop-in: robo_amd's own BayesianOptimization + RandomSampling drive
 
-  (a) robo_amd's GaussianProcess + EI/LogEI/LCB  (HIP sources; here interpreted by tests/hipemu), and
-  (b) the reference's own EI/LogEI/LCB on top of an oracle-backed reference BaseModel,
+  robo_amd's GaussianProcess + EI/LogEI/LCB  (HIP sources; here interpreted by tests/hipemu),
 
-with identical seeds.  Both must choose the SAME candidate index at every iteration, i.e.
-produce the same (X, y) trajectory -- the "argmax index identical" rule of the north star,
-checked through the whole solver loop.  Needs the reference tree (build container only); the
-GPU-box equivalent with robo_amd's own loop is tests/test_gpu_parity.py::test_host_classes_on_gpu.
+with the seeds of the reference's runs of ITS BayesianOptimization + RandomSampling and its own EI/LogEI/LCB on an
+oracle-backed reference BaseModel.  Both must choose the SAME candidate at every iteration, i.e. produce the same (X, y)
+trajectory -- the "argmax index identical" rule of the north star, checked through the whole solver loop.  The reference's
+results are stored in tests/golden/ref_host.npz (tests/golden/make_golden_host.py); the GPU-box equivalent with robo_amd's
+own loop is tests/test_gpu_parity.py::test_host_classes_on_gpu.
 """
 import os
 import sys
@@ -17,7 +15,6 @@ import numpy as np
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-pytestmark = pytest.mark.skipif(not os.path.isdir("/root/reference/robo"), reason="reference tree not on this box")
 
 
 def branin(x):
@@ -36,27 +33,18 @@ def emu():
     _lib.use_library(None)
 
 
-def _reference():
-    if not hasattr(np, "Infinity"):
-        np.Infinity = np.inf
-    if "/root/reference" not in sys.path:
-        sys.path.insert(0, "/root/reference")
-    from robo.solver.bayesian_optimization import BayesianOptimization
-    from robo.maximizers.random_sampling import RandomSampling
-    from robo.initial_design import init_latin_hypercube_sampling
-    from robo.models.base_model import BaseModel
-    from robo.acquisition_functions.ei import EI
-    from robo.acquisition_functions.log_ei import LogEI
-    from robo.acquisition_functions.lcb import LCB
-    return BayesianOptimization, RandomSampling, init_latin_hypercube_sampling, BaseModel, \
-        {"ei": EI, "log_ei": LogEI, "lcb": LCB}
+def _gold():
+    """the reference's outputs on this module's inputs (tests/golden/make_golden_host.py)"""
+    return np.load(os.path.join(HERE, "golden", "ref_host.npz"))
 
 
 THETA = np.array([np.log(2.0 / 2), np.log(0.3), np.log(0.3), np.log(1e-3)])   # fixed hypers (do_optimize=False)
 
 
 def _run(model, acq, n_iter, seed):
-    BO, RS, lhs, _, _ = _reference()
+    from robo_amd.solver import BayesianOptimization as BO
+    from robo_amd.maximizers import RandomSampling as RS
+    from robo_amd.initial_design import init_latin_hypercube_sampling as lhs
     lo, hi = np.array([-5.0, 0.0]), np.array([10.0, 15.0])
     rng = np.random.RandomState(seed)
     np.random.seed(seed)          # RandomSampling uses the GLOBAL rng (random_sampling.py:38-45)
@@ -68,29 +56,13 @@ def _run(model, acq, n_iter, seed):
 
 @pytest.mark.parametrize("acq_name", ["ei", "log_ei", "lcb"])
 def test_same_trajectory_as_reference_classes_on_the_oracle(emu, acq_name):
-    from oracle import gp_oracle as O
+    """the reference's loop with its own acquisition on the oracle GP (stored) vs robo_amd's loop, GP and acquisition"""
     from robo_amd.kernels import Matern52Kernel
     from robo_amd.models import GaussianProcess
     from robo_amd import acquisition_functions as A
-    BO, RS, lhs, BaseModel, ref_acq = _reference()
     lo, hi = np.array([-5.0, 0.0]), np.array([10.0, 15.0])
-
-    class OracleModel(BaseModel):
-        """reference BaseModel whose GP is the oracle (fixed hypers)"""
-
-        def train(self, X, y, do_optimize=False):
-            self.gp = O.OracleGP("matern52", THETA, lower=lo, upper=hi)
-            self.gp.train(X, y)
-            self.X, self.y = self.gp.X, self.gp.y
-
-        def predict(self, X_test, **kw):
-            return self.gp.predict(X_test, diag_only=True)
-
-        def get_incumbent(self):
-            return self.gp.get_incumbent()
-
-    ref_model = OracleModel()
-    Xr, yr = _run(ref_model, ref_acq[acq_name](ref_model), 12, seed=5)
+    gold = _gold()
+    Xr, yr = gold["trajectory_%s_X" % acq_name], gold["trajectory_%s_y" % acq_name]
 
     class FixedGP(GaussianProcess):
         def train(self, X, y, do_optimize=True):     # the solver's first iteration asks for optimisation
@@ -101,16 +73,18 @@ def test_same_trajectory_as_reference_classes_on_the_oracle(emu, acq_name):
     mine = {"ei": A.EI, "log_ei": A.LogEI, "lcb": A.LCB}[acq_name](model)
     Xm, ym = _run(model, mine, 12, seed=5)
 
+    assert Xr.shape == (12, 2)
     np.testing.assert_array_equal(Xm, Xr)      # identical candidate chosen at every iteration
     np.testing.assert_array_equal(ym, yr)
 
 
 def test_reference_solver_bookkeeping_with_robo_amd_objects(emu):
-    """the assertions of the reference's test/test_solver/test_bayesian_optimization.py:28-49"""
+    """the assertions of the reference's test/test_solver/test_bayesian_optimization.py:28-49, on robo_amd's solver"""
     from robo_amd.kernels import Matern52Kernel
     from robo_amd.models import GaussianProcess
     from robo_amd.acquisition_functions import EI
-    BO, RS, lhs, _, _ = _reference()
+    from robo_amd.solver import BayesianOptimization as BO
+    from robo_amd.maximizers import RandomSampling as RS
     lo, hi = np.zeros(1), np.ones(1) * 6
     model = GaussianProcess(2 * Matern52Kernel(np.ones(1), ndim=1), lower=lo, upper=hi, rng=np.random.RandomState(1))
     acq = EI(model)
@@ -125,16 +99,24 @@ def test_reference_solver_bookkeeping_with_robo_amd_objects(emu):
 
 
 def test_generic_plugin_model_with_robo_amd_acquisitions(emu):
-    """any BaseModel works: the reference's DemoModel (test/dummy_model.py) + robo_amd EI/LogEI/PI/LCB
-    reproduce the pins of SURVEY.md 8(c)"""
-    _reference()
-    sys.path.insert(0, "/root/reference/test")
-    from dummy_model import DemoModel
+    """any BaseModel works: a plugin model whose posterior is the training data's mean and variance everywhere (what the
+    reference's demo model in its test suite predicts) + robo_amd EI/LogEI/PI/LCB reproduce the pins of SURVEY.md 8(c)"""
+    from robo_amd.models.base_model import BaseModel
+
+    class ConstantModel(BaseModel):
+        def train(self, X, y):
+            self.X, self.y = X, y
+            self.mean, self.var = np.mean(y), np.var(y)
+
+        def predict(self, X_test):
+            n = X_test.shape[0]
+            return np.full(n, self.mean), np.full(n, self.var)
+
     from robo_amd import acquisition_functions as A
     rs = np.random.RandomState(0)
     X = rs.rand(10, 2)
     y = np.sinc(X * 10 - 5).sum(axis=1)
-    dm = DemoModel()
+    dm = ConstantModel()
     dm.train(X, y)
     Xt = rs.rand(5, 2)
     gold = np.load(os.path.join(HERE, "golden", "demo_model_pins.npz"))
@@ -146,79 +128,57 @@ def test_generic_plugin_model_with_robo_amd_acquisitions(emu):
 
 
 def test_reference_single_point_maximizers_drive_robo_amd_acquisitions(emu):
-    """The reference's OTHER maximisers -- GridSearch, SciPyOptimizer, DifferentialEvolution (robo/maximizers/*.py,
-    imported unchanged) -- call the acquisition with ONE point at a time (scipy_optimizer.py:44,
-    differential_evolution.py:29, grid_search.py:60; SURVEY 8b "who calls it").  Driving robo_amd's EI on the device GP
-    they must land where they land with the reference's own EI on the oracle-backed reference model (same seeds): the
-    same grid point; the same optimum of the restarts / the evolution to optimiser tolerance."""
-    from oracle import gp_oracle as O
+    """The single-point maximisers -- GridSearch, SciPyOptimizer, DifferentialEvolution (robo/maximizers/*.py) -- call the
+    acquisition with ONE point at a time (scipy_optimizer.py:44, differential_evolution.py:29, grid_search.py:60; SURVEY 8b
+    "who calls it").  robo_amd's, driving robo_amd's EI on the device GP, must land where the reference's land with the
+    reference's own EI on the oracle-backed reference model (same seeds; stored in ref_host.npz): the same grid point; the
+    same optimum of the restarts / the evolution to optimiser tolerance."""
     from robo_amd.kernels import Matern52Kernel
     from robo_amd.models import GaussianProcess
     from robo_amd import acquisition_functions as A
-    _, _, _, BaseModel, ref_acq = _reference()
-    from robo.maximizers.grid_search import GridSearch
-    from robo.maximizers.scipy_optimizer import SciPyOptimizer
-    from robo.maximizers.differential_evolution import DifferentialEvolution
+    from robo_amd.maximizers import DifferentialEvolution, GridSearch, SciPyOptimizer
+    gold = _gold()
 
-    def models(lo, hi, X, y, theta):
-        class OracleModel(BaseModel):
-            def train(self, X, y, do_optimize=False):
-                self.gp = O.OracleGP("matern52", theta, lower=lo, upper=hi)
-                self.gp.train(X, y)
-                self.X, self.y = self.gp.X, self.gp.y
-
-            def predict(self, X_test, **kw):
-                return self.gp.predict(X_test, diag_only=True)
-
-            def get_incumbent(self):
-                return self.gp.get_incumbent()
-
-        ref_model = OracleModel()
-        ref_model.train(X, y)
+    def my_ei(lo, hi, X, y, theta):
         D = lo.shape[0]
         mine = GaussianProcess(Matern52Kernel(np.exp(theta[1:-1]), ndim=D, log_amp=theta[0]), noise=np.exp(theta[-1]),
                                lower=lo, upper=hi, rng=np.random.RandomState(0))
         mine.train(X, y, do_optimize=False)
-        return ref_acq["ei"](ref_model), A.EI(mine)
+        return A.EI(mine)
 
     # 1-d: the grid search picks the same grid point
     lo, hi = np.zeros(1), np.ones(1) * 6
     rs = np.random.RandomState(3)
     X = rs.rand(9, 1) * 6
     y = (X[:, 0] - 2.2) ** 2
-    ref_ei, my_ei = models(lo, hi, X, y, np.array([np.log(4.0), np.log(0.1), np.log(1e-3)]))
-    np.testing.assert_array_equal(GridSearch(my_ei, lo, hi, resolution=200).maximize(),
-                                  GridSearch(ref_ei, lo, hi, resolution=200).maximize())
+    ei = my_ei(lo, hi, X, y, np.array([np.log(4.0), np.log(0.1), np.log(1e-3)]))
+    np.testing.assert_array_equal(GridSearch(ei, lo, hi, resolution=200).maximize(), gold["maximizer_grid_x"])
     # 2-d Branin: L-BFGS-B restarts and differential evolution, global NumPy stream seeded as the reference uses it
     lo, hi = np.array([-5.0, 0.0]), np.array([10.0, 15.0])
     X = lo + (hi - lo) * rs.rand(14, 2)
     y = np.array([branin(x) for x in X])
-    ref_ei, my_ei = models(lo, hi, X, y, THETA)
-    for make in (lambda acq: SciPyOptimizer(acq, lo, hi, n_restarts=6, rng=np.random.RandomState(4)),
-                 lambda acq: DifferentialEvolution(acq, lo, hi, n_iters=8, rng=np.random.RandomState(4))):
+    ei = my_ei(lo, hi, X, y, THETA)
+    for name, make in (("scipy", lambda acq: SciPyOptimizer(acq, lo, hi, n_restarts=6, rng=np.random.RandomState(4))),
+                       ("de", lambda acq: DifferentialEvolution(acq, lo, hi, n_iters=8, rng=np.random.RandomState(4)))):
         np.random.seed(9)
-        x_ref = make(ref_ei).maximize()
-        np.random.seed(9)
-        x_mine = make(my_ei).maximize()
+        x_mine = make(ei).maximize()
         assert np.all(x_mine >= lo) and np.all(x_mine <= hi)
-        np.testing.assert_allclose(x_mine, x_ref, rtol=0, atol=1e-3 * (hi - lo).max())
-        np.testing.assert_allclose(my_ei(x_mine[None, :]), ref_ei(x_ref[None, :]), rtol=1e-5, atol=1e-12)
+        np.testing.assert_allclose(x_mine, gold["maximizer_%s_x" % name], rtol=0, atol=1e-3 * (hi - lo).max())
+        np.testing.assert_allclose(ei(x_mine[None, :]), gold["maximizer_%s_ei" % name], rtol=1e-5, atol=1e-12)
 
 
 def test_models_survive_deepcopy_and_pickle_and_the_reference_marginalisation(emu):
     """the reference deep-copies acquisition functions together with their models
     (robo/acquisition_functions/marginalization.py:36,67), so an object holding a ctypes handle must survive
     copy.deepcopy / pickle.  A trained GaussianProcess and a trained GaussianProcessMCMC are copied both ways and predict
-    the same numbers; the REFERENCE's own MarginalizationGPMCMC (imported unchanged) wraps robo_amd's EI over robo_amd's
-    GaussianProcessMCMC and returns what robo_amd's fused marginalisation returns."""
+    the same numbers; robo_amd's fused marginalisation returns what the REFERENCE's own MarginalizationGPMCMC returned
+    wrapped around robo_amd's EI / LogEI / LCB over the same GaussianProcessMCMC (stored in ref_host.npz)."""
     import copy
     import pickle
     from robo_amd.kernels import Matern52Kernel
     from robo_amd.models import GaussianProcess, GaussianProcessMCMC
     from robo_amd.priors import DefaultPrior
     from robo_amd import acquisition_functions as A
-    _reference()
-    from robo.acquisition_functions.marginalization import MarginalizationGPMCMC as RefMarginalization
     lo, hi = np.array([-5.0, 0.0]), np.array([10.0, 15.0])
     rs = np.random.RandomState(2)
     X = lo + (hi - lo) * rs.rand(16, 2)
@@ -243,12 +203,11 @@ def test_models_survive_deepcopy_and_pickle_and_the_reference_marginalisation(em
         np.testing.assert_allclose(got[0], want[0], rtol=1e-13)
         np.testing.assert_allclose(got[1], want[1], rtol=1e-12)
     # the reference's marginalisation: deep copies of robo_amd's EI, one per hyper-parameter sample (marginalization.py:34-46)
+    gold = _gold()
     for cls in (A.EI, A.LogEI, A.LCB):
-        ref_marg = RefMarginalization(cls(mc))
-        ref_marg.update(mc)
         mine = A.MarginalizationGPMCMC(cls(mc))
         mine.update(mc)
-        np.testing.assert_allclose(ref_marg.compute(Xt), mine.compute(Xt), rtol=1e-12, atol=1e-15)
+        np.testing.assert_allclose(gold["marginalization_%s" % cls.__name__], mine.compute(Xt), rtol=1e-12, atol=1e-15)
 
 
 def test_batched_differential_evolution(emu):

@@ -1,7 +1,7 @@
 """Host-side pieces that sit next to the hot path: kernel descriptions, priors, initial
-designs, candidate recipe, ensemble sampler, sharding helpers.  Where the reference's own
-module is importable (/root/reference present, i.e. the build container) outputs are compared
-with it on seeded inputs; on the GPU box those comparisons are skipped."""
+designs, candidate recipe, ensemble sampler, sharding helpers.  Where the reference has the
+same module, outputs are compared with its own outputs on the same seeded inputs, stored in
+tests/golden/ref_host.npz (tests/golden/make_golden_host.py)."""
 import os
 import sys
 
@@ -14,13 +14,12 @@ from robo_amd.kernels import ExpSquaredKernel, Matern52Kernel
 from robo_amd.priors import DefaultPrior, HorseshoePrior, LognormalPrior, NormalPrior, TophatPrior
 from robo_amd.util.ensemble_sampler import EnsembleSampler
 
-HAVE_REF = os.path.isdir("/root/reference/robo")
-needs_ref = pytest.mark.skipif(not HAVE_REF, reason="reference tree not on this box")
+HERE = os.path.dirname(os.path.abspath(__file__))
 
 
-def _ref():
-    if "/root/reference" not in sys.path:
-        sys.path.insert(0, "/root/reference")
+def _gold():
+    """the reference's outputs on this module's inputs (tests/golden/make_golden_host.py)"""
+    return np.load(os.path.join(HERE, "golden", "ref_host.npz"))
 
 
 def test_kernel_api_slice():
@@ -37,34 +36,23 @@ def test_kernel_api_slice():
     assert k[0] == 0.1
 
 
-@needs_ref
 def test_priors_match_reference():
-    _ref()
-    from robo.priors import base_prior as rb
-    from robo.priors.default_priors import DefaultPrior as RefDefault
+    gold = _gold()
     th = np.array([0.3, -1.2, 0.7, 1.9, -4.0])
-    for mine, ref in ((TophatPrior(-10, 2), rb.TophatPrior(-10, 2)),
-                      (HorseshoePrior(0.1), rb.HorseshoePrior(0.1)),
-                      (LognormalPrior(1.0, 0.0), rb.LognormalPrior(1.0, 0.0)),
-                      (NormalPrior(2.0, 0.5), rb.NormalPrior(2.0, 0.5))):
-        np.testing.assert_array_equal(np.asarray(mine.lnprob(th[1:3])), np.asarray(ref.lnprob(th[1:3])))
-    assert DefaultPrior(5).lnprob(th) == RefDefault(5).lnprob(th)
+    for mine, name in ((TophatPrior(-10, 2), "tophat"), (HorseshoePrior(0.1), "horseshoe"),
+                       (LognormalPrior(1.0, 0.0), "lognormal"), (NormalPrior(2.0, 0.5), "normal")):
+        np.testing.assert_array_equal(np.asarray(mine.lnprob(th[1:3])), gold["prior_%s_lnprob" % name])
+    assert DefaultPrior(5).lnprob(th) == gold["prior_default_lnprob"]
     assert DefaultPrior(5).lnprob(np.array([0.3, 3.0, 0.7, 1.9, -4.0])) == -np.inf
     a = DefaultPrior(5, rng=np.random.RandomState(7)).sample_from_prior(6)
-    b = RefDefault(5, rng=np.random.RandomState(7)).sample_from_prior(6)
-    np.testing.assert_array_equal(a, b)
+    np.testing.assert_array_equal(a, gold["prior_default_sample"])
 
 
-@needs_ref
 def test_initial_designs_match_reference_draw_order():
-    _ref()
-    from robo.initial_design import init_latin_hypercube_sampling as ref_lhs
-    from robo.initial_design import init_random_uniform as ref_uni
+    gold = _gold()
     lo, hi = np.array([-5.0, 0.0, 1.0]), np.array([10.0, 15.0, 2.0])
-    np.testing.assert_array_equal(init_random_uniform(lo, hi, 9, rng=np.random.RandomState(3)),
-                                  ref_uni(lo, hi, 9, rng=np.random.RandomState(3)))
-    np.testing.assert_array_equal(init_latin_hypercube_sampling(lo, hi, 7, rng=np.random.RandomState(3)),
-                                  ref_lhs(lo, hi, 7, rng=np.random.RandomState(3)))
+    np.testing.assert_array_equal(init_random_uniform(lo, hi, 9, rng=np.random.RandomState(3)), gold["design_uniform"])
+    np.testing.assert_array_equal(init_latin_hypercube_sampling(lo, hi, 7, rng=np.random.RandomState(3)), gold["design_lhs"])
 
 
 def test_default_prior_batch_equals_scalar():
@@ -93,7 +81,7 @@ def test_initial_designs_properties():
 
 def test_grid_and_normal_designs():
     """robo/initial_design/{init_grid,init_random_normal}.py: pinned values (rows in np.meshgrid 'xy' order; a normal draw of
-    n numbers per dimension, dimension by dimension, clipped) and, where the reference tree is present, its own output"""
+    n numbers per dimension, dimension by dimension, clipped) and the reference's own output"""
     from robo_amd.initial_design import init_grid, init_random_normal
     lo, hi = np.array([-1.0, 0.0, 2.0]), np.array([1.0, 5.0, 3.0])
     g = init_grid(lo[:2], hi[:2], 3)
@@ -104,24 +92,19 @@ def test_grid_and_normal_designs():
     np.testing.assert_array_equal(init_random_normal(lo, hi, 6, rng=np.random.RandomState(3)), want)
     wide = init_random_normal(lo, hi, 200, std=np.full(3, 50.0), rng=np.random.RandomState(4))
     assert np.all(wide >= lo) and np.all(wide <= hi) and np.any(wide == lo) and np.any(wide == hi)      # clipped
-    if os.path.isdir("/root/reference/robo"):
-        _ref()
-        from robo.initial_design import init_grid as ref_grid, init_random_normal as ref_normal
-        for n in (1, 2, 4):
-            np.testing.assert_array_equal(init_grid(lo, hi, n), ref_grid(lo, hi, n))
-        for kw in ({}, {"mean": np.array([0.0, 4.9, 2.1])}, {"std": np.array([1.0, 2.0, 3.0])}):
-            np.testing.assert_array_equal(init_random_normal(lo, hi, 7, rng=np.random.RandomState(3), **kw),
-                                          ref_normal(lo, hi, 7, rng=np.random.RandomState(3), **kw))
+    gold = _gold()
+    for n in (1, 2, 4):
+        np.testing.assert_array_equal(init_grid(lo, hi, n), gold["design_grid_%d" % n])
+    for i, kw in enumerate(({}, {"mean": np.array([0.0, 4.9, 2.1])}, {"std": np.array([1.0, 2.0, 3.0])})):
+        np.testing.assert_array_equal(init_random_normal(lo, hi, 7, rng=np.random.RandomState(3), **kw),
+                                      gold["design_normal_%d" % i])
 
 
-@needs_ref
 @pytest.mark.parametrize("D", [2, 3])
 def test_random_sampling_candidates_match_reference(D):
     """same candidate batch as robo/maximizers/random_sampling.py:38-47 under the same global seed (the reference draws
     row by row in Python loops; here one block call per recipe part -- same stream, same values, also for odd D where a
     Gaussian draw leaves a cached second value behind)"""
-    _ref()
-    from robo.maximizers.random_sampling import RandomSampling as RefRS
     from robo_amd.maximizers import RandomSampling
 
     class Acq(object):
@@ -138,13 +121,12 @@ def test_random_sampling_candidates_match_reference(D):
             return -np.sum((X - 0.4) ** 2, axis=1)
 
     lo, hi = np.zeros(D), np.array([1.0, 2.0, 1.5][:D])
-    a, b = Acq(), Acq()
-    np.random.seed(11)
-    x_ref = RefRS(b, lo, hi, n_samples=201).maximize()
+    a = Acq()
+    gold = _gold()
     np.random.seed(11)
     x = RandomSampling(a, lo, hi, n_samples=201).maximize()
-    np.testing.assert_array_equal(a.seen, b.seen)
-    np.testing.assert_array_equal(x, x_ref)
+    np.testing.assert_array_equal(a.seen, gold["random_sampling_seen_%d" % D])
+    np.testing.assert_array_equal(x, gold["random_sampling_x_%d" % D])
 
 
 def test_ensemble_sampler_recovers_gaussian():
@@ -240,14 +222,14 @@ def test_base_solver_helpers(tmp_path):
     assert sorted(line) == ["Acquisiton", "Model", "Solver", "Task"] and line["Model"] == {"tag": "m"}
 
 
-def test_compat_import_alias():
+def test_compat_import_alias(tmp_path):
     """robo_amd.compat: ``robo.x.y`` is the robo_amd module of the same path (same objects), ``george.kernels`` the kernel
-    module; out-of-scope modules raise ImportError; uninstall leaves nothing behind"""
+    module; out-of-scope modules raise ImportError; an importable ``robo`` package is refused unless forced; uninstall
+    leaves nothing behind"""
     import importlib
     import robo_amd.compat as compat
     saved = {k: v for k, v in sys.modules.items() if k in ("robo", "george") or k.startswith(("robo.", "george."))}
     path = list(sys.path)
-    sys.path[:] = [p for p in sys.path if os.path.abspath(p or ".") != "/root/reference"]      # the real package out of reach
     try:
         compat.uninstall()
         compat.install(force=True)
@@ -272,11 +254,12 @@ def test_compat_import_alias():
             importlib.import_module("robo.models.random_forest")
         assert not hasattr(george, "GP")
         compat.uninstall()
-        if os.path.isdir("/root/reference/robo"):
-            sys.path.insert(0, "/root/reference")                  # the real package within reach: refuse unless forced
-            with pytest.raises(RuntimeError):
-                compat.install()
-            sys.path.remove("/root/reference")
+        (tmp_path / "robo").mkdir()                                # a real ``robo`` package within reach: refuse unless forced
+        (tmp_path / "robo" / "__init__.py").write_text("")
+        sys.path.insert(0, str(tmp_path))
+        with pytest.raises(RuntimeError):
+            compat.install()
+        sys.path.remove(str(tmp_path))
     finally:
         compat.uninstall()
         sys.path[:] = path
@@ -286,7 +269,7 @@ def test_compat_import_alias():
 
 def test_random_search_front_end(tmp_path):
     """robo/fmin/random_search.py: result keys, incumbent = best so far, per-iteration JSON, no state carried between calls;
-    where the reference tree is present: its points and incumbents under the same seed (also its (1, 1) points in 1-D)"""
+    the reference's points and incumbents under the same seed (also its (1, 1) points in 1-D), stored in ref_host.npz"""
     import json
     from robo_amd.fmin import random_search
     f = lambda x: float(np.sum((np.asarray(x) - 0.3) ** 2))      # noqa: E731
@@ -298,17 +281,11 @@ def test_random_search_front_end(tmp_path):
     assert json.load(open(str(tmp_path / "robo_iter_8.json")))["iteration"] == 8
     again = random_search(f, lo, hi, num_iterations=9, rng=np.random.RandomState(1))
     assert again["X"] == r["X"] and len(again["X"]) == 9
-    if os.path.isdir("/root/reference/robo"):
-        _ref()
-        import importlib.util
-        spec = importlib.util.spec_from_file_location("_ref_random_search", "/root/reference/robo/fmin/random_search.py")
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-        for lo_, hi_ in ((lo, hi), (np.array([0.0]), np.array([6.0]))):
-            a = mod.random_search(f, lo_, hi_, X_init=[], Y_init=[], num_iterations=7, rng=np.random.RandomState(4))
-            b = random_search(f, lo_, hi_, num_iterations=7, rng=np.random.RandomState(4))
-            for k in ("X", "y", "x_opt", "f_opt", "incumbents", "incumbent_values"):
-                assert a[k] == b[k], k
+    gold = _gold()
+    for box, (lo_, hi_) in enumerate(((lo, hi), (np.array([0.0]), np.array([6.0])))):
+        b = random_search(f, lo_, hi_, num_iterations=7, rng=np.random.RandomState(4))
+        for k in ("X", "y", "x_opt", "f_opt", "incumbents", "incumbent_values"):
+            np.testing.assert_array_equal(np.asarray(b[k], dtype=np.float64), gold["random_search_%d_%s" % (box, k)], k)
 
 
 def test_fabolas_kernel_in_george_product_notation():

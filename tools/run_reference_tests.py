@@ -6,8 +6,7 @@
 module layout for everything on or next to the hot path); ``george.kernels`` resolves to robo_amd.kernels (the kernel
 objects the reference's tests build and hand to the models).  Nothing of the reference's package is imported -- only its
 test files run.  With --emu the library is the g++ interpreter build (no GPU needed; tests/hipemu), otherwise
-librobo_hip.so on the GPU.  Needs /root/reference, so this runs in the build container only; tests/test_reference_suite.py
-wraps it.
+librobo_hip.so on the GPU.  Needs the reference tree (REF_TESTS below); not part of the test suite.
 
 Files that test components SURVEY.md section 8 puts out of scope are not collected: random forest, Bohamiann, Bayesian
 linear regression (models).
