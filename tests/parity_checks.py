@@ -7,6 +7,7 @@ The same functions run in two settings:
 Tolerances are the stated fp64 tolerances of tests/_tol.py.
 """
 import os
+import time
 
 import numpy as np
 
@@ -104,11 +105,12 @@ def check_case(ctx, name, full=True):
 
 def check_device_chain(ctx, cases=(("matern52", 150, 3, 10, 14), ("rbf", 40, 2, 8, 10), ("matern52", 100, 4, 12, 9),
                                    ("fabolas", 50, 3, 12, 8), ("fabolas", 60, 3, 12, 8, "env"),
-                                   ("fabolas", 170, 4, 14, 6, "env"))):
+                                   ("fabolas", 170, 4, 14, 6, "env")), model_classes=True):
     """robo_gp_mcmc_run (the whole stretch-move chain on the device) against the host sampler around the batched
     likelihood with the same RandomState: same accept decisions, positions and log-probabilities to rounding, the random
     stream ends in the same state; against the CPU oracle's log-probability through the same sampler; walkers outside
-    the reference's |theta| <= 20 bounds and outside the prior's support (-inf); the model class end to end."""
+    the reference's |theta| <= 20 bounds and outside the prior's support (-inf); the model classes end to end
+    (model_classes)."""
     from robo_amd.util.ensemble_sampler import EnsembleSampler
     from robo_amd.priors import DefaultPrior, EnvPrior
     for case in cases:
@@ -255,6 +257,8 @@ def check_device_chain(ctx, cases=(("matern52", 150, 3, 10, 14), ("rbf", 40, 2, 
         except ValueError as e:
             assert "+inf" in str(e), str(e)
         g.close()
+    if not model_classes:
+        return
     # the model class: device chain (default) == host sampler (ROBO_MCMC_HOST=1)
     from robo_amd.kernels import Matern52Kernel
     from robo_amd.models.gaussian_process_mcmc import GaussianProcessMCMC
@@ -1571,3 +1575,171 @@ def check_batched_followers(ctx, sizes=((520, 3, 5), (512, 3, 4), (300, 2, 7)), 
             for h in gps:
                 h.close()
             g.close()
+
+
+# every knob check_factor_schedules sets: all of them go back to their defaults between two schedules and at the end
+SCHEDULE_KEYS = ("potrf_fused", "potrf_fused_panels", "potrf_tm4_min", "potrf_max_wg", "potrf_group", "potrf_tail_split",
+                 "potrf_follow", "potrf_follow_from", "potrf_follow_rows", "potrf_batch_roll", "potrf_batch_follow",
+                 "potrf_batch_tm4_min", "potrf_thin_last", "potrf_split", "potrf_gram_split", "potrf_split_min", "potrf_lead")
+
+
+def factor_schedules(emulated):
+    """(name, knobs) of the single-theta and of the batched schedules of launch_potrf.  `emulated`: the interpreter's
+    device has one CU, so the persistent 128-row tiles (potrf_tm4_min / potrf_batch_tm4_min) and the follower / fused forms'
+    residency (potrf_max_wg) are reached through the test knobs."""
+    tm4 = {"potrf_tm4_min": 1} if emulated else {}
+    btm4 = {"potrf_batch_tm4_min": 1} if emulated else {}
+    cap16 = {"potrf_max_wg": 16} if emulated else {}
+    cap256 = {"potrf_max_wg": 256} if emulated else {}
+    single = (
+        ("launch-per-phase", dict(potrf_follow=0)),
+        ("launch-per-phase, 128-row tiles", dict(potrf_follow=0, **tm4, **cap16)),
+        ("followers from panel 0, 64 rows", dict(potrf_follow=1, potrf_follow_from=-1, potrf_follow_rows=64, **cap256)),
+        ("followers from step 1, 128 rows", dict(potrf_follow=1, potrf_follow_from=1, potrf_follow_rows=128, **tm4, **cap16)),
+        ("followers by step, tail not split", dict(potrf_follow=1, potrf_follow_rows=-1, potrf_tail_split=0, **tm4, **cap256)),
+        ("default", {}),
+        ("grouped (batched path, one sample)", dict(potrf_fused=0, potrf_batch_follow=0)),
+        ("grouped, merged diagonal + panel", dict(potrf_fused=0, potrf_batch_follow=1, **btm4)),
+    )
+    batched = (
+        ("default", {}),
+        ("grouped, launch-per-phase", dict(potrf_fused_panels=0, potrf_batch_follow=0, potrf_split=1)),
+        ("grouped, launch-per-phase, 128-row tiles, thin last row off",
+         dict(potrf_fused_panels=0, potrf_batch_follow=0, potrf_split=1, potrf_thin_last=0, **btm4)),
+        ("grouped, merged", dict(potrf_fused_panels=0, potrf_batch_follow=1, potrf_batch_roll=0, potrf_split=1, **btm4)),
+        ("grouped, merged, rolling layout", dict(potrf_fused_panels=0, potrf_batch_follow=1, potrf_batch_roll=1,
+                                                 potrf_split=1)),
+        ("groups of 1, three streams", dict(potrf_fused_panels=0, potrf_batch_follow=0, potrf_group=1, potrf_split=3,
+                                            potrf_split_min=2, **btm4)),
+        ("groups of 2, two streams, lead 1, gram per stream",
+         dict(potrf_fused_panels=0, potrf_batch_follow=1, potrf_group=2, potrf_split=2, potrf_split_min=2, potrf_lead=1,
+              potrf_gram_split=1)),
+        ("fused, followers", dict(potrf_fused_panels=64, **cap256)),
+        ("fused, followers from step 1, 128 rows", dict(potrf_fused_panels=64, potrf_follow_from=1, potrf_follow_rows=128,
+                                                        **tm4, **cap16)),
+        ("fused, launch-per-phase", dict(potrf_fused_panels=64, potrf_follow=0, **tm4, **cap16)),
+    )
+    return single, batched
+
+
+def check_factor_schedules(ctx, sizes=(100, 127, 255, 256, 257, 383, 384, 511, 512, 513, 767, 768),
+                           samples=(1, 2, 3, 12, 26), emulated=True, D=3, kind="matern52", n_cand=40, verbose=False):
+    """Every schedule of launch_potrf (potrf.hip) against the fp64 oracle, not only against each other: the launch-per-phase
+    form, the fused step kernels, the panel followers (potrf_follow, _from, _rows), the grouped batched panels (potrf_group,
+    _lead), sub-batches on split streams (potrf_split, potrf_gram_split), the merged diagonal + panel launch
+    (potrf_batch_follow, _roll), the fused batches (potrf_fused_panels; by default chosen by residency), the thin last row
+    (potrf_thin_last) and the one-block launch.
+      single theta: log-likelihood, factor and posterior (n_cand candidates) == oracle;
+      loglik_batch: EVERY sample's log-likelihood == oracle;
+      fit_batch:    every sample's kept factor and its posterior == oracle;
+    and, as before, every schedule's results equal the first schedule's bit for bit -- so a fault that two forms share, or
+    one in the form that serves as the reference, fails here too.
+    Sizes: one block (N < 128), N % 128 in {0, 1, 127} (at 0 the augmented row sits alone in its block), both sides of
+    the default fused-batch rule S * (workgroups of the first step) <= 3 * CUs for S = 26 on 256 CUs (N = 767: six panels,
+    fused; 768: seven, grouped) and of the older one-round rule (N = 383 / 384).  S <= 2 is always fused."""
+    from oracle import gp_oracle as O
+    single, batched = factor_schedules(emulated)
+    P = O.n_kernel_params(kind, D) + 1
+    t_start = time.perf_counter()
+
+    def apply(knobs):
+        for key in SCHEDULE_KEYS:
+            ctx.set_tuning(key, None)
+        for key, value in knobs.items():
+            ctx.set_tuning(key, value)
+
+    def oracle_fit(X, y, theta, mean_c, Xc):
+        ogp = O.OracleGP(kind, theta, normalize_input=False)
+        ogp.train(X, y)
+        assert ogp.mean == mean_c
+        mu, var = ogp.predict(Xc, diag_only=True)
+        return ogp.loglikelihood(theta), ogp.L, mu, var
+
+    def against_oracle(what, ll, L, mu, var, ref, theta):
+        ll_o, L_o, mu_o, var_o = ref
+        np.testing.assert_allclose(ll, ll_o, rtol=LOGLIK_RTOL, err_msg=what)
+        if L is not None:
+            np.testing.assert_allclose(L, L_o, rtol=0, atol=1e-10, err_msg=what)
+        if mu is not None:
+            np.testing.assert_allclose(mu, mu_o, rtol=MU_RTOL, atol=MU_ATOL * max(1.0, np.abs(mu_o).max()), err_msg=what)
+            np.testing.assert_allclose(var, var_o, rtol=0, atol=VAR_ATOL_REL_AMP * np.exp(theta[0]), err_msg=what)
+
+    try:
+        for N in sizes:
+            rs = np.random.RandomState(1000 + N)
+            X = rs.rand(N, D)
+            y = np.cos(3 * X.sum(axis=1)) + 0.1 * rs.randn(N)
+            mean_c = float(np.mean(y))
+            theta = np.concatenate([[0.1], np.log(0.5 + 0.2 * np.arange(D)), [np.log(1e-2)]])
+            Xc = rs.rand(n_cand, D)
+            g = _lib.DeviceGP(ctx, kind, N, D)
+            g.set_data(X, y)
+            try:
+                # ---- single theta
+                ref = oracle_fit(X, y, theta, mean_c, Xc)
+                first = None
+                for name, knobs in single:
+                    apply(knobs)
+                    what = "N=%d single theta, %s %s" % (N, name, knobs)
+                    ll = g.fit(theta, mean_c)
+                    L = g.factor()
+                    mu, var = g.predict(Xc)
+                    against_oracle(what, ll, L, mu, var, ref, theta)
+                    if first is None:
+                        first = (ll, L, mu, var)
+                    else:
+                        assert ll == first[0], (what, ll, first[0])
+                        for a, b in zip((L, mu, var), first[1:]):
+                            np.testing.assert_array_equal(a, b, err_msg=what)
+                apply({})
+                # ---- batches
+                for S in samples:
+                    thetas = theta[None, :] + 0.1 * rs.randn(S, P)
+                    refs = [oracle_fit(X, y, th, mean_c, Xc) for th in thetas]
+                    gps = [_lib.DeviceGP(ctx, kind, N, D) for _ in range(S)]
+                    gps[0].set_data(X, y)
+                    try:
+                        first_ll = first_fit = None
+                        for name, knobs in batched:
+                            apply(knobs)
+                            what = "N=%d S=%d, %s %s" % (N, S, name, knobs)
+                            g.loglik_batch(thetas + 0.01, mean_c)        # other matrices through the workspace first
+                            ll, st = g.loglik_batch(thetas, mean_c)
+                            assert np.all(st == _lib.OK), (what, st)
+                            for s in range(S):
+                                against_oracle(what + " loglik_batch sample %d" % s, ll[s], None, None, None, refs[s],
+                                               thetas[s])
+                            if first_ll is None:
+                                first_ll = ll
+                            np.testing.assert_array_equal(ll, first_ll, err_msg=what + " loglik_batch")
+                            llk, st = _lib.fit_batch(gps, thetas, mean_c)
+                            assert np.all(st == _lib.OK), (what, st)
+                            np.testing.assert_array_equal(llk, first_ll, err_msg=what + " fit_batch vs loglik_batch")
+                            kept = []
+                            for s, h in enumerate(gps):
+                                L = h.factor()
+                                mu, var = h.predict(Xc)
+                                against_oracle(what + " fit_batch sample %d" % s, llk[s], L, mu, var, refs[s], thetas[s])
+                                kept.append((L, mu, var))
+                            if first_fit is None:
+                                first_fit = kept
+                            for s in range(S):
+                                for a, b in zip(kept[s], first_fit[s]):
+                                    np.testing.assert_array_equal(a, b, err_msg=what + " fit_batch sample %d" % s)
+                        # the single-theta fit of every sample: the same bits as the batch
+                        apply({})
+                        for s in range(S):
+                            assert g.fit(thetas[s], mean_c) == first_ll[s], (N, S, s)
+                    finally:
+                        apply({})
+                        for h in gps:
+                            h.close()
+                if verbose:
+                    print("N=%d: %d single-theta + %d batched schedules x S in %s against the oracle: ok  (%.1f s so far)"
+                          % (N, len(single), len(batched), samples, time.perf_counter() - t_start),
+                          flush=True)
+            finally:
+                g.close()
+    finally:
+        for key in SCHEDULE_KEYS:
+            ctx.set_tuning(key, None)

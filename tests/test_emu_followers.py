@@ -36,3 +36,12 @@ def test_panel_followers(emu_ctx):
 def test_batched_followers(emu_ctx):
     """the merged diagonal-block + panel launch of the batched factorisation: same likelihoods, kept factors, posteriors"""
     P.check_batched_followers(emu_ctx, sizes=((512, 3, 4),), groups=(0, 1))
+
+
+def test_factor_schedules_against_oracle(emu_ctx):
+    """every schedule of the factorisation against the fp64 oracle (single theta, every sample of a batch, kept factors and
+    their posteriors) and bit for bit against each other: one block, N % 128 in {0, 1, 127}, three and four panels;
+    potrf_tm4_min / potrf_batch_tm4_min / potrf_max_wg take the interpreter's one-CU device to the persistent 128-row
+    tiles, the followers and the fused batches"""
+    P.check_factor_schedules(emu_ctx, sizes=(127, 256, 257), samples=(1, 3))
+    P.check_factor_schedules(emu_ctx, sizes=(384,), samples=(2,))

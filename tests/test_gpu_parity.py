@@ -71,6 +71,16 @@ def test_follower_hand_offs_under_concurrent_load():
     assert res.stdout.count("all bit-identical") == 3
 
 
+def test_factor_schedules_against_oracle(ctx):
+    """every schedule launch_potrf can choose (launch-per-phase, fused step kernels, panel followers, grouped / split /
+    merged / fused batches, thin last row, one block) against the fp64 oracle -- single-theta fit, every sample of
+    loglik_batch, every kept factor of fit_batch and its posterior -- and bit for bit against each other; sizes on both
+    sides of the block, augmented-row and fused-batch residency edges, S = 1 .. 26"""
+    t0 = time.perf_counter()
+    P.check_factor_schedules(ctx, emulated=False, verbose=True)
+    print("schedules against the oracle: %.1f s" % (time.perf_counter() - t0))
+
+
 def test_batched_followers_hand_off(ctx):
     """potrf_batch_follow on the hardware: S diagonal workgroups publish, their samples' followers read in the same launch --
     likelihoods, kept factors and posteriors equal the launch-per-phase form's bit for bit (three passes per setting)"""
@@ -569,6 +579,13 @@ def test_host_array_handle_reuse(ctx):
 def test_device_resident_chain(ctx):
     P.check_device_chain(ctx)
     P.check_device_chain(ctx, cases=(("matern52", 300, 16, 36, 20),))
+
+
+def test_device_chain_fused_batches_beyond_residency(ctx):
+    """the device chain where its half-steps (26 likelihoods: 52 walkers) take the fused batched factorisation with more
+    workgroups than CUs (six panels: 26 x 26 workgroups in the first step on 256 CUs): the same chain as the host sampler
+    and the oracle's"""
+    P.check_device_chain(ctx, cases=(("matern52", 700, 4, 52, 4),), model_classes=False)
 
 
 # ---- single-process multi-device entry points (multi.hip): two contexts on the one MI355X of the test box --------------
