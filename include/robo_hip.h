@@ -38,7 +38,9 @@ enum robo_status {
                                           (gaussian_process.py:241,273,322)                  */
     ROBO_BAD_SHAPE = 3,             /* the reference asserts (base_model.py:68-70,76)        */
     ROBO_RUNTIME_ERROR = 4,         /* HIP error; text in robo_last_error_string()           */
-    ROBO_BAD_ARGUMENT = 5
+    ROBO_BAD_ARGUMENT = 5,
+    ROBO_NUMERIC_ERROR = 6          /* -> Exception('... Resulting variance contains NaN')
+                                          (robo/util/epmgp.py: the EP working covariance)   */
 };
 
 enum robo_kernel_kind {
@@ -309,6 +311,19 @@ int32_t robo_ig_eval_moments(robo_ctx* ctx, int64_t m, int32_t nb, int32_t n_out
 /* posterior covariances cov(x_c, z_b) (m, nref <= 64), floored at DBL_EPSILON like the reference's
  * predict(full_cov=True) -> predict_variance path (gaussian_process.py:243-246,290-294)            */
 int32_t robo_gp_cross_cov(robo_gp* gp, robo_cand* cand, robo_cand* ref, double* out_cov);
+/* EP approximation of p_min over nb representer points and its derivatives, for S beliefs N(mu_s, sigma_s) at once:
+ * robo/util/epmgp.py joint_min (robo_amd/util/epmgp.py) per belief, one workgroup per (belief, candidate minimiser).
+ * mu (S, nb), sigma (S, nb, nb) as predict(full_cov=True) returns them (not required to be exactly symmetric).
+ * Outputs per belief in the layouts robo_ig_eval_cand consumes: logP (S, nb); with_derivatives != 0: dlogPdMu
+ * (S, nb, nb), dlogPdSigma (S, nb, nb(nb+1)/2) lower-triangle packed, dlogPdMudMu (S, nb, nb, nb) -- NULL allowed when
+ * with_derivatives = 0.  out_sweeps (S, nb), nullable: EP sweeps run for each minimiser, -1 where a site's cavity
+ * z < -6 killed it (log p floored at -500).  out_status (S): ROBO_OK, ROBO_NOT_POSITIVE_DEFINITE (the closed form's
+ * I + R^T Sigma R is singular or not factorable with jitter up to 1e-6; np.linalg.LinAlgError) or ROBO_NUMERIC_ERROR
+ * (NaN in the working covariance); a belief's outputs are defined only where its status is ROBO_OK.
+ * 1 <= nb <= 64, S >= 1, else ROBO_BAD_ARGUMENT.  Same bits on every call and at every batch position.             */
+int32_t robo_ep_joint_min(robo_ctx* ctx, int32_t S, int32_t nb, const double* mu, const double* sigma,
+                          int32_t with_derivatives, double* logP, double* dlogPdMu, double* dlogPdSigma,
+                          double* dlogPdMudMu, int32_t* out_sweeps, int32_t* out_status);
 
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI (SURVEY.md 8b "robo_comm_init + _sharded variants", 8e) -------
  * The reference is single-process; these entry points shard its two independent axes -- the candidate batch of

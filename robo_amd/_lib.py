@@ -19,7 +19,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIBRARY = os.path.join(_HERE, "librobo_hip.so")
 DEFAULT_DIAG_LIBRARY = os.path.join(_HERE, "librobo_hip_diag.so")   # self-checks / micro-benchmarks (not product)
 
-OK, NOT_POSITIVE_DEFINITE, NOT_FITTED, BAD_SHAPE, RUNTIME_ERROR, BAD_ARGUMENT = range(6)
+OK, NOT_POSITIVE_DEFINITE, NOT_FITTED, BAD_SHAPE, RUNTIME_ERROR, BAD_ARGUMENT, NUMERIC_ERROR = range(7)
+EP_MAX_NB = 64                                   # robo_ep_joint_min's cap on the representer points of one belief
+EP_NAN_MESSAGE = ("an error occurs while running expectation propagation in entropy search. "
+                  "Resulting variance contains NaN")
 KERNEL_KINDS = {"matern52": 0, "rbf": 1, "fabolas": 2}
 ACQ_KINDS = {"ei": 0, "log_ei": 1, "pi": 2, "lcb": 3}
 FLAG_ZERO_SIGMA, FLAG_NEGATIVE_EI, FLAG_NAN = 1, 2, 4
@@ -38,6 +41,7 @@ SYMBOLS = [
     "robo_gp_predict_cand", "robo_gp_predict", "robo_gp_predict_cov", "robo_gp_predict_grad", "robo_gp_predict_mixture_cand",
     "robo_acq_eval_cand", "robo_acq_eval", "robo_acq_eval_moments", "robo_acq_eval_marginal_cand", "robo_acq_eval_sum_cand",
     "robo_ig_eval_cand", "robo_ig_eval_per_cost_cand", "robo_ig_eval_moments", "robo_gp_cross_cov",
+    "robo_ep_joint_min",
     "robo_comm_create_id", "robo_comm_init", "robo_comm_destroy", "robo_comm_info", "robo_comm_allgather",
     "robo_acq_eval_cand_sharded", "robo_acq_eval_marginal_cand_sharded", "robo_ig_eval_per_cost_cand_sharded",
     "robo_multi_create", "robo_multi_destroy", "robo_multi_info", "robo_gp_set_data_multi", "robo_gp_fit_multi",
@@ -171,6 +175,7 @@ def lib():
                                                _dp, _dp, C.POINTER(i64), C.POINTER(i32)],
         "robo_ig_eval_moments": [vp, i64, i32, i32, dbl, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp],
         "robo_gp_cross_cov": [vp, vp, vp, _dp],
+        "robo_ep_joint_min": [vp, i32, i32, _dp, _dp, i32, _dp, _dp, _dp, _dp, C.POINTER(i32), C.POINTER(i32)],
         "robo_comm_create_id": [C.c_char_p],
         "robo_comm_init": [vp, i32, i32, C.c_char_p, pp],
         "robo_comm_destroy": [vp],
@@ -255,6 +260,8 @@ def check(status, msg=None):
         raise RoboBadShape(msg)                               # base_model.py:68-70,76 use assert
     if status == BAD_ARGUMENT:
         raise ValueError(msg)
+    if status == NUMERIC_ERROR:
+        raise Exception(EP_NAN_MESSAGE)                       # robo/util/epmgp.py (the EP working covariance)
     raise RoboHipError(msg)
 
 
@@ -1050,6 +1057,33 @@ def ig_from_moments(ctx, s, v, ep, sn2):
     check(lib().robo_ig_eval_moments(ctx._h, s.shape[0], ep.nb, ep.W.size, float(sn2), _arr(s), _arr(v), *ep.args(),
                                      _arr(out)))
     return out
+
+
+def ep_joint_min(ctx, mu, sigma, with_derivatives=False):
+    """EP p_min of S beliefs on the device (robo_ep_joint_min): mu (S, N), sigma (S, N, N) ->
+    (logP (S, N), dlogPdMu (S, N, N), dlogPdSigma (S, N, N(N+1)/2), dlogPdMudMu (S, N, N, N), sweeps (S, N)), the three
+    derivatives None without ``with_derivatives``; sweeps[s, k] = EP sweeps of minimiser k, -1 where it was killed.
+    The first belief whose status is not OK raises what epmgp.joint_min raises on it (LinAlgError / Exception)."""
+    mu = _f64(mu)
+    if mu.ndim != 2:
+        raise AssertionError("mu must be (S, N), got %r" % (mu.shape,))
+    S, n = mu.shape
+    sigma = _f64(sigma, (S, n, n))
+    i32p = C.POINTER(C.c_int32)
+    logP = np.empty((S, n))
+    d = (np.empty((S, n, n)), np.empty((S, n, n * (n + 1) // 2)), np.empty((S, n, n, n))) if with_derivatives else None
+    sweeps = np.empty((S, n), dtype=np.int32)
+    status = np.empty(S, dtype=np.int32)
+    check(lib().robo_ep_joint_min(ctx._h, int(S), int(n), _arr(mu), _arr(sigma), 1 if with_derivatives else 0,
+                                  _arr(logP), *([_arr(a) for a in d] if d else [None, None, None]),
+                                  sweeps.ctypes.data_as(i32p), status.ctypes.data_as(i32p)))
+    for st in status:
+        if st == NOT_POSITIVE_DEFINITE:
+            raise np.linalg.LinAlgError("Matrix is not positive definite")
+        check(int(st), msg="robo_ep_joint_min: belief status %d" % st)
+    if d is None:
+        return logP, None, None, None, sweeps
+    return (logP,) + d + (sweeps,)
 
 
 def cross_cov(gp, cand, ref):

@@ -7,7 +7,8 @@ robo/acquisition_functions/information_gain.py:19-272:
   update(model)   sample Nb representer points with an ensemble sampler on the proposal
                   acquisition (LogEI by default; 50 steps, up to 5 restarts while any log-value
                   is infinite, :132-151), posterior over them with full covariance, EP for
-                  log p_min and its derivatives (host, robo_amd/util/epmgp.py), outcome quantiles W.
+                  log p_min and its derivatives (robo_amd/util/epmgp.py: on the host, or with
+                  ``ep="device"`` one robo_ep_joint_min call on the model's device), outcome quantiles W.
   compute(X)      for every candidate the innovation of the belief at the representer points and
                   the resulting expected entropy change -- the reference's Python loop with one
                   (Nb+1)-point covariance solve per candidate (:112-116, :253-272) is one batched
@@ -42,7 +43,14 @@ def outcome_quantiles(Np):
 class InformationGain(BaseAcquisitionFunction):
 
     def __init__(self, model, lower, upper, Nb=50, Np=400, sampling_acquisition=None,
-                 sampling_acquisition_kw={"par": 0.0}, rng=None, **kwargs):
+                 sampling_acquisition_kw={"par": 0.0}, rng=None, ep=None, **kwargs):
+        """``ep``: where update() runs the EP for p_min -- "host" (epmgp.joint_min), "device" (epmgp.joint_min_device
+        on the model's context, Nb <= 64) or None = epmgp.default_backend, read at every update()"""
+        if ep not in (None,) + epmgp.BACKENDS:
+            raise ValueError("ep must be None, 'host' or 'device', not %r" % (ep,))
+        if ep == "device" and Nb > _lib.EP_MAX_NB:
+            raise ValueError("ep='device' handles at most %d representer points, Nb = %d" % (_lib.EP_MAX_NB, Nb))
+        self.ep = ep
         self.Nb = Nb
         super(InformationGain, self).__init__(model)
         self.lower = lower
@@ -102,8 +110,13 @@ class InformationGain(BaseAcquisitionFunction):
                 row0 = sharding.allgather_rows(np.concatenate([zb.ravel(), lmb.ravel()]))[0]
                 self.zb, self.lmb = row0[:zb.size].reshape(zb.shape), row0[zb.size:].reshape(lmb.shape)
         mu, var = self.model.predict(np.array(self.zb), full_cov=True)
-        self.logP, self.dlogPdMu, self.dlogPdSigma, self.dlogPdMudMu = epmgp.joint_min(mu, var,
-                                                                                       with_derivatives=True)
+        if (self.ep or epmgp.default_backend) == "device":
+            gp = getattr(self.model, "gp", None)
+            ctx = gp.ctx if isinstance(gp, _lib.DeviceGP) else _lib.default_context()
+            ep = epmgp.joint_min_device(mu, var, with_derivatives=True, ctx=ctx)
+        else:
+            ep = epmgp.joint_min(mu, var, with_derivatives=True)
+        self.logP, self.dlogPdMu, self.dlogPdSigma, self.dlogPdMudMu = ep
         self.W = outcome_quantiles(self.Np)
         self.logP = np.reshape(self.logP, (self.logP.shape[0], 1))
         self._ep = _lib.EPState(self.logP, self.lmb, self.W, self.dlogPdMu, self.dlogPdSigma, self.dlogPdMudMu)

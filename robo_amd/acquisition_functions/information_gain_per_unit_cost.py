@@ -18,13 +18,13 @@ from robo_amd.util.ensemble_sampler import EnsembleSampler
 class InformationGainPerUnitCost(InformationGain):
 
     def __init__(self, model, cost_model, lower, upper, is_env_variable, sampling_acquisition=None,
-                 n_representer=50, Np=400, rng=None):
+                 n_representer=50, Np=400, rng=None, ep=None):
         self.cost_model = cost_model
         self.n_dims = lower.shape[0]
         self.is_env = is_env_variable
         self.overhead = 0
         super(InformationGainPerUnitCost, self).__init__(model, lower, upper, Nb=n_representer, Np=Np,
-                                                         sampling_acquisition=sampling_acquisition, rng=rng)
+                                                         sampling_acquisition=sampling_acquisition, rng=rng, ep=ep)
 
     def update(self, model, cost_model, overhead=None):
         self.cost_model = cost_model

@@ -103,6 +103,7 @@ static void ctx_free(robo_ctx* c) {
     hipFree(c->d_fail);
     hipFree(c->d_prog);
     hipHostFree(c->h_pinned);
+    ep_release(c);
     if (c->own_stream) hipStreamDestroy(c->stream);
     delete c;
     --g_ctx_live;

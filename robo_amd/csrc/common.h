@@ -171,6 +171,8 @@ void tuning_from_env(Tuning* t);
 }  // namespace robo
 struct robo_ctx;
 namespace robo {
+struct EpWork;                          // ep.hip: grow-once buffers of robo_ep_joint_min
+void ep_release(robo_ctx* ctx);         // ... freed with the context
 int ctx_aux_streams(robo_ctx* ctx);   // api.hip: create ctx->aux / ev_fork / ev_join once
 void ctx_retain(robo_ctx* ctx);        // a handle was created on ctx
 void ctx_release(robo_ctx* ctx);       // ... destroyed: frees a closing context with its last handle
@@ -201,6 +203,7 @@ struct robo_ctx {
     int* d_fail;         // first failing column + 1, or 0
     unsigned* d_prog;    // [2][PROG_STRIDE] progress words of the follower hand-off (potrf.hip), zeroed per factorisation
     double* h_pinned;    // small pinned staging (64 doubles)
+    robo::EpWork* ep;    // robo_ep_joint_min's buffers (ep.hip), allocated on first use, grown, never shrunk
 };
 
 namespace robo {

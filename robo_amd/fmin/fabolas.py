@@ -29,7 +29,7 @@ def retransform(s_transform, s_min, s_max):
 
 
 def build_fabolas(lower, upper, burnin=100, chain_length=100, n_hypers=12, rng=None, n_candidates=500,
-                  n_representer=50, n_outcomes=400, devices=None):
+                  n_representer=50, n_outcomes=400, devices=None, ep=None):
     """the objects robo/fmin/fabolas.py:99-199 wires together -> (objective model, cost model, acquisition
     function, maximiser)"""
     n_dims = lower.shape[0]
@@ -51,7 +51,8 @@ def build_fabolas(lower, upper, burnin=100, chain_length=100, n_hypers=12, rng=N
     is_env = np.zeros(extend_lower.shape[0])
     is_env[-1] = 1
     ig = InformationGainPerUnitCost(model_objective, model_cost, extend_lower, extend_upper, sampling_acquisition=EI,
-                                    is_env_variable=is_env, n_representer=n_representer, Np=n_outcomes, rng=rng)
+                                    is_env_variable=is_env, n_representer=n_representer, Np=n_outcomes, rng=rng,
+                                    ep=ep)
     acquisition_func = MarginalizationGPMCMC(ig)
     maximizer = RandomSampling(acquisition_func, extend_lower, extend_upper, n_samples=n_candidates)
     return model_objective, model_cost, acquisition_func, maximizer
@@ -59,13 +60,14 @@ def build_fabolas(lower, upper, burnin=100, chain_length=100, n_hypers=12, rng=N
 
 def fabolas(objective_function, lower, upper, s_min, s_max, n_init=40, num_iterations=100, subsets=[256, 128, 64],
             inc_estimation="mean", burnin=100, chain_length=100, n_hypers=12, output_path=None, rng=None,
-            n_candidates=500, n_representer=50, n_outcomes=400, n_gpus=None, devices=None):
+            n_candidates=500, n_representer=50, n_outcomes=400, n_gpus=None, devices=None, ep=None):
     """objective_function(x, s) -> (validation error, cost); returns the reference's result dict.
 
     ``n_gpus`` / ``devices``: single-process multi-GPU -- the hyper-parameter samples of both models are split over the
     listed devices (sample s of the loss model and sample s of the cost model share a device); every sample's
     information gain per unit cost is evaluated on its device, all devices at once; one objective evaluation per
-    iteration as in robo/fmin/fabolas.py:222-296."""
+    iteration as in robo/fmin/fabolas.py:222-296.
+    ``ep``: where each estimator's EP for p_min runs, "host" or "device" (InformationGain; None = epmgp.default_backend)."""
     time_start = time.time()
     if rng is None:
         rng = np.random.RandomState(np.random.randint(0, 10000))
@@ -84,7 +86,7 @@ def fabolas(objective_function, lower, upper, s_min, s_max, n_init=40, num_itera
     from robo_amd import _lib
     model_objective, model_cost, acquisition_func, maximizer = build_fabolas(
         lower, upper, burnin, chain_length, n_hypers, rng, n_candidates, n_representer, n_outcomes,
-        devices=_lib.resolve_devices(devices, n_gpus))
+        devices=_lib.resolve_devices(devices, n_gpus), ep=ep)
 
     x_init = init_latin_hypercube_sampling(lower, upper, n_init, rng)
     for it in range(n_init):

@@ -2,8 +2,11 @@
 Nb representer points, with the derivatives entropy search needs (Cunningham, Hennig &
 Lacoste-Julien 2011, "Gaussian probabilities and expectation propagation"; Hennig & Schuler 2012).
 
-Host code by design (Nb = 50, inherently sequential rank-1 site
-updates, runs once per ``InformationGain.update``); same entry point and return convention as
+``joint_min`` is host code (Nb = 50, inherently sequential rank-1 site
+updates, runs once per ``InformationGain.update``); ``joint_min_device`` / ``joint_min_batch`` run the same
+computation on the GPU (robo_ep_joint_min, robo_amd/csrc/ep.hip: one workgroup per candidate minimiser) and are
+opted into per estimator (``InformationGain(..., ep="device")``) or through ``default_backend``.  Same entry point and
+return convention as
 ``robo/util/epmgp.py:11-81`` -- ``joint_min(mu, var, with_derivatives)`` ->
 ``logP (N,)`` or ``(logP, dlogPdMu (N,N), dlogPdSigma (N, N(N+1)/2), dlogPdMudMu (N,N,N))`` with the
 covariance derivative packed as the row-major LOWER triangle (what
@@ -21,6 +24,9 @@ import numpy as np
 from scipy import special
 
 SQRT2 = np.sqrt(2.0)
+# backend of InformationGain.update when its ``ep`` argument is None: "host" (joint_min) or "device" (joint_min_device)
+default_backend = "host"
+BACKENDS = ("host", "device")
 EPS32 = np.finfo(np.float32).eps
 LOG_2PI = np.log(2.0) + np.log(np.pi)
 
@@ -188,3 +194,25 @@ def joint_min(mu, var, with_derivatives=False, **kwargs):
     # over rows, not the outer product.  Mirrored (it changes every information-gain value the
     # reference produces); DESIGN.md "Mirrored quirks".
     return logP, d_mu - Zm, d_sigma - Zs, d_mumu + (-gg + (Zm * Zm)[None, :])[None, :, :]
+
+
+def joint_min_batch(mu, var, with_derivatives=False, ctx=None):
+    """joint_min of S beliefs at once on the device: mu (S, N), var (S, N, N), N <= 64 -> logP (S, N) or
+    (logP, dlogPdMu (S, N, N), dlogPdSigma (S, N, N(N+1)/2), dlogPdMudMu (S, N, N, N)); row s equals
+    joint_min_device(mu[s], var[s]) bit for bit.  ctx: a robo_amd._lib.Context (default: the process's default one)."""
+    from robo_amd import _lib
+    ctx = _lib.default_context() if ctx is None else ctx
+    logP, d_mu, d_sigma, d_mumu, _ = _lib.ep_joint_min(ctx, mu, var, with_derivatives)
+    if not with_derivatives:
+        return logP
+    return logP, d_mu, d_sigma, d_mumu
+
+
+def joint_min_device(mu, var, with_derivatives=False, ctx=None):
+    """joint_min on the device (robo_ep_joint_min), same arguments and return convention; N <= 64."""
+    mu = np.asarray(mu, dtype=np.float64)
+    var = np.asarray(var, dtype=np.float64)
+    res = joint_min_batch(mu.reshape(1, -1), var.reshape((1,) + var.shape), with_derivatives, ctx)
+    if not with_derivatives:
+        return res[0]
+    return tuple(a[0] for a in res)
