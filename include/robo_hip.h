@@ -64,6 +64,8 @@ enum robo_acq_kind {
 #define ROBO_FLAG_ZERO_SIGMA 1u   /* some s == 0           (ei.py:72-74)  */
 #define ROBO_FLAG_NEGATIVE_EI 2u  /* some EI < 0           (ei.py:86-88)  */
 #define ROBO_FLAG_NAN 4u          /* some acquisition value is NaN        */
+#define ROBO_FLAG_NOT_FACTORED 8u /* Monte-Carlo information gain: some candidate's covariance
+                                     had no Cholesky factor with jitter up to 1e4              */
 
 /* ---- context ---------------------------------------------------------------------- */
 int32_t robo_device_count(int32_t* out_n);
@@ -324,6 +326,36 @@ int32_t robo_gp_cross_cov(robo_gp* gp, robo_cand* cand, robo_cand* ref, double* 
 int32_t robo_ep_joint_min(robo_ctx* ctx, int32_t S, int32_t nb, const double* mu, const double* sigma,
                           int32_t with_derivatives, double* logP, double* dlogPdMu, double* dlogPdSigma,
                           double* dlogPdMudMu, int32_t* out_sweeps, int32_t* out_status);
+
+/* ---- Monte-Carlo entropy search: InformationGainMC (robo/acquisition_functions/information_gain_mc.py, with the
+ * intended semantics of DESIGN.md "Monte-Carlo entropy search") and robo/util/mc_part.py joint_pmin with given draws
+ * z (nf, nb) row-major: the standard normals, draw f in row f.  The same z is meant for the baseline p_min and every
+ * candidate of an update (common random numbers); it is uploaded only when it differs from the last one on the context.
+ * Factors: Cholesky of V + j I with j = 0, then 1e-9, x10 while j <= 1e4 (mc_part.joint_pmin's ladder).  A draw's
+ * minimum is the first index of the smallest value (np.argmin); p = max(count / nf, 1e-70), not renormalised.
+ * Limits: 1 <= nb <= 64, 1 <= n_outcomes <= 512, 1 <= nf <= 65535, else ROBO_BAD_ARGUMENT.  Same bits on every call
+ * and at every batch position.                                                                                    */
+/* p_min of S beliefs N(mu_s, sigma_s): mu (S, nb), sigma (S, nb, nb) (lower triangle read) -> out_pmin (S, nb),
+ * out_jitter (S, nullable) the jitter each factor used, out_status (S): ROBO_OK or ROBO_NOT_POSITIVE_DEFINITE (no factor
+ * with jitter up to 1e4; np.linalg.LinAlgError), out_pmin defined only where ROBO_OK.                                */
+int32_t robo_pmin_mc(robo_ctx* ctx, int32_t S, int32_t nb, int32_t nf, const double* mu, const double* sigma,
+                     const double* z, double* out_pmin, double* out_jitter, int32_t* out_status);
+/* information gain of every candidate: s = cov(x, z_b) and v = predictive variance exactly as robo_ig_eval_cand uses
+ * them; u = v - sn2, a = s sqrt(v + 1e-10) / u, V_x = Vb - s s^T / u; per outcome p the draws  (Mb + a W_p) + L_x z_f
+ * are counted into q[p] (nb); dH = mean_p (H0 - H_p), H = -sum_b p_b (log p_b + lmb_b), H0 from exp(logP).
+ * Mb (nb), Vb (nb, nb): the belief at the representer points rep (predict(full_cov=True)); logP (nb) log of its p_min;
+ * lmb (nb); W (n_outcomes).  A non-finite dH becomes -DBL_MAX; a candidate whose V_x has no factor gets -DBL_MAX and sets
+ * ROBO_FLAG_NOT_FACTORED in out_flags (nullable).  out_dh (m,) nullable; out_max / out_argmax as robo_acq_eval.    */
+int32_t robo_igmc_eval_cand(robo_gp* gp, robo_cand* cand, robo_cand* rep, int32_t n_outcomes, int32_t nf, double sn2,
+                            const double* Mb, const double* Vb, const double* logP, const double* lmb, const double* W,
+                            const double* z, double* out_dh, double* out_max, int64_t* out_argmax, uint32_t* out_flags);
+/* the same from innovation inputs supplied by any other model: s (m, nb), v (m).  out_counts (m, n_outcomes, nb),
+ * nullable: the raw counts; out_jitter (m), nullable: the jitter each candidate's factor used (the first rung above 1e4
+ * where it failed).                                                                                                 */
+int32_t robo_igmc_eval_moments(robo_ctx* ctx, int64_t m, int32_t nb, int32_t n_outcomes, int32_t nf, double sn2,
+                               const double* s, const double* v, const double* Mb, const double* Vb, const double* logP,
+                               const double* lmb, const double* W, const double* z, double* out_dh,
+                               int32_t* out_counts, double* out_jitter);
 
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI (SURVEY.md 8b "robo_comm_init + _sharded variants", 8e) -------
  * The reference is single-process; these entry points shard its two independent axes -- the candidate batch of

@@ -25,7 +25,8 @@ EP_NAN_MESSAGE = ("an error occurs while running expectation propagation in entr
                   "Resulting variance contains NaN")
 KERNEL_KINDS = {"matern52": 0, "rbf": 1, "fabolas": 2}
 ACQ_KINDS = {"ei": 0, "log_ei": 1, "pi": 2, "lcb": 3}
-FLAG_ZERO_SIGMA, FLAG_NEGATIVE_EI, FLAG_NAN = 1, 2, 4
+FLAG_ZERO_SIGMA, FLAG_NEGATIVE_EI, FLAG_NAN, FLAG_NOT_FACTORED = 1, 2, 4, 8
+MC_MAX_NB, MC_MAX_NP, MC_MAX_NF = 64, 512, 65535   # limits of the Monte-Carlo p_min entry points (robo_pmin_mc, robo_igmc_*)
 
 # every symbol include/robo_hip.h declares (tests check the library exports all of them)
 SYMBOLS = [
@@ -41,7 +42,7 @@ SYMBOLS = [
     "robo_gp_predict_cand", "robo_gp_predict", "robo_gp_predict_cov", "robo_gp_predict_grad", "robo_gp_predict_mixture_cand",
     "robo_acq_eval_cand", "robo_acq_eval", "robo_acq_eval_moments", "robo_acq_eval_marginal_cand", "robo_acq_eval_sum_cand",
     "robo_ig_eval_cand", "robo_ig_eval_per_cost_cand", "robo_ig_eval_moments", "robo_gp_cross_cov",
-    "robo_ep_joint_min",
+    "robo_ep_joint_min", "robo_pmin_mc", "robo_igmc_eval_cand", "robo_igmc_eval_moments",
     "robo_comm_create_id", "robo_comm_init", "robo_comm_destroy", "robo_comm_info", "robo_comm_allgather",
     "robo_acq_eval_cand_sharded", "robo_acq_eval_marginal_cand_sharded", "robo_ig_eval_per_cost_cand_sharded",
     "robo_multi_create", "robo_multi_destroy", "robo_multi_info", "robo_gp_set_data_multi", "robo_gp_fit_multi",
@@ -176,6 +177,11 @@ def lib():
         "robo_ig_eval_moments": [vp, i64, i32, i32, dbl, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp],
         "robo_gp_cross_cov": [vp, vp, vp, _dp],
         "robo_ep_joint_min": [vp, i32, i32, _dp, _dp, i32, _dp, _dp, _dp, _dp, C.POINTER(i32), C.POINTER(i32)],
+        "robo_pmin_mc": [vp, i32, i32, i32, _dp, _dp, _dp, _dp, _dp, C.POINTER(i32)],
+        "robo_igmc_eval_cand": [vp, vp, vp, i32, i32, dbl, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(i64),
+                                C.POINTER(C.c_uint32)],
+        "robo_igmc_eval_moments": [vp, i64, i32, i32, i32, dbl, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
+                                   C.POINTER(i32), _dp],
         "robo_comm_create_id": [C.c_char_p],
         "robo_comm_init": [vp, i32, i32, C.c_char_p, pp],
         "robo_comm_destroy": [vp],
@@ -1084,6 +1090,73 @@ def ep_joint_min(ctx, mu, sigma, with_derivatives=False):
     if d is None:
         return logP, None, None, None, sweeps
     return (logP,) + d + (sweeps,)
+
+
+def pmin_mc(ctx, mu, sigma, z):
+    """Monte-Carlo p_min of S beliefs on the device with the given draws (robo_pmin_mc): mu (S, N), sigma (S, N, N),
+    z (Nf, N) standard normals -> (pmin (S, N), jitter (S,)).  A belief without a factor (jitter beyond 1e4) raises
+    np.linalg.LinAlgError, as mc_part.joint_pmin does."""
+    mu = _f64(mu)
+    if mu.ndim != 2:
+        raise AssertionError("mu must be (S, N), got %r" % (mu.shape,))
+    S, n = mu.shape
+    sigma = _f64(sigma, (S, n, n))
+    z = _f64(z)
+    if z.ndim != 2 or z.shape[1] != n:
+        raise AssertionError("z must be (Nf, %d), got %r" % (n, z.shape))
+    pmin, jitter = np.empty((S, n)), np.empty(S)
+    status = np.empty(S, dtype=np.int32)
+    check(lib().robo_pmin_mc(ctx._h, int(S), int(n), int(z.shape[0]), _arr(mu), _arr(sigma), _arr(z), _arr(pmin),
+                             _arr(jitter), status.ctypes.data_as(C.POINTER(C.c_int32))))
+    for st in status:
+        if st == NOT_POSITIVE_DEFINITE:
+            raise np.linalg.LinAlgError("Cholesky decomposition failed.")
+        check(int(st), msg="robo_pmin_mc: belief status %d" % st)
+    return pmin, jitter
+
+
+class MCState(object):
+    """the per-update state of InformationGainMC, contiguous fp64: the draws z (Nf, Nb), the belief Mb (Nb), Vb (Nb, Nb)
+    at the representer points, logP (Nb) = log of its p_min, lmb (Nb) and the outcome quantiles W (Np).  The library
+    uploads z once and reuses it while the same draws come back (every compute() of an update)."""
+
+    def __init__(self, z, Mb, Vb, logP, lmb, W):
+        self.z = _f64(z)
+        self.nf, self.nb = self.z.shape
+        self.Mb = _f64(np.asarray(Mb).reshape(-1))
+        self.Vb = _f64(Vb, (self.nb, self.nb))
+        self.logP = _f64(np.asarray(logP).reshape(-1))
+        self.lmb = _f64(np.asarray(lmb).reshape(-1))
+        self.W = _f64(np.asarray(W).reshape(-1))
+        assert self.Mb.size == self.logP.size == self.lmb.size == self.nb
+
+    def args(self):
+        return [_arr(a) for a in (self.Mb, self.Vb, self.logP, self.lmb, self.W, self.z)]
+
+
+def igmc_eval(gp, cand, rep, mc, sn2, want_values=True):
+    """Monte-Carlo information gain of every candidate (robo_igmc_eval_cand) -> (values or None, max, argmax, flags)"""
+    assert rep.m == mc.nb
+    out = np.empty(cand.m) if want_values else None
+    mx, am, fl = C.c_double(0), C.c_int64(0), C.c_uint32(0)
+    check(lib().robo_igmc_eval_cand(gp._h, cand._h, rep._h, mc.W.size, mc.nf, float(sn2), *mc.args(),
+                                    _arr(out) if want_values else None, C.byref(mx), C.byref(am), C.byref(fl)))
+    return out, mx.value, am.value, fl.value
+
+
+def igmc_from_moments(ctx, s, v, mc, sn2, with_counts=False):
+    """the same from s (m, Nb) and v (m,) of any model (robo_igmc_eval_moments) -> values, or (values, counts
+    (m, Np, Nb) int32, jitter (m,)) with ``with_counts``"""
+    s, v = _f64(s), _f64(v)
+    assert s.ndim == 2 and s.shape[1] == mc.nb and v.shape == (s.shape[0],)
+    m = s.shape[0]
+    out = np.empty(m)
+    counts = np.empty((m, mc.W.size, mc.nb), dtype=np.int32) if with_counts else None
+    jitter = np.empty(m) if with_counts else None
+    check(lib().robo_igmc_eval_moments(ctx._h, m, mc.nb, mc.W.size, mc.nf, float(sn2), _arr(s), _arr(v), *mc.args(),
+                                       _arr(out), counts.ctypes.data_as(C.POINTER(C.c_int32)) if with_counts else None,
+                                       _arr(jitter) if with_counts else None))
+    return (out, counts, jitter) if with_counts else out
 
 
 def cross_cov(gp, cand, ref):

@@ -42,6 +42,8 @@ def outcome_quantiles(Np):
 
 class InformationGain(BaseAcquisitionFunction):
 
+    sampler_steps = 50      # ensemble-sampler steps per representer draw (information_gain.py:139-142)
+
     def __init__(self, model, lower, upper, Nb=50, Np=400, sampling_acquisition=None,
                  sampling_acquisition_kw={"par": 0.0}, rng=None, ep=None, **kwargs):
         """``ep``: where update() runs the EP for p_min -- "host" (epmgp.joint_min), "device" (epmgp.joint_min_device
@@ -89,7 +91,7 @@ class InformationGain(BaseAcquisitionFunction):
         for _ in range(5):
             restarts = self.lower + (self.upper - self.lower) * self.rng.uniform(size=(self.Nb, self.D))
             sampler = EnsembleSampler(self.Nb, self.D, lnprob_batch=self._proposal_batch)
-            self.zb, self.lmb, _ = sampler.run_mcmc(restarts, 50, rstate0=self.rng)
+            self.zb, self.lmb, _ = sampler.run_mcmc(restarts, self.sampler_steps, rstate0=self.rng)
             if not np.any(np.isinf(self.lmb)):
                 break
             logger.debug("representer proposal hit -inf, resampling")

@@ -104,6 +104,7 @@ static void ctx_free(robo_ctx* c) {
     hipFree(c->d_prog);
     hipHostFree(c->h_pinned);
     ep_release(c);
+    mc_release(c);
     if (c->own_stream) hipStreamDestroy(c->stream);
     delete c;
     --g_ctx_live;
@@ -1705,6 +1706,30 @@ int32_t robo_ig_eval_moments(robo_ctx* ctx, int64_t m, int32_t nb, int32_t npts,
     }
     robo_cand_destroy(k);
     return st;
+}
+
+int32_t robo_igmc_eval_cand(robo_gp* g, robo_cand* k, robo_cand* rep, int32_t n_outcomes, int32_t nf, double sn2,
+                            const double* Mb, const double* Vb, const double* logP, const double* lmb, const double* W,
+                            const double* z, double* out_dh, double* out_max, int64_t* out_argmax, uint32_t* out_flags) {
+    if (!g || !k || !rep) return ROBO_BAD_ARGUMENT;
+    if (rep->m < 1 || rep->m > 64) {
+        set_error("Monte-Carlo information gain: %lld representer points, must be in [1, 64]", (long long)rep->m);
+        return ROBO_BAD_ARGUMENT;
+    }
+    const int nb = (int)rep->m;
+    // the representer points' solve is kept across calls, as in ig_core
+    if (!(rep->solved_gen != 0 && rep->solved_gp == g && rep->solved_gen == g->fit_gen)) {
+        ROBO_TRY(predict_core(g, rep, true, nullptr, true));
+        rep->solved_gp = g;
+        rep->solved_gen = g->fit_gen;
+    }
+    ROBO_TRY(cand_ensure_workspace(k, g->n_pad, false));
+    ROBO_TRY(ig_ensure(k, 16));
+    ROBO_TRY(predict_core(g, k, false, [&](int64_t c0, int64_t cn) { return launch_cross_cov(g, k, rep, c0, cn, k->d_S); }));
+    ROBO_TRY(clear_flags_on_error(k, mc_eval_gains(g->ctx, k->m, nb, n_outcomes, nf, sn2, k->d_S, NB, k->d_var, Mb, Vb,
+                                                   logP, lmb, W, z, k->d_acq_sum, nullptr, nullptr, k->d_flags)));
+    ROBO_TRY(clear_flags_on_error(k, launch_argmax(k, k->d_acq_sum, 1.0)));
+    return clear_flags_on_error(k, acq_read_back(k, k->d_acq, out_dh, out_max, out_argmax, out_flags));
 }
 
 // ---------------------------------------------------------------------------------------

@@ -173,6 +173,8 @@ struct robo_ctx;
 namespace robo {
 struct EpWork;                          // ep.hip: grow-once buffers of robo_ep_joint_min
 void ep_release(robo_ctx* ctx);         // ... freed with the context
+struct McWork;                          // igmc.hip: grow-once buffers and uploaded draws of the Monte-Carlo p_min
+void mc_release(robo_ctx* ctx);         // ... freed with the context
 int ctx_aux_streams(robo_ctx* ctx);   // api.hip: create ctx->aux / ev_fork / ev_join once
 void ctx_retain(robo_ctx* ctx);        // a handle was created on ctx
 void ctx_release(robo_ctx* ctx);       // ... destroyed: frees a closing context with its last handle
@@ -204,6 +206,7 @@ struct robo_ctx {
     unsigned* d_prog;    // [2][PROG_STRIDE] progress words of the follower hand-off (potrf.hip), zeroed per factorisation
     double* h_pinned;    // small pinned staging (64 doubles)
     robo::EpWork* ep;    // robo_ep_joint_min's buffers (ep.hip), allocated on first use, grown, never shrunk
+    robo::McWork* mc;    // the Monte-Carlo p_min's buffers (igmc.hip), likewise
 };
 
 namespace robo {
@@ -390,6 +393,11 @@ int launch_cross_cov(robo_gp* gp, robo_cand* cand, robo_cand* rep, int64_t c0, i
 int launch_ig_dh(robo_ctx* ctx, const double* d_S, const double* d_var, double* d_F, double* d_Q, const double* d_G,
                  const double* d_consts, int64_t c0, int64_t cn, int64_t m, int nb, int npts, int kf, double sn2,
                  double H, double* d_out);
+// igmc.hip: Monte-Carlo information gain of m candidates whose cross-covariances s (m, lds) and variances v (m) are on
+// the device, into d_gain (asynchronous); d_counts / d_jit nullable; d_flags nullable (ROBO_FLAG_NOT_FACTORED)
+int mc_eval_gains(robo_ctx* c, int64_t m, int nb, int np, int nf, double sn2, const double* d_s, int lds,
+                  const double* d_v, const double* Mb, const double* Vb, const double* logP, const double* lmb,
+                  const double* W, const double* z, double* d_gain, int* d_counts, double* d_jit, unsigned* d_flags);
 int launch_random_candidates(robo_ctx* ctx, double* d_out, int64_t m_pad, int dim, uint64_t seed, int64_t n_uniform,
                              const double* d_loc, const double* d_scale);
 int launch_uniform(robo_ctx* ctx, double* d_out, int64_t m, int64_t m_pad, int dim, uint64_t seed);

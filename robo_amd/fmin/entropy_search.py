@@ -1,9 +1,10 @@
 """``entropy_search`` front end with the signature of robo/fmin/entropy_search.py:20-131:
 GP / GP-MCMC model + InformationGain (representer proposal: EI) + RandomSampling, run by the
-BO loop.  The information gain of the whole candidate batch is one device call."""
+BO loop.  The information gain of the whole candidate batch is one device call.  ``pmin="mc"`` swaps in
+InformationGainMC (Monte-Carlo p_min) for the EP estimator."""
 import numpy as np
 
-from robo_amd.acquisition_functions import EI, InformationGain, MarginalizationGPMCMC
+from robo_amd.acquisition_functions import EI, InformationGain, InformationGainMC, MarginalizationGPMCMC
 from robo_amd.initial_design import init_latin_hypercube_sampling
 from robo_amd.kernels import Matern52Kernel
 from robo_amd.maximizers import DifferentialEvolution, RandomSampling, SciPyOptimizer
@@ -13,8 +14,15 @@ from robo_amd.solver import BayesianOptimization
 
 
 def build_entropy_search(lower, upper, maximizer="random", model="gp_mcmc", rng=None, n_candidates=500,
-                         chain_length=200, burnin_steps=100, n_representer=50, n_outcomes=400, devices=None, ep=None):
+                         chain_length=200, burnin_steps=100, n_representer=50, n_outcomes=400, devices=None, ep=None,
+                         pmin="ep", n_func_samples=500):
     """the objects robo/fmin/entropy_search.py:69-121 wires together -> (model, acquisition function, maximiser)"""
+    if pmin not in ("ep", "mc"):
+        raise ValueError("pmin must be 'ep' or 'mc', not %r" % (pmin,))
+    if pmin == "mc" and ep is not None:
+        raise ValueError("ep=%r selects where the EP for p_min runs; pmin='mc' has no EP" % (ep,))
+    if pmin == "mc" and devices:
+        raise ValueError("pmin='mc' runs on one device, not on %r" % (devices,))
     n_dims = lower.shape[0]
     kernel = 2 * Matern52Kernel(np.ones([n_dims]), ndim=n_dims)
     prior = DefaultPrior(len(kernel) + 1)
@@ -30,8 +38,12 @@ def build_entropy_search(lower, upper, maximizer="random", model="gp_mcmc", rng=
                                  lower=lower, upper=upper, devices=devices)
     else:
         raise ValueError("%s is not a valid model!" % model)
-    a = InformationGain(gp, lower=lower, upper=upper, sampling_acquisition=EI, Nb=n_representer, Np=n_outcomes, rng=rng,
-                        ep=ep)
+    if pmin == "mc":
+        a = InformationGainMC(gp, lower=lower, upper=upper, Nb=n_representer, Np=n_outcomes, Nf=n_func_samples,
+                              sampling_acquisition=EI, rng=rng)
+    else:
+        a = InformationGain(gp, lower=lower, upper=upper, sampling_acquisition=EI, Nb=n_representer, Np=n_outcomes,
+                            rng=rng, ep=ep)
     acquisition_func = MarginalizationGPMCMC(a) if model == "gp_mcmc" else a
     if maximizer == "random":
         max_func = RandomSampling(acquisition_func, lower, upper, n_samples=n_candidates, rng=rng)
@@ -48,11 +60,13 @@ def build_entropy_search(lower, upper, maximizer="random", model="gp_mcmc", rng=
 def entropy_search(objective_function, lower, upper, num_iterations=30, maximizer="random", model="gp_mcmc",
                    X_init=None, Y_init=None, n_init=3, output_path=None, rng=None, n_candidates=500,
                    chain_length=200, burnin_steps=100, n_representer=50, n_outcomes=400, n_gpus=None, devices=None,
-                   ep=None):
+                   ep=None, pmin="ep", n_func_samples=500):
     """``n_gpus`` / ``devices``: single-process multi-GPU (see robo_amd.fmin.bayesian_optimization): ``model="gp"`` splits the
     candidate batch of the information gain over replicas of the model, ``"gp_mcmc"`` splits the hyper-parameter samples --
     each sample's estimator (representer points, EP, gains) works on its sample's device, all devices at once.
-    ``ep``: where each estimator's EP for p_min runs, "host" or "device" (InformationGain; None = epmgp.default_backend)."""
+    ``ep``: where each estimator's EP for p_min runs, "host" or "device" (InformationGain; None = epmgp.default_backend).
+    ``pmin``: how p_min is estimated, "ep" (InformationGain) or "mc" (InformationGainMC with ``n_func_samples`` draws,
+    one device, ``ep`` unset)."""
     assert upper.shape[0] == lower.shape[0], "Dimension miss match"
     assert np.all(lower < upper), "Lower bound >= upper bound"
     assert n_init <= num_iterations, "Number of initial design point has to be <= than the number of iterations"
@@ -61,7 +75,8 @@ def entropy_search(objective_function, lower, upper, num_iterations=30, maximize
     from robo_amd import _lib
     gp, acquisition_func, max_func = build_entropy_search(lower, upper, maximizer, model, rng, n_candidates,
                                                           chain_length, burnin_steps, n_representer, n_outcomes,
-                                                          devices=_lib.resolve_devices(devices, n_gpus), ep=ep)
+                                                          devices=_lib.resolve_devices(devices, n_gpus), ep=ep,
+                                                          pmin=pmin, n_func_samples=n_func_samples)
     bo = BayesianOptimization(objective_function, lower, upper, acquisition_func, gp, max_func,
                               initial_design=init_latin_hypercube_sampling, initial_points=n_init, rng=rng,
                               output_path=output_path)

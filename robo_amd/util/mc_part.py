@@ -36,3 +36,20 @@ def joint_pmin(m, V, Nf):
     draws = (m[:, None, :] + chol.dot(z.T)[:, :, None]).reshape(n, -1)          # one column per joint sample
     wins = np.bincount(np.argmin(draws, axis=0), minlength=n).astype(np.float64)
     return np.maximum(wins / draws.shape[1], 1e-70)
+
+
+def joint_pmin_device(m, V, Nf=None, z=None, ctx=None):
+    """joint_pmin on the device (robo_pmin_mc): the same ladder, argmin rule and floor.  ``z`` (Nf, N): the standard
+    normals to use; if None, Nf of them are drawn from the global NumPy stream exactly as joint_pmin draws them.
+    ``ctx``: a robo_amd._lib.Context (the default context if None).  -> p_min (N,)"""
+    from robo_amd import _lib
+    m = np.asarray(m, dtype=np.float64).reshape(-1)
+    n = m.shape[0]
+    if z is None:
+        if Nf is None:
+            raise ValueError("joint_pmin_device needs Nf or z")
+        z = np.random.multivariate_normal(mean=np.zeros(n), cov=np.eye(n), size=Nf)
+    pmin, jitter = _lib.pmin_mc(ctx or _lib.default_context(), m[None, :], np.asarray(V, dtype=np.float64)[None], z)
+    if jitter[0] > 0:
+        logger.error("Add %f noise on the diagonal." % jitter[0])
+    return pmin[0]
