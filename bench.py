@@ -16,6 +16,12 @@ against its own replica of the fitted GP); the only exchange is the all-gather o
 (max, index) pair per rank over RCCL.  GP-fit ms (gram + Cholesky + log-likelihood) is
 reported next to it.  Prints ONE JSON line on rank 0.
 
+A plain run does what the headline figure needs and no more: set-up (incl. the fits behind ``gp_fit_ms``), ``--warmup``
+untimed steps, ``--steps`` timed steps, ``--dump-outputs`` if asked, the line.  ``--full`` adds everything else the
+benchmark measures: the fit's phases, batched fit and gradient, the PCIe-inclusive rate, small batches, the roofline
+block's micro-benchmarks and shader clock, a multi-rank run's other scaling, ``cpu_baseline``, the BO-iteration and
+hyper-parameter-inference blocks and, on the default headline, BASELINE's configurations 2-5 as ``configs``.
+
 ``--config`` selects one of BASELINE.json's other configurations (same JSON shape, their own workload and
 roofline; the default, and what the driver runs, is the headline):
     c2   GP Matern-5/2 N=1024 D=8, 65 536 candidates, EI                          (candidate shard)
@@ -722,12 +728,14 @@ def roofline_trsm(ctx, N, M_rows, trsm_ms_per_step, passes=1, kernel="trsm_step_
             "avg_launch_ms": avg_launch_ms}
 
 
-def clock_during_step(D_, ctx, step, ms_per_step):
+def clock_during_step(D_, ctx, step, ms_per_step, full):
     """shader clock while one more `step` runs (include/robo_hip_diag.h: sampler waves on a second stream) -> the block
     for `roofline.shader_clock_under_kernel`.  EVERY rank calls it (a step of a sharded run contains a collective); the
     peak at that clock is attached on rank 0 by with_clock().  Information only, and only in single-process runs: on the
     HIP runtime a torch.distributed process brings along the sampler's stream did not run beside the
-    library's (r03zo: it reported the idle clock), so process-group runs skip it."""
+    library's (r03zo: it reported the idle clock), so process-group runs skip it.  A plain run (no --full) skips it too."""
+    if not full:
+        return {"skipped": "plain run; --full samples it"}
     if D_.mode == "torch":
         return {"skipped": "process-group run; see the single-process line"}
     err = None
@@ -880,13 +888,13 @@ def run_headline(args, D_, _lib, sharding):
         if rank == 0:
             dump_outputs(args.dump_outputs, [("acq_max", [best[0]]), ("acq_argmax", [best[1]]),
                                              ("acq_values_rank0", vals)])
-    clock = clock_during_step(D_, ctx, step, elapsed / args.steps * 1e3)  # every rank: the step holds a collective
+    clock = clock_during_step(D_, ctx, step, elapsed / args.steps * 1e3, args.full)  # every rank: the step holds a collective
 
-    # the OTHER scaling of the same job, in the same run (multi-rank runs only; every rank takes part): the driver's
-    # `--gpus N` line then carries both the weak figure (--m candidates per GPU) and SURVEY 8(d)'s strong headline
+    # the OTHER scaling of the same job, in the same run (multi-rank --full runs only; every rank takes part): the
+    # `--gpus N --full` line then carries both the weak figure (--m candidates per GPU) and SURVEY 8(d)'s strong headline
     # (--m candidates in total, split N ways)
     other = None
-    if world > 1:
+    if world > 1 and args.full:
         o_scaling = "weak" if args.scaling == "strong" else "strong"
         Xo, Mo, off_o, Mo_total = synthetic_candidates(args, D_, sharding, o_scaling)
         cand_o = _lib.Candidates(ctx, Xo)
@@ -1089,7 +1097,7 @@ def run_c3(args, D_, _lib, sharding):
         return float(mx), int(am)
 
     elapsed, best, trsm_ms = timed_steps(D_, ctx, step, args.steps, args.warmup)
-    clock = clock_during_step(D_, ctx, step, elapsed / args.steps * 1e3)  # every rank: the step holds a collective
+    clock = clock_during_step(D_, ctx, step, elapsed / args.steps * 1e3, args.full)  # every rank: the step holds a collective
     if rank != 0:
         return None
     ms = elapsed / args.steps * 1e3
@@ -1180,7 +1188,7 @@ def run_c4(args, D_, _lib, sharding):
         return float(mx), int(am)
 
     elapsed, best, trsm_ms = timed_steps(D_, ctx, step, args.steps, args.warmup)
-    clock = clock_during_step(D_, ctx, step, elapsed / args.steps * 1e3)  # every rank: the step holds a collective
+    clock = clock_during_step(D_, ctx, step, elapsed / args.steps * 1e3, args.full)  # every rank: the step holds a collective
     if rank != 0:
         return None
     ms = elapsed / args.steps * 1e3
@@ -1249,7 +1257,7 @@ def run_c5(args, D_, _lib, sharding):
         return mx, am
 
     elapsed, best, trsm_ms = timed_steps(D_, ctx, step, args.steps, args.warmup)
-    clock = clock_during_step(D_, ctx, step, elapsed / args.steps * 1e3)  # every rank: the step holds a collective
+    clock = clock_during_step(D_, ctx, step, elapsed / args.steps * 1e3, args.full)  # every rank: the step holds a collective
     if rank != 0:
         return None
     ms = elapsed / args.steps * 1e3
@@ -1344,7 +1352,7 @@ def run_inproc(args, _lib):
             return _lib.CandidateShards(parts, offs), total
 
         results = {}
-        for scaling in ([args.scaling] + (["weak" if args.scaling == "strong" else "strong"] if G > 1 else [])):
+        for scaling in ([args.scaling] + (["weak" if args.scaling == "strong" else "strong"] if G > 1 and args.full else [])):
             shards, total = shards_for(scaling)
             for c in ctxs:
                 c.set_phase_events(total // G <= 16384)
@@ -1485,7 +1493,10 @@ def main():
     ap.add_argument("--d", type=int, default=None)
     ap.add_argument("--m", type=int, default=None, help="candidates per GPU (config 3: candidates in total)")
     ap.add_argument("--acq", default="ei")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything the benchmark measures besides the headline figure (see the module docstring); a "
+                         "plain run sets up, warms up, times --steps steps, writes --dump-outputs and prints its line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no cpu_baseline")
     ap.add_argument("--lib", default=None, help="alternative build of librobo_hip.so (A/B runs of kernel variants)")
     ap.add_argument("--scaling", default=None, choices=["weak", "strong"],
                     help="weak (default): --m candidates per GPU; strong: --m candidates in TOTAL, split over the ranks "
@@ -1496,12 +1507,17 @@ def main():
     ap.add_argument("--devices", default=None, help="inproc: comma-separated HIP device ids (default 0..gpus-1; a device "
                                                     "may repeat: several contexts on it)")
     ap.add_argument("--lean", action="store_true",
-                    help="the timed region and the fit only: no side measurements (phases, micro-benchmarks, small batches)")
+                    help="with --full: no side measurements (phases, micro-benchmarks, small batches, BO iteration, "
+                         "hyper-parameter inference, configs)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="headline / c2: after the timed steps write what the last one returned (acq_max, acq_argmax) and "
                          "the per-candidate values of rank 0's candidates (acq_values_rank0) as DIR/<name>.npy, float64, "
                          "at most 64 MB in all; the inputs are seeded, so equal arguments give equal inputs")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run leaves out what --lean and --no-cpu-baseline leave out; the rest of what --full adds (the roofline
+        # block's clock sample, a multi-rank run's other scaling, the diagnostics library) checks args.full itself
+        args.lean = args.no_cpu_baseline = True
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
     if args.steps is not None and args.steps < 1:
@@ -1546,17 +1562,18 @@ def main():
     from robo_amd import _lib, sharding
     if args.lib:
         _lib.use_library(os.path.abspath(args.lib))
-    try:
-        # the diagnostics library (micro-benchmarks of the roofline block) is loaded BEFORE the first kernel launch:
-        # under rocprofv3 a code object that appears after thousands of dispatches crashed the profiler's launch
-        # interception (r02v: SIGSEGV at the first mfma_bench_kernel launch)
-        _lib.diag()
-    except Exception:
-        pass
+    if args.full:
+        # the diagnostics library (micro-benchmarks and clock sampler of the roofline block) is loaded BEFORE the first
+        # kernel launch: under rocprofv3 a code object that appears after thousands of dispatches crashed the profiler's
+        # launch interception (r02v: SIGSEGV at the first mfma_bench_kernel launch)
+        try:
+            _lib.diag()
+        except Exception:
+            pass
     runners = {"headline": run_headline, "c2": run_headline, "c3": run_c3, "c4": run_c4, "c5": run_c5}
     if args.config == "all":
-        # every configuration of BASELINE.json that fits one GPU, each its own complete line (own cpu_baseline unless
-        # --no-cpu-baseline), printed as ONE JSON array: `python bench.py --gpus 1 --config all`
+        # every configuration of BASELINE.json that fits one GPU, each its own complete line (with --full its own
+        # cpu_baseline unless --no-cpu-baseline), printed as ONE JSON array: `python bench.py --gpus 1 --config all`
         lines = []
         for cfg in ("headline", "c2", "c3", "c4", "c5"):
             o = runners[cfg](config_args(args, cfg), D_, _lib, sharding)
@@ -1571,9 +1588,9 @@ def main():
     out = runners[args.config](args, D_, _lib, sharding)
     if D_.rank == 0 and D_.world == 1 and args.config == "headline" and (args.n, args.d) == (4096, 16) and not args.lean \
             and os.environ.get("ROBO_BENCH_NO_CONFIGS") != "1":
-        # the DEFAULT run (what the round's driver times) also carries BASELINE's configurations 2-5 at their one-GPU
-        # sizes, each measured by its own runner in this process (sustained step counts as in `--config cN`; no CPU legs
-        # here -- `--config cN` / `--config all` print the full lines with their cpu_baseline blocks)
+        # a --full run of the default headline also carries BASELINE's configurations 2-5 at their one-GPU sizes, each
+        # measured by its own runner in this process (sustained step counts as in `--config cN`; no CPU legs here --
+        # `--config cN --full` / `--config all --full` print the full lines with their cpu_baseline blocks)
         out["configs"] = {}
         for cfg in ("c2", "c3", "c4", "c5"):
             try:

@@ -59,21 +59,25 @@ def test_dump_outputs(single, tmp_path):
 @pytest.mark.parametrize("world", [2, 3])
 def test_self_launch_strong(single, world):
     """SURVEY 8(d)'s strong-scaled headline: the SAME 601 candidates split over the ranks -> the single-rank argmax"""
-    out = _line(_run(["--gpus", str(world), "--scaling", "strong"]))
+    out = _line(_run(["--gpus", str(world), "--scaling", "strong", "--full"]))
     assert out["n_gpus"] == world and out["ranks"] == list(range(world)) and out["devices"] == list(range(world))
     assert out["comm_world"] == world and out["launcher"] == "spawn" and "librobo_hip" in out["exchange"]
     assert out["scaling"] == "strong" and out["config"]["candidates_total"] == 601
     assert out["config"]["candidates_per_gpu"] == -(-601 // world)          # rank 0 holds the larger shard
     assert out["argmax"] == single["argmax"]                                 # value AND global index, bit for bit
-    # the other scaling of the same job rides along: weak = 601 candidates on every rank
+    # with --full the other scaling of the same job rides along: weak = 601 candidates on every rank
     assert out["other_scaling"]["scaling"] == "weak" and out["other_scaling"]["candidates_total"] == 601 * world
 
 
 def test_self_launch_weak():
-    out = _line(_run(["--gpus", "2"]))
+    out = _line(_run(["--gpus", "2", "--full"]))
     assert out["n_gpus"] == 2 and out["scaling"] == "weak" and out["ranks"] == [0, 1]
     assert out["config"]["candidates_total"] == 1202
     assert out["other_scaling"]["scaling"] == "strong" and out["other_scaling"]["candidates_total"] == 601
+    # a plain run times the scaling it was asked for, and that alone
+    plain = _line(_run(["--gpus", "2"]))
+    assert "other_scaling" not in plain and plain["argmax"] == out["argmax"]
+    assert plain["roofline"]["shader_clock_under_kernel"] == {"skipped": "plain run; --full samples it"}
 
 
 def test_config4_sharded_information_gain_per_unit_cost():
@@ -112,7 +116,7 @@ def test_a_dead_rank_ends_the_job():
 def test_inproc_strong(single, world):
     """`bench.py --gpus G --launcher inproc`: the same line shape as the one-process-per-GPU forms (ranks, devices,
     launcher) and, for the strong-scaled headline, the single-device argmax -- value and global index, bit for bit"""
-    out = _line(_run(["--gpus", str(world), "--launcher", "inproc", "--scaling", "strong"],
+    out = _line(_run(["--gpus", str(world), "--launcher", "inproc", "--scaling", "strong", "--full"],
                      env_extra={"HIPEMU_DEVICES": str(world)}))
     assert out["n_gpus"] == world and out["ranks"] == list(range(world)) and out["devices"] == list(range(world))
     assert out["launcher"] == "inproc" and out["comm_world"] == world and out["worker_threads"] == world
@@ -128,7 +132,8 @@ def test_inproc_strong(single, world):
 def test_inproc_eight_devices_dry_run(single):
     """the round-end scaling run's shape, `bench.py --gpus 8 --launcher inproc --scaling strong`, on eight emulated
     devices: one line, eight shards, and the strong-scaled argmax IS the one-device argmax (value and global index)"""
-    out = _line(_run(["--gpus", "8", "--launcher", "inproc", "--scaling", "strong"], env_extra={"HIPEMU_DEVICES": "8"}))
+    out = _line(_run(["--gpus", "8", "--launcher", "inproc", "--scaling", "strong", "--full"],
+                     env_extra={"HIPEMU_DEVICES": "8"}))
     assert out["n_gpus"] == 8 and out["devices"] == list(range(8)) and out["worker_threads"] == 8
     assert out["config"]["candidates_total"] == 601 and out["config"]["candidates_per_gpu"] == 76
     assert out["argmax"] == single["argmax"]

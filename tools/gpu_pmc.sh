@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 cd "$(dirname "$0")/.."
 for C in FETCH_SIZE WRITE_SIZE "SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE" "SQ_BUSY_CYCLES SQ_WAVES"; do
   name=$(echo $C | tr ' ' '_')
-  timeout 600 rocprofv3 --kernel-trace --pmc $C -d $OUT/$name -o pmc -- python bench.py --gpus 1 --steps 1 --warmup 0 --no-cpu-baseline > $OUT/$name.json 2> $OUT/$name.err
+  timeout 600 rocprofv3 --kernel-trace --pmc $C -d $OUT/$name -o pmc -- python bench.py --gpus 1 --full --steps 1 --warmup 0 --no-cpu-baseline > $OUT/$name.json 2> $OUT/$name.err
   echo "$C rc=$?" >> $OUT/summary.txt
 done
 python tools/rocpd_pmc.py $OUT > $OUT/pmc_summary.txt 2>&1

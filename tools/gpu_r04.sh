@@ -11,7 +11,7 @@ tests)
 smoke)
   timeout 300 python __graft_entry__.py smoke > $OUT/smoke.txt 2>&1; echo "smoke rc=$?" >> $OUT/summary.txt ;;
 bench)
-  timeout 600 python bench.py --gpus 1 > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?" >> $OUT/summary.txt
+  timeout 600 python bench.py --gpus 1 --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?" >> $OUT/summary.txt
   python - <<PY >> $OUT/summary.txt 2>&1
 import json; d=json.load(open('$OUT/bench.json'))
 print('value', d['value'], 'ms', d['ms_per_step'], 'frac', d['roofline']['frac'], 'fit', d['gp_fit_ms'], d.get('gp_fit_data_resident_ms'), d['gp_fit_phases_ms'], 'k1', d['k_assembly'], 'small', d['small_batch_latency_ms'], 'batched', d['gp_fit_batched'])
@@ -22,30 +22,30 @@ configs)
   # c2 / c4 steps last 1.4 / 5.4 ms: the default 5 timed steps (7 / 27 ms behind 2 warm-up steps) end before the part has
   # left its idle power state (c2: 0.59 of peak over 5 steps, 0.65 over 20, 0.69 over 100) -- sustained runs for those two
   for c in "c2 --steps 100 --warmup 5" "c3" "c4 --steps 50 --warmup 5" "c5"; do
-    timeout 900 python bench.py --gpus 1 --config $c >> $OUT/configs.jsonl 2>> $OUT/configs.err; echo "$c rc=$?" >> $OUT/summary.txt
+    timeout 900 python bench.py --gpus 1 --full --config $c >> $OUT/configs.jsonl 2>> $OUT/configs.err; echo "$c rc=$?" >> $OUT/summary.txt
   done
-  timeout 300 python bench.py --gpus 1 --config c2 --no-cpu-baseline > $OUT/c2_default_5_steps.json 2>> $OUT/configs.err
-  timeout 900 python bench.py --gpus 1 --config c5 --m 1048576 --steps 2 --warmup 1 --no-cpu-baseline >> $OUT/configs.jsonl 2>> $OUT/configs.err; echo "c5 full rc=$?" >> $OUT/summary.txt
+  timeout 300 python bench.py --gpus 1 --full --config c2 --no-cpu-baseline > $OUT/c2_default_5_steps.json 2>> $OUT/configs.err
+  timeout 900 python bench.py --gpus 1 --full --config c5 --m 1048576 --steps 2 --warmup 1 --no-cpu-baseline >> $OUT/configs.jsonl 2>> $OUT/configs.err; echo "c5 full rc=$?" >> $OUT/summary.txt
   cut -c1-300 $OUT/configs.jsonl >> $OUT/summary.txt ;;
 dist)
   # the RCCL path on ONE rank, both scalings (torchrun-style process group) + the self-launcher's one-rank form (no torch)
   for sc in weak strong; do
-    ROBO_BENCH_FORCE_DIST=1 timeout 600 python bench.py --gpus 1 --scaling $sc --no-cpu-baseline --lean > $OUT/forcedist_$sc.json 2> $OUT/forcedist_$sc.err; echo "forcedist $sc rc=$?" >> $OUT/summary.txt
+    ROBO_BENCH_FORCE_DIST=1 timeout 600 python bench.py --gpus 1 --full --scaling $sc --no-cpu-baseline --lean > $OUT/forcedist_$sc.json 2> $OUT/forcedist_$sc.err; echo "forcedist $sc rc=$?" >> $OUT/summary.txt
   done
-  RDV=$(mktemp -d); RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 ROBO_BENCH_RENDEZVOUS=$RDV timeout 600 python bench.py --gpus 1 --scaling strong --no-cpu-baseline --lean > $OUT/spawn1_strong.json 2> $OUT/spawn1.err; echo "spawn1 rc=$?" >> $OUT/summary.txt
-  ROBO_BENCH_FORCE_DIST=1 timeout 600 python bench.py --gpus 1 --config c3 --no-cpu-baseline > $OUT/forcedist_c3.json 2>> $OUT/forcedist.err; echo "forcedist c3 rc=$?" >> $OUT/summary.txt
+  RDV=$(mktemp -d); RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 ROBO_BENCH_RENDEZVOUS=$RDV timeout 600 python bench.py --gpus 1 --full --scaling strong --no-cpu-baseline --lean > $OUT/spawn1_strong.json 2> $OUT/spawn1.err; echo "spawn1 rc=$?" >> $OUT/summary.txt
+  ROBO_BENCH_FORCE_DIST=1 timeout 600 python bench.py --gpus 1 --full --config c3 --no-cpu-baseline > $OUT/forcedist_c3.json 2>> $OUT/forcedist.err; echo "forcedist c3 rc=$?" >> $OUT/summary.txt
   # what --gpus 2 does on a one-GPU box: both ranks fail or run on device 0/1 -- must end non-zero, not hang
-  timeout 300 python bench.py --gpus 2 --lean --no-cpu-baseline > $OUT/gpus2_on_one_gpu.json 2> $OUT/gpus2_on_one_gpu.err; echo "gpus2-on-1-gpu rc=$? (expected non-zero)" >> $OUT/summary.txt
+  timeout 300 python bench.py --gpus 2 --full --lean --no-cpu-baseline > $OUT/gpus2_on_one_gpu.json 2> $OUT/gpus2_on_one_gpu.err; echo "gpus2-on-1-gpu rc=$? (expected non-zero)" >> $OUT/summary.txt
   cut -c1-260 $OUT/forcedist_weak.json $OUT/forcedist_strong.json $OUT/spawn1_strong.json $OUT/forcedist_c3.json >> $OUT/summary.txt; tail -3 $OUT/forcedist_strong.err >> $OUT/summary.txt ;;
 prof)
-  timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/prof -o bench -- python bench.py --gpus 1 --no-cpu-baseline > $OUT/prof_bench.json 2> $OUT/prof.err; echo "rocprof rc=$?" >> $OUT/summary.txt
+  timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/prof -o bench -- python bench.py --gpus 1 --full --no-cpu-baseline > $OUT/prof_bench.json 2> $OUT/prof.err; echo "rocprof rc=$?" >> $OUT/summary.txt
   python tools/rocpd_stats.py $OUT/prof/bench_results.db > $OUT/bench_kernel_stats.csv 2>> $OUT/prof.err
   find $OUT/prof -size +20M -delete
   head -16 $OUT/bench_kernel_stats.csv >> $OUT/summary.txt ;;
 pmc)
   for C in FETCH_SIZE WRITE_SIZE "SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE"; do
     name=$(echo $C | tr ' ' '_')
-    timeout 600 rocprofv3 --kernel-trace --pmc $C -d $OUT/pmc/$name -o pmc -- python bench.py --gpus 1 --steps 1 --warmup 0 --no-cpu-baseline > $OUT/pmc_$name.json 2> $OUT/pmc_$name.err
+    timeout 600 rocprofv3 --kernel-trace --pmc $C -d $OUT/pmc/$name -o pmc -- python bench.py --gpus 1 --full --steps 1 --warmup 0 --no-cpu-baseline > $OUT/pmc_$name.json 2> $OUT/pmc_$name.err
     echo "pmc $C rc=$?" >> $OUT/summary.txt
   done
   python tools/rocpd_pmc.py $OUT/pmc > $OUT/pmc_summary.txt 2>&1
@@ -56,7 +56,7 @@ pmcconf)
   for cfg in "c2 trsm_step_gen_kernel 1024 8 65536" "c3 trsm_step_gen_kernel 2048 16 65536" "c4 winv_row_kernel 4096 11 8192" "c5 trsm_step_kernel 8192 64 131072"; do
     set -- $cfg
     for C in FETCH_SIZE WRITE_SIZE; do
-      timeout 600 rocprofv3 --kernel-trace --pmc $C -d $OUT/pmc_$1/$C -o pmc -- python bench.py --gpus 1 --config $1 --steps 1 --warmup 0 --no-cpu-baseline > /dev/null 2> $OUT/pmc_$1_$C.err
+      timeout 600 rocprofv3 --kernel-trace --pmc $C -d $OUT/pmc_$1/$C -o pmc -- python bench.py --gpus 1 --full --config $1 --steps 1 --warmup 0 --no-cpu-baseline > /dev/null 2> $OUT/pmc_$1_$C.err
       echo "pmc $1 $C rc=$?" >> $OUT/summary.txt
     done
     python tools/rocpd_pmc.py $OUT/pmc_$1 > $OUT/pmc_summary_$1.txt 2>&1
@@ -70,7 +70,7 @@ fit)
   cat $OUT/diag_timeline.txt >> $OUT/summary.txt; tail -3 $OUT/trace_4096.txt >> $OUT/summary.txt 2>/dev/null ;;
 sustained)
   # the headline under steady power: 200 timed steps, the shader clock sampled during one more step at the end
-  timeout 600 python bench.py --gpus 1 --steps 200 --warmup 5 --lean --no-cpu-baseline > $OUT/bench_sustained.json 2> $OUT/bench_sustained.err; echo "sustained rc=$?" >> $OUT/summary.txt
+  timeout 600 python bench.py --gpus 1 --full --steps 200 --warmup 5 --lean --no-cpu-baseline > $OUT/bench_sustained.json 2> $OUT/bench_sustained.err; echo "sustained rc=$?" >> $OUT/summary.txt
   python - <<PY >> $OUT/summary.txt 2>&1
 import json; d=json.load(open('$OUT/bench_sustained.json'))
 print('sustained: value', d['value'], 'ms/step', d['ms_per_step'], 'frac', d['roofline']['frac'], 'clock', d['roofline'].get('shader_clock_under_kernel'))

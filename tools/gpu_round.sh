@@ -16,12 +16,12 @@ timeout 1500 python -m pytest tests -m gpu -q -rA -s --durations=20 > $OUT/pytes
 echo "pytest rc=$?" | tee -a $OUT/summary.txt
 tail -40 $OUT/pytest_gpu.log >> $OUT/summary.txt
 echo "== bench" | tee -a $OUT/summary.txt
-timeout 900 python bench.py --gpus 1 --steps 5 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err
+timeout 900 python bench.py --gpus 1 --full --steps 5 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err
 echo "bench rc=$?" | tee -a $OUT/summary.txt
 cat $OUT/bench.json >> $OUT/summary.txt
 tail -5 $OUT/bench.err >> $OUT/summary.txt
 echo "== rocprofv3 kernel trace" | tee -a $OUT/summary.txt
-timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/prof -o bench -- python bench.py --gpus 1 --steps 5 --warmup 2 --no-cpu-baseline > $OUT/prof_bench.json 2> $OUT/prof.err
+timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/prof -o bench -- python bench.py --gpus 1 --full --steps 5 --warmup 2 --no-cpu-baseline > $OUT/prof_bench.json 2> $OUT/prof.err
 echo "rocprof rc=$?" | tee -a $OUT/summary.txt
 find $OUT/prof -name "*stats*" | head >> $OUT/summary.txt
 for f in $(find $OUT/prof -name "*kernel_stats.csv"); do head -30 $f >> $OUT/summary.txt; done
