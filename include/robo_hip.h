@@ -66,6 +66,8 @@ enum robo_acq_kind {
 #define ROBO_FLAG_NAN 4u          /* some acquisition value is NaN        */
 #define ROBO_FLAG_NOT_FACTORED 8u /* Monte-Carlo information gain: some candidate's covariance
                                      had no Cholesky factor with jitter up to 1e4              */
+#define ROBO_FLAG_FROZEN 16u      /* gradient refinement: some start stopped early (variance on its floor, value
+                                     not finite, or no ascent direction left inside the box)   */
 
 /* ---- context ---------------------------------------------------------------------- */
 int32_t robo_device_count(int32_t* out_n);
@@ -280,6 +282,34 @@ int32_t robo_acq_eval_marginal_cand(robo_gp* const* gps, int32_t S, int32_t acq_
 /* partial form for sample-sharded multi-GPU runs: returns sum_s acq_s (no division)          */
 int32_t robo_acq_eval_sum_cand(robo_gp* const* gps, int32_t S, int32_t acq_kind, double par, const double* etas,
                                robo_cand* cand, double* out_acq_sum, uint32_t* out_flags);
+
+/* ---- gradient refinement of the acquisition maximum (no counterpart in the reference, whose maximisers return a
+ * candidate or run SciPy from the host): sweep over `cand` exactly as robo_acq_eval_cand, the n_starts (K <= 1024) best
+ * candidates -- descending value, ties by ascending index, NaN never -- become the starts of K lock-step projected
+ * gradient ascents in the box [0, 1]^dim of the GP's normalised input space, all on the device:
+ *   evaluate value f and gradient g of the acquisition at the K points (D + 1 right-hand sides each: robo_gp_predict_grad's
+ *   solve, one fused epilogue); n_steps times: g_proj = g with the components pointing out of the box at an active bound
+ *   set to 0; |g_proj| = 0 -> the start is frozen; y = clip(x + alpha g_proj / |g_proj|, 0, 1); accept iff f(y) > f(x)
+ *   (then x := y, alpha := min(2 alpha, 0.5)), else alpha := alpha / 2.  alpha starts at step0.  A trial whose variance
+ *   sits on the floor or whose value is not finite freezes its start at the last accepted point (ROBO_FLAG_FROZEN).
+ * Result: the start with the largest final value (first on ties): out_x (dim), *out_value, *out_start_index (its row in
+ * `cand`; -1 when every candidate was NaN), *out_flags = the sweep's flags | ROBO_FLAG_FROZEN.  n_steps = 0 returns the
+ * sweep's own argmax, point and value.  LogEI has a gradient here: d log EI = ds / s + (Phi / h)(z) dz, h = z Phi + phi.
+ * Diagnostics (nullable): out_starts (n_starts) the rows the starts came from in selection order, -1 for unused slots
+ * (fewer eligible candidates than n_starts); out_trace ((n_steps + 1) x n_starts x (2 dim + 3)): per iteration (0 = the
+ * evaluation of the starts) and start the trial point, its value, its gradient, the step length it was made with, and
+ * 1 / 0 / 2 / 3 = accepted / rejected / start frozen earlier (no trial made: the point is the start's own) / this
+ * point has its variance on the floor or a value that is not finite (not taken; the start is frozen from here on).
+ * One synchronisation per call; state and solve workspace stay with gp (gps[0]) between calls of one (n_starts, dim).  */
+int32_t robo_acq_refine_cand(robo_gp* gp, int32_t acq_kind, double par, double eta, robo_cand* cand, int32_t n_starts,
+                             int32_t n_steps, double step0, double* out_x, double* out_value, int64_t* out_start_index,
+                             uint32_t* out_flags, int64_t* out_starts, double* out_trace);
+/* the same for the mean over S fitted GPs (robo_acq_eval_marginal_cand's sweep): per sample the points are scaled with that
+ * sample's length scales and solved against its factor; f and g are accumulated in sample order and divided by S.       */
+int32_t robo_acq_refine_marginal_cand(robo_gp* const* gps, int32_t S, int32_t acq_kind, double par, const double* etas,
+                                      robo_cand* cand, int32_t n_starts, int32_t n_steps, double step0, double* out_x,
+                                      double* out_value, int64_t* out_start_index, uint32_t* out_flags,
+                                      int64_t* out_starts, double* out_trace);
 
 /* ---- entropy search: replaces InformationGain.innovations/_dh_fun/compute ---------------
  * (robo/acquisition_functions/information_gain.py:87-125,169-203,253-272), batched over candidates.

@@ -25,7 +25,8 @@ EP_NAN_MESSAGE = ("an error occurs while running expectation propagation in entr
                   "Resulting variance contains NaN")
 KERNEL_KINDS = {"matern52": 0, "rbf": 1, "fabolas": 2}
 ACQ_KINDS = {"ei": 0, "log_ei": 1, "pi": 2, "lcb": 3}
-FLAG_ZERO_SIGMA, FLAG_NEGATIVE_EI, FLAG_NAN, FLAG_NOT_FACTORED = 1, 2, 4, 8
+FLAG_ZERO_SIGMA, FLAG_NEGATIVE_EI, FLAG_NAN, FLAG_NOT_FACTORED, FLAG_FROZEN = 1, 2, 4, 8, 16
+REFINE_MAX_STARTS = 1024                         # robo_acq_refine_*: cap on n_starts
 MC_MAX_NB, MC_MAX_NP, MC_MAX_NF = 64, 512, 65535   # limits of the Monte-Carlo p_min entry points (robo_pmin_mc, robo_igmc_*)
 
 # every symbol include/robo_hip.h declares (tests check the library exports all of them)
@@ -41,6 +42,7 @@ SYMBOLS = [
     "robo_cand_create_random", "robo_cand_create_sobol", "robo_cand_get_point", "robo_cand_workspace_chunk", "robo_cand_last_solve_kernel",
     "robo_gp_predict_cand", "robo_gp_predict", "robo_gp_predict_cov", "robo_gp_predict_grad", "robo_gp_predict_mixture_cand",
     "robo_acq_eval_cand", "robo_acq_eval", "robo_acq_eval_moments", "robo_acq_eval_marginal_cand", "robo_acq_eval_sum_cand",
+    "robo_acq_refine_cand", "robo_acq_refine_marginal_cand",
     "robo_ig_eval_cand", "robo_ig_eval_per_cost_cand", "robo_ig_eval_moments", "robo_gp_cross_cov",
     "robo_ep_joint_min", "robo_pmin_mc", "robo_igmc_eval_cand", "robo_igmc_eval_moments",
     "robo_comm_create_id", "robo_comm_init", "robo_comm_destroy", "robo_comm_info", "robo_comm_allgather",
@@ -169,6 +171,10 @@ def lib():
         "robo_acq_eval_marginal_cand": [pp, i32, i32, dbl, _dp, vp, _dp, _dp, C.POINTER(i64),
                                         C.POINTER(C.c_uint32)],
         "robo_acq_eval_sum_cand": [pp, i32, i32, dbl, _dp, vp, _dp, C.POINTER(C.c_uint32)],
+        "robo_acq_refine_cand": [vp, i32, dbl, dbl, vp, i32, i32, dbl, _dp, _dp, C.POINTER(i64), C.POINTER(C.c_uint32),
+                                 C.POINTER(i64), _dp],
+        "robo_acq_refine_marginal_cand": [pp, i32, i32, dbl, _dp, vp, i32, i32, dbl, _dp, _dp, C.POINTER(i64),
+                                          C.POINTER(C.c_uint32), C.POINTER(i64), _dp],
         "robo_ig_eval_cand": [vp, vp, vp, i32, dbl, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(i64)],
         "robo_ig_eval_per_cost_cand": [vp, vp, vp, i32, dbl, _dp, _dp, _dp, _dp, _dp, _dp, vp, vp, dbl, _dp, _dp,
                                        C.POINTER(i64)],
@@ -730,6 +736,47 @@ class DeviceGP(object):
             check(lib().robo_acq_eval(self._h, ACQ_KINDS[kind], float(par), float(eta), _arr(Xc), m,
                                       _arr(out) if want_values else None, C.byref(mx), C.byref(am), C.byref(fl)))
         return out, mx.value, am.value, fl.value
+
+
+    def refine(self, kind, par, eta, cand, n_starts=256, n_steps=50, step0=0.05, diagnostics=False):
+        """sweep over ``cand`` + multi-start projected gradient ascent on the device (robo_acq_refine_cand)
+        -> RefineResult; see :func:`acq_refine`"""
+        return acq_refine([self], kind, par, eta, cand, n_starts, n_steps, step0, diagnostics, marginal=False)
+
+
+class RefineResult(object):
+    """x (D,) in the GP's normalised input space, value, start_index (row of the candidate batch the winning start came
+    from, -1: every candidate was NaN), flags; with diagnostics: starts (K,) rows of all starts in selection order (-1 =
+    slot unused) and trace (T + 1, K, 2 D + 3) = [trial point, value, gradient, step length, 1 accepted / 0 rejected /
+    2 frozen earlier / 3 variance floored or value not finite at this point] per iteration and start (include/robo_hip.h)"""
+
+    def __init__(self, x, value, start_index, flags, starts=None, trace=None):
+        self.x, self.value, self.start_index, self.flags = x, float(value), int(start_index), int(flags)
+        self.starts, self.trace = starts, trace
+
+
+def acq_refine(gps, kind, par, eta, cand, n_starts=256, n_steps=50, step0=0.05, diagnostics=False, marginal=True):
+    """the gradient-refined maximiser of a closed-form acquisition over device GPs (one: robo_acq_refine_cand; the mean
+    over several hyper-parameter samples: robo_acq_refine_marginal_cand).  eta: one incumbent value, or one per sample."""
+    S = len(gps)
+    K, T, D = int(n_starts), int(n_steps), cand.dim
+    x = np.empty(D)
+    val, idx, fl = C.c_double(0), C.c_int64(0), C.c_uint32(0)
+    want = bool(diagnostics) and 1 <= K <= REFINE_MAX_STARTS and T >= 0
+    starts = np.empty(K, dtype=np.int64) if want else None
+    trace = np.empty((T + 1, K, 2 * D + 3)) if want else None
+    p_starts = starts.ctypes.data_as(C.POINTER(C.c_int64)) if want else None
+    p_trace = _arr(trace) if want else None
+    if marginal:
+        arr = (C.c_void_p * S)(*[g._h for g in gps])
+        etas = _f64(np.broadcast_to(np.asarray(eta, dtype=np.float64), (S,)))
+        check(lib().robo_acq_refine_marginal_cand(arr, S, ACQ_KINDS[kind], float(par), _arr(etas), cand._h, K, T,
+                                                  float(step0), _arr(x), C.byref(val), C.byref(idx), C.byref(fl),
+                                                  p_starts, p_trace))
+    else:
+        check(lib().robo_acq_refine_cand(gps[0]._h, ACQ_KINDS[kind], float(par), float(eta), cand._h, K, T, float(step0),
+                                         _arr(x), C.byref(val), C.byref(idx), C.byref(fl), p_starts, p_trace))
+    return RefineResult(x, val.value, idx.value, fl.value, starts, trace)
 
 
 class Comm(object):

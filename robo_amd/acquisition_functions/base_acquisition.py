@@ -40,6 +40,44 @@ class BaseAcquisitionFunction(object):
     def get_json_data(self):
         return {"type": __name__}
 
+    def refine(self, X, n_starts=256, n_steps=50, step0=0.05):
+        """Gradient-refined maximiser (device-resident multi-start ascent): EI / LogEI / PI / LCB over robo_amd GP models only."""
+        raise TypeError("%s has no gradient refinement on the device: refine() is available for EI, LogEI, PI and LCB "
+                        "over a robo_amd GaussianProcess (or MarginalizationGPMCMC over them)" % self.__class__.__name__)
+
+
+def refine_model_check(model, who):
+    """the model requirements of the device refinement, as TypeError / NotImplementedError with a plain message"""
+    # FabolasGP (models/fabolas_gp.py) is a GaussianProcess whose inputs go through its own normalize(): a basis function on
+    # the fidelity column, so its input space is not the box [0, 1]^D the ascent is projected onto
+    from robo_amd.models.fabolas_gp import FabolasGP
+    if not (hasattr(model, "acquisition") and hasattr(model, "gp") and hasattr(model, "_normalised")) \
+            or isinstance(model, FabolasGP):
+        raise TypeError("%s.refine needs a robo_amd GaussianProcess model (got %s)" % (who, type(model).__name__))
+    if not getattr(model, "normalize_input", False):
+        raise TypeError("%s.refine works in the box [0, 1]^D of the normalised inputs: the model needs "
+                        "normalize_input=True" % who)
+    if getattr(model, "devices", None):
+        raise NotImplementedError("%s.refine runs on one device; multi-device sharding of the refinement is not "
+                                  "implemented" % who)
+    if not model.is_trained:
+        raise Exception('Model has to be trained first!')
+
+
+def refine_finish(acq, kind, model, res, cand):
+    """shared tail of the refine() methods: the reference's EI guards on the sweep's flags, the point in the caller's
+    input space"""
+    acq.last_refine = res
+    acq.last_max, acq.last_argmax = res.value, res.start_index
+    x = res.x
+    if kind == "ei":
+        if res.flags & _lib.FLAG_ZERO_SIGMA:          # ei.py:72-74: the batch collapses to [[0]], argmax 0
+            x = cand.point(0)
+        elif res.flags & _lib.FLAG_NEGATIVE_EI:
+            raise ValueError
+    lower, upper = np.asarray(model.lower, dtype=np.float64), np.asarray(model.upper, dtype=np.float64)
+    return lower + (upper - lower) * x
+
 
 class ClosedFormAcquisition(BaseAcquisitionFunction):
     """EI / LogEI / PI / LCB on (mean, var, eta); subclasses set ``kind`` and the guards."""
@@ -91,6 +129,22 @@ class ClosedFormAcquisition(BaseAcquisitionFunction):
                     raise ValueError
             return int(am)
         return int(np.argmax(self.compute(X, eta=eta)))
+
+    def refine(self, X, n_starts=256, n_steps=50, step0=0.05, eta=None, diagnostics=False):
+        """The maximiser refined by gradient ascent on the device (robo_acq_refine_cand): sweep over the candidates X
+        ((M, D) in the caller's input space, or a device batch ``_lib.Candidates`` in the normalised one), the
+        ``n_starts`` best of them climb ``n_steps`` projected steps in lock step -> the best point found, in the
+        caller's input space.  ``last_refine`` keeps the library's result (value, start index, flags, diagnostics)."""
+        model = self.model
+        refine_model_check(model, self.__class__.__name__)
+        model._materialise()
+        cand = X if isinstance(X, _lib.Candidates) else _lib.Candidates(model.gp.ctx, model._normalised(np.asarray(X)))
+        try:
+            res = model.gp.refine(self.kind, self.par, self._eta(eta), cand, n_starts, n_steps, step0, diagnostics)
+            return refine_finish(self, self.kind, model, res, cand)
+        finally:
+            if cand is not X:
+                cand.close()
 
     def argmax_sharded(self, comm, X_slice, global_offset):
         """Candidate shard (robo_amd.sharding.sharded_argmax): this rank's slice of the candidate matrix, whose first

@@ -247,6 +247,34 @@ class MarginalizationGPMCMC(BaseAcquisitionFunction):
             acquisition_values[i] = self.estimators[i].compute(X_test, derivative=derivative)
         return acquisition_values.mean(axis=0)
 
+    def refine(self, X_test, n_starts=256, n_steps=50, step0=0.05, diagnostics=False):
+        """Gradient-refined maximiser of the marginalised acquisition (robo_acq_refine_marginal_cand): as
+        ClosedFormAcquisition.refine, value and gradient averaged over the hyper-parameter samples in sample order."""
+        from robo_amd.acquisition_functions.base_acquisition import refine_finish, refine_model_check
+        if not isinstance(self.acquisition_func, ClosedFormAcquisition) or not self.estimators:
+            raise TypeError("MarginalizationGPMCMC.refine is available for EI, LogEI, PI and LCB only (got %s)"
+                            % type(self.acquisition_func).__name__)
+        if getattr(self.model, "devices", None) or self._shard() is not None:
+            raise NotImplementedError("MarginalizationGPMCMC.refine runs on one device; multi-device and multi-process "
+                                      "sharding of the refinement is not implemented")
+        for e in self.estimators:
+            refine_model_check(e.model, "MarginalizationGPMCMC")
+            e.model._materialise()
+        est = self.estimators
+        gps = [e.model.gp for e in est]
+        if len({id(g.ctx) for g in gps}) != 1:
+            raise NotImplementedError("MarginalizationGPMCMC.refine: the sub-models live on several contexts")
+        eta = np.array([e._eta(None) for e in est])
+        m0 = est[0].model
+        cand = X_test if isinstance(X_test, _lib.Candidates) else _lib.Candidates(gps[0].ctx,
+                                                                                  m0._normalised(np.asarray(X_test)))
+        try:
+            res = _lib.acq_refine(gps, est[0].kind, est[0].par, eta, cand, n_starts, n_steps, step0, diagnostics)
+            return refine_finish(self, est[0].kind, m0, res, cand)
+        finally:
+            if cand is not X_test:
+                cand.close()
+
     def argmax(self, X_test):
         if self._shard() is not None:
             return int(np.argmax(self._sharded_eval(X_test)))

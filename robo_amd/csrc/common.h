@@ -180,6 +180,48 @@ void ctx_retain(robo_ctx* ctx);        // a handle was created on ctx
 void ctx_release(robo_ctx* ctx);       // ... destroyed: frees a closing context with its last handle
 }
 
+struct robo_cand;
+namespace robo {
+// ---- multi-start gradient refinement of an acquisition maximum (refine.hip) ------------------------------------------------
+// Radix selection of the K best sweep values: the 96-bit key (order-preserving bits of the value, inverted index) of the
+// K-th best candidate is found digit by digit, 8 bits per pass.
+struct RefineSel {
+    unsigned long long hi;      // value part of the threshold key (the digits fixed so far)
+    unsigned lo;                // inverted-index part
+    unsigned remaining;         // rank of the threshold among the keys that share the fixed digits
+    unsigned keff;              // min(K, candidates whose value is not NaN)
+    unsigned count;             // slots handed out by the collect kernel
+};
+// everything a start carries between two launches; all arrays [K] or [K][D], device memory of one block
+struct RefineState {
+    int K, D;
+    double *x, *f, *g, *alpha;      // accepted point, its value and gradient, current step length
+    double *aused;                  // step length the pending trial was made with
+    double *y, *ys;                 // pending trial points, raw and scaled by the current sample's metrics
+    double *fy, *gy;                // value / gradient of the trial, accumulated over the hyper-parameter samples
+    int *frozen, *bad;              // start takes no more steps; some sample saw the variance floor at the trial
+    long long* start;               // index in the candidate batch the start came from (-1: slot unused)
+    double* sel_val;                // [2][K] selected values: as collected, then sorted
+    long long* sel_idx;             // [2][K]
+    unsigned* hist;                 // [256] digit counts of the current selection pass
+    unsigned* flags;                // ROBO_FLAG_* raised by the refinement
+    RefineSel* sel;
+    double* out;                    // [D + 4]: point, value, start index, flags, starts in use
+    double* trace;                  // (T + 1) x K x (2 D + 3), or nullptr
+};
+struct RefineWork {
+    int K, D;
+    ::robo_cand* ws;                // the K (D + 1) pseudo-rows of the solve
+    char* d_block;                  // one allocation behind `st`
+    double* d_trace;
+    size_t trace_cap;               // doubles
+    RefineState st;
+};
+int refine_alloc(robo_ctx* ctx, int K, int D, RefineWork** out);
+void refine_free(RefineWork* w);               // the state block and the trace; `ws` belongs to the caller
+int refine_ensure_trace(RefineWork* w, size_t doubles);
+}  // namespace robo
+
 constexpr int ROBO_AUX_STREAMS = 3;
 struct robo_ctx {
     int device;
@@ -268,6 +310,7 @@ struct robo_gp {
     double* d_wnorm;                // [2]: |L|_inf, |W|_inf (bit patterns, atomicMax)
     double* h_wnorm;                // pinned copy of the two norms (written by an asynchronous copy behind the build)
     unsigned long long winv_launched;   // fit_gen whose W build has been LAUNCHED (robo_gp_prefetch_inverse) but not yet read
+    robo::RefineWork* refine;       // state + solve workspace of robo_acq_refine_* (refine.hip), kept between calls of one (K, D)
 };
 
 struct robo_cand {
@@ -373,6 +416,10 @@ int winv_ensure(robo_gp* gp);
 int winv_launch(robo_gp* gp);
 int launch_per_cost(robo_ctx* ctx, double* d_dh, const double* d_log_cost, double overhead, int64_t m);
 int launch_predict_winv(robo_gp* gp, robo_cand* cand, int64_t c0, int64_t cn, bool store_v);
+// rows already in memory (the pseudo-rows of the gradient refinement): the buffer to fill, then V = rows W^T into cand->d_V
+// with q / mu, in the one form whose rounding does not depend on the row count
+int winv_rows_buffer(robo_gp* gp, robo_cand* cand, int64_t rows, double** out);
+int launch_winv_rows(robo_gp* gp, robo_cand* cand, int64_t rows);
 int launch_trsm(robo_gp* gp, robo_cand* cand, int64_t c0, int64_t cn);
 int launch_predict_fused(robo_gp* gp, robo_cand* cand, int64_t c0, int64_t cn);
 int launch_pack_linv(robo_gp* gp);
@@ -384,6 +431,12 @@ int launch_cross_grad(robo_gp* gp, const double* d_Xcs, double* d_V, int64_t c_f
 int launch_predgrad_post(robo_gp* gp, const double* d_V, const double* d_q, const double* d_mu, const double* d_Xcs,
                          int64_t c_first, int64_t c_count, double* d_mean, double* d_var, double* d_dmean,
                          double* d_dvar);
+// refine.hip: top-K of d_vals (m) -> starts gathered from d_Xc; one value-and-gradient + step launch; the winner
+int launch_refine_select(robo_ctx* ctx, const RefineState& st, const double* d_vals, int64_t m, const double* d_Xc,
+                         double step0);
+int launch_refine_eval(robo_gp* gp, const RefineState& st, const robo_cand* ws, int acq_kind, double par, double eta, int s,
+                       int S, int t, int T);
+int launch_refine_result(robo_ctx* ctx, const RefineState& st, unsigned* d_cand_flags, bool sweep_only);
 int launch_acq(robo_ctx* ctx, robo_cand* cand, int acq_kind, double par, double eta, bool accumulate, bool first);
 int launch_argmax(robo_cand* cand, const double* d_vals, double scale);
 int launch_report_best(robo_cand* cand, double* h_pinned);

@@ -371,7 +371,27 @@ static int grow(double** p, size_t* have, size_t need) {
     return ROBO_OK;
 }
 
+// V = Ks W^T of cn rows and its reductions; Ks = cand->d_Ks holds the right-hand sides (cn x n_pad, columns >= n zero).
+// fixed_units: always the chunked units at the batch depth, whatever the row count -- the association of every entry is then
+// fixed by n_pad alone (the gradient refinement, whose starts must not feel how many other starts share the launch).
+static int winv_product(robo_gp* gp, robo_cand* cand, int64_t c0, int64_t cn, bool store_v, bool fixed_units);
+
 int launch_predict_winv(robo_gp* gp, robo_cand* cand, int64_t c0, int64_t cn, bool store_v) {
+    int s = grow(&cand->d_Ks, &cand->ks_bytes, (size_t)cn * gp->n_pad * sizeof(double));
+    if (s == ROBO_OK) s = launch_cross_gram(gp, cand, c0, cn, cand->d_Ks);
+    if (s != ROBO_OK) return s;
+    return winv_product(gp, cand, c0, cn, store_v, false);
+}
+
+int winv_rows_buffer(robo_gp* gp, robo_cand* cand, int64_t rows, double** out) {
+    ROBO_TRY(grow(&cand->d_Ks, &cand->ks_bytes, (size_t)rows * gp->n_pad * sizeof(double)));
+    *out = cand->d_Ks;
+    return ROBO_OK;
+}
+
+int launch_winv_rows(robo_gp* gp, robo_cand* cand, int64_t rows) { return winv_product(gp, cand, 0, rows, true, true); }
+
+static int winv_product(robo_gp* gp, robo_cand* cand, int64_t c0, int64_t cn, bool store_v, bool fixed_units) {
     hipStream_t st = gp->ctx->stream;
     const int n_pad = gp->n_pad, nbk = gp->winv_nbk;
     const unsigned cts = (unsigned)(cn / NB);
@@ -383,27 +403,26 @@ int launch_predict_winv(robo_gp* gp, robo_cand* cand, int64_t c0, int64_t cn, bo
     // pass reads twice the unit tiles): the third table is only reachable through the tuning key.
     const long long cts_total = cand->m_pad / NB;
     const int shift = gp->ctx->tune.winv_kc_shift;
-    const int v = shift >= 0 ? (shift > 2 ? 2 : shift) : (cts_total >= 8 ? 0 : 1);
+    const int v = fixed_units ? 0 : (shift >= 0 ? (shift > 2 ? 2 : shift) : (cts_total >= 8 ? 0 : 1));
     const int nu = gp->winv_units[v];
     // whole contraction range per (candidate tile, block row) when those pairs fill the chip by themselves: decided from
     // the handle's TOTAL batch (not this workspace pass), so a chunked workspace yields the values of a single pass
     const long long slots = 2LL * gp->ctx->num_cu;
     const int rows_mode = gp->ctx->tune.winv_rows;                 // -1 auto, 0 never, 1 always (A/B, tests)
-    const bool whole = rows_mode >= 0 ? rows_mode != 0 : (cand->m_pad / NB) * (long long)(nbk + 1) >= 2 * slots;
+    const bool whole = !fixed_units && (rows_mode >= 0 ? rows_mode != 0 : (cand->m_pad / NB) * (long long)(nbk + 1) >= 2 * slots);
     // a handful of candidates: matrix-vector form (tuning winv_gemv: -1 auto = at most 8 candidates unless another form is
     // forced, 0 never, 1 whenever it applies)
     const int gemv_mode = gp->ctx->tune.winv_gemv;
-    const bool gemv = (gemv_mode > 0 || (gemv_mode < 0 && rows_mode < 0 && shift < 0)) && cand->m <= 8 && cand->m_pad == NB;
+    const bool gemv = !fixed_units && (gemv_mode > 0 || (gemv_mode < 0 && rows_mode < 0 && shift < 0)) && cand->m <= 8 &&
+                      cand->m_pad == NB;
     const int nslab = nbk * NB / GV_ROWS;       // through the last block row: its columns >= n are stored as 0, like the other forms
     const int nparts = gemv ? nslab : nbk;
-    int s = grow(&cand->d_Ks, &cand->ks_bytes, (size_t)cn * n_pad * sizeof(double));
-    if (s == ROBO_OK && !whole && !gemv) s = grow(&cand->d_P, &cand->p_bytes, (size_t)cts * nu * NB * NB * sizeof(double));
+    int s = ROBO_OK;
+    if (!whole && !gemv) s = grow(&cand->d_P, &cand->p_bytes, (size_t)cts * nu * NB * NB * sizeof(double));
     if (s == ROBO_OK) s = grow(&cand->d_qpart, &cand->qpart_bytes, (size_t)2 * nparts * cn * sizeof(double));
     if (s != ROBO_OK) return s;
     double* qpart = cand->d_qpart;
     double* mupart = cand->d_qpart + (size_t)nparts * cn;
-    s = launch_cross_gram(gp, cand, c0, cn, cand->d_Ks);
-    if (s != ROBO_OK) return s;
     const double* z = gp->d_K + (size_t)gp->n * n_pad;
     if (gemv) {
         cand->solve_kernel = "winv_gemv_kernel";

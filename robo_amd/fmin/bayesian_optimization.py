@@ -9,6 +9,7 @@ without george, pybnn and pyrfr: :2,5,8,11), wired to the MI355X GP path:
     acq      EI | LogEI | PI | LCB, wrapped in MarginalizationGPMCMC for gp_mcmc       (:114-129)
 
     maximiser RandomSampling | SciPyOptimizer | DifferentialEvolution                    (:131-139)
+              | DeviceRandomSampling | DeviceGradientAscent (not in the reference)
 
 Model types other than the two GP ones (rf / bohamiann / dngo) are outside this project's hot path
 (SURVEY.md section 2, rows 6, 8).
@@ -20,7 +21,8 @@ import numpy as np
 from robo_amd.acquisition_functions import EI, LCB, PI, LogEI, MarginalizationGPMCMC
 from robo_amd.initial_design import init_latin_hypercube_sampling
 from robo_amd.kernels import Matern52Kernel
-from robo_amd.maximizers import DeviceRandomSampling, DifferentialEvolution, RandomSampling, SciPyOptimizer
+from robo_amd.maximizers import (DeviceGradientAscent, DeviceRandomSampling, DifferentialEvolution, RandomSampling,
+                                 SciPyOptimizer)
 from robo_amd.models import GaussianProcess, GaussianProcessMCMC
 from robo_amd.priors import DefaultPrior
 from robo_amd.solver import BayesianOptimization
@@ -81,6 +83,9 @@ def bayesian_optimization(objective_function, lower, upper, num_iterations=30, X
     elif maximizer == "device_random":
         # same recipe, candidates generated and scored on the device, only x* comes back
         max_func = DeviceRandomSampling(acq, lower, upper, n_samples=n_candidates, rng=rng)
+    elif maximizer == "device_gradient":
+        # the same candidates; the best of them are refined by gradient ascent on the device (n_candidates = sweep size)
+        max_func = DeviceGradientAscent(acq, lower, upper, n_samples=n_candidates, rng=rng)
     elif maximizer == "scipy":
         max_func = SciPyOptimizer(acq, lower, upper, rng=rng)
     elif maximizer == "differential_evolution":
