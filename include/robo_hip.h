@@ -311,6 +311,38 @@ int32_t robo_acq_refine_marginal_cand(robo_gp* const* gps, int32_t S, int32_t ac
                                       double* out_value, int64_t* out_start_index, uint32_t* out_flags,
                                       int64_t* out_starts, double* out_trace);
 
+/* ---- greedy batch proposals with fantasised picks (no counterpart in the reference, which proposes one point per model
+ * fit: robo/solver/bayesian_optimization.py:156-203).  q points are chosen from ONE candidate batch at FIXED theta, FIXED
+ * constant mean and FIXED output transform (y_mean, y_std): nothing is re-estimated between the picks -- the result equals
+ * appending every fantasy observation and refitting with those three frozen at the real data's values.
+ * Pick 0 is robo_acq_eval_cand's sweep and argmax.  After pick j at candidate x_j a fantasy target y_f is chosen,
+ *   ROBO_FANTASY_KRIGING_BELIEVER: y_f = mu(x_j) (per hyper-parameter sample in the marginal form),
+ *   ROBO_FANTASY_CONSTANT_LIAR:    y_f = liar,
+ * and every candidate's latent moments are conditioned on (x_j, y_f) observed with the model's noise:
+ *   c(x) = cov(x, x_j | data and the earlier fantasies) = k(x, x_j) - k_*(x)^T beta_j - sum_{t<j} c_t(x) c_t(x_j) / d_t,
+ *   beta_j = K^-1 k_*(x_j) (K: the fitted gram),  d = var_lat(x_j) + sigma^2 + 1.25e-12 (robo_gp_fit's diagonal),
+ *   var_lat(x) -= c(x)^2 / d,   mu_lat(x) += c(x) (y_f - mu(x_j)) / d,   eta := min(eta, y_f)   (LCB ignores eta).
+ * The state is kept unfloored in the latent scale; transform and DBL_EPSILON floor are applied when the acquisition is
+ * formed, as in the sweep.  Nothing is masked: a picked point competes again with its collapsed variance.  beta_j always
+ * comes from the two triangular solves with the factor, never from the explicit inverse W (no dependence on winv_cond_max).
+ * A pick whose winning value is NaN is recorded and ends the selection: the remaining out_idx are -1, out_values /
+ * out_fantasy NaN, and the call still succeeds.  *out_n_made = picks recorded.
+ * out_idx / out_values / out_flags [q]: argmax (np.argmax: first index, NaN maximal), its value, the ROBO_FLAG_* of the
+ * values the pick was made from.  out_fantasy [q] ([q][S] in the marginal form): the target fantasised at pick j (NaN for
+ * the last pick made: nothing is conditioned on it).  out_trace, nullable, q x m x 2 (q x S x m x 2): the transformed,
+ * floored (mean, var) every pick was made from -- diagnostics.  q outside 1 .. min(m, 1024) (the history of the
+ * conditioning steps is S x q x m doubles), an unknown fantasy_kind, or a GP with
+ * fp32 covariance entries: ROBO_BAD_ARGUMENT.  q = 1 is robo_acq_eval_cand / robo_acq_eval_marginal_cand bit for bit.
+ * One synchronisation per call; the state stays with gp (gps[0]) between calls of one (m, S).                          */
+enum robo_fantasy_kind { ROBO_FANTASY_KRIGING_BELIEVER = 0, ROBO_FANTASY_CONSTANT_LIAR = 1 };
+int32_t robo_acq_batch_cand(robo_gp* gp, int32_t acq_kind, double par, double eta, robo_cand* cand, int32_t q,
+                            int32_t fantasy_kind, double liar, int64_t* out_idx, double* out_values, double* out_fantasy,
+                            uint32_t* out_flags, int32_t* out_n_made, double* out_trace);
+int32_t robo_acq_batch_marginal_cand(robo_gp* const* gps, int32_t S, int32_t acq_kind, double par, const double* etas,
+                                     robo_cand* cand, int32_t q, int32_t fantasy_kind, double liar, int64_t* out_idx,
+                                     double* out_values, double* out_fantasy, uint32_t* out_flags, int32_t* out_n_made,
+                                     double* out_trace);
+
 /* ---- entropy search: replaces InformationGain.innovations/_dh_fun/compute ---------------
  * (robo/acquisition_functions/information_gain.py:87-125,169-203,253-272), batched over candidates.
  * rep: the Nb <= 64 representer points as a candidate batch (same normalised space).  The EP

@@ -26,6 +26,7 @@ EP_NAN_MESSAGE = ("an error occurs while running expectation propagation in entr
 KERNEL_KINDS = {"matern52": 0, "rbf": 1, "fabolas": 2}
 ACQ_KINDS = {"ei": 0, "log_ei": 1, "pi": 2, "lcb": 3}
 FLAG_ZERO_SIGMA, FLAG_NEGATIVE_EI, FLAG_NAN, FLAG_NOT_FACTORED, FLAG_FROZEN = 1, 2, 4, 8, 16
+FANTASY_KINDS = {"kriging_believer": 0, "constant_liar": 1}   # robo_acq_batch_*: how a pick's fantasy target is chosen
 REFINE_MAX_STARTS = 1024                         # robo_acq_refine_*: cap on n_starts
 MC_MAX_NB, MC_MAX_NP, MC_MAX_NF = 64, 512, 65535   # limits of the Monte-Carlo p_min entry points (robo_pmin_mc, robo_igmc_*)
 
@@ -43,6 +44,7 @@ SYMBOLS = [
     "robo_gp_predict_cand", "robo_gp_predict", "robo_gp_predict_cov", "robo_gp_predict_grad", "robo_gp_predict_mixture_cand",
     "robo_acq_eval_cand", "robo_acq_eval", "robo_acq_eval_moments", "robo_acq_eval_marginal_cand", "robo_acq_eval_sum_cand",
     "robo_acq_refine_cand", "robo_acq_refine_marginal_cand",
+    "robo_acq_batch_cand", "robo_acq_batch_marginal_cand",
     "robo_ig_eval_cand", "robo_ig_eval_per_cost_cand", "robo_ig_eval_moments", "robo_gp_cross_cov",
     "robo_ep_joint_min", "robo_pmin_mc", "robo_igmc_eval_cand", "robo_igmc_eval_moments",
     "robo_comm_create_id", "robo_comm_init", "robo_comm_destroy", "robo_comm_info", "robo_comm_allgather",
@@ -175,6 +177,10 @@ def lib():
                                  C.POINTER(i64), _dp],
         "robo_acq_refine_marginal_cand": [pp, i32, i32, dbl, _dp, vp, i32, i32, dbl, _dp, _dp, C.POINTER(i64),
                                           C.POINTER(C.c_uint32), C.POINTER(i64), _dp],
+        "robo_acq_batch_cand": [vp, i32, dbl, dbl, vp, i32, i32, dbl, C.POINTER(i64), _dp, _dp, C.POINTER(C.c_uint32),
+                                C.POINTER(i32), _dp],
+        "robo_acq_batch_marginal_cand": [pp, i32, i32, dbl, _dp, vp, i32, i32, dbl, C.POINTER(i64), _dp, _dp,
+                                         C.POINTER(C.c_uint32), C.POINTER(i32), _dp],
         "robo_ig_eval_cand": [vp, vp, vp, i32, dbl, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(i64)],
         "robo_ig_eval_per_cost_cand": [vp, vp, vp, i32, dbl, _dp, _dp, _dp, _dp, _dp, _dp, vp, vp, dbl, _dp, _dp,
                                        C.POINTER(i64)],
@@ -742,6 +748,51 @@ class DeviceGP(object):
         """sweep over ``cand`` + multi-start projected gradient ascent on the device (robo_acq_refine_cand)
         -> RefineResult; see :func:`acq_refine`"""
         return acq_refine([self], kind, par, eta, cand, n_starts, n_steps, step0, diagnostics, marginal=False)
+
+
+    def select_batch(self, kind, par, eta, cand, q, fantasy="kriging_believer", liar=0.0, diagnostics=False):
+        """q greedy picks from ``cand`` with fantasised observations in between (robo_acq_batch_cand) -> BatchResult;
+        see :func:`acq_batch`"""
+        return acq_batch([self], kind, par, eta, cand, q, fantasy, liar, diagnostics, marginal=False)
+
+
+class BatchResult(object):
+    """indices (q,) rows of the candidate batch in pick order (-1: not made, a NaN winner ended the selection), values (q,),
+    fantasies (q, S) the target fantasised after every pick (NaN after the last one made), flags (q,), n_made; with
+    diagnostics: trace (q, S, m, 2) the transformed, floored (mean, var) every pick was made from (include/robo_hip.h)"""
+
+    def __init__(self, indices, values, fantasies, flags, n_made, trace=None):
+        self.indices, self.values, self.fantasies, self.flags = indices, values, fantasies, flags
+        self.n_made, self.trace = int(n_made), trace
+
+
+def acq_batch(gps, kind, par, eta, cand, q, fantasy="kriging_believer", liar=0.0, diagnostics=False, marginal=True):
+    """greedy batch selection over device GPs (one: robo_acq_batch_cand; the mean over several hyper-parameter samples:
+    robo_acq_batch_marginal_cand).  eta: one incumbent value, or one per sample.  theta, the constant mean and the output
+    transform stay frozen between the picks."""
+    if fantasy not in FANTASY_KINDS:
+        raise ValueError("fantasy must be one of %s, got %r" % (sorted(FANTASY_KINDS), fantasy))
+    S, q = len(gps), int(q)
+    ok = 1 <= q <= cand.m
+    n = max(q, 1)
+    idx = np.full(n, -1, dtype=np.int64)
+    val, fant = np.full(n, np.nan), np.full((n, S), np.nan)
+    fl = np.zeros(n, dtype=np.uint32)
+    made = C.c_int32(0)
+    trace = np.empty((q, S, cand.m, 2)) if (diagnostics and ok) else None
+    p_idx, p_fl = idx.ctypes.data_as(C.POINTER(C.c_int64)), fl.ctypes.data_as(C.POINTER(C.c_uint32))
+    p_trace = _arr(trace) if trace is not None else None
+    if marginal:
+        arr = (C.c_void_p * S)(*[g._h for g in gps])
+        etas = _f64(np.broadcast_to(np.asarray(eta, dtype=np.float64), (S,)))
+        check(lib().robo_acq_batch_marginal_cand(arr, S, ACQ_KINDS[kind], float(par), _arr(etas), cand._h, q,
+                                                 FANTASY_KINDS[fantasy], float(liar), p_idx, _arr(val), _arr(fant), p_fl,
+                                                 C.byref(made), p_trace))
+    else:
+        check(lib().robo_acq_batch_cand(gps[0]._h, ACQ_KINDS[kind], float(par), float(eta), cand._h, q,
+                                        FANTASY_KINDS[fantasy], float(liar), p_idx, _arr(val), _arr(fant), p_fl,
+                                        C.byref(made), p_trace))
+    return BatchResult(idx, val, fant, fl, made.value, trace)
 
 
 class RefineResult(object):

@@ -46,20 +46,59 @@ class BaseAcquisitionFunction(object):
                         "over a robo_amd GaussianProcess (or MarginalizationGPMCMC over them)" % self.__class__.__name__)
 
 
-def refine_model_check(model, who):
-    """the model requirements of the device refinement, as TypeError / NotImplementedError with a plain message"""
+    def select_batch(self, X, q, fantasy="kriging_believer", liar=None, diagnostics=False):
+        """Greedy batch of q proposals with fantasised picks: EI / LogEI / PI / LCB over robo_amd GP models only."""
+        raise TypeError("%s has no batch selection on the device: select_batch() is available for EI, LogEI, PI and LCB "
+                        "over a robo_amd GaussianProcess (or MarginalizationGPMCMC over them)" % self.__class__.__name__)
+
+
+def batch_liar(model, fantasy, liar):
+    """the constant liar's value in the model's output scale: "min" | "mean" | "max" of the observed targets, or a float"""
+    if fantasy != "constant_liar":
+        return 0.0
+    if liar is None:
+        liar = "min"
+    if isinstance(liar, str):
+        if liar not in ("min", "mean", "max"):
+            raise ValueError("liar must be 'min', 'mean', 'max' or a float, got %r" % (liar,))
+        y = np.asarray(model.y, dtype=np.float64)
+        v = float(getattr(np, liar)(y))
+        if getattr(model, "normalize_output", False):
+            v = v * model.y_std + model.y_mean
+        return v
+    return float(liar)
+
+
+def batch_finish(acq, kind, model, res, cand):
+    """shared tail of the select_batch() methods: the reference's EI guards act on pick 0's flags only (a floored variance
+    at an already-picked point is expected, not a degenerate batch); the picked rows in the caller's input space"""
+    acq.last_batch = res
+    acq.last_max, acq.last_argmax = float(res.values[0]), int(res.indices[0])
+    if kind == "ei":
+        if res.flags[0] & _lib.FLAG_ZERO_SIGMA:       # ei.py:72-74: the batch collapses to [[0]], argmax 0
+            res.indices[0] = 0
+        elif res.flags[0] & _lib.FLAG_NEGATIVE_EI:
+            raise ValueError
+    pts = np.array([cand.point(int(i)) for i in res.indices[:res.n_made]]).reshape(res.n_made, cand.dim)
+    lower, upper = np.asarray(model.lower, dtype=np.float64), np.asarray(model.upper, dtype=np.float64)
+    return lower + (upper - lower) * pts
+
+
+def refine_model_check(model, who, what="refine"):
+    """the model requirements of the device refinement (and of the batch selection, what="select_batch"), as TypeError /
+    NotImplementedError with a plain message"""
     # FabolasGP (models/fabolas_gp.py) is a GaussianProcess whose inputs go through its own normalize(): a basis function on
     # the fidelity column, so its input space is not the box [0, 1]^D the ascent is projected onto
     from robo_amd.models.fabolas_gp import FabolasGP
     if not (hasattr(model, "acquisition") and hasattr(model, "gp") and hasattr(model, "_normalised")) \
             or isinstance(model, FabolasGP):
-        raise TypeError("%s.refine needs a robo_amd GaussianProcess model (got %s)" % (who, type(model).__name__))
+        raise TypeError("%s.%s needs a robo_amd GaussianProcess model (got %s)" % (who, what, type(model).__name__))
     if not getattr(model, "normalize_input", False):
-        raise TypeError("%s.refine works in the box [0, 1]^D of the normalised inputs: the model needs "
-                        "normalize_input=True" % who)
+        raise TypeError("%s.%s works in the box [0, 1]^D of the normalised inputs: the model needs "
+                        "normalize_input=True" % (who, what))
     if getattr(model, "devices", None):
-        raise NotImplementedError("%s.refine runs on one device; multi-device sharding of the refinement is not "
-                                  "implemented" % who)
+        raise NotImplementedError("%s.%s runs on one device; multi-device sharding of it is not implemented"
+                                  % (who, what))
     if not model.is_trained:
         raise Exception('Model has to be trained first!')
 
@@ -142,6 +181,26 @@ class ClosedFormAcquisition(BaseAcquisitionFunction):
         try:
             res = model.gp.refine(self.kind, self.par, self._eta(eta), cand, n_starts, n_steps, step0, diagnostics)
             return refine_finish(self, self.kind, model, res, cand)
+        finally:
+            if cand is not X:
+                cand.close()
+
+    def select_batch(self, X, q, fantasy="kriging_believer", liar=None, diagnostics=False, eta=None):
+        """q proposals from ONE candidate batch X ((M, D) in the caller's input space, or a device batch
+        ``_lib.Candidates`` in the normalised one) by greedy selection with fantasised picks (robo_acq_batch_cand): pick 0
+        is the sweep's argmax; after every pick the posterior of all candidates is conditioned on a fantasy observation
+        there -- the posterior mean (``kriging_believer``) or the constant ``liar`` ("min" | "mean" | "max" of the observed
+        targets, or a float) -- with the hyper-parameters, the constant mean and the output normalisation frozen.
+        -> (q', D) points in the caller's input space, q' < q only when a NaN winner ended the selection.  ``last_batch``
+        keeps the library's result (indices, values, fantasies, flags, diagnostics)."""
+        model = self.model
+        refine_model_check(model, self.__class__.__name__, "select_batch")
+        model._materialise()
+        cand = X if isinstance(X, _lib.Candidates) else _lib.Candidates(model.gp.ctx, model._normalised(np.asarray(X)))
+        try:
+            res = model.gp.select_batch(self.kind, self.par, self._eta(eta), cand, q, fantasy,
+                                        batch_liar(model, fantasy, liar), diagnostics)
+            return batch_finish(self, self.kind, model, res, cand)
         finally:
             if cand is not X:
                 cand.close()

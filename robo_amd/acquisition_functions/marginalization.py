@@ -275,6 +275,36 @@ class MarginalizationGPMCMC(BaseAcquisitionFunction):
             if cand is not X_test:
                 cand.close()
 
+    def select_batch(self, X_test, q, fantasy="kriging_believer", liar=None, diagnostics=False):
+        """Greedy batch of q proposals under the marginalised acquisition (robo_acq_batch_marginal_cand): as
+        ClosedFormAcquisition.select_batch; every hyper-parameter sample is conditioned on its own fantasy (its own posterior
+        mean for the kriging believer) and keeps its own incumbent, the values are averaged in sample order."""
+        from robo_amd.acquisition_functions.base_acquisition import batch_finish, batch_liar, refine_model_check
+        if not isinstance(self.acquisition_func, ClosedFormAcquisition) or not self.estimators:
+            raise TypeError("MarginalizationGPMCMC.select_batch is available for EI, LogEI, PI and LCB only (got %s)"
+                            % type(self.acquisition_func).__name__)
+        if getattr(self.model, "devices", None) or self._shard() is not None:
+            raise NotImplementedError("MarginalizationGPMCMC.select_batch runs on one device; multi-device and "
+                                      "multi-process sharding of the batch selection is not implemented")
+        for e in self.estimators:
+            refine_model_check(e.model, "MarginalizationGPMCMC", "select_batch")
+            e.model._materialise()
+        est = self.estimators
+        gps = [e.model.gp for e in est]
+        if len({id(g.ctx) for g in gps}) != 1:
+            raise NotImplementedError("MarginalizationGPMCMC.select_batch: the sub-models live on several contexts")
+        eta = np.array([e._eta(None) for e in est])
+        m0 = est[0].model
+        cand = X_test if isinstance(X_test, _lib.Candidates) else _lib.Candidates(gps[0].ctx,
+                                                                                  m0._normalised(np.asarray(X_test)))
+        try:
+            res = _lib.acq_batch(gps, est[0].kind, est[0].par, eta, cand, q, fantasy, batch_liar(m0, fantasy, liar),
+                                 diagnostics)
+            return batch_finish(self, est[0].kind, m0, res, cand)
+        finally:
+            if cand is not X_test:
+                cand.close()
+
     def argmax(self, X_test):
         if self._shard() is not None:
             return int(np.argmax(self._sharded_eval(X_test)))

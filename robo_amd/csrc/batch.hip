@@ -1,0 +1,471 @@
+// Greedy batch proposals with fantasised picks, resident on the device (robo_acq_batch_cand, robo_acq_batch_marginal_cand;
+// the reference proposes one point per model fit: robo/solver/bayesian_optimization.py:156-203).
+//
+//   sweep (predict.hip + acq.hip, unchanged) -> batch_init_kernel: the unfloored latent moments of every candidate
+//   -> batch_record_kernel: pick 0
+//   -> (q - 1) x [ per hyper-parameter sample: batch_kstar_kernel (k_*(x_j), the fantasy target, eta)
+//                  -> forward / backward block rows (beta_j = K^-1 k_*(x_j)) -> batch_cond_kernel (rank-one conditioning
+//                  of every candidate + acquisition) ;  the sweep's final reduction (acq.hip) ; batch_record_kernel ]
+//
+// The rule (include/robo_hip.h): after pick j at x_j with fantasy target y_f, every candidate's LATENT moments (the scale
+// the factor lives in, before the output transform, never floored) are conditioned on (x_j, y_f) observed with the
+// model's noise, at FIXED theta, constant mean and output transform:
+//     c(x) = k(x, x_j) - k_*(x)^T beta_j - sum_{t < j} c_t(x) c_t(x_j) / d_t      (beta_j = K^-1 k_*(x_j), K the fitted gram)
+//     d = var_lat(x_j) + noise                                                   (noise: the diagonal term of the fit)
+//     var_lat(x) -= c(x)^2 / d                  mu_lat(x) += c(x) (y_f - mu(x_j)) / d
+// which is what appending (x_j, y_f) and refitting with everything else frozen gives.  The transform and the DBL_EPSILON
+// floor are applied where the sweep applies them: when the acquisition is formed.
+//
+// beta_j always comes from the two triangular solves with the factor and its inverted diagonal blocks, never from the
+// explicit inverse W: a result cannot depend on the winv_cond_max guard or on whether W exists.  The conditioning pass
+// generates k(x, X_n) in registers and writes no cross-gram tile; it needs no solve workspace.
+//
+// Ordering is the stream's alone: the winner's index stays in device memory (BatchState::idx) and the next pick's
+// kernels read x_j from the candidate buffer through it.  Every sum has a fixed order that does not depend on the grid.
+#include "common.h"
+#include "kern_math.h"
+
+namespace robo {
+
+constexpr int BC_CAND = 64;          // candidates per workgroup of the conditioning pass (one per lane; the 4 waves split the rows)
+constexpr int BC_ROWS = 32;          // training rows per wave and tile
+constexpr int BC_LD = NB + 2;
+
+__device__ __forceinline__ double batch_nan() { return __longlong_as_double(0x7FF8000000000000LL); }
+
+// everything the picks start from; one launch per sample right after that sample's posterior (d_q / d_mu / d_mean / d_var
+// of the candidate handle still hold it)
+__global__ __launch_bounds__(256) void batch_init_kernel(BatchState st, int s, const double* __restrict__ q,
+                                                         const double* __restrict__ mu, const double* __restrict__ mean,
+                                                         const double* __restrict__ var, const double* __restrict__ Xc,
+                                                         const double* __restrict__ ism, CovParams cp, double mean_c,
+                                                         double eta) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i == 0) st.eta[s] = eta;
+    if (i >= st.m) return;
+    const size_t at = (size_t)s * st.m_pad + i;
+    const double u = Xc[i * cp.dim + cp.dim - 1] * ism[cp.dim - 1];
+    st.mu_lat[at] = mu[i] + mean_c;
+    st.var_lat[at] = cov_self(cp, u) - q[i];
+    st.mean_t[at] = mean[i];
+    if (st.trace) {
+        double* row = st.trace + ((size_t)s * st.m + i) * 2;       // pick 0
+        row[0] = mean[i];
+        row[1] = var[i];
+    }
+}
+
+// outputs of a call: "no pick" everywhere
+__global__ __launch_bounds__(256) void batch_reset_kernel(BatchState st) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t < st.q) {
+        st.idx[t] = -1;
+        st.val[t] = batch_nan();
+        st.flg[t] = 0u;
+    }
+    if (t < st.q * st.S) st.fant[t] = batch_nan();
+    if (t == 0) {
+        *st.n_made = 0;
+        *st.stop = 0;
+    }
+}
+
+// pick j := the reduction's winner.  A NaN winner is recorded and ends the selection.  cand_flags: the sweep's flag word
+// (pick 0: reported and cleared, as the sweep's own read-back does), nullptr for the later picks, whose conditioning
+// pass raises its flags in st.flg[j] directly.
+__global__ void batch_record_kernel(BatchState st, int j, const double* __restrict__ best_val,
+                                    const long long* __restrict__ best_idx, unsigned* __restrict__ cand_flags) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    if (*st.stop) return;
+    const double v = *best_val;
+    st.val[j] = v;
+    st.idx[j] = *best_idx;
+    if (cand_flags) {
+        st.flg[j] = *cand_flags;
+        *cand_flags = 0u;
+    }
+    *st.n_made = j + 1;
+    if (v != v) *st.stop = 1;
+}
+
+// k_*(x_j) of sample s into st.w (rows >= n: 0), and the scalars of this conditioning step: the fantasy target, d,
+// the gain (y_f - mu(x_j)) / d in the latent scale (exactly 0 for the kriging believer: its mean state is never touched),
+// eta := min(eta, y_f)
+__global__ __launch_bounds__(256) void batch_kstar_kernel(BatchState st, int s, int j, const double* __restrict__ Xc,
+                                                          const double* __restrict__ Xs, const double* __restrict__ ism,
+                                                          CovParams cp, int n, int n_pad, double noise, double y_mean,
+                                                          double y_std, int fantasy_kind, double liar) {
+    __shared__ double sJ[MAX_DIM];
+    if (*st.stop) return;
+    const int D = cp.dim;
+    const long long pj = st.idx[j - 1];
+    for (int d = threadIdx.x; d < D; d += 256) sJ[d] = Xc[pj * D + d] * ism[d];
+    __syncthreads();
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r < n_pad) st.w[(size_t)s * n_pad + r] = r < n ? cov_rows(cp, sJ, Xs + (size_t)r * D) : 0.0;
+    if (r == 0) {
+        const size_t at = (size_t)s * st.m_pad + pj;
+        const double d = st.var_lat[at] + noise;
+        const bool believer = fantasy_kind == ROBO_FANTASY_KRIGING_BELIEVER;
+        const double yf = believer ? st.mean_t[at] : liar;
+        const double gain = believer ? 0.0 : ((yf - y_mean) / y_std - st.mu_lat[at]) / d;
+        st.fant[(size_t)(j - 1) * st.S + s] = yf;
+        st.scal[2 * s] = d;
+        st.dhist[(size_t)s * st.qcap + (j - 1)] = d;
+        st.scal[2 * s + 1] = gain;
+        const double e = st.eta[s];
+        st.eta[s] = yf < e ? yf : e;
+    }
+}
+
+// ---- beta = L^-T L^-1 k_*: one right-hand side, block rows of 128 with the fit's inverted diagonal blocks -------------
+// The MFMA block-row substitution of predict.hip works on tiles of 128 right-hand sides; with ONE it would spend 127 / 128
+// of its products on padding (2 GFLOP on one CU at N = 4096).  The same recurrence on a vector is bound by reading L once
+// per direction (67 MB at N = 4096), so it is written as matrix-vector products:
+//   forward, step i:   v_i = Linv_ii w_i ;  w_j -= L[j, i] v_i   for the block rows j > i   (one workgroup per j)
+//   backward, step i:  b_i = Linv_ii^T v_i ;  v_j -= L[i, j]^T b_i   for the block columns j < i
+// Every workgroup of a step forms the 128-entry diagonal solve itself (128 KB out of L2) instead of waiting for another
+// one: a launch boundary per step is the only ordering.  Block i is final when its step starts and no workgroup of the
+// step writes it.  Rows >= n (the augmented row, the padding) take no part.
+__global__ __launch_bounds__(256) void batch_fwd_kernel(const double* __restrict__ L, int ld, const double* __restrict__ Linv,
+                                                        double* __restrict__ w, double* __restrict__ v, int i, int n,
+                                                        const int* __restrict__ stop) {
+    __shared__ double sw[NB], sv[NB];
+    if (*stop) return;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nv = n - i * NB < NB ? n - i * NB : NB;
+    if (tid < NB) sw[tid] = tid < nv ? w[i * NB + tid] : 0.0;
+    __syncthreads();
+    const double* Li = Linv + (size_t)i * NB * NB;
+    for (int r = wave * 32; r < wave * 32 + 32; ++r) {
+        double a = 0.0;
+        if (r < nv) {
+            a = Li[r * NB + lane] * sw[lane];
+            a = fma(Li[r * NB + 64 + lane], sw[64 + lane], a);
+        }
+        for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
+        if (lane == 0) sv[r] = a;
+    }
+    __syncthreads();
+    if (blockIdx.x == 0 && tid < NB) v[i * NB + tid] = sv[tid];
+    const int jb = i + 1 + blockIdx.x;                      // the block row this workgroup updates
+    if (jb * NB >= n) return;
+    const double v0 = sv[lane], v1 = sv[64 + lane];
+    for (int r = wave * 32; r < wave * 32 + 32; ++r) {
+        const int row = jb * NB + r;
+        double a = 0.0;
+        if (row < n) {
+            const double* Lr = L + (size_t)row * ld + (size_t)i * NB;
+            a = Lr[lane] * v0;
+            a = fma(Lr[64 + lane], v1, a);
+        }
+        for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
+        if (lane == 0 && row < n) w[row] -= a;
+    }
+}
+
+__global__ __launch_bounds__(256) void batch_bwd_kernel(const double* __restrict__ L, int ld, const double* __restrict__ Linv,
+                                                        double* __restrict__ v, double* __restrict__ beta, int i, int n,
+                                                        const int* __restrict__ stop) {
+    __shared__ double sv[NB], sb[NB], sp[NB];
+    if (*stop) return;
+    const int tid = threadIdx.x, c = tid & (NB - 1), half = tid >> 7;
+    const int nv = n - i * NB < NB ? n - i * NB : NB;
+    if (tid < NB) sv[tid] = tid < nv ? v[i * NB + tid] : 0.0;
+    __syncthreads();
+    const double* Li = Linv + (size_t)i * NB * NB;
+    double a = 0.0;
+    for (int r = half * 64; r < half * 64 + 64; ++r)
+        if (r < nv && r >= c) a = fma(Li[r * NB + c], sv[r], a);
+    if (half == 1) sp[c] = a;
+    __syncthreads();
+    if (half == 0) sb[c] = c < nv ? a + sp[c] : 0.0;
+    __syncthreads();
+    if (blockIdx.x == 0 && tid < NB) beta[i * NB + tid] = sb[tid];
+    const int jb = blockIdx.x;                              // the block column this workgroup updates
+    if (jb >= i) return;
+    a = 0.0;
+    for (int r = half * 64; r < half * 64 + 64; ++r)
+        if (r < nv) a = fma(L[(size_t)(i * NB + r) * ld + (size_t)jb * NB + c], sb[r], a);
+    __syncthreads();
+    if (half == 1) sp[c] = a;
+    __syncthreads();
+    if (half == 0) v[jb * NB + c] -= a + sp[c];
+}
+
+// ---- the fused conditioning pass ----------------------------------------------------------------------------------------
+// A workgroup owns 64 candidates, one per lane; its four waves split every tile of 128 training points (32 rows each,
+// staged as [dimension][row]: all lanes of a wave read the same word, a broadcast).  A lane keeps its candidate's scaled
+// coordinates in registers while dim <= 16 (SMALLD) and re-reads them per chunk of 16 dimensions otherwise.  Per pair the
+// covariance is accumulated dimension by dimension with direct differences, as the cross-gram generators of predict.hip
+// do, and multiplied into the lane's running k_*(x)^T beta.  The four partial sums are added in wave order.
+// Then lane by lane: c, the update of (mu_lat, var_lat) in memory, transform + floor, the acquisition as acq_kernel
+// forms it, accumulated over the samples in sample order.  The reduction over the candidates is the sweep's own
+// (launch_argmax, acq.hip).
+template <int KIND, bool SMALLD>
+__global__ __launch_bounds__(256) void batch_cond_kernel(BatchState st, int s, int j, const double* __restrict__ Xc,
+                                                         const double* __restrict__ Xs, const double* __restrict__ ism,
+                                                         CovParams cp, int n, int n_pad, double y_mean, double y_std,
+                                                         int acq_kind, double par, int fantasy_kind,
+                                                         double* __restrict__ acq_sum) {
+    __shared__ double sX[16 * BC_LD];
+    __shared__ double sB[NB];
+    __shared__ double sJ[MAX_DIM];
+    __shared__ double sP[4][BC_CAND];
+    if (*st.stop) return;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, D = cp.dim;
+    const long long i = (long long)blockIdx.x * BC_CAND + lane;
+    const bool live = i < st.m;
+    const long long ii = live ? i : 0;
+    const long long pj = st.idx[j - 1];
+    for (int d = tid; d < D; d += 256) sJ[d] = Xc[pj * D + d] * ism[d];
+    double xc[16];
+    if (SMALLD) {
+#pragma unroll
+        for (int d = 0; d < 16; ++d) xc[d] = d < D ? Xc[ii * D + d] * ism[d] : 0.0;
+    }
+    const double* beta = st.beta + (size_t)s * n_pad;
+    const int nbk = (n + NB - 1) / NB;
+    double dot = 0.0;
+    for (int tile = 0; tile < nbk; ++tile) {
+        double acc[BC_ROWS], uu[BC_ROWS];
+#pragma unroll
+        for (int r = 0; r < BC_ROWS; ++r) cov_init<double, KIND>(cp, acc[r], uu[r]);
+        for (int d0 = 0; d0 < D; d0 += 16) {
+            __syncthreads();
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const int idx = tid + e * 256, row = idx >> 4, d = idx & 15;
+                const int rg = tile * NB + row;
+                sX[d * BC_LD + row] = (d0 + d < D && rg < n) ? Xs[(size_t)rg * D + d0 + d] : 0.0;
+            }
+            if (d0 == 0 && tid < NB) sB[tid] = tile * NB + tid < n ? beta[tile * NB + tid] : 0.0;
+            __syncthreads();
+            const int dn = D - d0 < 16 ? D - d0 : 16;
+            const double* sx = sX + wave * BC_ROWS;
+            if (SMALLD) {
+#pragma unroll
+                for (int d = 0; d < 16; ++d) {
+                    if (d < dn) {
+#pragma unroll
+                        for (int r = 0; r < BC_ROWS; ++r)
+                            cov_step<double, KIND>(cp, d, xc[d], sx[d * BC_LD + r], acc[r], uu[r]);
+                    }
+                }
+            } else {
+                for (int d = 0; d < dn; ++d) {
+                    const double xi = Xc[ii * D + d0 + d] * ism[d0 + d];
+#pragma unroll
+                    for (int r = 0; r < BC_ROWS; ++r)
+                        cov_step<double, KIND>(cp, d0 + d, xi, sx[d * BC_LD + r], acc[r], uu[r]);
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < BC_ROWS; ++r)
+            dot = fma(cov_finish<double, KIND>(cp, acc[r], uu[r]), sB[wave * BC_ROWS + r], dot);
+    }
+    sP[wave][lane] = dot;
+    __syncthreads();
+    if (wave != 0 || !live) return;
+    const double ktb = (sP[0][lane] + sP[1][lane]) + (sP[2][lane] + sP[3][lane]);
+    double a0, u0;
+    cov_init<double, KIND>(cp, a0, u0);
+    for (int d = 0; d < D; ++d) cov_step<double, KIND>(cp, d, Xc[i * D + d] * ism[d], sJ[d], a0, u0);
+    // covariance of x and x_j under the real data, then under the earlier fantasies as well: c_t(x) of every earlier
+    // conditioning step t is kept, and  cov_t+1(x, x') = cov_t(x, x') - c_t(x) c_t(x') / d_t
+    double c = cov_finish<double, KIND>(cp, a0, u0) - ktb;
+    for (int t = 0; t < j - 1; ++t) {
+        const double* ct = st.chist + ((size_t)s * st.qcap + t) * st.m_pad;
+        c -= ct[i] * (ct[pj] / st.dhist[(size_t)s * st.qcap + t]);
+    }
+    st.chist[((size_t)s * st.qcap + (j - 1)) * st.m_pad + i] = c;
+
+    const size_t at = (size_t)s * st.m_pad + i;
+    const double dd = st.scal[2 * s], gain = st.scal[2 * s + 1], eta = st.eta[s];
+    const double vl = st.var_lat[at] - c * c / dd;
+    st.var_lat[at] = vl;
+    double mt;
+    if (fantasy_kind == ROBO_FANTASY_KRIGING_BELIEVER) {
+        mt = st.mean_t[at];                       // innovation exactly 0: the mean state is not rewritten
+    } else {
+        const double ml = st.mu_lat[at] + c * gain;
+        st.mu_lat[at] = ml;
+        mt = ml * y_std + y_mean;
+        st.mean_t[at] = mt;
+    }
+    double vt = vl * (y_std * y_std);
+    const double eps = 2.220446049250313e-16;
+    vt = vt < eps ? eps : vt;                     // np.clip(var, eps, inf); NaN propagates like np.clip
+    if (st.trace) {
+        double* row = st.trace + (((size_t)j * st.S + s) * st.m + i) * 2;
+        row[0] = mt;
+        row[1] = vt;
+    }
+    unsigned f = 0;
+    double a;
+    if (acq_kind == ROBO_ACQ_EI) {
+        a = acq_ei(mt, vt, eta, par);
+        if (a < 0.0 && a > -2.2250738585072014e-308) a = 0.0;    // as acq_kernel
+        if (a < 0.0) f |= ROBO_FLAG_NEGATIVE_EI;
+    } else if (acq_kind == ROBO_ACQ_LOG_EI) {
+        a = acq_log_ei(mt, vt, eta, par);
+    } else if (acq_kind == ROBO_ACQ_PI) {
+        a = acq_pi(mt, vt, eta, par);
+    } else {
+        a = acq_lcb(mt, vt, par);
+    }
+    if (sqrt(vt) == 0.0) f |= ROBO_FLAG_ZERO_SIGMA;
+    if (isnan(a)) f |= ROBO_FLAG_NAN;
+    if (f != 0) atomicOr(&st.flg[j], f);
+    if (s == 0) acq_sum[i] = a;
+    else acq_sum[i] += a;
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------------
+int batch_alloc(robo_ctx* ctx, int64_t m, int64_t m_pad, int S, int n_pad, int q, BatchWork** out) {
+    BatchWork* w = new BatchWork();
+    memset(w, 0, sizeof(*w));
+    w->m = m;
+    w->S = S;
+    w->n_pad = n_pad;
+    w->q = q;
+    size_t bytes = 0;
+    auto take = [&bytes](size_t n) {
+        const size_t at = bytes;
+        bytes += (n + 15) / 16 * 16;
+        return at;
+    };
+    const size_t sm = (size_t)S * m_pad * 8, sn = (size_t)S * n_pad * 8;
+    const size_t o_mu = take(sm), o_var = take(sm), o_mt = take(sm), o_w = take(sn), o_v = take(sn), o_beta = take(sn);
+    const size_t o_ch = take((size_t)S * q * m_pad * 8), o_dh = take((size_t)S * q * 8);
+    const size_t o_scal = take((size_t)2 * S * 8), o_eta = take((size_t)S * 8), o_val = take((size_t)q * 8);
+    const size_t o_fant = take((size_t)q * S * 8), o_idx = take((size_t)q * 8), o_flg = take((size_t)q * 4), o_int = take(16);
+    if (hipMalloc((void**)&w->d_block, bytes) != hipSuccess) {
+        set_error("hipMalloc of %zu bytes failed (batch selection state)", bytes);
+        delete w;
+        return ROBO_RUNTIME_ERROR;
+    }
+    // everything a call reports (values, fantasies, indices, flags, picks made) is one contiguous range: ONE copy into
+    // pinned memory, as the sweep's own report
+    w->rep_off = o_val;
+    w->rep_bytes = bytes - o_val;
+    w->off_fant = o_fant - o_val;
+    w->off_idx = o_idx - o_val;
+    w->off_flg = o_flg - o_val;
+    w->off_int = o_int - o_val;
+    if (hipHostMalloc((void**)&w->h_report, w->rep_bytes) != hipSuccess) {
+        set_error("hipHostMalloc of %zu bytes failed (batch selection report)", w->rep_bytes);
+        hipFree(w->d_block);
+        delete w;
+        return ROBO_RUNTIME_ERROR;
+    }
+    char* b = w->d_block;
+    BatchState& st = w->st;
+    st.S = S;
+    st.q = q;
+    st.m = m;
+    st.m_pad = m_pad;
+    st.mu_lat = (double*)(b + o_mu);
+    st.var_lat = (double*)(b + o_var);
+    st.mean_t = (double*)(b + o_mt);
+    st.w = (double*)(b + o_w);
+    st.v = (double*)(b + o_v);
+    st.beta = (double*)(b + o_beta);
+    st.chist = (double*)(b + o_ch);
+    st.dhist = (double*)(b + o_dh);
+    st.qcap = q;
+    st.scal = (double*)(b + o_scal);
+    st.eta = (double*)(b + o_eta);
+    st.val = (double*)(b + o_val);
+    st.fant = (double*)(b + o_fant);
+    st.idx = (long long*)(b + o_idx);
+    st.flg = (unsigned*)(b + o_flg);
+    st.n_made = (int*)(b + o_int);
+    st.stop = st.n_made + 1;
+    st.trace = nullptr;
+    (void)ctx;
+    *out = w;
+    return ROBO_OK;
+}
+
+void batch_free(BatchWork* w) {
+    if (!w) return;
+    hipFree(w->d_block);
+    hipFree(w->d_trace);
+    if (w->h_report) hipHostFree(w->h_report);
+    delete w;
+}
+
+int batch_ensure_trace(BatchWork* w, size_t doubles) {
+    if (doubles > w->trace_cap) {
+        if (w->d_trace) ROBO_HIP_CHECK(hipFree(w->d_trace));
+        w->d_trace = nullptr;
+        w->trace_cap = 0;
+        ROBO_HIP_CHECK(hipMalloc((void**)&w->d_trace, doubles * sizeof(double)));
+        w->trace_cap = doubles;
+    }
+    return ROBO_OK;
+}
+
+int launch_batch_reset(robo_ctx* ctx, const BatchState& st) {
+    hipLaunchKernelGGL(batch_reset_kernel, dim3((unsigned)((st.q * st.S + 255) / 256)), dim3(256), 0, ctx->stream, st);
+    ROBO_LAUNCH_CHECK();
+    return ROBO_OK;
+}
+
+int launch_batch_init(robo_gp* gp, const BatchState& st, const robo_cand* cand, int s, double eta) {
+    hipLaunchKernelGGL(batch_init_kernel, dim3((unsigned)((st.m + 255) / 256)), dim3(256), 0, gp->ctx->stream, st, s,
+                       (const double*)cand->d_q, (const double*)cand->d_mu, (const double*)cand->d_mean,
+                       (const double*)cand->d_var, (const double*)cand->d_Xc, (const double*)gp->d_theta, gp->cov,
+                       gp->mean_c, eta);
+    ROBO_LAUNCH_CHECK();
+    return ROBO_OK;
+}
+
+int launch_batch_record(robo_ctx* ctx, const BatchState& st, const robo_cand* cand, int j, bool take_flags) {
+    hipLaunchKernelGGL(batch_record_kernel, dim3(1), dim3(64), 0, ctx->stream, st, j,
+                       (const double*)(cand->d_part_val + cand->n_part), (const long long*)(cand->d_part_idx + cand->n_part),
+                       take_flags ? cand->d_flags : nullptr);
+    ROBO_LAUNCH_CHECK();
+    return ROBO_OK;
+}
+
+// one conditioning step of sample s for pick j >= 1: k_*(x_j) and the scalars, beta, the pass over the candidates
+int launch_batch_condition(robo_gp* gp, const BatchState& st, const robo_cand* cand, int s, int j, int acq_kind, double par,
+                           int fantasy_kind, double liar) {
+    hipStream_t stream = gp->ctx->stream;
+    const int n = gp->n, n_pad = gp->n_pad, nbk = (n + NB - 1) / NB;
+    const double* Xc = cand->d_Xc;
+    const double* Xs = gp->d_Xs;
+    const double* ism = gp->d_theta;
+    double* w = st.w + (size_t)s * n_pad;
+    double* v = st.v + (size_t)s * n_pad;
+    double* beta = st.beta + (size_t)s * n_pad;
+    hipLaunchKernelGGL(batch_kstar_kernel, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, stream, st, s, j, Xc, Xs, ism,
+                       gp->cov, n, n_pad, gp->noise, gp->y_mean, gp->y_std, fantasy_kind, liar);
+    for (int i = 0; i < nbk; ++i)
+        hipLaunchKernelGGL(batch_fwd_kernel, dim3((unsigned)(nbk - 1 - i > 1 ? nbk - 1 - i : 1)), dim3(256), 0, stream,
+                           (const double*)gp->d_K, n_pad, (const double*)gp->d_Linv, w, v, i, n, (const int*)st.stop);
+    for (int i = nbk - 1; i >= 0; --i)
+        hipLaunchKernelGGL(batch_bwd_kernel, dim3((unsigned)(i > 1 ? i : 1)), dim3(256), 0, stream, (const double*)gp->d_K,
+                           n_pad, (const double*)gp->d_Linv, v, beta, i, n, (const int*)st.stop);
+    const dim3 grid((unsigned)((st.m + BC_CAND - 1) / BC_CAND));
+#define ROBO_COND_CALL(KIND)                                                                                              \
+    do {                                                                                                                  \
+        if (gp->dim <= 16)                                                                                                \
+            hipLaunchKernelGGL((batch_cond_kernel<KIND, true>), grid, dim3(256), 0, stream, st, s, j, Xc, Xs, ism, gp->cov, n, \
+                               n_pad, gp->y_mean, gp->y_std, acq_kind, par, fantasy_kind, cand->d_acq_sum);               \
+        else                                                                                                              \
+            hipLaunchKernelGGL((batch_cond_kernel<KIND, false>), grid, dim3(256), 0, stream, st, s, j, Xc, Xs, ism, gp->cov, n, \
+                               n_pad, gp->y_mean, gp->y_std, acq_kind, par, fantasy_kind, cand->d_acq_sum);               \
+    } while (0)
+    if (gp->kind == ROBO_KERNEL_MATERN52_ARD) ROBO_COND_CALL(ROBO_KERNEL_MATERN52_ARD);
+    else if (gp->kind == ROBO_KERNEL_RBF_ARD) ROBO_COND_CALL(ROBO_KERNEL_RBF_ARD);
+    else ROBO_COND_CALL(ROBO_KERNEL_FABOLAS);
+#undef ROBO_COND_CALL
+    ROBO_LAUNCH_CHECK();
+    return ROBO_OK;
+}
+
+}  // namespace robo

@@ -220,6 +220,39 @@ struct RefineWork {
 int refine_alloc(robo_ctx* ctx, int K, int D, RefineWork** out);
 void refine_free(RefineWork* w);               // the state block and the trace; `ws` belongs to the caller
 int refine_ensure_trace(RefineWork* w, size_t doubles);
+
+// ---- greedy batch proposals with fantasised picks (batch.hip) -----------------------------------------------------------------
+// the state of one selection; all arrays device memory of one block, per-sample arrays [S][m_pad] / [S][n_pad]
+constexpr int BATCH_MAX_Q = 1024;   // picks per call: the c_t history is S x q x m doubles
+struct BatchState {
+    int S, q, qcap;                 // qcap: picks the history arrays were sized for
+    long long m, m_pad;
+    double *mu_lat, *var_lat;       // latent moments of every candidate (before the output transform, never floored)
+    double* mean_t;                 // transformed mean: the sweep's own bits until a conditioning step moves the mean
+    double *w, *v, *beta;           // k_*(x_j) -> L^-1 k_*(x_j) -> K^-1 k_*(x_j)
+    double* chist;                  // [S][qcap][m_pad] c_t(x) of every conditioning step so far
+    double* dhist;                  // [S][qcap] its d_t
+    double* scal;                   // [S][2]: d, (y_f - mu(x_j)) / d of the current conditioning step
+    double* eta;                    // [S] incumbent per sample, lowered by every fantasy
+    double *val, *fant;             // [q] winning values, [q][S] fantasy targets
+    long long* idx;                 // [q] picks (-1: none)
+    unsigned* flg;                  // [q] ROBO_FLAG_* of every pick's values
+    int *n_made, *stop;             // picks recorded; a NaN winner ended the selection
+    double* trace;                  // q x S x m x 2 transformed, floored (mean, var) every pick was made from, or nullptr
+};
+struct BatchWork {
+    int64_t m;
+    int S, n_pad, q;
+    char* d_block;
+    double* d_trace;
+    size_t trace_cap;               // doubles
+    char* h_report;                 // pinned copy of the block's tail [val | fant | idx | flg | n_made, stop]: one D2H per call
+    size_t rep_off, rep_bytes, off_fant, off_idx, off_flg, off_int;
+    BatchState st;
+};
+int batch_alloc(robo_ctx* ctx, int64_t m, int64_t m_pad, int S, int n_pad, int q, BatchWork** out);
+void batch_free(BatchWork* w);
+int batch_ensure_trace(BatchWork* w, size_t doubles);
 }  // namespace robo
 
 constexpr int ROBO_AUX_STREAMS = 3;
@@ -311,6 +344,7 @@ struct robo_gp {
     double* h_wnorm;                // pinned copy of the two norms (written by an asynchronous copy behind the build)
     unsigned long long winv_launched;   // fit_gen whose W build has been LAUNCHED (robo_gp_prefetch_inverse) but not yet read
     robo::RefineWork* refine;       // state + solve workspace of robo_acq_refine_* (refine.hip), kept between calls of one (K, D)
+    robo::BatchWork* batch;         // state of robo_acq_batch_* (batch.hip), kept between calls of one (m, S)
 };
 
 struct robo_cand {
@@ -437,6 +471,13 @@ int launch_refine_select(robo_ctx* ctx, const RefineState& st, const double* d_v
 int launch_refine_eval(robo_gp* gp, const RefineState& st, const robo_cand* ws, int acq_kind, double par, double eta, int s,
                        int S, int t, int T);
 int launch_refine_result(robo_ctx* ctx, const RefineState& st, unsigned* d_cand_flags, bool sweep_only);
+// batch.hip: outputs to "no pick"; a sample's latent moments after its posterior; the reduction's winner -> pick j; one
+// conditioning step (k_*(x_j), beta, the pass over the candidates) of sample s for pick j >= 1
+int launch_batch_reset(robo_ctx* ctx, const BatchState& st);
+int launch_batch_init(robo_gp* gp, const BatchState& st, const robo_cand* cand, int s, double eta);
+int launch_batch_record(robo_ctx* ctx, const BatchState& st, const robo_cand* cand, int j, bool take_flags);
+int launch_batch_condition(robo_gp* gp, const BatchState& st, const robo_cand* cand, int s, int j, int acq_kind, double par,
+                           int fantasy_kind, double liar);
 int launch_acq(robo_ctx* ctx, robo_cand* cand, int acq_kind, double par, double eta, bool accumulate, bool first);
 int launch_argmax(robo_cand* cand, const double* d_vals, double scale);
 int launch_report_best(robo_cand* cand, double* h_pinned);

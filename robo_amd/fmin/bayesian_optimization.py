@@ -33,7 +33,7 @@ logger = logging.getLogger(__name__)
 def bayesian_optimization(objective_function, lower, upper, num_iterations=30, X_init=None, Y_init=None,
                           maximizer="random", acquisition_func="log_ei", model_type="gp_mcmc", n_init=3, rng=None,
                           output_path=None, n_candidates=500, chain_length=200, burnin_steps=100, n_gpus=None,
-                          devices=None):
+                          devices=None, batch_size=1, fantasy="kriging_believer", liar="min", evaluate_batch=None):
     """Minimise ``objective_function`` over the box [lower, upper] -> dict with x_opt, f_opt,
     incumbents, incumbent_values, runtime, overhead, X, y (same keys as the reference).
 
@@ -93,8 +93,11 @@ def bayesian_optimization(objective_function, lower, upper, num_iterations=30, X
     else:
         raise ValueError("'{}' is not a valid function to maximize the acquisition function".format(maximizer))
 
+    # batch_size > 1: rounds of batch_size proposals from one model fit (greedy selection with fantasised picks on the
+    # device), evaluated one by one or by evaluate_batch(Xq) -> yq; batch_size = 1 is the reference's loop, untouched
+    batch = {} if batch_size == 1 else dict(batch_size=batch_size, fantasy=fantasy, liar=liar, evaluate_batch=evaluate_batch)
     bo = BayesianOptimization(objective_function, lower, upper, acq, model, max_func, initial_points=n_init, rng=rng,
-                              initial_design=init_latin_hypercube_sampling, output_path=output_path)
+                              initial_design=init_latin_hypercube_sampling, output_path=output_path, **batch)
     x_best, f_min = bo.run(num_iterations, X=X_init, y=Y_init)
 
     return {"x_opt": x_best, "f_opt": f_min,

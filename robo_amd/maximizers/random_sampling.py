@@ -65,6 +65,34 @@ class RandomSampling(BaseMaximizer):
         return X[y.argmax()]
 
 
+    def maximize_batch(self, q, fantasy="kriging_believer", liar=None):
+        """q proposals from ONE candidate draw (the same recipe and random streams as maximize()) by the acquisition's
+        greedy batch selection with fantasised picks (``select_batch``) -> (q', D).  q = 1 is maximize()."""
+        if int(q) == 1:
+            return np.asarray(self.maximize())[None, :]
+        if self.shard:
+            raise NotImplementedError("RandomSampling.maximize_batch: the candidate shard is not implemented for batches")
+        return _select_batch(self.objective_func, self.candidates(), q, fantasy, liar)
+
+
+def _select_batch(acq, X, q, fantasy, liar):
+    if not hasattr(acq, "select_batch"):
+        raise TypeError("%s has no select_batch" % type(acq).__name__)
+    return acq.select_batch(X, q, fantasy=fantasy, liar=liar)
+
+
+def _single_device_model(maximizer, what):
+    """the sub-model whose context holds the candidates; batches run on one device in one process"""
+    model = maximizer.objective_func.model
+    sub = model.models[0] if hasattr(model, "models") and len(model.models) > 0 else model
+    if not getattr(sub, "normalize_input", False) or not hasattr(sub, "gp"):
+        raise TypeError("%s needs a robo_amd GP model with normalize_input=True" % what)
+    if getattr(sub, "devices", None) or getattr(model, "devices", None) or maximizer.shard:
+        raise NotImplementedError("%s.maximize_batch runs on one device; multi-device and sharded batch selection is not "
+                                  "implemented" % what)
+    return model, sub
+
+
 class DeviceRandomSampling(BaseMaximizer):
     """Large-M variant of :class:`RandomSampling` whose candidates never exist on the host.
 
@@ -138,6 +166,24 @@ class DeviceRandomSampling(BaseMaximizer):
             cand.close()
 
 
+    def maximize_batch(self, q, fantasy="kriging_believer", liar=None):
+        """q proposals from ONE device-generated candidate batch (the recipe, the rng draw and the Philox seed of
+        maximize()) by greedy selection with fantasised picks -> (q', D).  q = 1 is maximize()."""
+        if int(q) == 1:
+            return np.asarray(self.maximize())[None, :]
+        from robo_amd import _lib
+        model, sub = _single_device_model(self, "DeviceRandomSampling")
+        lower, upper = np.asarray(sub.lower, dtype=np.float64), np.asarray(sub.upper, dtype=np.float64)
+        inc = np.asarray(model.get_incumbent()[0], dtype=np.float64)
+        seed = int(self.rng.randint(0, 2 ** 31 - 1))
+        cand = _lib.Candidates(sub.gp.ctx, m=max(self.n_samples, 1), seed=seed, n_uniform=int(self.n_samples * .7),
+                               loc=(inc - lower) / (upper - lower), scale=0.1 / (upper - lower))
+        try:
+            return _select_batch(self.objective_func, cand, q, fantasy, liar)
+        finally:
+            cand.close()
+
+
 class DeviceSobolSampling(BaseMaximizer):
     """Acquisition maximisation over the first ``n_samples`` points of a scrambled Sobol' sequence in the box,
     generated on the device (BASELINE config 5: 2^20 candidates in 64 dimensions -- 537 MB that never exist on the
@@ -190,5 +236,20 @@ class DeviceSobolSampling(BaseMaximizer):
                          < sharding.shard_range(self.n_samples, r, world)[1]][0]
                 point = points[owner]
             return lower + (upper - lower) * point
+        finally:
+            cand.close()
+
+    def maximize_batch(self, q, fantasy="kriging_believer", liar=None):
+        """q proposals from the same Sobol' points as maximize() by greedy selection with fantasised picks -> (q', D).
+        q = 1 is maximize()."""
+        if int(q) == 1:
+            return np.asarray(self.maximize())[None, :]
+        from scipy.stats import qmc
+        from robo_amd import _lib
+        model, sub = _single_device_model(self, "DeviceSobolSampling")
+        eng = qmc.Sobol(d=np.asarray(sub.lower).shape[0], scramble=True, seed=self.seed)
+        cand = _lib.Candidates(sub.gp.ctx, m=max(self.n_samples, 1), sobol=eng, first=0)
+        try:
+            return _select_batch(self.objective_func, cand, q, fantasy, liar)
         finally:
             cand.close()

@@ -72,8 +72,16 @@ class BayesianOptimization(BaseSolver):
 
     def __init__(self, objective_func, lower, upper, acquisition_func, model, maximize_func,
                  initial_design=init_random_uniform, initial_points=3, output_path=None, train_interval=1,
-                 n_restarts=1, rng=None):
+                 n_restarts=1, rng=None, batch_size=1, fantasy="kriging_believer", liar="min", evaluate_batch=None):
         self.rng = np.random.RandomState(np.random.randint(100000)) if rng is None else rng
+        # batch_size > 1: a round trains once, takes batch_size proposals from maximize_func.maximize_batch (greedy
+        # selection with fantasised picks) and evaluates them one by one -- or all at once with evaluate_batch(Xq) -> yq
+        self.batch_size, self.fantasy, self.liar, self.evaluate_batch = int(batch_size), fantasy, liar, evaluate_batch
+        if self.batch_size < 1:
+            raise ValueError("batch_size must be >= 1")
+        if self.batch_size > 1 and not hasattr(maximize_func, "maximize_batch"):      # before anything is evaluated
+            raise TypeError("%s has no maximize_batch: batch_size > 1 needs RandomSampling, DeviceRandomSampling or "
+                            "DeviceSobolSampling" % type(maximize_func).__name__)
         self.model = model
         self.acquisition_func = acquisition_func
         self.maximize_func = maximize_func
@@ -170,6 +178,8 @@ class BayesianOptimization(BaseSolver):
         else:
             self.X, self.y = X, y
 
+        if self.batch_size > 1:
+            return self._run_batched(num_iterations)
         for it in range(self.init_points, num_iterations):
             logger.info("Start iteration %d ... ", it)
             t0 = time.time()
@@ -186,6 +196,53 @@ class BayesianOptimization(BaseSolver):
             if self.output_path is not None:
                 self.save_output(it)
         return self.incumbents[-1], self.incumbents_values[-1]
+
+    def _run_batched(self, num_iterations):
+        """rounds of up to batch_size proposals from ONE model fit; num_iterations still counts evaluations (the last
+        round is truncated) and every per-evaluation list keeps one entry per evaluation"""
+        if self._spmd() is not None:
+            raise NotImplementedError("batch_size > 1 runs in one process on one device; sharded runs are not implemented")
+        it, rnd = self.init_points, 0           # as the one-point loop counts: evaluations so far
+        while it < num_iterations:
+            n = min(self.batch_size, num_iterations - it)
+            logger.info("Start round %d (%d proposals) ... ", rnd, n)
+            t0 = time.time()
+            Xq = np.atleast_2d(self.choose_next_batch(self.X, self.y, n, do_optimize=(rnd % self.train_interval == 0)))
+            overhead = (time.time() - t0) / Xq.shape[0]
+            t0 = time.time()
+            if self.evaluate_batch is not None:
+                yq = np.asarray(self.evaluate_batch(Xq), dtype=np.float64).reshape(-1)
+                if yq.shape[0] != Xq.shape[0]:
+                    raise ValueError("evaluate_batch returned %d values for %d points" % (yq.shape[0], Xq.shape[0]))
+                t_eval = [(time.time() - t0) / Xq.shape[0]] * Xq.shape[0]
+            else:
+                yq, t_eval = [], []
+                for x in Xq:
+                    t1 = time.time()
+                    yq.append(self._evaluate(x))
+                    t_eval.append(time.time() - t1)
+            for x, v, te in zip(Xq, yq, t_eval):
+                self.time_overhead.append(overhead)
+                self.time_func_evals.append(te)
+                self.X = np.append(self.X, x[None, :], axis=0)
+                self.y = np.append(self.y, v)
+                self._record_incumbent(self.X, self.y)
+                if self.output_path is not None:
+                    self.save_output(it)
+                it += 1
+            rnd += 1
+        return self.incumbents[-1], self.incumbents_values[-1]
+
+    def choose_next_batch(self, X, y, n, do_optimize=True):
+        """Train the model once, update the acquisition function -> n proposals (n', D) from maximize_batch."""
+        if not hasattr(self.maximize_func, "maximize_batch"):
+            raise TypeError("%s has no maximize_batch: batch_size > 1 needs RandomSampling, DeviceRandomSampling or "
+                            "DeviceSobolSampling" % type(self.maximize_func).__name__)
+        if X is None or X.shape[0] == 1:
+            return self.initial_design(self.lower, self.upper, n, rng=self.rng)
+        self.model.train(X, y, do_optimize=do_optimize)
+        self.acquisition_func.update(self.model)
+        return self.maximize_func.maximize_batch(n, fantasy=self.fantasy, liar=self.liar)
 
     def choose_next(self, X=None, y=None, do_optimize=True):
         """Train the model, update the acquisition function, maximise it -> next point (D,)."""

@@ -1,0 +1,726 @@
+"""Greedy batch proposals with fantasised picks (robo_amd/csrc/batch.hip, robo_acq_batch_cand /
+robo_acq_batch_marginal_cand, DeviceGP.select_batch) against append-and-refit through tests/batch_oracle.py.
+
+Whole selections are not compared: a rounding-level difference may flip one argmax and send two correct selections
+apart.  Every pick is checked on its own, conditioned on the device's OWN earlier picks and fantasies: the traced
+(mean, var) against the oracle's refit, the winning value against the acquisition of the device's own moments, the
+incumbent rule, and -- for seeds on which the oracle shows no near tie -- the pick against the oracle's greedy choice.
+CPU: through the interpreter (tests/hipemu), small sizes.  -m gpu: the MI355X at N = 4096, D = 16, 65 536 candidates,
+q = 8, and the marginal form at N = 2048 with 3 hyper-parameter samples.
+
+Moment tolerances.  The state is conditioned with beta = K^-1 k_*(x_j), whose error grows with cond(K).  Measured
+against the refit oracle (max over all cases of this file, all picks):
+    interpreter, N = 80, noise 1e-2:   max |dmu| 1.3e-13, max |dvar| / k(x,x) 3.1e-15  (1.0e-13 / 2.2e-15 against an
+                                       np.longdouble restatement of the refit: the fp64 refit is no better than the device)
+    interpreter, N = 80, noise 1e-8:   1.2e-11, 4.0e-14   (cond(K) ~ 1e10)
+    MI355X, N = 4096, noise 1e-2:      2.0e-12, 4.4e-15   (profiles/batch_pytest_gpu.txt)
+The bounds below are those measurements times a head-room of about 10 for other inputs.
+"""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from robo_amd import _lib
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+import batch_oracle as BO  # noqa: E402
+from _tol import ACQ_RTOL, assert_logei_close  # noqa: E402
+from oracle import gp_oracle as O  # noqa: E402
+
+BATCH_MU_ATOL = 2e-12            # |mean - refit mean|, O(1) targets
+BATCH_VAR_ATOL_REL_AMP = 5e-14   # |var - refit var| / k(x, x)
+BATCH_MU_ATOL_NOISE_1E8, BATCH_VAR_ATOL_REL_AMP_NOISE_1E8 = 2e-10, 5e-13     # the noise 1e-8 edge
+BATCH_MU_ATOL_GPU = 2e-11        # N = 4096 / 2048, noise 1e-2 .. 3e-2
+BATCH_VAR_ATOL_REL_AMP_GPU = 5e-14
+
+SMALL = dict(N=80, D=3, M=400, q=5)
+LARGE = dict(N=4096, D=16, M=65536, q=8)
+LARGE_MARGINAL = dict(N=2048, D=16, M=65536, q=4)
+ACQS = (("ei", 0.0), ("log_ei", 0.0), ("pi", 0.0), ("lcb", 1.0))
+
+
+@pytest.fixture(scope="module")
+def emu_ctx():
+    sys.path.insert(0, os.path.join(HERE, "hipemu"))
+    import build_emu
+    _lib.use_library(build_emu.build())
+    ctx = _lib.Context(0)
+    assert "hipemu" in ctx.name
+    yield ctx
+    ctx.close()
+    _lib.use_library(None)
+
+
+@pytest.fixture(scope="module")
+def gpu_ctx():
+    _lib.use_library(None)
+    if _lib.device_count() < 1:
+        pytest.skip("no HIP device")
+    yield _lib.default_context()
+
+
+# ---- helpers ---------------------------------------------------------------------------------------------------------
+def _theta(D, ls2, noise=1e-2, kind="matern52"):
+    if kind == "fabolas":
+        ls2 = ls2 if np.ndim(ls2) == 0 else np.asarray(ls2)[:D - 1]
+        return np.concatenate([[0.0], np.log(np.broadcast_to(ls2, (D - 1,))), [np.log(0.5), np.log(0.8)], [np.log(noise)]])
+    return np.concatenate([[0.0], np.log(np.broadcast_to(ls2, (D,))), [np.log(noise)]])
+
+
+def _data(N, D, seed):
+    rs = np.random.RandomState(seed)
+    X = rs.rand(N, D)
+    y = np.sin(3 * X.sum(axis=1) / np.sqrt(D / 3.0)) + 0.1 * rs.randn(N)
+    return rs, X, y
+
+
+def _ls2(D):
+    return np.array([0.3, 0.5, 0.8, 0.4, 0.6])[:D] if D <= 5 else 0.25 * D
+
+
+def _pair(ctx, kind, theta, X, y, y_mean=0.0, y_std=1.0):
+    """the same GP frozen for the oracle and fitted on the device; y is the latent target vector"""
+    mean = float(np.mean(y))
+    og = BO.FrozenGP(kind, theta, X, y, mean, y_mean, y_std)
+    g = _lib.DeviceGP(ctx, kind, X.shape[0], X.shape[1])
+    g.set_data(X, y)
+    g.set_output_transform(y_mean, y_std)
+    g.fit(theta, mean)
+    return og, g
+
+
+def _setup(ctx, sz, kernel="matern52", seed=0, noise=1e-2, transform=(0.0, 1.0)):
+    D = sz["D"]
+    rs, X, y = _data(sz["N"], D, seed)
+    og, g = _pair(ctx, kernel, _theta(D, _ls2(D), noise, kernel), X, y, *transform)
+    return rs, og, g, float(y.min() * transform[1] + transform[0]), rs.rand(sz["M"], D)
+
+
+def _check_each_pick(r, ogs, Xc, kind, par, etas, fantasy, liar, mu_atol, var_rel, label="", longdouble=False):
+    """every pick of a BatchResult with diagnostics on its own, given the device's own history"""
+    S, M = len(ogs), Xc.shape[0]
+    etas = np.array(np.broadcast_to(etas, (S,)), dtype=np.float64)
+    hist = [[] for _ in range(S)]
+    worst_mu = worst_var = worst_mu_ld = worst_var_ld = 0.0
+    assert r.n_made >= 1 and np.all(r.indices[:r.n_made] >= 0) and np.all(r.indices[r.n_made:] == -1)
+    for j in range(r.n_made):
+        means, vars_ = r.trace[j, :, :, 0], r.trace[j, :, :, 1]
+        for s, og in enumerate(ogs):
+            amp = O.kernel_diag(og.kind, og.theta[:-1], Xc) * og.y_std ** 2
+            mo, vo = og.refit(Xc, hist[s])
+            worst_mu = max(worst_mu, np.abs(means[s] - mo).max())
+            worst_var = max(worst_var, (np.abs(vars_[s] - vo) / amp).max())
+            if longdouble:
+                ml, vl = og.refit_longdouble(Xc, hist[s])
+                ml, vl = og.transform(ml, vl)
+                worst_mu_ld = max(worst_mu_ld, float(np.abs(means[s] - ml).max()))
+                worst_var_ld = max(worst_var_ld, float((np.abs(vars_[s] - vl) / amp).max()))
+            np.testing.assert_allclose(means[s], mo, rtol=0, atol=mu_atol * max(1.0, og.y_std))
+            assert np.all(np.abs(vars_[s] - vo) <= var_rel * amp)
+        # the value follows from the device's own moments; the pick is their argmax
+        a = BO.marginal_values(kind, par, etas, means, vars_)
+        i = int(r.indices[j])
+        if kind == "log_ei" and S == 1:
+            z = (etas[0] - par - means[0]) / np.sqrt(vars_[0])
+            assert_logei_close(np.array([r.values[j]]), a[i:i + 1], z[i:i + 1], rtol=ACQ_RTOL, tail_rtol=ACQ_RTOL)
+        else:
+            np.testing.assert_allclose(r.values[j], a[i], rtol=ACQ_RTOL, atol=0)
+        top = np.nanmax(a)
+        assert a[i] >= top - ACQ_RTOL * abs(top), (j, i, a[i], top)
+        first = np.flatnonzero((means == means[:, i:i + 1]).all(axis=0) & (vars_ == vars_[:, i:i + 1]).all(axis=0))[0]
+        assert i == first, (j, i, first)           # identical moments give identical values: the first index wins
+        # the fantasy and the incumbent rule
+        if j + 1 < r.n_made:
+            yf = r.fantasies[j]
+            if fantasy == "kriging_believer":
+                np.testing.assert_array_equal(yf, means[:, i])
+            else:
+                np.testing.assert_array_equal(yf, np.full(S, liar))
+            for s in range(S):
+                hist[s].append((Xc[i], yf[s]))
+            etas = np.minimum(etas, yf)
+        else:
+            assert np.all(np.isnan(r.fantasies[j]))
+    print("%s %s %s: %d picks, max |dmu| %.3e, max |dvar| / k(x,x) %.3e%s"
+          % (label, kind, fantasy, r.n_made, worst_mu, worst_var,
+             " (longdouble: %.3e, %.3e)" % (worst_mu_ld, worst_var_ld) if longdouble else ""))
+    return worst_mu, worst_var
+
+
+# ---- 1. the oracle on its own ----------------------------------------------------------------------------------------
+def test_oracle_rank_one_equals_refit():
+    for kernel in ("matern52", "rbf", "fabolas"):
+        for fantasy in ("kriging_believer", "constant_liar"):
+            _oracle_rank_one_equals_refit(kernel, fantasy)
+
+
+def _oracle_rank_one_equals_refit(kernel, fantasy):
+    rs, X, y = _data(60, 3, 3)
+    og = BO.FrozenGP(kernel, _theta(3, [0.3, 0.5, 0.8], kind=kernel), X, (y - 0.3) / 1.7, float(np.mean((y - 0.3) / 1.7)),
+                     0.3, 1.7)
+    Xc = rs.rand(50, 3)
+    ro = BO.RankOne(og, Xc)
+    hist = []
+    for j in (7, 21, 7, 40):                    # a point picked twice: collapsed variance, still consistent
+        m, _ = ro.moments()
+        yf = m[j] if fantasy == "kriging_believer" else float(y.min())
+        ro.condition(j, yf)
+        hist.append((Xc[j], yf))
+        mo, vo = og.refit(Xc, hist)
+        m, v = ro.moments()
+        np.testing.assert_allclose(m, mo, rtol=0, atol=1e-11)
+        np.testing.assert_allclose(v, vo, rtol=0, atol=1e-11)
+        ml, vl = og.transform(*og.refit_longdouble(Xc, hist))
+        np.testing.assert_allclose(mo, ml.astype(np.float64), rtol=0, atol=1e-11)
+        np.testing.assert_allclose(vo, vl.astype(np.float64), rtol=0, atol=1e-11)
+
+
+# ---- 2. q = 1 and pick 0 are the sweep -----------------------------------------------------------------------------------
+def _check_first_pick(ctx, sz, marginal_sz=None):
+    rs, og, g, eta, Xc = _setup(ctx, sz)
+    cand = _lib.Candidates(ctx, Xc)
+    try:
+        for kind, par in ACQS:
+            _, mx, am, fl = g.acq(kind, par, eta, cand, want_values=False)
+            for q in (1, 3):
+                r = g.select_batch(kind, par, eta, cand, q)
+                assert r.indices[0] == am and r.flags[0] == fl
+                assert np.array([r.values[0]]).tobytes() == np.array([mx]).tobytes()
+    finally:
+        cand.close()
+        g.close()
+    gps, ogs, etas, Xc = _marginal_setup(ctx, marginal_sz or sz)
+    cand = _lib.Candidates(ctx, Xc)
+    try:
+        for kind, par in ACQS[:2]:
+            _, mx, am, fl = _lib.acq_marginal(gps, kind, par, etas, cand, want_values=False)
+            for q in (1, 2):
+                r = _lib.acq_batch(gps, kind, par, etas, cand, q)
+                assert r.indices[0] == am and r.flags[0] == fl
+                assert np.array([r.values[0]]).tobytes() == np.array([mx]).tobytes()
+    finally:
+        cand.close()
+        for g in gps:
+            g.close()
+
+
+def _marginal_setup(ctx, sz, S=3):
+    D = sz["D"]
+    rs, X, y = _data(sz["N"], D, 11)
+    gps, ogs = [], []
+    for s in range(S):
+        theta = _theta(D, _ls2(D) * (0.8 + 0.2 * s), noise=1e-2 * (1 + s))
+        theta[0] = 0.1 * s
+        og, g = _pair(ctx, "matern52", theta, X, y)
+        gps.append(g)
+        ogs.append(og)
+    etas = np.array([y.min() - 0.01 * s for s in range(S)])
+    return gps, ogs, etas, rs.rand(sz["M"], D)
+
+
+def _first_pick_is_the_sweep_emu_small(emu_ctx):
+    _check_first_pick(emu_ctx, SMALL)
+
+
+@pytest.mark.gpu
+def test_first_pick_is_the_sweep_gpu(gpu_ctx):
+    _check_first_pick(gpu_ctx, LARGE, LARGE_MARGINAL)
+
+
+# ---- 3. + 5. every pick on its own; properties ---------------------------------------------------------------------------
+def _check_properties(r, og, fantasy):
+    mean, var = r.trace[:, 0, :, 0], r.trace[:, 0, :, 1]
+    n = r.n_made
+    if fantasy == "kriging_believer":
+        for j in range(1, n):
+            assert mean[j].tobytes() == mean[0].tobytes()          # innovation exactly 0: no rounding in the mean
+    assert np.all(var[1:n] <= var[:n - 1])
+    for j in range(n - 1):
+        i = int(r.indices[j])
+        v = var[j, i] / og.y_std ** 2
+        if v > 1e-12:                                              # (on the floor the latent value is not in the trace)
+            want = v * og.d0 / (v + og.d0)
+            # two variances within the moment bound each, and the quotient's own rounding
+            assert abs(var[j + 1, i] / og.y_std ** 2 - want) <= 2 * BATCH_VAR_ATOL_REL_AMP_GPU * np.exp(og.theta[0]) + 1e-14 * want
+
+
+def _check_picks(ctx, sz, kernel, fantasies, acqs, mu_atol, var_rel, label, longdouble=False, transform=(0.0, 1.0)):
+    rs, og, g, eta, Xc = _setup(ctx, sz, kernel, transform=transform)
+    Xc[9] = Xc[4]                                    # duplicated candidate rows
+    cand = _lib.Candidates(ctx, Xc)
+    worst = [0.0, 0.0]
+    try:
+        for fantasy in fantasies:
+            liar = eta
+            for kind, par in acqs:
+                r = g.select_batch(kind, par, eta, cand, sz["q"], fantasy, liar, diagnostics=True)
+                assert r.n_made == sz["q"]
+                w = _check_each_pick(r, [og], Xc, kind, par, eta, fantasy, liar, mu_atol, var_rel, label, longdouble)
+                worst = [max(a, b) for a, b in zip(worst, w)]
+                _check_properties(r, og, fantasy)
+    finally:
+        cand.close()
+        g.close()
+    return worst
+
+
+def _every_pick_emu_small(emu_ctx, kernel):
+    _check_picks(emu_ctx, SMALL, kernel, ("kriging_believer", "constant_liar"), ACQS if kernel == "matern52" else ACQS[:1],
+                 BATCH_MU_ATOL, BATCH_VAR_ATOL_REL_AMP, "emu " + kernel, longdouble=True)
+
+
+def _every_pick_with_output_transform_emu_small(emu_ctx):
+    _check_picks(emu_ctx, SMALL, "matern52", ("kriging_believer", "constant_liar"), ACQS[:1], BATCH_MU_ATOL,
+                 BATCH_VAR_ATOL_REL_AMP, "emu transform", transform=(0.4, 1.6))
+
+
+def _every_pick_beyond_16_dimensions_emu(emu_ctx):
+    """the conditioning pass re-reads the candidate per chunk of 16 dimensions; two block rows of the factor"""
+    _check_picks(emu_ctx, dict(N=150, D=19, M=200, q=3), "matern52", ("constant_liar",), ACQS[:1], BATCH_MU_ATOL,
+                 BATCH_VAR_ATOL_REL_AMP, "emu D=19")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("fantasy", ["kriging_believer", "constant_liar"])
+def test_every_pick_gpu(gpu_ctx, fantasy):
+    _check_picks(gpu_ctx, LARGE, "matern52", (fantasy,), ACQS[:1], BATCH_MU_ATOL_GPU, BATCH_VAR_ATOL_REL_AMP_GPU, "gpu")
+
+
+# ---- 4. against the oracle's own greedy choice -----------------------------------------------------------------------------
+def _check_against_greedy(ctx, sz, seeds, tol):
+    left_out = total = 0
+    for seed in seeds:
+        rs, og, g, eta, Xc = _setup(ctx, sz, seed=seed)
+        cand = _lib.Candidates(ctx, Xc)
+        try:
+            for fantasy in ("kriging_believer", "constant_liar"):
+                r = g.select_batch("ei", 0.0, eta, cand, sz["q"], fantasy, eta)
+                hist, e = [], eta
+                for j in range(sz["q"]):                    # the oracle's choice given the DEVICE's history
+                    m, v = og.refit(Xc, hist)
+                    a = BO.acquisition("ei", 0.0, e, m, v)
+                    top = np.sort(a)[-2:]
+                    total += 1
+                    if top[1] - top[0] <= tol * abs(top[1]):
+                        left_out += 1
+                    else:
+                        assert int(r.indices[j]) == O.np_argmax(a), (seed, fantasy, j)
+                    yf = r.fantasies[j, 0]
+                    hist.append((Xc[int(r.indices[j])], yf))
+                    e = min(e, yf) if j + 1 < sz["q"] else e
+        finally:
+            cand.close()
+            g.close()
+    assert left_out == 0, (left_out, total)       # the committed seeds show no near tie in the oracle
+
+
+def _picks_equal_the_oracles_greedy_choice_emu_small(emu_ctx):
+    _check_against_greedy(emu_ctx, SMALL, (0, 1, 2), ACQ_RTOL)
+
+
+# ---- 6. edges --------------------------------------------------------------------------------------------------------------
+def _edges_emu_small(emu_ctx):
+    ctx, sz = emu_ctx, SMALL
+    # noise 1e-8; a candidate equal to a training point (variance on the floor at once)
+    rs, og, g, eta, Xc = _setup(ctx, sz, noise=1e-8)
+    Xc[5] = og.X[3]
+    cand = _lib.Candidates(ctx, Xc)
+    try:
+        for fantasy in ("kriging_believer", "constant_liar"):
+            r = g.select_batch("ei", 0.0, eta, cand, 4, fantasy, eta, diagnostics=True)
+            _check_each_pick(r, [og], Xc, "ei", 0.0, eta, fantasy, eta, BATCH_MU_ATOL_NOISE_1E8,
+                             BATCH_VAR_ATOL_REL_AMP_NOISE_1E8, "emu noise 1e-8")
+            r2 = g.select_batch("ei", 0.0, eta, cand, 4, fantasy, eta, diagnostics=True)     # the state is reused
+            for a, b in ((r.indices, r2.indices), (r.values, r2.values), (r.trace, r2.trace), (r.fantasies, r2.fantasies)):
+                assert a.tobytes() == b.tobytes()
+        r = g.select_batch("lcb", 1.0, eta, cand, 4, "kriging_believer")
+        r3 = g.select_batch("lcb", 1.0, eta, cand, 2, "kriging_believer")                    # fewer picks, same state block
+        np.testing.assert_array_equal(r.indices[:2], r3.indices)
+        # argument errors
+        for q in (0, -1, sz["M"] + 1, 1025):
+            with pytest.raises(ValueError):
+                g.select_batch("ei", 0.0, eta, cand, q)
+        with pytest.raises(ValueError):
+            g.select_batch("ei", 0.0, eta, cand, 2, "thompson")
+        with pytest.raises(ValueError):
+            _lib.check(_lib.lib().robo_acq_batch_cand(g._h, 0, 0.0, eta, cand._h, 2, 7, 0.0, r.indices.ctypes.data_as(
+                _lib.C.POINTER(_lib.C.c_int64)), None, None, None, None, None))
+    finally:
+        cand.close()
+    # a NaN winner ends the selection: pick 0 already (a NaN candidate is np.argmax's winner)
+    Xn = rs.rand(40, sz["D"])
+    Xn[17, 1] = np.nan
+    few = _lib.Candidates(ctx, Xn)
+    try:
+        r = g.select_batch("ei", 0.0, eta, few, 3, diagnostics=True)
+        assert r.n_made == 1 and r.indices[0] == 17 and np.isnan(r.values[0]) and r.flags[0] & _lib.FLAG_NAN
+        np.testing.assert_array_equal(r.indices[1:], [-1, -1])
+        assert np.all(np.isnan(r.values[1:])) and np.all(np.isnan(r.fantasies))
+    finally:
+        few.close()
+        g.close()
+
+
+def _check_chunked(ctx, N, D, M, ws_blocks, q):
+    rs, og, g, eta, Xc = _setup(ctx, dict(N=N, D=D, M=M))
+    try:
+        ctx.set_tuning("ws_bytes", None)
+        c1 = _lib.Candidates(ctx, Xc)
+        r1 = g.select_batch("ei", 0.0, eta, c1, q, "constant_liar", eta, diagnostics=True)
+        c1.close()
+        n_pad = (N + 1 + 127) // 128 * 128
+        ctx.set_tuning("ws_bytes", ws_blocks * 128 * n_pad * 8)
+        c2 = _lib.Candidates(ctx, Xc)
+        r2 = g.select_batch("ei", 0.0, eta, c2, q, "constant_liar", eta, diagnostics=True)
+        assert c2.chunk() == ws_blocks * 128 and c2.chunk() < M
+        c2.close()
+    finally:
+        ctx.set_tuning("ws_bytes", None)
+        g.close()
+    for a, b in ((r1.indices, r2.indices), (r1.values, r2.values), (r1.trace, r2.trace), (r1.flags, r2.flags)):
+        assert a.tobytes() == b.tobytes()
+
+
+def _chunked_first_sweep_gives_the_same_bits_emu_small(emu_ctx):
+    _check_chunked(emu_ctx, 150, 3, 700, 2, 3)
+
+
+@pytest.mark.gpu
+def test_chunked_first_sweep_gives_the_same_bits_gpu(gpu_ctx):
+    _check_chunked(gpu_ctx, 1000, 6, 5000, 16, 4)
+
+
+# ---- 7. the marginal form ------------------------------------------------------------------------------------------------------
+def _check_marginal(ctx, sz, mu_atol, var_rel, label, S=3):
+    gps, ogs, etas, Xc = _marginal_setup(ctx, sz, S)
+    cand = _lib.Candidates(ctx, Xc)
+    try:
+        for fantasy in ("kriging_believer", "constant_liar"):
+            liar = float(etas[0])
+            r = _lib.acq_batch(gps, "ei", 0.0, etas, cand, sz["q"], fantasy, liar, diagnostics=True)
+            _check_each_pick(r, ogs, Xc, "ei", 0.0, etas, fantasy, liar, mu_atol, var_rel, label)
+            if fantasy == "kriging_believer":                  # per-sample fantasies
+                assert len(set(r.fantasies[0])) == S
+    finally:
+        cand.close()
+        for g in gps:
+            g.close()
+
+
+def _marginal_emu_small(emu_ctx):
+    _check_marginal(emu_ctx, SMALL, BATCH_MU_ATOL, BATCH_VAR_ATOL_REL_AMP, "emu marginal")
+
+
+@pytest.mark.gpu
+def test_marginal_gpu(gpu_ctx):
+    _check_marginal(gpu_ctx, LARGE_MARGINAL, BATCH_MU_ATOL_GPU, BATCH_VAR_ATOL_REL_AMP_GPU, "gpu marginal", S=3)
+
+
+# ---- 7b. independence from the explicit inverse W ------------------------------------------------------------------------------
+def _check_w_independence(ctx, N, D, M, q, mu_atol, var_rel, label):
+    """at a shape whose default sweep really goes through W = L^-1 (api.hip decide_winv: at most 32 768 candidates on a
+    factor of >= 6 block rows, or >= 3 for at most 8 candidates).  Three runs of the same call:
+      a  guard winv_cond_max = 0 on a factor whose W was never built     (sweep: block-row substitution)
+      c  the default                                                      (sweep: through W -- checked by its kernel name)
+      b  the guard at 0 again, W now in place                             (sweep: substitution)
+    a and b must agree in EVERY bit: neither the guard nor the existence of W reaches beta_j or the conditioning terms.
+    c starts from a different input: W's forward error is ~eps cond(L) where the substitution's is ~eps cond of a block,
+    so the sweep-derived state (mu_lat, var_lat at pick 0, hence d and the believer's fantasies) differs in rounding --
+    that is the sweep's documented behaviour, which q = 1 must reproduce bit for bit.  What c must share with a: the picks,
+    the oracle's moments within the bounds, and per pick the same conditioning increments up to that rounding."""
+    rs, og, g, eta, Xc = _setup(ctx, dict(N=N, D=D, M=M))
+    cand = _lib.Candidates(ctx, Xc)
+    amp = float(np.exp(og.theta[0]))
+    try:
+        for fantasy in ("kriging_believer", "constant_liar"):
+            runs, kernels = {}, {}
+            for name, guard in (("a", 0), ("c", None), ("b", 0)) if fantasy == "kriging_believer" else (("c", None), ("b", 0)):
+                ctx.set_tuning("winv_cond_max", guard)
+                try:
+                    runs[name] = g.select_batch("ei", 0.0, eta, cand, q, fantasy, eta, diagnostics=True)
+                    kernels[name] = cand.solve_kernel()
+                finally:
+                    ctx.set_tuning("winv_cond_max", None)
+            assert kernels["c"].startswith("winv_"), kernels           # the default sweep used W
+            assert not kernels["b"].startswith("winv_"), kernels
+            a, b, c = runs.get("a", runs["b"]), runs["b"], runs["c"]
+            if "a" in runs:
+                assert not kernels["a"].startswith("winv_"), kernels
+                for x, y in ((a.indices, b.indices), (a.values, b.values), (a.fantasies, b.fantasies), (a.flags, b.flags),
+                             (a.trace, b.trace)):
+                    assert x.tobytes() == y.tobytes()
+            _check_each_pick(c, [og], Xc, "ei", 0.0, eta, fantasy, eta, mu_atol, var_rel, label + " through W")
+            np.testing.assert_array_equal(b.indices, c.indices)
+            np.testing.assert_allclose(b.fantasies[:-1], c.fantasies[:-1], rtol=0, atol=2 * mu_atol)
+            db, dc = b.trace[1:] - b.trace[:-1], c.trace[1:] - c.trace[:-1]
+            assert np.abs(db[..., 0] - dc[..., 0]).max() <= 4 * mu_atol
+            assert np.abs(db[..., 1] - dc[..., 1]).max() <= 4 * var_rel * amp
+            print("%s %s: sweep %s / %s, pick-0 state differs by %.2e / %.2e, increments by %.2e / %.2e"
+                  % (label, fantasy, kernels["c"], kernels["b"], np.abs(b.trace[0, ..., 0] - c.trace[0, ..., 0]).max(),
+                     np.abs(b.trace[0, ..., 1] - c.trace[0, ..., 1]).max() / amp, np.abs(db[..., 0] - dc[..., 0]).max(),
+                     np.abs(db[..., 1] - dc[..., 1]).max() / amp))
+    finally:
+        cand.close()
+        g.close()
+
+
+def test_w_independence_emu_small(emu_ctx):
+    _check_w_independence(emu_ctx, 300, 3, 8, 3, BATCH_MU_ATOL, BATCH_VAR_ATOL_REL_AMP, "emu W")
+
+
+@pytest.mark.gpu
+def test_w_independence_gpu(gpu_ctx):
+    _check_w_independence(gpu_ctx, 1024, 8, 4096, 4, BATCH_MU_ATOL_GPU, BATCH_VAR_ATOL_REL_AMP_GPU, "gpu W")
+
+
+# ---- the interpreter run of 2. - 7. -------------------------------------------------------------------------------------------
+# ONE collected test: the files of this suite are spread over worker processes by their number of tests, and a file with
+# few tests leaves the placement of the existing files as it was
+def test_device_checks_emu_small(emu_ctx):
+    import traceback
+    checks = [("first pick", _first_pick_is_the_sweep_emu_small)]
+    checks += [("every pick " + k, lambda c, k=k: _every_pick_emu_small(c, k)) for k in ("matern52", "rbf", "fabolas")]
+    checks += [("output transform", _every_pick_with_output_transform_emu_small),
+               ("D = 19", _every_pick_beyond_16_dimensions_emu),
+               ("oracle's greedy choice", _picks_equal_the_oracles_greedy_choice_emu_small),
+               ("edges", _edges_emu_small), ("chunked first sweep", _chunked_first_sweep_gives_the_same_bits_emu_small),
+               ("marginal", _marginal_emu_small)]
+    failed = []
+    for name, fn in checks:                      # every item runs and is reported, whatever the earlier ones did
+        try:
+            fn(emu_ctx)
+            print("item ok: " + name)
+        except Exception:                        # noqa: BLE001
+            failed.append(name)
+            print("item FAILED: %s\n%s" % (name, traceback.format_exc()))
+    assert not failed, failed
+
+
+# ---- 9. interpreter schedules ----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("env", [{"HIPEMU_GUARD": "1", "HIPEMU_ORDER": "1"}, {"HIPEMU_ORDER": "2"}],
+                         ids=["fenced+descending", "rotating"])
+def test_small_checks_fenced_and_in_any_work_item_order(env):
+    """the small device checks again with every device buffer fenced by inaccessible pages and the work-items of a
+    workgroup run in descending order, and once in rotating order"""
+    e = dict(os.environ, ROBO_TESTS_SERIAL="1", **env)
+    e["PYTHONPATH"] = os.pathsep.join([os.path.dirname(HERE), e.get("PYTHONPATH", "")])
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-x", "-q", "-p", "no:cacheprovider",
+                        "-k", "emu_small"], env=e, cwd=os.path.dirname(HERE), capture_output=True, text=True, timeout=1800)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    assert " passed" in r.stdout and "failed" not in r.stdout
+
+
+# ---- 8. classes and front end (interpreter, Branin) ---------------------------------------------------------------------------
+def _branin(x):
+    a, b, c, r, s, t = 1.0, 5.1 / (4 * np.pi ** 2), 5.0 / np.pi, 6.0, 10.0, 1.0 / (8 * np.pi)
+    return float(a * (x[1] - b * x[0] ** 2 + c * x[0] - r) ** 2 + s * (1 - t) * np.cos(x[0]) + s)
+
+
+_BOX = (np.array([-5.0, 0.0]), np.array([10.0, 15.0]))
+
+
+def _bo(n_iter, seed=3, model_type="gp", **kw):
+    from robo_amd.fmin import bayesian_optimization
+    np.random.seed(seed)
+    calls = []
+
+    def f(x):
+        calls.append(np.array(x))
+        return _branin(x)
+    res = bayesian_optimization(f, _BOX[0], _BOX[1], num_iterations=n_iter, maximizer="random", acquisition_func="ei",
+                                model_type=model_type, n_init=3, rng=np.random.RandomState(seed), n_candidates=150, **kw)
+    return res, calls
+
+
+def _front_end_rounds_emu(emu_ctx, monkeypatch):
+    from robo_amd.models import GaussianProcess
+    trains = []
+    real = GaussianProcess.train
+    monkeypatch.setattr(GaussianProcess, "train", lambda self, X, y, **k: (trains.append(len(y)), real(self, X, y, **k))[1])
+    res, calls = _bo(11, batch_size=4)                       # 3 initial points + two rounds of 4
+    assert len(calls) == 11 and trains == [3, 7]
+    for key in ("incumbents", "incumbent_values", "runtime", "overhead"):
+        assert len(res[key]) == 11, key
+    assert np.shape(res["X"]) == (11, 2) and np.shape(res["y"]) == (11,)
+    # evaluate_batch: once per round; the last round is truncated (4 + 3)
+    del trains[:]
+    rounds = []
+    res, calls = _bo(10, batch_size=4, evaluate_batch=lambda Xq: (rounds.append(len(Xq)), [_branin(x) for x in Xq])[1],
+                     fantasy="constant_liar", liar="mean")
+    assert rounds == [4, 3] and trains == [3, 7] and len(calls) == 3 and np.shape(res["y"]) == (10,)
+
+
+def _batch_size_one_is_the_existing_loop_emu(emu_ctx):
+    a, _ = _bo(6)
+    b, _ = _bo(6, batch_size=1)
+    assert set(a) == set(b)
+    for key in a:
+        if key not in ("runtime", "overhead"):
+            np.testing.assert_array_equal(np.asarray(a[key]), np.asarray(b[key]), err_msg=key)
+
+
+def _class_errors_emu(emu_ctx):
+    from robo_amd.acquisition_functions import EI
+    from robo_amd.acquisition_functions.base_acquisition import BaseAcquisitionFunction
+    from robo_amd.kernels import Matern52Kernel
+    from robo_amd.maximizers import RandomSampling
+    from robo_amd.maximizers.random_sampling import BaseMaximizer
+    from robo_amd.models import GaussianProcess
+    from robo_amd.solver.bayesian_optimization import BayesianOptimization
+    rs = np.random.RandomState(0)
+    X = _BOX[0] + (_BOX[1] - _BOX[0]) * rs.rand(12, 2)
+    y = np.array([_branin(x) for x in X])
+    model = GaussianProcess(Matern52Kernel(np.array([0.5, 0.5]), ndim=2), noise=1e-3, lower=_BOX[0], upper=_BOX[1])
+    model.train(X, y, do_optimize=False)
+    Xc = _BOX[0] + (_BOX[1] - _BOX[0]) * rs.rand(100, 2)
+    with pytest.raises(TypeError):
+        BaseAcquisitionFunction(model).select_batch(Xc, 3)
+    acq = EI(model)
+    acq.update(model)
+    pts = acq.select_batch(Xc, 3, fantasy="constant_liar", liar="max")
+    assert pts.shape == (3, 2) and acq.last_batch.n_made == 3
+    np.testing.assert_allclose(pts, Xc[acq.last_batch.indices], rtol=0, atol=1e-12)
+    assert np.all(acq.last_batch.fantasies[:2] == y.max())
+    one = acq.select_batch(Xc, 1)
+    np.testing.assert_array_equal(one[0], Xc[acq.argmax(Xc)])
+    with pytest.raises(ValueError):
+        acq.select_batch(Xc, 3, fantasy="constant_liar", liar="median")
+    rsamp = RandomSampling(acq, _BOX[0], _BOX[1], n_samples=100)
+    np.random.seed(5)
+    a = rsamp.maximize()
+    np.random.seed(5)
+    np.testing.assert_array_equal(rsamp.maximize_batch(1)[0], a)
+    model.devices = [0, 1]                                  # sharded models: out of scope, said plainly
+    try:
+        with pytest.raises(NotImplementedError):
+            acq.select_batch(Xc, 3)
+    finally:
+        model.devices = None
+    with pytest.raises(TypeError):
+        BayesianOptimization(_branin, _BOX[0], _BOX[1], acq, model, BaseMaximizer(acq, _BOX[0], _BOX[1]),
+                             batch_size=2).choose_next_batch(X, y, 2)
+
+
+def _marginalised_select_batch_emu(emu_ctx):
+    """MarginalizationGPMCMC.select_batch over a small GaussianProcessMCMC == _lib.acq_batch on its sub-models"""
+    from robo_amd.acquisition_functions import EI
+    from robo_amd.acquisition_functions.marginalization import MarginalizationGPMCMC
+    from robo_amd.kernels import Matern52Kernel
+    from robo_amd.models.gaussian_process_mcmc import GaussianProcessMCMC
+    from robo_amd.priors.default_priors import DefaultPrior
+    rs = np.random.RandomState(2)
+    X = _BOX[0] + (_BOX[1] - _BOX[0]) * rs.rand(14, 2)
+    y = np.array([_branin(x) for x in X]) / 50.0
+    kernel = 2 * Matern52Kernel(np.ones(2), ndim=2)
+    model = GaussianProcessMCMC(kernel, prior=DefaultPrior(len(kernel) + 1, rng=np.random.RandomState(3)), n_hypers=8,
+                                chain_length=6, burnin_steps=4, rng=np.random.RandomState(4), lower=_BOX[0], upper=_BOX[1])
+    model.train(X, y)
+    acq = MarginalizationGPMCMC(EI(model))
+    acq.update(model)
+    Xc = _BOX[0] + (_BOX[1] - _BOX[0]) * rs.rand(120, 2)
+    gps = [e.model.gp for e in acq.estimators]
+    etas = np.array([e._eta(None) for e in acq.estimators])
+    cand = _lib.Candidates(gps[0].ctx, (Xc - _BOX[0]) / (_BOX[1] - _BOX[0]))
+    try:
+        for fantasy, liar, lv in (("kriging_believer", None, 0.0), ("constant_liar", "min", float(y.min())),
+                                  ("constant_liar", 0.25, 0.25)):
+            pts = acq.select_batch(Xc, 3, fantasy=fantasy, liar=liar)
+            want = _lib.acq_batch(gps, "ei", acq.estimators[0].par, etas, cand, 3, fantasy, lv)
+            got = acq.last_batch
+            assert got.n_made == 3 and pts.shape == (3, 2) and got.fantasies.shape == (3, len(gps))
+            np.testing.assert_array_equal(got.indices, want.indices)
+            assert got.values.tobytes() == want.values.tobytes() and got.fantasies.tobytes() == want.fantasies.tobytes()
+            np.testing.assert_allclose(pts, Xc[got.indices], rtol=0, atol=1e-12)
+        one = acq.select_batch(Xc, 1)
+        np.testing.assert_allclose(one[0], Xc[acq.argmax(Xc)], rtol=0, atol=1e-12)
+    finally:
+        cand.close()
+
+
+def _maximize_batch_emu(emu_ctx):
+    """the three sampling maximisers: q = 1 is maximize(); q > 1 picks from the candidate batch maximize() would draw for
+    the same rng state, pick 0 being maximize()'s point"""
+    from scipy.stats import qmc
+    from robo_amd.acquisition_functions import EI
+    from robo_amd.kernels import Matern52Kernel
+    from robo_amd.maximizers import RandomSampling
+    from robo_amd.maximizers.random_sampling import DeviceRandomSampling, DeviceSobolSampling
+    from robo_amd.models import GaussianProcess
+    lo, hi = _BOX
+    rs = np.random.RandomState(1)
+    X = lo + (hi - lo) * rs.rand(12, 2)
+    y = np.array([_branin(x) for x in X])
+    model = GaussianProcess(Matern52Kernel(np.array([0.5, 0.5]), ndim=2), noise=1e-3, lower=lo, upper=hi)
+    model.train(X, y, do_optimize=False)
+    acq = EI(model)
+    acq.update(model)
+
+    def rows_of(P, pool):
+        return all(np.abs(pool - p).max(axis=1).min() <= 1e-12 * np.abs(hi).max() for p in P)
+
+    rsamp = RandomSampling(acq, lo, hi, n_samples=100)
+    np.random.seed(5)
+    a = rsamp.maximize()
+    np.random.seed(5)
+    np.testing.assert_array_equal(rsamp.maximize_batch(1)[0], a)
+    np.random.seed(5)
+    P = rsamp.maximize_batch(3, fantasy="constant_liar", liar="min")
+    np.random.seed(5)
+    pool = rsamp.candidates()
+    assert P.shape == (3, 2) and rows_of(P, pool)
+    np.testing.assert_allclose(P[0], a, rtol=0, atol=1e-12)
+
+    mk = lambda: DeviceRandomSampling(acq, lo, hi, n_samples=300, rng=np.random.RandomState(9))   # noqa: E731
+    a = mk().maximize()
+    np.testing.assert_array_equal(mk().maximize_batch(1)[0], a)
+    P = mk().maximize_batch(3)
+    seed = int(np.random.RandomState(9).randint(0, 2 ** 31 - 1))
+    inc = np.asarray(model.get_incumbent()[0], dtype=np.float64)
+    c = _lib.Candidates(model.gp.ctx, m=300, seed=seed, n_uniform=int(300 * .7), loc=(inc - lo) / (hi - lo),
+                        scale=0.1 / (hi - lo))
+    pool = lo + (hi - lo) * c.points()
+    c.close()
+    assert P.shape == (3, 2) and rows_of(P, pool)
+    np.testing.assert_array_equal(P[0], a)
+
+    mk = lambda: DeviceSobolSampling(acq, lo, hi, n_samples=256, seed=4)                          # noqa: E731
+    a = mk().maximize()
+    np.testing.assert_array_equal(mk().maximize_batch(1)[0], a)
+    P = mk().maximize_batch(3, fantasy="constant_liar", liar=float(y.mean()))
+    pool = lo + (hi - lo) * qmc.Sobol(d=2, scramble=True, seed=4).random(256)
+    assert P.shape == (3, 2) and rows_of(P, pool)
+    np.testing.assert_array_equal(P[0], a)
+
+
+def _fabolas_type_error():
+    from robo_amd.acquisition_functions import EI
+    from robo_amd.kernels import FabolasKernel
+    from robo_amd.models.fabolas_gp import FabolasGP
+    model = FabolasGP(FabolasKernel(3), basis_function=lambda s: (1 - s) ** 2, noise=1e-3, lower=np.zeros(2),
+                      upper=np.ones(2), rng=np.random.RandomState(1))
+    with pytest.raises(TypeError):
+        EI(model).select_batch(np.random.RandomState(0).rand(10, 3), 2)
+
+
+def _front_end_gp_mcmc_emu(emu_ctx):
+    """the marginalised path of the front end: per-sample incumbents, the liar from the first sub-model's targets"""
+    rounds = []
+    res, calls = _bo(9, model_type="gp_mcmc", batch_size=3, fantasy="constant_liar", liar="max", chain_length=6,
+                     burnin_steps=4, evaluate_batch=lambda Xq: (rounds.append(len(Xq)), [_branin(x) for x in Xq])[1])
+    assert rounds == [3, 3] and len(calls) == 3 and np.shape(res["X"]) == (9, 2) and len(res["incumbents"]) == 9
+    res, calls = _bo(7, model_type="gp_mcmc", batch_size=2, chain_length=6, burnin_steps=4)
+    assert len(calls) == 7 and np.shape(res["y"]) == (7,)
+
+
+def test_classes_and_front_end_emu(emu_ctx, monkeypatch):
+    _class_errors_emu(emu_ctx)
+    _fabolas_type_error()
+    _marginalised_select_batch_emu(emu_ctx)
+    _maximize_batch_emu(emu_ctx)
+    _batch_size_one_is_the_existing_loop_emu(emu_ctx)
+    _front_end_rounds_emu(emu_ctx, monkeypatch)
+    _front_end_gp_mcmc_emu(emu_ctx)
