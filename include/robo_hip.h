@@ -343,6 +343,51 @@ int32_t robo_acq_batch_marginal_cand(robo_gp* const* gps, int32_t S, int32_t acq
                                      double* out_values, double* out_fantasy, uint32_t* out_flags, int32_t* out_n_made,
                                      double* out_trace);
 
+/* ---- max-value entropy search (Wang & Jegelka, ICML 2017; no counterpart in the reference), for minimisation.
+ * Inputs are the sweep's transformed, floored moments (mu_i, v_i) of the m candidates (what robo_gp_predict_cand returns),
+ * sigma_i = sqrt(v_i).  F(w) = sum_i log Phi((w + mu_i) / sigma_i) is the log-probability that max_i(-f_i) < w for
+ * independent f_i (a candidate with sigma_i == 0 is a step: -inf for w < -mu_i, else 0).
+ *   bracket    w_lo = max_i(-mu_i - 8 sigma_i), w_hi = max_i(-mu_i + 8 sigma_i):  F(w_lo) <= log Phi(-8) < log 1/4 and
+ *              F(w_hi) >= m log Phi(8) > log 3/4 for every m a handle can hold -- no bracket search.
+ *   quantiles  w_p solves F(w_p) = log p for p = 1/4, 1/2, 3/4: a sectioning search on the device (64 sections per pass,
+ *              all three quantiles per pass over the candidates, no host round trip) until every quantile's bracket is no
+ *              wider than max((w_hi - w_lo) 2^-46, 4 ulp of its larger end); w_p is the bracket's midpoint.
+ *   Gumbel fit b = (w_1/4 - w_3/4) / (log log(4/3) - log log 4),  a = w_1/2 + b log log 2.
+ *   draws      y*_k = -(a - b log(-log u_k)) for the CALLER's u_k in (0, 1), k < K, 1 <= K <= 128; with clamp != 0
+ *              y*_k := min(y*_k, eta).
+ *   value      alpha_i = (1/K) sum_k [ gamma phi(gamma) / (2 Phi(gamma)) - log Phi(gamma) ],  gamma = (mu_i - y*_k) / sigma_i,
+ *              summed in ascending k, phi / Phi = exp(log phi - log Phi); a term's 0 * inf (huge gamma) counts as 0.
+ *              sigma_i == 0: alpha_i = 0 and ROBO_FLAG_ZERO_SIGMA;  a NaN moment: alpha_i = NaN and ROBO_FLAG_NAN.
+ *              Accuracy: for gamma >= 0 a term is good to a few ulp.  For gamma < 0 it is the difference of two numbers
+ *              near gamma^2 / 2 that leaves ~log(-gamma) + 1.4: its relative error is about gamma^2 eps / (2 log(-gamma))
+ *              -- 3e-14 at gamma = -30 (the tested range), 1e-9 at -1e4, no digits beyond about -1e8, and NaN
+ *              (inf - inf, flagged) beyond |gamma| ~ 1e154.  With clamp != 0 every y* <= eta, so gamma < 0 occurs only
+ *              where a candidate's mean lies below the incumbent, and |gamma| <= (eta - mu_i) / sigma_i.
+ * Every sum has a fixed order (128 candidates per partial in index order, partials in block order): two calls on the same
+ * inputs return the same bits.  argmax follows np.argmax (first index, NaN maximal) through the sweep's own reduction.
+ * Diagnostics, all nullable: out_ystar (K), out_gumbel (7: w_lo, w_hi, w_1/4, w_1/2, w_3/4, a, b), out_trace (m x 2: the
+ * (mean, var) the call worked on).  out_acq (m) may be NULL.  A u outside the open interval (0, 1), K outside 1 .. 128, a GP
+ * that is not fitted, or a NaN moment in the sampling half: ROBO_BAD_ARGUMENT.
+ * One synchronisation per call; the state stays with gp (gps[0]) between calls of one (m, S, K).  Event slots 30 and 31
+ * are recorded behind the minimum sampling and the element-wise half of the last sample, under the condition of slots
+ * 24..27 (27 -> 30 -> 31: the tail's two phases).                                                                        */
+int32_t robo_mes_eval_cand(robo_gp* gp, double eta, robo_cand* cand, const double* u, int32_t K, int32_t clamp,
+                           double* out_acq, double* out_max, int64_t* out_argmax, uint32_t* out_flags, double* out_ystar,
+                           double* out_gumbel, double* out_trace);
+/* the mean over S fitted GPs: every sample runs its own sweep, bracket, quantiles, Gumbel fit and y*_{s,k} from u[s][k]
+ * (clamped to its own etas[s]); alpha = (sum_s alpha_s) / S accumulated in sample order, as robo_acq_eval_marginal_cand.
+ * u and out_ystar S x K, out_gumbel S x 7, out_trace S x m x 2.                                                           */
+int32_t robo_mes_eval_marginal_cand(robo_gp* const* gps, int32_t S, const double* etas, robo_cand* cand, const double* u,
+                                    int32_t K, int32_t clamp, double* out_acq, double* out_max, int64_t* out_argmax,
+                                    uint32_t* out_flags, double* out_ystar, double* out_gumbel, double* out_trace);
+/* the two halves on their own, for (mean, var) produced by any other BaseModel plugin (as robo_acq_eval_moments):
+ * the sampling half (bracket, quantiles, Gumbel fit, draws) over a discretisation's moments ...                          */
+int32_t robo_mes_sample_min_moments(robo_ctx* ctx, const double* mean, const double* var, int64_t m, const double* u,
+                                    int32_t K, int32_t clamp, double eta, double* out_ystar, double* out_gumbel);
+/* ... and the element-wise half with its argmax for given y* (K)                                                         */
+int32_t robo_mes_eval_moments(robo_ctx* ctx, const double* mean, const double* var, int64_t m, const double* ystar,
+                              int32_t K, double* out_acq, double* out_max, int64_t* out_argmax, uint32_t* out_flags);
+
 /* ---- entropy search: replaces InformationGain.innovations/_dh_fun/compute ---------------
  * (robo/acquisition_functions/information_gain.py:87-125,169-203,253-272), batched over candidates.
  * rep: the Nb <= 64 representer points as a candidate batch (same normalised space).  The EP

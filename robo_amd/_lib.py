@@ -27,6 +27,7 @@ KERNEL_KINDS = {"matern52": 0, "rbf": 1, "fabolas": 2}
 ACQ_KINDS = {"ei": 0, "log_ei": 1, "pi": 2, "lcb": 3}
 FLAG_ZERO_SIGMA, FLAG_NEGATIVE_EI, FLAG_NAN, FLAG_NOT_FACTORED, FLAG_FROZEN = 1, 2, 4, 8, 16
 FANTASY_KINDS = {"kriging_believer": 0, "constant_liar": 1}   # robo_acq_batch_*: how a pick's fantasy target is chosen
+MES_MAX_K = 128                                  # robo_mes_*: cap on the sampled minima per model
 REFINE_MAX_STARTS = 1024                         # robo_acq_refine_*: cap on n_starts
 MC_MAX_NB, MC_MAX_NP, MC_MAX_NF = 64, 512, 65535   # limits of the Monte-Carlo p_min entry points (robo_pmin_mc, robo_igmc_*)
 
@@ -45,6 +46,7 @@ SYMBOLS = [
     "robo_acq_eval_cand", "robo_acq_eval", "robo_acq_eval_moments", "robo_acq_eval_marginal_cand", "robo_acq_eval_sum_cand",
     "robo_acq_refine_cand", "robo_acq_refine_marginal_cand",
     "robo_acq_batch_cand", "robo_acq_batch_marginal_cand",
+    "robo_mes_eval_cand", "robo_mes_eval_marginal_cand", "robo_mes_sample_min_moments", "robo_mes_eval_moments",
     "robo_ig_eval_cand", "robo_ig_eval_per_cost_cand", "robo_ig_eval_moments", "robo_gp_cross_cov",
     "robo_ep_joint_min", "robo_pmin_mc", "robo_igmc_eval_cand", "robo_igmc_eval_moments",
     "robo_comm_create_id", "robo_comm_init", "robo_comm_destroy", "robo_comm_info", "robo_comm_allgather",
@@ -181,6 +183,11 @@ def lib():
                                 C.POINTER(i32), _dp],
         "robo_acq_batch_marginal_cand": [pp, i32, i32, dbl, _dp, vp, i32, i32, dbl, C.POINTER(i64), _dp, _dp,
                                          C.POINTER(C.c_uint32), C.POINTER(i32), _dp],
+        "robo_mes_eval_cand": [vp, dbl, vp, _dp, i32, i32, _dp, _dp, C.POINTER(i64), C.POINTER(C.c_uint32), _dp, _dp, _dp],
+        "robo_mes_eval_marginal_cand": [pp, i32, _dp, vp, _dp, i32, i32, _dp, _dp, C.POINTER(i64), C.POINTER(C.c_uint32),
+                                        _dp, _dp, _dp],
+        "robo_mes_sample_min_moments": [vp, _dp, _dp, i64, _dp, i32, i32, dbl, _dp, _dp],
+        "robo_mes_eval_moments": [vp, _dp, _dp, i64, _dp, i32, _dp, _dp, C.POINTER(i64), C.POINTER(C.c_uint32)],
         "robo_ig_eval_cand": [vp, vp, vp, i32, dbl, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(i64)],
         "robo_ig_eval_per_cost_cand": [vp, vp, vp, i32, dbl, _dp, _dp, _dp, _dp, _dp, _dp, vp, vp, dbl, _dp, _dp,
                                        C.POINTER(i64)],
@@ -754,6 +761,73 @@ class DeviceGP(object):
         """q greedy picks from ``cand`` with fantasised observations in between (robo_acq_batch_cand) -> BatchResult;
         see :func:`acq_batch`"""
         return acq_batch([self], kind, par, eta, cand, q, fantasy, liar, diagnostics, marginal=False)
+
+
+    def mes(self, eta, cand, u, clamp=True, want_values=True, diagnostics=False):
+        """max-value entropy search over ``cand`` with the caller's uniforms u (K,) (robo_mes_eval_cand) -> MESResult;
+        see :func:`mes_marginal`"""
+        return mes_marginal([self], eta, cand, u, clamp, want_values, diagnostics, marginal=False)
+
+
+class MESResult(object):
+    """values (m,) or None, max, argmax, flags, ystar (K,) the sampled minima ((S, K) in the marginal form); with
+    diagnostics: gumbel (7,) / (S, 7) = w_lo, w_hi, w_1/4, w_1/2, w_3/4, a, b and trace (m, 2) / (S, m, 2) the (mean, var)
+    the call worked on (include/robo_hip.h)"""
+
+    def __init__(self, values, max, argmax, flags, ystar, gumbel=None, trace=None):
+        self.values, self.max, self.argmax, self.flags = values, float(max), int(argmax), int(flags)
+        self.ystar, self.gumbel, self.trace = ystar, gumbel, trace
+
+
+def mes_marginal(gps, eta, cand, u, clamp=True, want_values=True, diagnostics=False, marginal=True):
+    """max-value entropy search over device GPs (one: robo_mes_eval_cand; the mean over several hyper-parameter samples,
+    each with its own sampled minima: robo_mes_eval_marginal_cand).  eta: one incumbent value, or one per sample;
+    u: (K,) or (S, K) uniforms in (0, 1), in the order they are used."""
+    S = len(gps)
+    u = _f64(u)
+    if u.ndim not in (1, 2) or (u.ndim == 2 and u.shape[0] != S) or (u.ndim == 1 and marginal and S != 1):
+        raise ValueError("u must be (K,) for one model or (S, K) for %d, got %r" % (S, u.shape))
+    K = u.shape[-1]
+    ok = 1 <= K <= MES_MAX_K
+    shape = (S, K) if marginal else (K,)
+    out = np.empty(cand.m) if want_values else None
+    ystar = np.full(shape, np.nan)
+    gumbel = np.full(shape[:-1] + (7,), np.nan) if diagnostics else None
+    trace = np.empty(shape[:-1] + (cand.m, 2)) if (diagnostics and ok) else None
+    mx, am, fl = C.c_double(0), C.c_int64(0), C.c_uint32(0)
+    tail = (_arr(out) if want_values else None, C.byref(mx), C.byref(am), C.byref(fl), _arr(ystar),
+            _arr(gumbel) if diagnostics else None, _arr(trace) if trace is not None else None)
+    if marginal:
+        arr = (C.c_void_p * S)(*[g._h for g in gps])
+        etas = _f64(np.broadcast_to(np.asarray(eta, dtype=np.float64), (S,)))
+        check(lib().robo_mes_eval_marginal_cand(arr, S, _arr(etas), cand._h, _arr(u), K, int(bool(clamp)), *tail))
+    else:
+        check(lib().robo_mes_eval_cand(gps[0]._h, float(eta), cand._h, _arr(u), K, int(bool(clamp)), *tail))
+    return MESResult(out, mx.value, am.value, fl.value, ystar, gumbel, trace)
+
+
+def mes_sample_min(ctx, mean, var, u, clamp=True, eta=0.0, diagnostics=False):
+    """the sampling half of max-value entropy search for (mean, var) of any model over a discretisation
+    (robo_mes_sample_min_moments) -> ystar (K,), or (ystar, gumbel (7,)) with diagnostics"""
+    mean, var, u = _f64(mean), _f64(var), _f64(u)
+    assert mean.ndim == 1 and mean.shape == var.shape and u.ndim == 1
+    K = u.shape[0]
+    ystar, gumbel = np.full(max(K, 1), np.nan), np.full(7, np.nan)
+    check(lib().robo_mes_sample_min_moments(ctx._h, _arr(mean), _arr(var), mean.shape[0], _arr(u), K, int(bool(clamp)),
+                                            float(eta), _arr(ystar), _arr(gumbel)))
+    return (ystar, gumbel) if diagnostics else ystar
+
+
+def mes_from_moments(ctx, mean, var, ystar):
+    """the element-wise half of max-value entropy search on the device for (mean, var) of any model and given sampled
+    minima (robo_mes_eval_moments) -> (values, max, argmax, flags)"""
+    mean, var, ystar = _f64(mean), _f64(var), _f64(ystar)
+    assert mean.ndim == 1 and mean.shape == var.shape and ystar.ndim == 1
+    out = np.empty(mean.shape[0])
+    mx, am, fl = C.c_double(0), C.c_int64(0), C.c_uint32(0)
+    check(lib().robo_mes_eval_moments(ctx._h, _arr(mean), _arr(var), mean.shape[0], _arr(ystar), ystar.shape[0], _arr(out),
+                                      C.byref(mx), C.byref(am), C.byref(fl)))
+    return out, mx.value, am.value, fl.value
 
 
 class BatchResult(object):

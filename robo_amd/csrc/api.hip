@@ -312,6 +312,7 @@ int32_t robo_gp_destroy(robo_gp* g) {
         refine_free(g->refine);
     }
     batch_free(g->batch);
+    mes_free(g->mes);
     hipFree(g->d_X);
     hipFree(g->d_Xs);
     hipFree(g->d_y);
@@ -2012,4 +2013,7 @@ int api_acq_read_back(robo_cand* k, const double* d_vec, double* out_vec, double
 }
 int api_clear_flags(robo_cand* k, int status) { return clear_flags_on_error(k, status); }
 int api_predict_samples(robo_gp* const* gps, int S, robo_cand* k, int cap) { return predict_samples(gps, S, k, cap); }
+// the sweep and an empty candidate handle for the entry points of mes.hip
+int api_predict_core(robo_gp* g, robo_cand* k) { return predict_core(g, k, false); }
+int api_cand_alloc(robo_ctx* ctx, int64_t m, int32_t dim, robo_cand** out) { return cand_alloc(ctx, m, dim, out); }
 }  // namespace robo

@@ -253,6 +253,31 @@ struct BatchWork {
 int batch_alloc(robo_ctx* ctx, int64_t m, int64_t m_pad, int S, int n_pad, int q, BatchWork** out);
 void batch_free(BatchWork* w);
 int batch_ensure_trace(BatchWork* w, size_t doubles);
+
+// ---- max-value entropy search (mes.hip) ------------------------------------------------------------------------------------
+// the state of one call; all arrays device memory of one block, per-sample arrays [S][K] / [S][7]
+struct MesState {
+    long long m;
+    int K, nblk;                    // draws per sample; workgroups of the F pass (128 candidates each)
+    double *ystar, *gumbel;         // [S][K] sampled minima; [S][7] w_lo, w_hi, w_1/4, w_1/2, w_3/4, a, b
+    double* status;                 // [S] 0 converged, 1 search still open, 2 a NaN moment
+    double* u;                      // [S][K] the caller's uniforms
+    double* brk;                    // [8]: lower ends [3], upper ends [3] of the quantiles' brackets, the width to reach
+    double *bpart, *fpart;          // [nblk][3] bracket partials; [nblk][192] partial F of every grid point
+    int* done;                      // the current sample's search has ended: the remaining passes return at once
+};
+struct MesWork {
+    int64_t m;
+    int S, K;
+    double* d_block;
+    double* d_trace;
+    size_t trace_cap;               // doubles
+    double* h_stage;                // pinned: [ystar | gumbel | status] of the block's head (one D2H per call), then u
+    size_t rep_doubles;
+    MesState st;
+};
+int mes_alloc(int64_t m, int S, int K, MesWork** out);
+void mes_free(MesWork* w);
 }  // namespace robo
 
 constexpr int ROBO_AUX_STREAMS = 3;
@@ -345,6 +370,7 @@ struct robo_gp {
     unsigned long long winv_launched;   // fit_gen whose W build has been LAUNCHED (robo_gp_prefetch_inverse) but not yet read
     robo::RefineWork* refine;       // state + solve workspace of robo_acq_refine_* (refine.hip), kept between calls of one (K, D)
     robo::BatchWork* batch;         // state of robo_acq_batch_* (batch.hip), kept between calls of one (m, S)
+    robo::MesWork* mes;             // state of robo_mes_eval_* (mes.hip), kept between calls of one (m, S, K)
 };
 
 struct robo_cand {

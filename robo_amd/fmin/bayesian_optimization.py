@@ -18,7 +18,7 @@ import logging
 
 import numpy as np
 
-from robo_amd.acquisition_functions import EI, LCB, PI, LogEI, MarginalizationGPMCMC
+from robo_amd.acquisition_functions import EI, LCB, MES, PI, LogEI, MarginalizationGPMCMC
 from robo_amd.initial_design import init_latin_hypercube_sampling
 from robo_amd.kernels import Matern52Kernel
 from robo_amd.maximizers import (DeviceGradientAscent, DeviceRandomSampling, DifferentialEvolution, RandomSampling,
@@ -72,7 +72,8 @@ def bayesian_optimization(objective_function, lower, upper, num_iterations=30, X
     else:
         raise ValueError("'{}' is not a valid model (robo_amd provides 'gp' and 'gp_mcmc')".format(model_type))
 
-    acq_classes = {"ei": EI, "log_ei": LogEI, "pi": PI, "lcb": LCB}
+    # "mes": max-value entropy search; its draws (discretisation, uniforms) come from this call's rng
+    acq_classes = {"ei": EI, "log_ei": LogEI, "pi": PI, "lcb": LCB, "mes": lambda m: MES(m, rng=rng)}
     if acquisition_func not in acq_classes:
         raise ValueError("'{}' is not a valid acquisition function".format(acquisition_func))
     a = acq_classes[acquisition_func](model)

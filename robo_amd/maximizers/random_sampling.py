@@ -26,6 +26,19 @@ class BaseMaximizer(object):
         pass
 
 
+def _check_candidate_shard(maximizer):
+    """shard=True with an acquisition that cannot be evaluated slice by slice (``candidate_shard = False`` on it, or on the
+    function a MarginalizationGPMCMC wraps): refused before anything is drawn or exchanged"""
+    if not maximizer.shard:
+        return
+    acq = maximizer.objective_func
+    inner = getattr(acq, "acquisition_func", acq)
+    if not getattr(inner, "candidate_shard", True) or not getattr(acq, "candidate_shard", True):
+        raise NotImplementedError("%s(shard=True) with %s: its values on a slice of the candidates depend on that slice alone "
+                                  "(a shard-consistent y* needs a cross-rank reduction), so the candidate shard is not "
+                                  "implemented for it" % (type(maximizer).__name__, type(inner).__name__))
+
+
 class RandomSampling(BaseMaximizer):
 
     def __init__(self, objective_function, lower, upper, n_samples=500, rng=None, device_argmax=True, shard=False):
@@ -51,6 +64,7 @@ class RandomSampling(BaseMaximizer):
         return np.concatenate((rand, local), axis=0)
 
     def maximize(self):
+        _check_candidate_shard(self)
         X = self.candidates()
         if self.shard:
             from robo_amd import sharding
@@ -114,6 +128,7 @@ class DeviceRandomSampling(BaseMaximizer):
 
     def maximize(self):
         from robo_amd import _lib
+        _check_candidate_shard(self)
         acq = self.objective_func
         model = acq.model
         sub = model.models[0] if hasattr(model, "models") and len(model.models) > 0 else model
@@ -201,6 +216,7 @@ class DeviceSobolSampling(BaseMaximizer):
     def maximize(self):
         from scipy.stats import qmc
         from robo_amd import _lib, sharding
+        _check_candidate_shard(self)
         acq = self.objective_func
         model = acq.model
         sub = model.models[0] if hasattr(model, "models") and len(model.models) > 0 else model
