@@ -95,6 +95,35 @@ def _f64(a, shape=None):
     return a
 
 
+def _handles(gps):
+    """the handle array of a list of device GPs (at least one slot, so that an empty list still has an address)"""
+    return (C.c_void_p * max(len(gps), 1))(*[g._h for g in gps])
+
+
+def _etas(eta, S):
+    """one incumbent value for all S samples, or one per sample -> (S,) contiguous fp64"""
+    return _f64(np.broadcast_to(np.asarray(eta, dtype=np.float64), (S,)))
+
+
+def _ensemble_head(gps, eta, marginal, *between):
+    """the leading arguments of an entry point that comes in a single-model and a marginal form: (handle, [between], eta) or
+    (handle array, S, [between], etas); the pointer of ``etas`` keeps its array alive (ndarray.ctypes.data_as)"""
+    if not marginal:
+        return (gps[0]._h,) + between + (float(eta),)
+    return (_handles(gps), len(gps)) + between + (_arr(_etas(eta, len(gps))),)
+
+
+class _Best(object):
+    """the (max, argmax, flags) out-triple of the sweeps"""
+
+    def __init__(self):
+        self.max, self.argmax, self.flags = C.c_double(0), C.c_int64(0), C.c_uint32(0)
+        self.refs = (C.byref(self.max), C.byref(self.argmax), C.byref(self.flags))
+
+    def values(self):
+        return self.max.value, self.argmax.value, self.flags.value
+
+
 def use_library(path):
     """Point the binding at another build of the same C ABI (test hook)."""
     global _lib, _lib_path, _default_ctx, _diag, _extra_ctx, _multis
@@ -734,21 +763,20 @@ class DeviceGP(object):
 
     def acq(self, kind, par, eta, Xc, want_values=True):
         """-> (values or None, max, argmax, flags)"""
-        mx, am, fl = C.c_double(0), C.c_int64(0), C.c_uint32(0)
+        best = _Best()
         if isinstance(Xc, Candidates):
             m = Xc.m
             out = np.empty(m) if want_values else None
             check(lib().robo_acq_eval_cand(self._h, ACQ_KINDS[kind], float(par), float(eta), Xc._h,
-                                           _arr(out) if want_values else None, C.byref(mx), C.byref(am),
-                                           C.byref(fl)))
+                                           _arr(out) if want_values else None, *best.refs))
         else:
             Xc = _f64(Xc)
             assert Xc.ndim == 2 and Xc.shape[1] == self.dim
             m = Xc.shape[0]
             out = np.empty(m) if want_values else None
             check(lib().robo_acq_eval(self._h, ACQ_KINDS[kind], float(par), float(eta), _arr(Xc), m,
-                                      _arr(out) if want_values else None, C.byref(mx), C.byref(am), C.byref(fl)))
-        return out, mx.value, am.value, fl.value
+                                      _arr(out) if want_values else None, *best.refs))
+        return (out,) + best.values()
 
 
     def refine(self, kind, par, eta, cand, n_starts=256, n_steps=50, step0=0.05, diagnostics=False):
@@ -794,16 +822,12 @@ def mes_marginal(gps, eta, cand, u, clamp=True, want_values=True, diagnostics=Fa
     ystar = np.full(shape, np.nan)
     gumbel = np.full(shape[:-1] + (7,), np.nan) if diagnostics else None
     trace = np.empty(shape[:-1] + (cand.m, 2)) if (diagnostics and ok) else None
-    mx, am, fl = C.c_double(0), C.c_int64(0), C.c_uint32(0)
-    tail = (_arr(out) if want_values else None, C.byref(mx), C.byref(am), C.byref(fl), _arr(ystar),
-            _arr(gumbel) if diagnostics else None, _arr(trace) if trace is not None else None)
-    if marginal:
-        arr = (C.c_void_p * S)(*[g._h for g in gps])
-        etas = _f64(np.broadcast_to(np.asarray(eta, dtype=np.float64), (S,)))
-        check(lib().robo_mes_eval_marginal_cand(arr, S, _arr(etas), cand._h, _arr(u), K, int(bool(clamp)), *tail))
-    else:
-        check(lib().robo_mes_eval_cand(gps[0]._h, float(eta), cand._h, _arr(u), K, int(bool(clamp)), *tail))
-    return MESResult(out, mx.value, am.value, fl.value, ystar, gumbel, trace)
+    best = _Best()
+    fn = lib().robo_mes_eval_marginal_cand if marginal else lib().robo_mes_eval_cand
+    head = _ensemble_head(gps, eta, marginal)
+    check(fn(*head, cand._h, _arr(u), K, int(bool(clamp)), _arr(out) if want_values else None, *best.refs, _arr(ystar),
+             _arr(gumbel) if diagnostics else None, _arr(trace) if trace is not None else None))
+    return MESResult(out, *best.values(), ystar, gumbel, trace)
 
 
 def mes_sample_min(ctx, mean, var, u, clamp=True, eta=0.0, diagnostics=False):
@@ -824,10 +848,10 @@ def mes_from_moments(ctx, mean, var, ystar):
     mean, var, ystar = _f64(mean), _f64(var), _f64(ystar)
     assert mean.ndim == 1 and mean.shape == var.shape and ystar.ndim == 1
     out = np.empty(mean.shape[0])
-    mx, am, fl = C.c_double(0), C.c_int64(0), C.c_uint32(0)
+    best = _Best()
     check(lib().robo_mes_eval_moments(ctx._h, _arr(mean), _arr(var), mean.shape[0], _arr(ystar), ystar.shape[0], _arr(out),
-                                      C.byref(mx), C.byref(am), C.byref(fl)))
-    return out, mx.value, am.value, fl.value
+                                      *best.refs))
+    return (out,) + best.values()
 
 
 class BatchResult(object):
@@ -856,16 +880,10 @@ def acq_batch(gps, kind, par, eta, cand, q, fantasy="kriging_believer", liar=0.0
     trace = np.empty((q, S, cand.m, 2)) if (diagnostics and ok) else None
     p_idx, p_fl = idx.ctypes.data_as(C.POINTER(C.c_int64)), fl.ctypes.data_as(C.POINTER(C.c_uint32))
     p_trace = _arr(trace) if trace is not None else None
-    if marginal:
-        arr = (C.c_void_p * S)(*[g._h for g in gps])
-        etas = _f64(np.broadcast_to(np.asarray(eta, dtype=np.float64), (S,)))
-        check(lib().robo_acq_batch_marginal_cand(arr, S, ACQ_KINDS[kind], float(par), _arr(etas), cand._h, q,
-                                                 FANTASY_KINDS[fantasy], float(liar), p_idx, _arr(val), _arr(fant), p_fl,
-                                                 C.byref(made), p_trace))
-    else:
-        check(lib().robo_acq_batch_cand(gps[0]._h, ACQ_KINDS[kind], float(par), float(eta), cand._h, q,
-                                        FANTASY_KINDS[fantasy], float(liar), p_idx, _arr(val), _arr(fant), p_fl,
-                                        C.byref(made), p_trace))
+    fn = lib().robo_acq_batch_marginal_cand if marginal else lib().robo_acq_batch_cand
+    head = _ensemble_head(gps, eta, marginal, ACQ_KINDS[kind], float(par))
+    check(fn(*head, cand._h, q, FANTASY_KINDS[fantasy], float(liar), p_idx, _arr(val), _arr(fant), p_fl, C.byref(made),
+             p_trace))
     return BatchResult(idx, val, fant, fl, made.value, trace)
 
 
@@ -883,25 +901,18 @@ class RefineResult(object):
 def acq_refine(gps, kind, par, eta, cand, n_starts=256, n_steps=50, step0=0.05, diagnostics=False, marginal=True):
     """the gradient-refined maximiser of a closed-form acquisition over device GPs (one: robo_acq_refine_cand; the mean
     over several hyper-parameter samples: robo_acq_refine_marginal_cand).  eta: one incumbent value, or one per sample."""
-    S = len(gps)
     K, T, D = int(n_starts), int(n_steps), cand.dim
     x = np.empty(D)
-    val, idx, fl = C.c_double(0), C.c_int64(0), C.c_uint32(0)
+    best = _Best()                           # (value, start index, flags)
     want = bool(diagnostics) and 1 <= K <= REFINE_MAX_STARTS and T >= 0
     starts = np.empty(K, dtype=np.int64) if want else None
     trace = np.empty((T + 1, K, 2 * D + 3)) if want else None
     p_starts = starts.ctypes.data_as(C.POINTER(C.c_int64)) if want else None
     p_trace = _arr(trace) if want else None
-    if marginal:
-        arr = (C.c_void_p * S)(*[g._h for g in gps])
-        etas = _f64(np.broadcast_to(np.asarray(eta, dtype=np.float64), (S,)))
-        check(lib().robo_acq_refine_marginal_cand(arr, S, ACQ_KINDS[kind], float(par), _arr(etas), cand._h, K, T,
-                                                  float(step0), _arr(x), C.byref(val), C.byref(idx), C.byref(fl),
-                                                  p_starts, p_trace))
-    else:
-        check(lib().robo_acq_refine_cand(gps[0]._h, ACQ_KINDS[kind], float(par), float(eta), cand._h, K, T, float(step0),
-                                         _arr(x), C.byref(val), C.byref(idx), C.byref(fl), p_starts, p_trace))
-    return RefineResult(x, val.value, idx.value, fl.value, starts, trace)
+    fn = lib().robo_acq_refine_marginal_cand if marginal else lib().robo_acq_refine_cand
+    head = _ensemble_head(gps, eta, marginal, ACQ_KINDS[kind], float(par))
+    check(fn(*head, cand._h, K, T, float(step0), _arr(x), *best.refs, p_starts, p_trace))
+    return RefineResult(x, *best.values(), starts, trace)
 
 
 class Comm(object):
@@ -966,14 +977,13 @@ class Comm(object):
         """sample shard: this rank's fitted GPs (possibly none) -> (mean over ALL s_total samples or None, max,
         argmax, flags), identical on every rank"""
         S = len(gps)
-        arr = (C.c_void_p * max(S, 1))(*[g._h for g in gps])
         etas = _f64(np.asarray(etas, dtype=np.float64).reshape(-1)) if S else np.zeros(1)
         out = np.empty(cand.m) if want_values else None
-        mx, am, fl = C.c_double(0), C.c_int64(0), C.c_uint32(0)
-        check(lib().robo_acq_eval_marginal_cand_sharded(self._h, arr, S, int(s_total), ACQ_KINDS[kind], float(par),
+        best = _Best()
+        check(lib().robo_acq_eval_marginal_cand_sharded(self._h, _handles(gps), S, int(s_total), ACQ_KINDS[kind], float(par),
                                                         _arr(etas), cand._h, _arr(out) if want_values else None,
-                                                        C.byref(mx), C.byref(am), C.byref(fl)))
-        return out, mx.value, am.value, fl.value
+                                                        *best.refs))
+        return (out,) + best.values()
 
 
 class CandidateShards(object):
@@ -1137,12 +1147,11 @@ class Multi(object):
         etas = _f64(np.concatenate([np.asarray(e, dtype=np.float64).reshape(-1) for e in eta_groups] or [np.zeros(0)]))
         assert etas.shape[0] == len(flat)
         out = np.empty(cands[0].m) if want_values else None
-        mx, am, fl = C.c_double(0), C.c_int64(0), C.c_uint32(0)
+        best = _Best()
         check(lib().robo_acq_eval_marginal_cand_multi(self._h, self._handles(flat), counts, ACQ_KINDS[kind], float(par),
                                                       _arr(etas), self._handles(cands),
-                                                      _arr(out) if want_values else None, C.byref(mx), C.byref(am),
-                                                      C.byref(fl)))
-        return out, mx.value, am.value, fl.value
+                                                      _arr(out) if want_values else None, *best.refs))
+        return (out,) + best.values()
 
     def predict_mixture(self, gp_groups, cands):
         """GaussianProcessMCMC.predict over samples that live on several devices -> (mean (M,), var (M,))"""
@@ -1161,10 +1170,9 @@ def fit_batch(gps, thetas, mean_c):
     S = len(gps)
     thetas = _f64(_full_theta(gps[0], np.atleast_2d(thetas)))
     assert thetas.shape == (S, gps[0].n_theta)
-    arr = (C.c_void_p * S)(*[g._h for g in gps])
     ll = np.empty(S)
     st = np.empty(S, dtype=np.int32)
-    check(lib().robo_gp_fit_batch(arr, S, _arr(thetas), float(mean_c), _arr(ll), st.ctypes.data_as(C.POINTER(C.c_int32))))
+    check(lib().robo_gp_fit_batch(_handles(gps), S, _arr(thetas), float(mean_c), _arr(ll), st.ctypes.data_as(C.POINTER(C.c_int32))))
     for g in gps:
         g.n = gps[0].n
     return ll, st
@@ -1173,9 +1181,8 @@ def fit_batch(gps, thetas, mean_c):
 def predict_mixture(gps, cand):
     """GaussianProcessMCMC.predict over device GPs -> (mean (M,), var (M,))"""
     S = len(gps)
-    arr = (C.c_void_p * S)(*[g._h for g in gps])
     mean, var = np.empty(cand.m), np.empty(cand.m)
-    check(lib().robo_gp_predict_mixture_cand(arr, S, cand._h, _arr(mean), _arr(var)))
+    check(lib().robo_gp_predict_mixture_cand(_handles(gps), S, cand._h, _arr(mean), _arr(var)))
     return mean, var
 
 
@@ -1184,10 +1191,10 @@ def acq_from_moments(ctx, kind, par, eta, mean, var):
     mean, var = _f64(mean), _f64(var)
     assert mean.ndim == 1 and mean.shape == var.shape
     out = np.empty(mean.shape[0])
-    mx, am, fl = C.c_double(0), C.c_int64(0), C.c_uint32(0)
+    best = _Best()
     check(lib().robo_acq_eval_moments(ctx._h, ACQ_KINDS[kind], float(par), float(eta), _arr(mean), _arr(var),
-                                      mean.shape[0], _arr(out), C.byref(mx), C.byref(am), C.byref(fl)))
-    return out, mx.value, am.value, fl.value
+                                      mean.shape[0], _arr(out), *best.refs))
+    return (out,) + best.values()
 
 
 class EPState(object):
@@ -1310,10 +1317,10 @@ def igmc_eval(gp, cand, rep, mc, sn2, want_values=True):
     """Monte-Carlo information gain of every candidate (robo_igmc_eval_cand) -> (values or None, max, argmax, flags)"""
     assert rep.m == mc.nb
     out = np.empty(cand.m) if want_values else None
-    mx, am, fl = C.c_double(0), C.c_int64(0), C.c_uint32(0)
+    best = _Best()
     check(lib().robo_igmc_eval_cand(gp._h, cand._h, rep._h, mc.W.size, mc.nf, float(sn2), *mc.args(),
-                                    _arr(out) if want_values else None, C.byref(mx), C.byref(am), C.byref(fl)))
-    return out, mx.value, am.value, fl.value
+                                    _arr(out) if want_values else None, *best.refs))
+    return (out,) + best.values()
 
 
 def igmc_from_moments(ctx, s, v, mc, sn2, with_counts=False):
@@ -1341,15 +1348,13 @@ def acq_marginal(gps, kind, par, eta, cand, want_values=True, reduce="mean"):
     """MarginalizationGPMCMC.compute over device GPs -> (values, max, argmax, flags).
     eta: one incumbent value for all samples, or one per sample (S,)."""
     S = len(gps)
-    arr = (C.c_void_p * S)(*[g._h for g in gps])
-    etas = _f64(np.broadcast_to(np.asarray(eta, dtype=np.float64), (S,)))
-    mx, am, fl = C.c_double(0), C.c_int64(0), C.c_uint32(0)
+    arr, etas = _handles(gps), _etas(eta, S)
+    best = _Best()
     out = np.empty(cand.m) if (want_values or reduce == "sum") else None
     if reduce == "sum":
         check(lib().robo_acq_eval_sum_cand(arr, S, ACQ_KINDS[kind], float(par), _arr(etas), cand._h, _arr(out),
-                                           C.byref(fl)))
-        return out, None, None, fl.value
+                                           best.refs[2]))
+        return out, None, None, best.flags.value
     check(lib().robo_acq_eval_marginal_cand(arr, S, ACQ_KINDS[kind], float(par), _arr(etas), cand._h,
-                                            _arr(out) if want_values else None, C.byref(mx), C.byref(am),
-                                            C.byref(fl)))
-    return out, mx.value, am.value, fl.value
+                                            _arr(out) if want_values else None, *best.refs))
+    return (out,) + best.values()

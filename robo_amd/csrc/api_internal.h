@@ -1,0 +1,67 @@
+// Host helpers shared by the files that hold C ABI entry points (api_*.hip, refine.hip, batch.hip, mes.hip, comm.hip,
+// multi.hip): each is declared here once and defined in the file named above its group.  An ensemble driver reads as
+// "ensemble_check, acq_sweep, its own kernels, finish_call".
+#pragma once
+#include <functional>
+#include <initializer_list>
+
+#include "common.h"
+
+namespace robo {
+
+inline size_t workspace_bytes(const robo_ctx* c) { return (size_t)c->tune.ws_bytes; }
+
+template <class T>
+inline int dev_alloc(T** p, size_t count) {
+    ROBO_HIP_CHECK(hipMalloc((void**)p, (count ? count : 1) * sizeof(T)));
+    return ROBO_OK;
+}
+
+// ---- api_predict.hip: candidate handles and the posterior ---------------------------------------------------------------------
+int cand_alloc(robo_ctx* ctx, int64_t m, int32_t dim, robo_cand** out);       // an empty handle (points not uploaded)
+int cand_ensure_workspace(robo_cand* k, int n_pad, bool single_chunk);        // the (chunk x n_pad) solve workspace
+int decide_winv(robo_gp* g, const robo_cand* k, bool* use);                   // the solve goes through W = L^-1 (built here)
+// fills k->d_mean / d_var (asynchronous); after_chunk(c0, cn) runs while the chunk's V = L^-1 K*^T is in the workspace;
+// need_v: the caller consumes V itself, not only its reductions
+int predict_core(robo_gp* g, robo_cand* k, bool single_chunk = false,
+                 const std::function<int(int64_t, int64_t)>& after_chunk = nullptr, bool need_v = false);
+int predict_samples(robo_gp* const* gps, int32_t S, robo_cand* k, int cap);   // -> rows of k->d_mu_all / d_var_all
+int host_cand(robo_gp* g, const double* Xc, int64_t m, robo_cand** out, bool* kept);   // the handle behind host arrays
+
+// ---- api_acq.hip: closed-form acquisitions and what the ensemble drivers share -------------------------------------------------
+int check_acq_kind(int kind);
+int clear_flags_on_error(robo_cand* k, int status);        // -> status; a failed call leaves no stale flag bits in k
+// D2H of (max, argmax, flags) [+ d_vec] and the one synchronisation of the call
+int acq_read_back(robo_cand* k, const double* d_vec, double* out_vec, double* out_max, int64_t* out_argmax,
+                  uint32_t* out_flags);
+// sum over the samples of the acquisition into k->d_acq_sum (asynchronous)
+int acq_accumulate(robo_gp* const* gps, int32_t S, int32_t acq_kind, double par, const double* etas, robo_cand* k);
+// the sweep into k->d_acq and the argmax partials (asynchronous): gps[0]'s acquisition, or (marginal) the mean over S samples
+int acq_sweep(robo_gp* const* gps, int32_t S, bool marginal, int32_t acq_kind, double par, const double* etas, robo_cand* k);
+// the samples of an ensemble call against the candidates, then hipSetDevice.  `label` opens the messages.
+constexpr unsigned ENSEMBLE_MES_VERDICTS = 1;      // an unfitted sample is ROBO_BAD_ARGUMENT naming the sample; no shape checks
+constexpr unsigned ENSEMBLE_ONE_KIND_FP64 = 2;     // every sample has the first one's kernel kind and fp64 covariance entries
+int ensemble_check(const char* label, unsigned flags, robo_gp* const* gps, int32_t S, const robo_cand* k);
+// The end of a driver.  status != ROBO_OK: wait for the stream, clear k's flags, return status.  Otherwise issue the copies
+// (dst == nullptr: not asked for) and synchronise once; sync = false leaves that to an acq_read_back that follows.
+struct ReadBack {
+    void* dst;
+    const void* src;
+    size_t bytes;
+};
+int finish_call(robo_cand* k, const char* label, int status, std::initializer_list<ReadBack> copies, bool sync = true);
+int grow_trace(double** d_buf, size_t* cap, size_t doubles);                  // a diagnostics buffer: grows, never shrinks
+// a one-dimensional candidate handle holding (mean, var) of any model; failure reads "<what> failed: <hip error>"
+int moments_handle(robo_ctx* ctx, const double* mean, const double* var, int64_t m, const char* what, robo_cand** out);
+// dH / (exp(log-cost mean) + overhead) of every candidate into k->d_acq and the argmax partials (asynchronous)
+int ig_per_cost_core(robo_gp* g, robo_cand* k, robo_cand* rep, int32_t npts, double sn2, const double* logP,
+                     const double* lmb, const double* W, const double* dlogPdMu, const double* dlogPdSigma,
+                     const double* dlogPdMudMu, robo_gp* cost_gp, robo_cand* cost_k, double overhead);
+
+// ---- comm.hip: the exchange kernels multi.hip reduces with, too ------------------------------------------------------------------
+int launch_comm_pack_sum(hipStream_t st, const double* d_part, long long m, int have, const unsigned* d_flags, int status,
+                         double* d_send);
+int launch_comm_ordered_sum(hipStream_t st, const double* d_recv, long long stride, int world, long long m, double* d_total,
+                            unsigned* d_flags, int* h_status);
+
+}  // namespace robo

@@ -22,7 +22,7 @@
 //
 // Ordering is the stream's alone: the winner's index stays in device memory (BatchState::idx) and the next pick's
 // kernels read x_j from the candidate buffer through it.  Every sum has a fixed order that does not depend on the grid.
-#include "common.h"
+#include "api_internal.h"
 #include "kern_math.h"
 
 namespace robo {
@@ -397,17 +397,6 @@ void batch_free(BatchWork* w) {
     delete w;
 }
 
-int batch_ensure_trace(BatchWork* w, size_t doubles) {
-    if (doubles > w->trace_cap) {
-        if (w->d_trace) ROBO_HIP_CHECK(hipFree(w->d_trace));
-        w->d_trace = nullptr;
-        w->trace_cap = 0;
-        ROBO_HIP_CHECK(hipMalloc((void**)&w->d_trace, doubles * sizeof(double)));
-        w->trace_cap = doubles;
-    }
-    return ROBO_OK;
-}
-
 int launch_batch_reset(robo_ctx* ctx, const BatchState& st) {
     hipLaunchKernelGGL(batch_reset_kernel, dim3((unsigned)((st.q * st.S + 255) / 256)), dim3(256), 0, ctx->stream, st);
     ROBO_LAUNCH_CHECK();
@@ -468,4 +457,98 @@ int launch_batch_condition(robo_gp* gp, const BatchState& st, const robo_cand* c
     return ROBO_OK;
 }
 
+// ---- the driver ---------------------------------------------------------------------------------------------------------------
+static int select_ensure(robo_gp* g, const robo_cand* k, int S, int q, BatchWork** out) {
+    BatchWork* w = g->batch;
+    if (w && (w->m != k->m || w->S != S || w->n_pad < g->n_pad || w->q < q)) {
+        ROBO_HIP_CHECK(hipStreamSynchronize(g->ctx->stream));
+        batch_free(w);
+        g->batch = w = nullptr;
+    }
+    if (!w) ROBO_TRY(batch_alloc(g->ctx, k->m, k->m_pad, S, g->n_pad_max, q, &g->batch));
+    *out = g->batch;
+    return ROBO_OK;
+}
+
+// marginal: pick 0 is robo_acq_eval_marginal_cand's sweep (accumulate, divide); otherwise robo_acq_eval_cand's
+static int batch_core(robo_gp* const* gps, int32_t S, bool marginal, int32_t acq_kind, double par, const double* etas,
+                      robo_cand* k, int32_t q, int32_t fantasy_kind, double liar, int64_t* out_idx, double* out_values,
+                      double* out_fantasy, uint32_t* out_flags, int32_t* out_n_made, double* out_trace) {
+    if (!gps || S < 1 || !etas || !k || !out_idx) return ROBO_BAD_ARGUMENT;
+    ROBO_TRY(check_acq_kind(acq_kind));
+    if (q < 1 || (int64_t)q > k->m || q > BATCH_MAX_Q) {
+        set_error("batch selection: q = %d outside 1 .. min(m = %lld, %d)", q, (long long)k->m, BATCH_MAX_Q);
+        return ROBO_BAD_ARGUMENT;
+    }
+    if (fantasy_kind != ROBO_FANTASY_KRIGING_BELIEVER && fantasy_kind != ROBO_FANTASY_CONSTANT_LIAR) {
+        set_error("unknown fantasy kind %d", fantasy_kind);
+        return ROBO_BAD_ARGUMENT;
+    }
+    ROBO_TRY(ensemble_check("batch selection", ENSEMBLE_ONE_KIND_FP64, gps, S, k));
+    robo_gp* g0 = gps[0];
+    robo_ctx* c = g0->ctx;
+    BatchWork* w = nullptr;
+    ROBO_TRY(select_ensure(g0, k, S, q, &w));
+    const size_t trace_len = (size_t)q * S * k->m * 2;
+    if (out_trace) ROBO_TRY(grow_trace(&w->d_trace, &w->trace_cap, trace_len));
+    w->st.q = q;
+    w->st.trace = out_trace ? w->d_trace : nullptr;
+    const BatchState& st = w->st;
+    const bool state = q > 1 || out_trace;        // q = 1: the sweep alone
+
+    // pick 0: the sweep, launch for launch; every sample's latent moments are taken while its posterior is in the handle
+    ROBO_TRY(launch_batch_reset(c, st));
+    for (int s = 0; s < S; ++s) {
+        ROBO_TRY(clear_flags_on_error(k, predict_core(gps[s], k)));
+        ROBO_TRY(clear_flags_on_error(k, launch_acq(c, k, acq_kind, par, etas[s], marginal, s == 0)));
+        if (state) ROBO_TRY(clear_flags_on_error(k, launch_batch_init(gps[s], st, k, s, etas[s])));
+    }
+    if (marginal) ROBO_TRY(clear_flags_on_error(k, launch_argmax(k, k->d_acq_sum, (double)S)));
+    int status = launch_batch_record(c, st, k, 0, true);
+    // the later picks: launches only, ordered by the stream
+    for (int j = 1; status == ROBO_OK && j < q; ++j) {
+        for (int s = 0; status == ROBO_OK && s < S; ++s)
+            status = launch_batch_condition(gps[s], st, k, s, j, acq_kind, par, fantasy_kind, liar);
+        if (status == ROBO_OK) status = launch_argmax(k, k->d_acq_sum, marginal ? (double)S : 1.0);
+        if (status == ROBO_OK) status = launch_batch_record(c, st, k, j, false);
+    }
+    // read-back: one copy of the report range into pinned memory (+ the trace, diagnostics), the one synchronisation
+    ROBO_TRY(finish_call(k, "batch selection", status, {{w->h_report, w->d_block + w->rep_off, w->rep_bytes},
+                                                        {out_trace, w->d_trace, trace_len * sizeof(double)}}));
+    const double* hv = reinterpret_cast<const double*>(w->h_report);
+    const long long* hi = reinterpret_cast<const long long*>(w->h_report + w->off_idx);
+    const unsigned* hf = reinterpret_cast<const unsigned*>(w->h_report + w->off_flg);
+    for (int j = 0; j < q; ++j) {
+        out_idx[j] = (int64_t)hi[j];
+        if (out_values) out_values[j] = hv[j];
+        if (out_flags) out_flags[j] = hf[j];
+    }
+    if (out_fantasy) memcpy(out_fantasy, w->h_report + w->off_fant, (size_t)q * S * sizeof(double));
+    int made = 0;
+    memcpy(&made, w->h_report + w->off_int, sizeof(int));
+    if (out_n_made) *out_n_made = made;
+    return ROBO_OK;
+}
+
 }  // namespace robo
+
+using namespace robo;
+
+extern "C" {
+
+int32_t robo_acq_batch_cand(robo_gp* g, int32_t acq_kind, double par, double eta, robo_cand* k, int32_t q,
+                            int32_t fantasy_kind, double liar, int64_t* out_idx, double* out_values, double* out_fantasy,
+                            uint32_t* out_flags, int32_t* out_n_made, double* out_trace) {
+    return batch_core(&g, g ? 1 : 0, false, acq_kind, par, &eta, k, q, fantasy_kind, liar, out_idx, out_values, out_fantasy,
+                      out_flags, out_n_made, out_trace);
+}
+
+int32_t robo_acq_batch_marginal_cand(robo_gp* const* gps, int32_t S, int32_t acq_kind, double par, const double* etas,
+                                     robo_cand* k, int32_t q, int32_t fantasy_kind, double liar, int64_t* out_idx,
+                                     double* out_values, double* out_fantasy, uint32_t* out_flags, int32_t* out_n_made,
+                                     double* out_trace) {
+    return batch_core(gps, S, true, acq_kind, par, etas, k, q, fantasy_kind, liar, out_idx, out_values, out_fantasy,
+                      out_flags, out_n_made, out_trace);
+}
+
+}  // extern "C"

@@ -15,17 +15,9 @@
 #include <cstdlib>
 #include <mutex>
 
-#include "common.h"
+#include "api_internal.h"
 
 namespace robo {
-int api_acq_local(robo_gp* g, int kind, double par, double eta, robo_cand* k);
-int api_acq_accumulate(robo_gp* const* gps, int S, int kind, double par, const double* etas, robo_cand* k);
-int api_acq_read_back(robo_cand* k, const double* d_vec, double* out_vec, double* out_max, int64_t* out_argmax,
-                      uint32_t* out_flags);
-int api_clear_flags(robo_cand* k, int status);
-int api_ig_per_cost_local(robo_gp* g, robo_cand* k, robo_cand* rep, int npts, double sn2, const double* const* ep,
-                          robo_gp* cost_gp, robo_cand* cost_k, double overhead);
-
 // rccl.h, the five entry points used (signatures as in /opt/rocm/include/rccl/rccl.h:187,220,260,339,678)
 struct NcclId { char internal[ROBO_COMM_ID_BYTES]; };
 typedef int (*nccl_get_unique_id_t)(NcclId*);
@@ -358,7 +350,7 @@ int32_t robo_acq_eval_cand_sharded(robo_comm* c, robo_gp* g, int32_t acq_kind, d
         return ROBO_BAD_ARGUMENT;
     }
     ROBO_HIP_CHECK(hipSetDevice(c->ctx->device));
-    const int status = api_acq_local(g, acq_kind, par, eta, k);
+    const int status = acq_sweep(&g, 1, false, acq_kind, par, &eta, k);
     return exchange_best(c, k, status, global_offset, "robo_acq_eval_cand_sharded", out_acq, out_max, out_argmax,
                          out_owner_rank, out_flags);
 }
@@ -374,8 +366,8 @@ int32_t robo_ig_eval_per_cost_cand_sharded(robo_comm* c, robo_gp* g, robo_cand* 
         return ROBO_BAD_ARGUMENT;
     }
     ROBO_HIP_CHECK(hipSetDevice(c->ctx->device));
-    const double* ep[6] = {logP, lmb, W, dlogPdMu, dlogPdSigma, dlogPdMudMu};
-    const int status = api_ig_per_cost_local(g, k, rep, npts, sn2, ep, cost_gp, cost_k, overhead);
+    const int status = clear_flags_on_error(k, ig_per_cost_core(g, k, rep, npts, sn2, logP, lmb, W, dlogPdMu, dlogPdSigma,
+                                                                dlogPdMudMu, cost_gp, cost_k, overhead));
     return exchange_best(c, k, status, global_offset, "robo_ig_eval_per_cost_cand_sharded", out_values, out_max,
                          out_argmax, out_owner_rank, nullptr);
 }
@@ -395,7 +387,7 @@ int32_t robo_acq_eval_marginal_cand_sharded(robo_comm* c, robo_gp* const* gps, i
     // (out of device memory for the exchange buffers: nothing to send from -- the one error that leaves before the collective)
     ROBO_TRY_COMM(comm_reserve(c, (size_t)m + 2));
     int status = ROBO_OK;
-    if (S_local > 0) status = api_acq_accumulate(gps, S_local, acq_kind, par, etas, k);
+    if (S_local > 0) status = acq_accumulate(gps, S_local, acq_kind, par, etas, k);
     const bool ok = status == ROBO_OK;
     // a failed rank still takes part in the collective (zeros): the others must not hang
     hipLaunchKernelGGL(comm_pack_sum_kernel, dim3((unsigned)((m + 1 + 255) / 256)), dim3(256), 0, st,
@@ -408,18 +400,18 @@ int32_t robo_acq_eval_marginal_cand_sharded(robo_comm* c, robo_gp* const* gps, i
     // EVERY rank learns whether any rank's local half failed (a sum with a rank's samples missing must not be returned
     // as ROBO_OK anywhere): one stream synchronisation before the argmax
     hipStreamSynchronize(st);
-    if (!ok) return api_clear_flags(k, status);
+    if (!ok) return clear_flags_on_error(k, status);
     {
         int bad[2];
         memcpy(bad, c->h_pinned + 4, sizeof(bad));
         if (bad[0] != ROBO_OK) {
             set_error("robo_acq_eval_marginal_cand_sharded: the local half of rank %d failed with status %d", bad[1],
                       bad[0]);
-            return api_clear_flags(k, bad[0]);
+            return clear_flags_on_error(k, bad[0]);
         }
     }
-    ROBO_TRY_COMM(api_clear_flags(k, launch_argmax(k, k->d_acq_sum, (double)S_total)));
-    return api_clear_flags(k, api_acq_read_back(k, k->d_acq, out_acq, out_max, out_argmax, out_flags));
+    ROBO_TRY_COMM(clear_flags_on_error(k, launch_argmax(k, k->d_acq_sum, (double)S_total)));
+    return clear_flags_on_error(k, acq_read_back(k, k->d_acq, out_acq, out_max, out_argmax, out_flags));
 }
 
 }  // extern "C"

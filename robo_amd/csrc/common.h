@@ -175,7 +175,7 @@ struct EpWork;                          // ep.hip: grow-once buffers of robo_ep_
 void ep_release(robo_ctx* ctx);         // ... freed with the context
 struct McWork;                          // igmc.hip: grow-once buffers and uploaded draws of the Monte-Carlo p_min
 void mc_release(robo_ctx* ctx);         // ... freed with the context
-int ctx_aux_streams(robo_ctx* ctx);   // api.hip: create ctx->aux / ev_fork / ev_join once
+int ctx_aux_streams(robo_ctx* ctx);   // api_ctx.hip: create ctx->aux / ev_fork / ev_join once
 void ctx_retain(robo_ctx* ctx);        // a handle was created on ctx
 void ctx_release(robo_ctx* ctx);       // ... destroyed: frees a closing context with its last handle
 }
@@ -219,7 +219,6 @@ struct RefineWork {
 };
 int refine_alloc(robo_ctx* ctx, int K, int D, RefineWork** out);
 void refine_free(RefineWork* w);               // the state block and the trace; `ws` belongs to the caller
-int refine_ensure_trace(RefineWork* w, size_t doubles);
 
 // ---- greedy batch proposals with fantasised picks (batch.hip) -----------------------------------------------------------------
 // the state of one selection; all arrays device memory of one block, per-sample arrays [S][m_pad] / [S][n_pad]
@@ -252,7 +251,6 @@ struct BatchWork {
 };
 int batch_alloc(robo_ctx* ctx, int64_t m, int64_t m_pad, int S, int n_pad, int q, BatchWork** out);
 void batch_free(BatchWork* w);
-int batch_ensure_trace(BatchWork* w, size_t doubles);
 
 // ---- max-value entropy search (mes.hip) ------------------------------------------------------------------------------------
 // the state of one call; all arrays device memory of one block, per-sample arrays [S][K] / [S][7]
@@ -290,7 +288,7 @@ struct robo_ctx {
     hipEvent_t ev_fork, ev_join[ROBO_AUX_STREAMS];
     bool aux_ready;
     // lifetime: handles created on this context (robo_gp, robo_cand, robo_comm, robo_multi) keep it alive.  robo_ctx_destroy
-    // marks it `closing`; stream, events and scratch are released when the last such handle is destroyed (api.hip
+    // marks it `closing`; stream, events and scratch are released when the last such handle is destroyed (api_ctx.hip
     // ctx_retain / ctx_release).  A binding whose garbage collector finalises a context before the objects that live on it
     // (Python's cyclic GC gives no order) therefore cannot make a later robo_gp_destroy touch a dead stream.
     int users;
@@ -455,7 +453,7 @@ struct McmcState {
     const double *d_uz, *d_ua;                        // (n_steps x 2 x k/2) each, emcee's draw order
     const int* d_partner;
     double *d_chain, *d_lnprob;                       // (k x n_steps x P), (k x n_steps); nullable
-    FitSample* d_sp;                                  // the batched fit's inputs / outputs (api.hip batch_ensure)
+    FitSample* d_sp;                                  // the batched fit's inputs / outputs (api_fit.hip batch_ensure)
     double* d_ism;
     const double* d_out;
     const int* d_fail;

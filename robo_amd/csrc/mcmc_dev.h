@@ -91,7 +91,7 @@ __device__ __forceinline__ bool mcmc_block_proposal(const McmcState& st, int sta
     return ok;
 }
 
-// the batch fit's per-sample inputs of proposal q (api.hip theta_to_sample)
+// the batch fit's per-sample inputs of proposal q (api_fit.hip theta_to_sample)
 __device__ __forceinline__ FitSample mcmc_fit_sample(const McmcState& st, const double* sq, bool ok) {
     const bool fab = st.kind == ROBO_KERNEL_FABOLAS;
     FitSample sp;

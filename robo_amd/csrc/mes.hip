@@ -16,16 +16,11 @@
 // kernels, a pass that finds every bracket narrow enough raises `done` and the remaining passes return at once.
 // Every sum has a fixed order: a workgroup of the F pass adds ITS 128 candidates in index order per grid point, the
 // section kernel adds the workgroups' partials in block order; no floating-point atomics.
-#include "common.h"
+#include "api_internal.h"
 #include "kern_math.h"
 
 namespace robo {
-int api_predict_core(robo_gp* g, robo_cand* k);
-int api_cand_alloc(robo_ctx* ctx, int64_t m, int32_t dim, robo_cand** out);
-int api_acq_read_back(robo_cand* k, const double* d_vec, double* out_vec, double* out_max, int64_t* out_argmax,
-                      uint32_t* out_flags);
-int api_clear_flags(robo_cand* k, int status);
-
+constexpr const char* MES_LABEL = "max-value entropy search";
 constexpr int MES_G = 64;                       // sections per pass and quantile
 constexpr int MES_PTS = 3 * (MES_G - 1);        // interior grid points of the three brackets: 189
 constexpr int MES_F_THREADS = 192;              // one grid point per work-item (3 idle)
@@ -390,66 +385,31 @@ static int mes_core(robo_gp* const* gps, int32_t S, const double* etas, robo_can
                     double* out_ystar, double* out_gumbel, double* out_trace) {
     if (!gps || S < 1 || !etas || !k || !u) return ROBO_BAD_ARGUMENT;
     ROBO_TRY(mes_check_draws(u, (int64_t)S * (K > 0 ? K : 0), K));
-    for (int s = 0; s < S; ++s) {
-        if (!gps[s]) return ROBO_BAD_ARGUMENT;
-        if (!gps[s]->fitted) {
-            set_error("max-value entropy search: sample %d has no fitted model (Model has to be trained first!)", s);
-            return ROBO_BAD_ARGUMENT;
-        }
-    }
+    ROBO_TRY(ensemble_check(MES_LABEL, ENSEMBLE_MES_VERDICTS, gps, S, k));
     robo_gp* g0 = gps[0];
     robo_ctx* c = g0->ctx;
-    ROBO_HIP_CHECK(hipSetDevice(c->device));
     MesWork* w = nullptr;
     ROBO_TRY(mes_ensure(g0, k, S, K, &w));
     const size_t trace_len = (size_t)S * k->m * 2;
-    if (out_trace && trace_len > w->trace_cap) {
-        if (w->d_trace) ROBO_HIP_CHECK(hipFree(w->d_trace));
-        w->d_trace = nullptr;
-        w->trace_cap = 0;
-        ROBO_HIP_CHECK(hipMalloc((void**)&w->d_trace, trace_len * sizeof(double)));
-        w->trace_cap = trace_len;
-    }
+    if (out_trace) ROBO_TRY(grow_trace(&w->d_trace, &w->trace_cap, trace_len));
     const MesState& st = w->st;
     ROBO_TRY(mes_upload_draws(c, w, u));
     // event slots 27 -> 30 -> 31 bracket the tail of the LAST sample: minimum sampling, element-wise half
     const bool ev = c->phase_events || k->m_pad > 16384;
     for (int s = 0; s < S; ++s) {
-        ROBO_TRY(api_clear_flags(k, api_predict_core(gps[s], k)));
-        ROBO_TRY(api_clear_flags(k, launch_mes_sample(c, st, s, k->d_mean, k->d_var,
+        ROBO_TRY(clear_flags_on_error(k, predict_core(gps[s], k)));
+        ROBO_TRY(clear_flags_on_error(k, launch_mes_sample(c, st, s, k->d_mean, k->d_var,
                                                       out_trace ? w->d_trace + (size_t)s * k->m * 2 : nullptr, clamp, etas[s])));
         if (ev) ROBO_HIP_CHECK(hipEventRecord(c->events[30], c->stream));
-        ROBO_TRY(api_clear_flags(k, launch_mes_value(k, st.ystar + (size_t)s * K, K, s == 0)));
+        ROBO_TRY(clear_flags_on_error(k, launch_mes_value(k, st.ystar + (size_t)s * K, K, s == 0)));
         if (ev) ROBO_HIP_CHECK(hipEventRecord(c->events[31], c->stream));
     }
-    ROBO_TRY(api_clear_flags(k, launch_argmax(k, k->d_acq_sum, (double)S)));
-    hipError_t e = hipMemcpyAsync(w->h_stage, w->d_block, w->rep_doubles * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess && out_trace)
-        e = hipMemcpyAsync(out_trace, w->d_trace, trace_len * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-    if (e != hipSuccess) {
-        set_error("max-value entropy search: read-back failed: %s", hipGetErrorString(e));
-        hipStreamSynchronize(c->stream);
-        return api_clear_flags(k, ROBO_RUNTIME_ERROR);
-    }
+    ROBO_TRY(clear_flags_on_error(k, launch_argmax(k, k->d_acq_sum, (double)S)));
+    ROBO_TRY(finish_call(k, MES_LABEL, ROBO_OK, {{w->h_stage, w->d_block, w->rep_doubles * sizeof(double)},
+                                                 {out_trace, w->d_trace, trace_len * sizeof(double)}}, false));
     // (max, argmax, flags) [+ the values] and the one synchronisation of the call
-    ROBO_TRY(api_clear_flags(k, api_acq_read_back(k, k->d_acq, out_acq, out_max, out_argmax, out_flags)));
+    ROBO_TRY(clear_flags_on_error(k, acq_read_back(k, k->d_acq, out_acq, out_max, out_argmax, out_flags)));
     return mes_take_report(w, out_ystar, out_gumbel);
-}
-
-// a one-dimensional candidate handle holding (mean, var) of any model, as robo_acq_eval_moments
-static int mes_moments_handle(robo_ctx* ctx, const double* mean, const double* var, int64_t m, robo_cand** out) {
-    robo_cand* k = nullptr;
-    ROBO_TRY(api_cand_alloc(ctx, m, 1, &k));
-    hipError_t e = hipMemcpyAsync(k->d_mean, mean, (size_t)m * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(k->d_var, var, (size_t)m * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-    if (e != hipSuccess) {
-        set_error("max-value entropy search: upload of the moments failed: %s", hipGetErrorString(e));
-        hipStreamSynchronize(ctx->stream);
-        robo_cand_destroy(k);
-        return ROBO_RUNTIME_ERROR;
-    }
-    *out = k;
-    return ROBO_OK;
 }
 
 }  // namespace robo
@@ -476,21 +436,12 @@ int32_t robo_mes_sample_min_moments(robo_ctx* ctx, const double* mean, const dou
     if (!ctx || !mean || !var || !u) return ROBO_BAD_ARGUMENT;
     ROBO_TRY(mes_check_draws(u, K > 0 ? K : 0, K));
     robo_cand* k = nullptr;
-    ROBO_TRY(mes_moments_handle(ctx, mean, var, m, &k));
+    ROBO_TRY(moments_handle(ctx, mean, var, m, "max-value entropy search: upload of the moments", &k));
     MesWork* w = nullptr;
     int st = mes_alloc(m, 1, K, &w);
     if (st == ROBO_OK) st = mes_upload_draws(ctx, w, u);
     if (st == ROBO_OK) st = launch_mes_sample(ctx, w->st, 0, k->d_mean, k->d_var, nullptr, clamp, eta);
-    if (st == ROBO_OK) {
-        hipError_t e = hipMemcpyAsync(w->h_stage, w->d_block, w->rep_doubles * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) {
-            set_error("max-value entropy search: read-back failed: %s", hipGetErrorString(e));
-            st = ROBO_RUNTIME_ERROR;
-        }
-    } else {
-        hipStreamSynchronize(ctx->stream);
-    }
+    if (w) st = finish_call(k, MES_LABEL, st, {{w->h_stage, w->d_block, w->rep_doubles * sizeof(double)}});
     if (st == ROBO_OK) st = mes_take_report(w, out_ystar, out_gumbel);
     mes_free(w);
     robo_cand_destroy(k);
@@ -505,7 +456,7 @@ int32_t robo_mes_eval_moments(robo_ctx* ctx, const double* mean, const double* v
         return ROBO_BAD_ARGUMENT;
     }
     robo_cand* k = nullptr;
-    ROBO_TRY(mes_moments_handle(ctx, mean, var, m, &k));
+    ROBO_TRY(moments_handle(ctx, mean, var, m, "max-value entropy search: upload of the moments", &k));
     // y* (K <= 128 <= m_pad doubles) rides in the handle's d_q, which the moments form never fills: no state block, no
     // pinned allocation -- this entry point runs once per point under the single-point maximisers
     int st = ROBO_OK;
@@ -515,7 +466,7 @@ int32_t robo_mes_eval_moments(robo_ctx* ctx, const double* mean, const double* v
     }
     if (st == ROBO_OK) st = launch_mes_value(k, k->d_q, K, true);
     if (st == ROBO_OK) st = launch_argmax(k, k->d_acq_sum, 1.0);
-    if (st == ROBO_OK) st = api_acq_read_back(k, k->d_acq, out_acq, out_max, out_argmax, out_flags);
+    if (st == ROBO_OK) st = acq_read_back(k, k->d_acq, out_acq, out_max, out_argmax, out_flags);
     else hipStreamSynchronize(ctx->stream);
     robo_cand_destroy(k);
     return st;

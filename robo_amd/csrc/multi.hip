@@ -24,19 +24,9 @@
 #include <thread>
 #include <vector>
 
-#include "common.h"
+#include "api_internal.h"
 
 namespace robo {
-int api_acq_accumulate(robo_gp* const* gps, int S, int kind, double par, const double* etas, robo_cand* k);
-int api_acq_read_back(robo_cand* k, const double* d_vec, double* out_vec, double* out_max, int64_t* out_argmax,
-                      uint32_t* out_flags);
-int api_clear_flags(robo_cand* k, int status);
-int api_predict_samples(robo_gp* const* gps, int S, robo_cand* k, int cap);
-int launch_comm_pack_sum(hipStream_t st, const double* d_part, long long m, int have, const unsigned* d_flags, int status,
-                         double* d_send);
-int launch_comm_ordered_sum(hipStream_t st, const double* d_recv, long long stride, int world, long long m, double* d_total,
-                            unsigned* d_flags, int* h_status);
-
 // a C++ exception (an allocation failure inside an entry point) must not leave a worker thread: the caller would wait
 // for ever, and an exception escaping a std::thread ends the process
 static int guarded(const std::function<int()>& fn) {
@@ -527,7 +517,7 @@ int32_t robo_acq_eval_marginal_cand_multi(robo_multi* m, robo_gp* const* gps, co
         ROBO_HIP_CHECK(hipSetDevice(c->device));
         int status = ROBO_OK;
         const int ns = S_dev[g];
-        if (ns > 0) status = api_acq_accumulate(gps + off[(size_t)g], ns, acq_kind, par, etas + off[(size_t)g], cands[g]);
+        if (ns > 0) status = acq_accumulate(gps + off[(size_t)g], ns, acq_kind, par, etas + off[(size_t)g], cands[g]);
         if (ns > 0 && status == ROBO_OK)
             status = launch_comm_pack_sum(c->stream, cands[g]->d_acq_sum, mm, 1, cands[g]->d_flags, ROBO_OK, m->d_send[(size_t)g]);
         else
@@ -541,7 +531,7 @@ int32_t robo_acq_eval_marginal_cand_multi(robo_multi* m, robo_gp* const* gps, co
         for (int g = 0; g < m->G; ++g)
             if (cands[g]) {
                 hipSetDevice(m->ctx[(size_t)g]->device);
-                api_clear_flags(cands[g], st);
+                clear_flags_on_error(cands[g], st);
             }
         hipSetDevice(m->ctx[0]->device);
         hipStreamSynchronize(m->ctx[0]->stream);
@@ -555,10 +545,10 @@ int32_t robo_acq_eval_marginal_cand_multi(robo_multi* m, robo_gp* const* gps, co
     for (int g = 0; g < m->G; ++g)
         ROBO_TRY(gather_to_first(m, g, m->d_recv + (size_t)g * ((size_t)mm + 2), m->d_send[(size_t)g],
                                  ((size_t)mm + 2) * sizeof(double)));
-    ROBO_TRY(api_clear_flags(k0, launch_comm_ordered_sum(c0->stream, m->d_recv, mm + 2, m->G, mm, k0->d_acq_sum, k0->d_flags,
+    ROBO_TRY(clear_flags_on_error(k0, launch_comm_ordered_sum(c0->stream, m->d_recv, mm + 2, m->G, mm, k0->d_acq_sum, k0->d_flags,
                                                          reinterpret_cast<int*>(m->h_pinned + 4))));
-    ROBO_TRY(api_clear_flags(k0, launch_argmax(k0, k0->d_acq_sum, (double)S_total)));
-    return api_clear_flags(k0, api_acq_read_back(k0, k0->d_acq, out_acq, out_max, out_argmax, out_flags));
+    ROBO_TRY(clear_flags_on_error(k0, launch_argmax(k0, k0->d_acq_sum, (double)S_total)));
+    return clear_flags_on_error(k0, acq_read_back(k0, k0->d_acq, out_acq, out_max, out_argmax, out_flags));
 }
 
 int32_t robo_gp_predict_mixture_cand_multi(robo_multi* m, robo_gp* const* gps, const int32_t* S_dev, robo_cand* const* cands,
@@ -582,7 +572,7 @@ int32_t robo_gp_predict_mixture_cand_multi(robo_multi* m, robo_gp* const* gps, c
     ROBO_TRY(multi_run(m, [&](int g) -> int {
         if (!cands[g] || (g != 0 && S_dev[g] == 0)) return (int)ROBO_OK;
         robo_ctx* c = m->ctx[(size_t)g];
-        ROBO_TRY(api_predict_samples(gps + off[(size_t)g], S_dev[g], cands[g], g == 0 ? S_total : S_dev[g]));
+        ROBO_TRY(predict_samples(gps + off[(size_t)g], S_dev[g], cands[g], g == 0 ? S_total : S_dev[g]));
         ROBO_HIP_CHECK(hipStreamSynchronize(c->stream));
         return (int)ROBO_OK;
     }));

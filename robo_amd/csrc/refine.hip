@@ -10,7 +10,9 @@
 // Every start is one workgroup of the epilogue and never looks at another start, so its trajectory does not depend on K
 // or on its slot.  The decisions a host restatement must reproduce (accept test, step-length update, the trial point
 // and its clip) are single rn_* operations on stored doubles (common.h), never contracted.
-#include "common.h"
+#include <vector>
+
+#include "api_internal.h"
 #include "kern_math.h"
 
 namespace robo {
@@ -440,17 +442,6 @@ void refine_free(RefineWork* w) {
     delete w;
 }
 
-int refine_ensure_trace(RefineWork* w, size_t doubles) {
-    if (doubles > w->trace_cap) {
-        if (w->d_trace) ROBO_HIP_CHECK(hipFree(w->d_trace));
-        w->d_trace = nullptr;
-        w->trace_cap = 0;
-        ROBO_HIP_CHECK(hipMalloc((void**)&w->d_trace, doubles * sizeof(double)));
-        w->trace_cap = doubles;
-    }
-    return ROBO_OK;
-}
-
 int launch_refine_select(robo_ctx* ctx, const RefineState& st, const double* d_vals, int64_t m, const double* d_Xc,
                          double step0) {
     int blocks = (int)((m + 255) / 256);
@@ -487,4 +478,117 @@ int launch_refine_result(robo_ctx* ctx, const RefineState& st, unsigned* d_cand_
     return ROBO_OK;
 }
 
+// ---- the driver ---------------------------------------------------------------------------------------------------------------
+// state + pseudo-row workspace for K starts in D dimensions, kept with the GP like the host-array candidate handle
+static int refine_ensure(robo_gp* g, int K, int D, RefineWork** out) {
+    if (g->refine && (g->refine->K != K || g->refine->D != D)) {
+        ROBO_HIP_CHECK(hipStreamSynchronize(g->ctx->stream));
+        robo_cand_destroy(g->refine->ws);
+        refine_free(g->refine);
+        g->refine = nullptr;
+    }
+    if (!g->refine) {
+        RefineWork* w = nullptr;
+        ROBO_TRY(refine_alloc(g->ctx, K, D, &w));
+        const int st = cand_alloc(g->ctx, round_up64((int64_t)K * (D + 1), NB), 1, &w->ws);
+        if (st != ROBO_OK) {
+            refine_free(w);
+            return st;
+        }
+        g->refine = w;
+    }
+    *out = g->refine;
+    return ROBO_OK;
+}
+
+// marginal: the sweep is robo_acq_eval_marginal_cand's (accumulate, divide); otherwise robo_acq_eval_cand's
+static int refine_core(robo_gp* const* gps, int32_t S, bool marginal, int32_t acq_kind, double par, const double* etas,
+                       robo_cand* k, int32_t n_starts, int32_t n_steps, double step0, double* out_x, double* out_value,
+                       int64_t* out_start_index, uint32_t* out_flags, int64_t* out_starts, double* out_trace) {
+    if (!gps || S < 1 || !etas || !k || !out_x) return ROBO_BAD_ARGUMENT;
+    ROBO_TRY(check_acq_kind(acq_kind));
+    if (n_starts < 1 || n_starts > 1024 || n_steps < 0 || !(step0 > 0.0) || !(step0 <= 0.5)) {
+        set_error("refine: n_starts %d (1 .. 1024), n_steps %d (>= 0), step0 %g (0 < step0 <= 0.5)", n_starts, n_steps, step0);
+        return ROBO_BAD_ARGUMENT;
+    }
+    ROBO_TRY(ensemble_check("refine", 0, gps, S, k));
+    robo_gp* g0 = gps[0];
+    robo_ctx* c = g0->ctx;
+    const int K = n_starts, T = n_steps, D = g0->dim, E = D + 1;
+    const int64_t rows_pad = round_up64((int64_t)K * E, NB);
+    if ((size_t)rows_pad * g0->n_pad * sizeof(double) > workspace_bytes(c)) {
+        set_error("refine: %d starts x %d rows of %d columns exceed the solve workspace (ws_bytes)", K, E, g0->n_pad);
+        return ROBO_BAD_SHAPE;
+    }
+    RefineWork* w = nullptr;
+    ROBO_TRY(refine_ensure(g0, K, D, &w));
+    ROBO_TRY(cand_ensure_workspace(w->ws, g0->n_pad, true));
+    const size_t trace_len = (size_t)(T + 1) * K * (2 * D + 3);
+    if (out_trace) ROBO_TRY(grow_trace(&w->d_trace, &w->trace_cap, trace_len));
+    w->st.trace = out_trace ? w->d_trace : nullptr;
+    const RefineState& st = w->st;
+
+    ROBO_TRY(acq_sweep(gps, S, marginal, acq_kind, par, etas, k));
+    // The solve of the K (D + 1) rows follows the library's rule for a batch of that many rows (decide_winv): through the
+    // explicit inverse factor where the factor qualifies (one triangular product per pass), else the block-row substitution
+    // (n / 128 dependent launches).  Decided, and W built, before the first iteration: nothing below waits for the device.
+    const bool iterate = T > 0 || out_trace;
+    std::vector<char> use_w((size_t)S, 0);
+    double* d_rhs = nullptr;
+    for (int s = 0; iterate && s < S; ++s) {
+        bool use = false;
+        ROBO_TRY(clear_flags_on_error(k, decide_winv(gps[s], w->ws, &use)));
+        use_w[s] = use ? 1 : 0;
+        if (use && !d_rhs) ROBO_TRY(clear_flags_on_error(k, winv_rows_buffer(gps[s], w->ws, rows_pad, &d_rhs)));
+    }
+    // starts, iterations, winner: launches only
+    int status = launch_refine_select(c, st, k->d_acq, k->m, k->d_Xc, step0);
+    for (int t = 0; status == ROBO_OK && iterate && t <= T; ++t) {
+        for (int s = 0; status == ROBO_OK && s < S; ++s) {
+            robo_gp* g = gps[s];
+            status = launch_scale_inputs(c, st.y, st.ys, g->d_theta, K, K, D);
+            if (status == ROBO_OK) status = launch_cross_grad(g, st.ys, use_w[s] ? d_rhs : w->ws->d_V, 0, K, rows_pad);
+            if (status == ROBO_OK) status = use_w[s] ? launch_winv_rows(g, w->ws, rows_pad) : launch_trsm(g, w->ws, 0, rows_pad);
+            if (status == ROBO_OK) status = launch_refine_eval(g, st, w->ws, acq_kind, par, etas[s], s, S, t, T);
+        }
+    }
+    if (status == ROBO_OK) status = launch_refine_result(c, st, k->d_flags, T == 0);
+    // read-back: the one synchronisation of the call
+    std::vector<double> h((size_t)D + 4);
+    std::vector<long long> hs(out_starts ? (size_t)K : 0);
+    ROBO_TRY(finish_call(k, "refine", status, {{h.data(), st.out, h.size() * sizeof(double)},
+                                               {hs.data(), st.start, hs.size() * sizeof(long long)},
+                                               {out_trace, w->d_trace, trace_len * sizeof(double)}}));
+    memcpy(out_x, h.data(), (size_t)D * sizeof(double));
+    if (out_value) *out_value = h[D];
+    long long v;
+    memcpy(&v, &h[D + 1], sizeof(v));
+    if (out_start_index) *out_start_index = (int64_t)v;
+    memcpy(&v, &h[D + 2], sizeof(v));
+    if (out_flags) *out_flags = (uint32_t)v;
+    for (size_t i = 0; i < hs.size(); ++i) out_starts[i] = (int64_t)hs[i];
+    return ROBO_OK;
+}
+
 }  // namespace robo
+
+using namespace robo;
+
+extern "C" {
+
+int32_t robo_acq_refine_cand(robo_gp* g, int32_t acq_kind, double par, double eta, robo_cand* k, int32_t n_starts,
+                             int32_t n_steps, double step0, double* out_x, double* out_value, int64_t* out_start_index,
+                             uint32_t* out_flags, int64_t* out_starts, double* out_trace) {
+    return refine_core(&g, g ? 1 : 0, false, acq_kind, par, &eta, k, n_starts, n_steps, step0, out_x, out_value,
+                       out_start_index, out_flags, out_starts, out_trace);
+}
+
+int32_t robo_acq_refine_marginal_cand(robo_gp* const* gps, int32_t S, int32_t acq_kind, double par, const double* etas,
+                                      robo_cand* k, int32_t n_starts, int32_t n_steps, double step0, double* out_x,
+                                      double* out_value, int64_t* out_start_index, uint32_t* out_flags,
+                                      int64_t* out_starts, double* out_trace) {
+    return refine_core(gps, S, true, acq_kind, par, etas, k, n_starts, n_steps, step0, out_x, out_value, out_start_index,
+                       out_flags, out_starts, out_trace);
+}
+
+}  // extern "C"

@@ -24,7 +24,7 @@
 // batch-size classes to rounding, like across the other paths.
 //
 // Numerics: W carries a forward error of ~eps cond(L) (the block-row solve: eps cond of a 128-block), so the caller
-// (api.hip) takes this path only while cond_inf(L) = |L|_inf |W|_inf -- measured here when W is built
+// (api_predict.hip) takes this path only while cond_inf(L) = |L|_inf |W|_inf -- measured here when W is built
 // (winv_norm_kernel) -- stays below a bound and keeps the substitution otherwise.
 #include <algorithm>
 #include <vector>

@@ -1370,7 +1370,7 @@ def check_winv_path(ctx, cases=(("matern52", 300, 5, 700), ("fabolas", 280, 4, 1
 
 def check_winv_guard_sweep(ctx, n=768, min_blocks=None, m=400, verbose=True,
                            sweep=((2, (1e-3, 1e-5, 1e-7, 1e-9)), (1, (1e-7, 1e-9, 1e-10, 1e-11, 1e-12)))):
-    """The guard of the explicit-inverse posterior (api.hip decide_winv): cond_inf(L) = |L|_inf |W|_inf, exact, measured when
+    """The guard of the explicit-inverse posterior (api_predict.hip decide_winv): cond_inf(L) = |L|_inf |W|_inf, exact, measured when
     W = L^-1 is built.  Sweep noise x {uniform, clustered-near-incumbent} designs (2-d: the review's noise range; dense
     1-d designs reach the bound):
       * robo_gp_factor_cond equals NumPy's |L|_inf |L^-1|_inf of the factor read back;

@@ -422,7 +422,7 @@ def test_marginal_gpu(gpu_ctx):
 
 # ---- 7b. independence from the explicit inverse W ------------------------------------------------------------------------------
 def _check_w_independence(ctx, N, D, M, q, mu_atol, var_rel, label):
-    """at a shape whose default sweep really goes through W = L^-1 (api.hip decide_winv: at most 32 768 candidates on a
+    """at a shape whose default sweep really goes through W = L^-1 (api_predict.hip decide_winv: at most 32 768 candidates on a
     factor of >= 6 block rows, or >= 3 for at most 8 candidates).  Three runs of the same call:
       a  guard winv_cond_max = 0 on a factor whose W was never built     (sweep: block-row substitution)
       c  the default                                                      (sweep: through W -- checked by its kernel name)
