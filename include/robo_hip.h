@@ -311,6 +311,31 @@ int32_t robo_acq_refine_marginal_cand(robo_gp* const* gps, int32_t S, int32_t ac
                                       double* out_value, int64_t* out_start_index, uint32_t* out_flags,
                                       int64_t* out_starts, double* out_trace);
 
+/* ---- entropy search's representer points: the ensemble sampler's whole run on the device (the reference drives emcee from
+ * the host around one acquisition value per walker, robo/acquisition_functions/information_gain.py:132-151).  One chain of
+ * n_walkers (k, even, >= 2 dim) walkers in the CALLER's input space samples exp(acquisition) of the fitted gp inside the box
+ * [lower, upper] (a point with any coordinate < lower or > upper, or NaN, has log-probability -inf); normalize != 0: the
+ * model's inputs are (x - lower) / (upper - lower).  Per half-step q = c - z (c - s), z = ((a - 1) u + 1)^2 / a (unfused,
+ * NumPy's bits), the posterior of the k / 2 proposals exactly as robo_acq_eval forms it for a batch of that size, the
+ * acquisition value as the log-density as it stands, and emcee 2's accept test (dim - 1) log z + lnp(q) - lnp(s) > log u.
+ * u_stretch / partner / u_accept: [n_steps][2][k / 2], the draw order of robo_mcmc_draws.  pos (k, dim) and lnp (k) are
+ * in-out; eval_start != 0: lnp is computed for the start positions, else taken as given.  out_accepted (k) counts the
+ * accepted moves, out_flags is the OR of ROBO_FLAG_NEGATIVE_EI / ZERO_SIGMA / NAN over the chain's acquisition values.
+ * out_trace (nullable): [n_steps][2][k / 2][dim + 2] = q, lnp(q), code 0 rejected / 1 accepted / 2 outside the box.
+ * ROBO_BAD_ARGUMENT: odd k, k < 2 dim, lower >= upper, a partner outside [0, k / 2); ROBO_BAD_SHAPE: the k / 2 rows do not
+ * fit the solve workspace (ws_bytes) -- the caller runs its host loop instead.  One synchronisation per call.             */
+int32_t robo_rep_sample(robo_gp* gp, int32_t acq_kind, double par, double eta, const double* lower, const double* upper,
+                        int32_t normalize, int32_t n_walkers, int32_t n_steps, double a, const double* u_stretch,
+                        const int32_t* partner, const double* u_accept, double* pos, double* lnp, int32_t eval_start,
+                        int64_t* out_accepted, uint32_t* out_flags, double* out_trace);
+/* S independent chains in lock step, chain s against gps[s] (distinct fitted handles on one context with one N and dim) and
+ * etas[s]; every per-chain array has a leading S axis.  Chain s equals robo_rep_sample on gps[s] bit for bit.             */
+int32_t robo_rep_sample_batch(robo_gp* const* gps, int32_t S, int32_t acq_kind, double par, const double* etas,
+                              const double* lower, const double* upper, int32_t normalize, int32_t n_walkers,
+                              int32_t n_steps, double a, const double* u_stretch, const int32_t* partner,
+                              const double* u_accept, double* pos, double* lnp, int32_t eval_start, int64_t* out_accepted,
+                              uint32_t* out_flags, double* out_trace);
+
 /* ---- greedy batch proposals with fantasised picks (no counterpart in the reference, which proposes one point per model
  * fit: robo/solver/bayesian_optimization.py:156-203).  q points are chosen from ONE candidate batch at FIXED theta, FIXED
  * constant mean and FIXED output transform (y_mean, y_std): nothing is re-estimated between the picks -- the result equals

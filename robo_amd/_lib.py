@@ -45,6 +45,7 @@ SYMBOLS = [
     "robo_gp_predict_cand", "robo_gp_predict", "robo_gp_predict_cov", "robo_gp_predict_grad", "robo_gp_predict_mixture_cand",
     "robo_acq_eval_cand", "robo_acq_eval", "robo_acq_eval_moments", "robo_acq_eval_marginal_cand", "robo_acq_eval_sum_cand",
     "robo_acq_refine_cand", "robo_acq_refine_marginal_cand",
+    "robo_rep_sample", "robo_rep_sample_batch",
     "robo_acq_batch_cand", "robo_acq_batch_marginal_cand",
     "robo_mes_eval_cand", "robo_mes_eval_marginal_cand", "robo_mes_sample_min_moments", "robo_mes_eval_moments",
     "robo_ig_eval_cand", "robo_ig_eval_per_cost_cand", "robo_ig_eval_moments", "robo_gp_cross_cov",
@@ -208,6 +209,10 @@ def lib():
                                  C.POINTER(i64), _dp],
         "robo_acq_refine_marginal_cand": [pp, i32, i32, dbl, _dp, vp, i32, i32, dbl, _dp, _dp, C.POINTER(i64),
                                           C.POINTER(C.c_uint32), C.POINTER(i64), _dp],
+        "robo_rep_sample": [vp, i32, dbl, dbl, _dp, _dp, i32, i32, i32, dbl, _dp, C.POINTER(i32), _dp, _dp, _dp, i32,
+                            C.POINTER(i64), C.POINTER(C.c_uint32), _dp],
+        "robo_rep_sample_batch": [pp, i32, i32, dbl, _dp, _dp, _dp, i32, i32, i32, dbl, _dp, C.POINTER(i32), _dp, _dp, _dp,
+                                  i32, C.POINTER(i64), C.POINTER(C.c_uint32), _dp],
         "robo_acq_batch_cand": [vp, i32, dbl, dbl, vp, i32, i32, dbl, C.POINTER(i64), _dp, _dp, C.POINTER(C.c_uint32),
                                 C.POINTER(i32), _dp],
         "robo_acq_batch_marginal_cand": [pp, i32, i32, dbl, _dp, vp, i32, i32, dbl, C.POINTER(i64), _dp, _dp,
@@ -913,6 +918,46 @@ def acq_refine(gps, kind, par, eta, cand, n_starts=256, n_steps=50, step0=0.05, 
     head = _ensemble_head(gps, eta, marginal, ACQ_KINDS[kind], float(par))
     check(fn(*head, cand._h, K, T, float(step0), _arr(x), *best.refs, p_starts, p_trace))
     return RefineResult(x, *best.values(), starts, trace)
+
+
+def rep_sample_batch(gps, kind, par, etas, lower, upper, normalize, pos, lnp, n_steps, u_stretch, partner, u_accept,
+                     a=2.0, diagnostics=False, single=False):
+    """S ensemble-sampler chains on the device in one call (robo_rep_sample_batch; ``single``: robo_rep_sample on gps[0]):
+    chain s samples exp(acquisition ``kind``) of gps[s] inside the box [lower, upper] of the caller's input space.
+    pos (S, k, D) start positions; lnp (S, k) their log-probabilities or None = evaluate them; draws (S, n_steps, 2, k / 2).
+    -> (pos, lnp, accepted (S, k) int64, flags (S,) uint32, trace (S, n_steps, 2, k / 2, D + 2) or None); a trace row is
+    (q, lnp(q), code 0 rejected / 1 accepted / 2 outside the box)."""
+    S = len(gps)
+    pos = np.array(pos, dtype=np.float64, order="C")
+    assert pos.ndim == 3 and pos.shape[0] == S
+    k, D = pos.shape[1], pos.shape[2]
+    T, half = int(n_steps), k // 2
+    eval_start = lnp is None
+    lnp = np.zeros((S, k)) if eval_start else np.array(lnp, dtype=np.float64, order="C").reshape(S, k)
+    uz = np.ascontiguousarray(u_stretch, dtype=np.float64).reshape(-1)
+    ua = np.ascontiguousarray(u_accept, dtype=np.float64).reshape(-1)
+    pa = np.ascontiguousarray(partner, dtype=np.int32).reshape(-1)
+    assert uz.size == ua.size == pa.size == S * T * 2 * half
+    lower, upper = _f64(lower, (D,)), _f64(upper, (D,))
+    acc = np.zeros((S, k), dtype=np.int64)
+    flags = np.zeros(S, dtype=np.uint32)
+    trace = np.empty((S, T, 2, half, D + 2)) if diagnostics else None
+    tail = (_arr(lower), _arr(upper), int(bool(normalize)), k, T, float(a), _arr(uz), pa.ctypes.data_as(C.POINTER(C.c_int32)),
+            _arr(ua), _arr(pos), _arr(lnp), int(eval_start), acc.ctypes.data_as(C.POINTER(C.c_int64)),
+            flags.ctypes.data_as(C.POINTER(C.c_uint32)), _arr(trace) if diagnostics else None)
+    fn = lib().robo_rep_sample if single else lib().robo_rep_sample_batch
+    check(fn(*_ensemble_head(gps, etas, not single, ACQ_KINDS[kind], float(par)), *tail))
+    return pos, lnp, acc, flags, trace
+
+
+def rep_sample(gp, kind, par, eta, lower, upper, normalize, pos, lnp, n_steps, u_stretch, partner, u_accept, a=2.0,
+               diagnostics=False):
+    """one chain (robo_rep_sample): the arrays of :func:`rep_sample_batch` without the leading S axis"""
+    pos = np.asarray(pos, dtype=np.float64)
+    res = rep_sample_batch([gp], kind, par, eta, lower, upper, normalize, pos[None], None if lnp is None else
+                           np.asarray(lnp, dtype=np.float64)[None], n_steps, u_stretch, partner, u_accept, a, diagnostics,
+                           single=True)
+    return tuple(None if r is None else r[0] for r in res)
 
 
 class Comm(object):

@@ -34,10 +34,34 @@ from robo_amd.util.ensemble_sampler import EnsembleSampler
 
 logger = logging.getLogger(__name__)
 
+REPRESENTERS = ("host", "device")
+default_representers = "host"      # where sample_representer_points runs its chain when representers=None
+
 
 def outcome_quantiles(Np):
     from scipy.stats import norm
     return norm.ppf(np.linspace(1. / (Np + 1), 1 - 1. / (Np + 1), Np))[np.newaxis, :]
+
+
+def chain_record(pos0, lnp0, res):
+    """robo_rep_sample's outputs of ONE chain (pos, lnp, accepted, flags, trace) as EnsembleSampler's ``device_chain``
+    returns them: the per-step record (chain (k, T, D), lnprobability (k, T)) is the replay of the trace's accepted
+    moves from the start positions and their log-probabilities"""
+    pos, lnp, acc, flags, trace = res
+    if int(flags) & _lib.FLAG_NAN:
+        raise ValueError("lnprob returned NaN.")
+    k, D = pos.shape
+    T, half = trace.shape[0], k // 2
+    chain, lnps = np.empty((k, T, D)), np.empty((k, T))
+    p, lp = np.array(pos0, dtype=np.float64), np.array(lnp0, dtype=np.float64)
+    taken = trace[..., D + 1] == 1
+    for it in range(T):
+        for h in range(2):
+            idx = np.arange(h * half, (h + 1) * half)[taken[it, h]]
+            p[idx] = trace[it, h, taken[it, h], :D]
+            lp[idx] = trace[it, h, taken[it, h], D]
+        chain[:, it], lnps[:, it] = p, lp
+    return pos, lnp, chain, lnps, acc
 
 
 class InformationGain(BaseAcquisitionFunction):
@@ -45,9 +69,14 @@ class InformationGain(BaseAcquisitionFunction):
     sampler_steps = 50      # ensemble-sampler steps per representer draw (information_gain.py:139-142)
 
     def __init__(self, model, lower, upper, Nb=50, Np=400, sampling_acquisition=None,
-                 sampling_acquisition_kw={"par": 0.0}, rng=None, ep=None, **kwargs):
+                 sampling_acquisition_kw={"par": 0.0}, rng=None, ep=None, representers=None, **kwargs):
         """``ep``: where update() runs the EP for p_min -- "host" (epmgp.joint_min), "device" (epmgp.joint_min_device
-        on the model's context, Nb <= 64) or None = epmgp.default_backend, read at every update()"""
+        on the model's context, Nb <= 64) or None = epmgp.default_backend, read at every update()
+        ``representers``: where update() runs the ensemble sampler of the representer points -- "host" (one library
+        call per half-step), "device" (the whole chain in one robo_rep_sample call) or None = default_representers"""
+        if representers not in (None,) + REPRESENTERS:
+            raise ValueError("representers must be None, 'host' or 'device', not %r" % (representers,))
+        self.representers = representers
         if ep not in (None,) + epmgp.BACKENDS:
             raise ValueError("ep must be None, 'host' or 'device', not %r" % (ep,))
         if ep == "device" and Nb > _lib.EP_MAX_NB:
@@ -86,15 +115,73 @@ class InformationGain(BaseAcquisitionFunction):
             out[inside] = np.asarray(self.sampling_acquisition(X[inside])).reshape(-1)
         return out
 
+    def _representers(self):
+        return self.representers or default_representers
+
+    def _chain_inputs(self):
+        """what robo_rep_sample needs of this estimator -> (gp, kind, par, eta, normalize), or None where the chain has
+        to stay on the host (a model or a proposal the library does not evaluate itself)"""
+        from robo_amd.acquisition_functions.base_acquisition import ClosedFormAcquisition
+        model, acq = self.model, self.sampling_acquisition
+        if hasattr(model, "normalize"):
+            raise NotImplementedError("representers='device' is not provided for Fabolas models: their representer "
+                                      "points are sampled in a projected space (use representers='host')")
+        if not (isinstance(acq, ClosedFormAcquisition) and acq.kind in _lib.ACQ_KINDS):
+            return None
+        if not (hasattr(model, "_materialise") and getattr(model, "is_trained", False)) or getattr(model, "devices", None):
+            return None
+        model._materialise()
+        if not isinstance(getattr(model, "gp", None), _lib.DeviceGP):
+            return None
+        normalize = bool(getattr(model, "normalize_input", False))
+        if normalize and not (np.array_equal(model.lower, self.lower) and np.array_equal(model.upper, self.upper)):
+            return None                   # the library normalises with the box itself
+        return model.gp, acq.kind, float(acq.par), acq._eta(None), normalize
+
+    def _device_chain(self):
+        """EnsembleSampler's ``device_chain`` hook on robo_rep_sample; None = the sampler runs its host loop"""
+        inputs = self._chain_inputs()
+        if inputs is None:
+            return None
+        gp, kind, par, eta, normalize = inputs
+
+        def run(p, lnp0, N, uz, pa, ua, a):
+            try:
+                start = None
+                if lnp0 is None:          # the start values on their own: the per-step record needs them
+                    start = _lib.rep_sample(gp, kind, par, eta, self.lower, self.upper, normalize, p, None, 0,
+                                            uz[:0], pa[:0], ua[:0], a)
+                    lnp0 = start[1]
+                res = _lib.rep_sample(gp, kind, par, eta, self.lower, self.upper, normalize, p, lnp0, N, uz, pa, ua, a,
+                                      diagnostics=True)
+            except _lib.RoboBadShape:
+                return None               # half an ensemble does not fit the solve workspace: the host loop
+            flags = int(res[3]) | (int(start[3]) if start is not None else 0)
+            if kind == "ei" and flags & (_lib.FLAG_ZERO_SIGMA | _lib.FLAG_NEGATIVE_EI):
+                return None               # EI's guards (ei.py:72-74,86-88) act per batch: the host loop reproduces them
+            return chain_record(p, lnp0, (res[0], res[1], res[2], flags, res[4]))
+        return run
+
     def sample_representer_points(self):
         self.sampling_acquisition.update(self.model)
+        device_chain = self._device_chain() if self._representers() == "device" else None
         for _ in range(5):
             restarts = self.lower + (self.upper - self.lower) * self.rng.uniform(size=(self.Nb, self.D))
-            sampler = EnsembleSampler(self.Nb, self.D, lnprob_batch=self._proposal_batch)
+            sampler = EnsembleSampler(self.Nb, self.D, lnprob_batch=self._proposal_batch, device_chain=device_chain)
+            sampler._random = self._sampler_stream()
             self.zb, self.lmb, _ = sampler.run_mcmc(restarts, self.sampler_steps, rstate0=self.rng)
             if not np.any(np.isinf(self.lmb)):
                 break
             logger.debug("representer proposal hit -inf, resampling")
+        self._shape_representers()
+
+    @staticmethod
+    def _sampler_stream():
+        """the ensemble sampler's own stream: seeded from OS entropy, as emcee's is in the reference (it ignores the
+        RandomState object handed to run_mcmc, information_gain.py:139-142)"""
+        return np.random.RandomState()
+
+    def _shape_representers(self):
         if len(self.zb.shape) == 1:
             self.zb = self.zb[:, None]
         if len(self.lmb.shape) == 1:
@@ -105,23 +192,35 @@ class InformationGain(BaseAcquisitionFunction):
         self.model = model
         self.sn2 = self.model.get_noise()
         self.sample_representer_points()
+        self._update_from_points()
+
+    def _update_from_points(self, ep=None):
+        """the rest of update() from the representer points in ``zb`` / ``lmb``; ``ep``: the EP's four outputs for the
+        belief ``_belief()`` returned, computed elsewhere (MarginalizationGPMCMC batches them)"""
+        if ep is None:
+            mu, var = self._belief()
+            if (self.ep or epmgp.default_backend) == "device":
+                ep = epmgp.joint_min_device(mu, var, with_derivatives=True, ctx=self._ep_ctx())
+            else:
+                ep = epmgp.joint_min(mu, var, with_derivatives=True)
+        self.logP, self.dlogPdMu, self.dlogPdSigma, self.dlogPdMudMu = ep
+        self.W = outcome_quantiles(self.Np)
+        self.logP = np.reshape(self.logP, (self.logP.shape[0], 1))
+        self._ep = _lib.EPState(self.logP, self.lmb, self.W, self.dlogPdMu, self.dlogPdSigma, self.dlogPdMudMu)
+
+    def _ep_ctx(self):
+        gp = getattr(self.model, "gp", None)
+        return gp.ctx if isinstance(gp, _lib.DeviceGP) else _lib.default_context()
+
+    def _belief(self):
+        """posterior (mean, full covariance) at the representer points; a rank-sharded estimator adopts rank 0's points"""
         if self.shard:
             from robo_amd import sharding
             if sharding.dist_info()[2] > 1:
                 zb, lmb = np.asarray(self.zb, dtype=np.float64), np.asarray(self.lmb, dtype=np.float64)
                 row0 = sharding.allgather_rows(np.concatenate([zb.ravel(), lmb.ravel()]))[0]
                 self.zb, self.lmb = row0[:zb.size].reshape(zb.shape), row0[zb.size:].reshape(lmb.shape)
-        mu, var = self.model.predict(np.array(self.zb), full_cov=True)
-        if (self.ep or epmgp.default_backend) == "device":
-            gp = getattr(self.model, "gp", None)
-            ctx = gp.ctx if isinstance(gp, _lib.DeviceGP) else _lib.default_context()
-            ep = epmgp.joint_min_device(mu, var, with_derivatives=True, ctx=ctx)
-        else:
-            ep = epmgp.joint_min(mu, var, with_derivatives=True)
-        self.logP, self.dlogPdMu, self.dlogPdSigma, self.dlogPdMudMu = ep
-        self.W = outcome_quantiles(self.Np)
-        self.logP = np.reshape(self.logP, (self.logP.shape[0], 1))
-        self._ep = _lib.EPState(self.logP, self.lmb, self.W, self.dlogPdMu, self.dlogPdSigma, self.dlogPdMudMu)
+        return self.model.predict(np.array(self.zb), full_cov=True)
 
     def _native(self):
         return isinstance(getattr(self.model, "gp", None), _lib.DeviceGP) and self.model.is_trained

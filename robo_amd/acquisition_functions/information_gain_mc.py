@@ -47,7 +47,8 @@ class InformationGainMC(InformationGain):
             raise ValueError("InformationGainMC handles 1 to %d function samples, Nf = %d" % (_lib.MC_MAX_NF, Nf))
         super(InformationGainMC, self).__init__(model, lower, upper, Nb=Nb, Np=Np,
                                                 sampling_acquisition=sampling_acquisition,
-                                                sampling_acquisition_kw=sampling_acquisition_kw, rng=rng)
+                                                sampling_acquisition_kw=sampling_acquisition_kw, rng=rng,
+                                                representers=kwargs.get("representers"))
         self.Nf = Nf
         self.Mb = self.Vb = self.pmin = None
         self.z = None
@@ -69,6 +70,10 @@ class InformationGainMC(InformationGain):
         self._single_device()
         self.sn2 = self.model.get_noise()
         self.sample_representer_points()
+        self._update_from_points()
+
+    def _update_from_points(self, ep=None):
+        """the rest of update() from the representer points in ``zb`` / ``lmb`` (``ep``: unused, there is no EP here)"""
         self.W = outcome_quantiles(self.Np)
         self.Mb, self.Vb = self.model.predict(np.array(self.zb), full_cov=True)
         # common random numbers: one set of draws per update for the baseline and every candidate (module docstring)

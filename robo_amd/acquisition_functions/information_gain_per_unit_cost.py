@@ -26,6 +26,9 @@ class InformationGainPerUnitCost(InformationGain):
         super(InformationGainPerUnitCost, self).__init__(model, lower, upper, Nb=n_representer, Np=Np,
                                                          sampling_acquisition=sampling_acquisition, rng=rng, ep=ep)
 
+    def _representers(self):
+        return "host"       # the representer points are sampled in a projected space: the host loop, whatever the default
+
     def update(self, model, cost_model, overhead=None):
         self.cost_model = cost_model
         self.overhead = 0 if overhead is None else overhead

@@ -22,6 +22,11 @@ from robo_amd.acquisition_functions.base_acquisition import BaseAcquisitionFunct
 logger = logging.getLogger(__name__)
 
 
+def _ig_update_from_points():
+    from robo_amd.acquisition_functions.information_gain import InformationGain
+    return InformationGain._update_from_points
+
+
 class MarginalizationGPMCMC(BaseAcquisitionFunction):
 
     def __init__(self, acquisition_func):
@@ -58,11 +63,115 @@ class MarginalizationGPMCMC(BaseAcquisitionFunction):
         if len(self.estimators) != len(self.model.models):
             self.estimators = []
             self._build_estimators()
+        if cost_model is None and not kwargs and self._update_representers_batched():
+            return
         for i in range(len(self.model.models)):
             if cost_model is not None:
                 self.estimators[i].update(self.model.models[i], self.cost_model.models[i], **kwargs)
             else:
                 self.estimators[i].update(self.model.models[i], **kwargs)
+
+    # ---- entropy search: the representer chains of all hyper-parameter samples in one call per context ------------------------
+    def _representer_plan(self):
+        """the estimators' chain inputs (InformationGain._chain_inputs) grouped by their sub-model's context, in sample order
+        -> [(indices, inputs)], or None where update() stays one estimator after the other"""
+        from robo_amd.acquisition_functions.information_gain import InformationGain
+        est = self.estimators
+        if not est or not all(isinstance(e, InformationGain) and e._representers() == "device" for e in est):
+            return None
+        inputs = []
+        for e, m in zip(est, self.model.models):
+            e.model = m
+            e.sampling_acquisition.update(m)
+            inputs.append(e._chain_inputs())           # (Fabolas sub-models raise NotImplementedError here)
+        if any(x is None for x in inputs):
+            return None
+        e0, x0 = est[0], inputs[0]
+        for e, x in zip(est, inputs):
+            if x[1:3] != x0[1:3] or x[4] != x0[4] or (e.Nb, e.D, e.sampler_steps) != (e0.Nb, e0.D, e0.sampler_steps) \
+                    or not (np.array_equal(e.lower, e0.lower) and np.array_equal(e.upper, e0.upper)):
+                return None
+        groups = {}
+        for i, x in enumerate(inputs):
+            groups.setdefault(id(x[0].ctx), []).append(i)
+        for idx in groups.values():
+            if len({inputs[i][0].n for i in idx}) != 1 or len({id(inputs[i][0]) for i in idx}) != len(idx):
+                return None
+        return [(idx, [inputs[i] for i in idx]) for idx in groups.values()]
+
+    def _update_representers_batched(self):
+        """update() of entropy-search estimators with ``representers="device"`` over trained device GPs: every estimator's
+        restarts and draws in estimator order, ONE robo_rep_sample_batch per context, a retry (up to 5 attempts, as
+        InformationGain.sample_representer_points) only for the chains that hit -inf, then the rest of each estimator's
+        update from its points -- with ``ep="device"`` the EP of all beliefs of a context in one joint_min_batch.
+        -> False: nothing was done, update() goes estimator by estimator"""
+        from robo_amd.acquisition_functions.information_gain import chain_record
+        from robo_amd.util import epmgp
+        plan = self._representer_plan()
+        if plan is None:
+            return False
+        est = self.estimators
+        e0 = est[0]
+        T, half = e0.sampler_steps, e0.Nb // 2
+        for e in est:
+            if hasattr(e, "_single_device"):
+                e._single_device()
+            e.sn2 = e.model.get_noise()
+        pending = list(range(len(est)))
+        alone = []                                           # estimators whose chain has to run the host's way
+        for _ in range(5):
+            if not pending:
+                break
+            start, draws = {}, {}
+            for i in pending:                                # estimator order: restarts, then the sampler's stream
+                e = est[i]
+                start[i] = e.lower + (e.upper - e.lower) * e.rng.uniform(size=(e.Nb, e.D))
+                draws[i] = _lib.mcmc_draws(e._sampler_stream(), T, half)
+            for idx, inputs in plan:
+                sel = [(i, x) for i, x in zip(idx, inputs) if i in start]
+                if not sel:
+                    continue
+                ids, xs = [i for i, _ in sel], [x for _, x in sel]
+                kind, par, normalize = xs[0][1], xs[0][2], xs[0][4]
+                pos0 = np.array([start[i] for i in ids])
+                uz, pa, ua = (np.array([draws[i][j] for i in ids]) for j in range(3))
+                try:
+                    pos, lnp, acc, flags, _ = _lib.rep_sample_batch([x[0] for x in xs], kind, par, [x[3] for x in xs],
+                                                                    e0.lower, e0.upper, normalize, pos0, None, T, uz, pa, ua)
+                except _lib.RoboBadShape:
+                    if len(pending) == len(est):
+                        return False                         # half an ensemble does not fit the solve workspace
+                    raise
+                for j, i in enumerate(ids):
+                    if flags[j] & _lib.FLAG_NAN:
+                        raise ValueError("lnprob returned NaN.")
+                    if kind == "ei" and flags[j] & (_lib.FLAG_ZERO_SIGMA | _lib.FLAG_NEGATIVE_EI):
+                        alone.append(i)                      # EI's per-batch guards: that estimator's own host loop
+                        continue
+                    est[i].zb, est[i].lmb = pos[j], lnp[j]
+            pending = [i for i in pending if i not in alone and np.any(np.isinf(est[i].lmb))]
+        for i in alone:
+            saved, est[i].representers = est[i].representers, "host"
+            try:
+                est[i].sample_representer_points()
+            finally:
+                est[i].representers = saved
+        for e in est:
+            e._shape_representers()
+        for idx, inputs in plan:
+            group = [est[i] for i in idx]
+            batched_ep = type(group[0])._update_from_points is _ig_update_from_points() and \
+                all((e.ep or epmgp.default_backend) == "device" for e in group)
+            if not batched_ep:
+                for e in group:
+                    e._update_from_points()
+                continue
+            beliefs = [e._belief() for e in group]
+            res = epmgp.joint_min_batch(np.array([b[0] for b in beliefs]), np.array([b[1] for b in beliefs]), True,
+                                        ctx=inputs[0][0].ctx)
+            for j, e in enumerate(group):
+                e._update_from_points(ep=tuple(r[j] for r in res))
+        return True
 
     def _device_groups(self):
         """Single-process multi-GPU (``GaussianProcessMCMC(devices=...)``): the estimators grouped by the device slot

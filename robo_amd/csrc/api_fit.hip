@@ -61,6 +61,7 @@ int32_t robo_gp_destroy(robo_gp* g) {
     }
     batch_free(g->batch);
     mes_free(g->mes);
+    rep_free(g->rep);
     hipFree(g->d_X);
     hipFree(g->d_Xs);
     hipFree(g->d_y);

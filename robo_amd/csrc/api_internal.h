@@ -25,8 +25,13 @@ int decide_winv(robo_gp* g, const robo_cand* k, bool* use);                   //
 // need_v: the caller consumes V itself, not only its reductions
 int predict_core(robo_gp* g, robo_cand* k, bool single_chunk = false,
                  const std::function<int(int64_t, int64_t)>& after_chunk = nullptr, bool need_v = false);
+// the rest of predict_core for points whose scaled rows are in k->d_Xcs already, the solve decided (decide_winv) and the
+// workspace sized: launches only
+int predict_scaled(robo_gp* g, robo_cand* k, bool winv, const std::function<int(int64_t, int64_t)>& after_chunk = nullptr,
+                   bool need_v = false);
 int predict_samples(robo_gp* const* gps, int32_t S, robo_cand* k, int cap);   // -> rows of k->d_mu_all / d_var_all
 int host_cand(robo_gp* g, const double* Xc, int64_t m, robo_cand** out, bool* kept);   // the handle behind host arrays
+int host_cand_rows(robo_gp* g, int64_t m, robo_cand** out);     // ... kept and sized for m points, nothing uploaded (m <= 16384)
 
 // ---- api_acq.hip: closed-form acquisitions and what the ensemble drivers share -------------------------------------------------
 int check_acq_kind(int kind);

@@ -117,6 +117,11 @@ int predict_core(robo_gp* g, robo_cand* k, bool single_chunk, const std::functio
     bool winv = false;
     ROBO_TRY(decide_winv(g, k, &winv));
     ROBO_TRY(launch_scale_inputs(g->ctx, k->d_Xc, k->d_Xcs, g->d_theta, k->m, k->m_pad, g->dim));
+    return predict_scaled(g, k, winv, after_chunk, need_v);
+}
+
+int predict_scaled(robo_gp* g, robo_cand* k, bool winv, const std::function<int(int64_t, int64_t)>& after_chunk, bool need_v) {
+    k->solved_gen = 0;
     // event slots 24..27 bracket the phases of the LAST chunk (bench.py reads them after a sync):
     //   24 -> 25 cross-gram, 25 -> 26 triangular solve (the MFMA kernel), 26 -> 27 post
     // (small batches are latency-bound and four event packets cost several microseconds: recorded for them only when
@@ -184,6 +189,17 @@ int host_cand(robo_gp* g, const double* Xc, int64_t m, robo_cand** out, bool* ke
         g->host_cand = nullptr;
         ROBO_TRY(robo_cand_create(g->ctx, Xc, m, g->dim, &g->host_cand));
     }
+    *out = g->host_cand;
+    return ROBO_OK;
+}
+
+int host_cand_rows(robo_gp* g, int64_t m, robo_cand** out) {
+    if (!(g->host_cand && g->host_cand->m == m)) {
+        robo_cand_destroy(g->host_cand);
+        g->host_cand = nullptr;
+        ROBO_TRY(cand_alloc(g->ctx, m, g->dim, &g->host_cand));
+    }
+    g->host_cand->solved_gen = 0;
     *out = g->host_cand;
     return ROBO_OK;
 }

@@ -276,6 +276,41 @@ struct MesWork {
 };
 int mes_alloc(int64_t m, int S, int K, MesWork** out);
 void mes_free(MesWork* w);
+
+// ---- entropy search's representer chains (represent.hip) ------------------------------------------------------------------
+// what the two kernels of a half-step need of ONE chain's model: the posterior of its moving half is formed in that model's
+// own candidate handle (the one behind the host-array entry points), exactly as robo_acq_eval forms it
+struct RepChain {
+    const double* ism;              // [D] inverse square-root metrics of the fitted theta (robo_gp::d_theta)
+    double* Xcs;                    // (m_pad, D) the handle's scaled input rows
+    const double *mean, *var;       // (m_pad) the handle's transformed mean and floored variance
+    double eta;
+};
+// the state of one call: S chains of k walkers in D dimensions; all arrays device memory of one block
+struct RepState {
+    int S, k, D, T, normalize;
+    long long m_pad;                // rows of a chain's candidate handle (pad rows replicate row 0)
+    double a;
+    double *pos, *lnp;              // [S][k][D], [S][k]
+    double *q, *z;                  // [S][k/2][D], [S][k/2] the pending proposals
+    int* outside;                   // [S][k/2] the pending proposal lies outside the box (or is NaN)
+    long long* nacc;                // [S][k]
+    unsigned* flags;                // [S] ROBO_FLAG_* of every chain's acquisition values
+    const double *uz, *ua;          // [S][T][2][k/2] the caller's uniforms, emcee's draw order
+    const int* partner;
+    const double *lower, *upper;    // [D]
+    const RepChain* chain;          // [S]
+    double* trace;                  // [S][T][2][k/2][D + 2]: q, lnp(q), code -- or nullptr
+};
+struct RepWork {
+    size_t bytes;                   // of d_block (grows, never shrinks)
+    char* d_block;
+    double* d_trace;
+    size_t trace_cap;               // doubles
+};
+void rep_free(RepWork* w);
+int launch_rep_propose(robo_ctx* ctx, const RepState& st, int start, int h, int it);
+int launch_rep_accept(robo_ctx* ctx, const RepState& st, int acq_kind, double par, int start, int h, int it);
 }  // namespace robo
 
 constexpr int ROBO_AUX_STREAMS = 3;
@@ -369,6 +404,7 @@ struct robo_gp {
     robo::RefineWork* refine;       // state + solve workspace of robo_acq_refine_* (refine.hip), kept between calls of one (K, D)
     robo::BatchWork* batch;         // state of robo_acq_batch_* (batch.hip), kept between calls of one (m, S)
     robo::MesWork* mes;             // state of robo_mes_eval_* (mes.hip), kept between calls of one (m, S, K)
+    robo::RepWork* rep;             // state of robo_rep_sample* (represent.hip), kept with gps[0] between calls
 };
 
 struct robo_cand {

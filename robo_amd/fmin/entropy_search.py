@@ -15,7 +15,7 @@ from robo_amd.solver import BayesianOptimization
 
 def build_entropy_search(lower, upper, maximizer="random", model="gp_mcmc", rng=None, n_candidates=500,
                          chain_length=200, burnin_steps=100, n_representer=50, n_outcomes=400, devices=None, ep=None,
-                         pmin="ep", n_func_samples=500):
+                         pmin="ep", n_func_samples=500, representers=None):
     """the objects robo/fmin/entropy_search.py:69-121 wires together -> (model, acquisition function, maximiser)"""
     if pmin not in ("ep", "mc"):
         raise ValueError("pmin must be 'ep' or 'mc', not %r" % (pmin,))
@@ -40,10 +40,10 @@ def build_entropy_search(lower, upper, maximizer="random", model="gp_mcmc", rng=
         raise ValueError("%s is not a valid model!" % model)
     if pmin == "mc":
         a = InformationGainMC(gp, lower=lower, upper=upper, Nb=n_representer, Np=n_outcomes, Nf=n_func_samples,
-                              sampling_acquisition=EI, rng=rng)
+                              sampling_acquisition=EI, rng=rng, representers=representers)
     else:
         a = InformationGain(gp, lower=lower, upper=upper, sampling_acquisition=EI, Nb=n_representer, Np=n_outcomes,
-                            rng=rng, ep=ep)
+                            rng=rng, ep=ep, representers=representers)
     acquisition_func = MarginalizationGPMCMC(a) if model == "gp_mcmc" else a
     if maximizer == "random":
         max_func = RandomSampling(acquisition_func, lower, upper, n_samples=n_candidates, rng=rng)
@@ -60,13 +60,16 @@ def build_entropy_search(lower, upper, maximizer="random", model="gp_mcmc", rng=
 def entropy_search(objective_function, lower, upper, num_iterations=30, maximizer="random", model="gp_mcmc",
                    X_init=None, Y_init=None, n_init=3, output_path=None, rng=None, n_candidates=500,
                    chain_length=200, burnin_steps=100, n_representer=50, n_outcomes=400, n_gpus=None, devices=None,
-                   ep=None, pmin="ep", n_func_samples=500):
+                   ep=None, pmin="ep", n_func_samples=500, representers=None):
     """``n_gpus`` / ``devices``: single-process multi-GPU (see robo_amd.fmin.bayesian_optimization): ``model="gp"`` splits the
     candidate batch of the information gain over replicas of the model, ``"gp_mcmc"`` splits the hyper-parameter samples --
     each sample's estimator (representer points, EP, gains) works on its sample's device, all devices at once.
     ``ep``: where each estimator's EP for p_min runs, "host" or "device" (InformationGain; None = epmgp.default_backend).
     ``pmin``: how p_min is estimated, "ep" (InformationGain) or "mc" (InformationGainMC with ``n_func_samples`` draws,
-    one device, ``ep`` unset)."""
+    one device, ``ep`` unset).
+    ``representers``: where each estimator's representer points are sampled, "host" or "device" (InformationGain; None =
+    information_gain.default_representers); with "device" and ``model="gp_mcmc"`` the chains of all hyper-parameter samples
+    run in one library call per device."""
     assert upper.shape[0] == lower.shape[0], "Dimension miss match"
     assert np.all(lower < upper), "Lower bound >= upper bound"
     assert n_init <= num_iterations, "Number of initial design point has to be <= than the number of iterations"
@@ -76,7 +79,8 @@ def entropy_search(objective_function, lower, upper, num_iterations=30, maximize
     gp, acquisition_func, max_func = build_entropy_search(lower, upper, maximizer, model, rng, n_candidates,
                                                           chain_length, burnin_steps, n_representer, n_outcomes,
                                                           devices=_lib.resolve_devices(devices, n_gpus), ep=ep,
-                                                          pmin=pmin, n_func_samples=n_func_samples)
+                                                          pmin=pmin, n_func_samples=n_func_samples,
+                                                          representers=representers)
     bo = BayesianOptimization(objective_function, lower, upper, acquisition_func, gp, max_func,
                               initial_design=init_latin_hypercube_sampling, initial_points=n_init, rng=rng,
                               output_path=output_path)
