@@ -146,6 +146,43 @@ int32_t robo_gp_grad_loglik(robo_gp* gp, const double* theta, double mean_c, dou
 int32_t robo_gp_loglik_batch(robo_gp* gp, const double* thetas, int32_t S, double mean_c, double* out_loglik,
                              int32_t* out_status);
 
+/* S likelihoods AND gradients in ONE batched pass per workspace group: per sample exactly robo_gp_grad_loglik's result, bit
+ * for bit (out_grad is S x theta_size, the last entry of a row d / d sigma^2 as there), on the batch workspace of
+ * robo_gp_loglik_batch plus two n_pad x n_pad matrices per sample; samples go in groups that fit the context's ws_bytes
+ * (ROBO_BAD_SHAPE if not even one does), one synchronisation per group.  out_status[s] (nullable) is a robo_status: a
+ * non-finite theta gives ROBO_BAD_ARGUMENT, a failed factorisation ROBO_NOT_POSITIVE_DEFINITE -- log-likelihood -inf and a
+ * NaN gradient for that sample only.  The GP itself is left UNFITTED.                                                        */
+int32_t robo_gp_grad_loglik_batch(robo_gp* gp, const double* thetas, int32_t S, double mean_c, double* out_loglik,
+                                  double* out_grad, int32_t* out_status);
+
+/* Multi-start MAP optimisation of the hyper-parameters, resident on the device: replaces the host loop of
+ * GaussianProcess.optimize (robo/models/gaussian_process.py:193-219, SciPy's L-BFGS-B on finite differences of nll from one
+ * start).  Maximises F(theta) = log p(y | X, theta) + log prior(theta) with prior_kind / prior_par exactly those of
+ * robo_gp_mcmc_run; F is invalid (the reference's protocol) when any |theta_p| > 20, the factorisation fails or the prior
+ * is +-inf or NaN.  Its gradient G is robo_gp_grad_loglik's with the last entry times exp(theta_last) (the chain rule
+ * to log sigma^2) plus the analytic gradient of the prior.
+ * All n_starts (1 .. 64) starts (n_starts x P) run in lock step, one batched evaluation of (F, G) per iteration, no read-back
+ * in between.  Iteration 0 evaluates the starts clipped to the box [lower, upper] (P each): an invalid F makes a start dead,
+ * otherwise alpha := step0.  Iteration t >= 1, per live start (x, f, g): d = the L-BFGS two-loop direction of its last
+ * <= history (1 .. 16) pairs (s_i, y_i), scaled by s.y / y.y of the newest (no pairs: g / |g|); d_p := 0 where x_p sits on a
+ * bound and d_p points out; if d.g <= 0 the pairs are dropped and d = the projected g, normalised (zero: the start freezes,
+ * "no direction"); trial z = clip(x + alpha d).  Accepted iff F(z) is valid and F(z) >= f + c1 (z - x).g: then the pair
+ * (z - x, g - G(z)) is pushed if s.y > 1e-10 |s| |y| (the oldest drops), x := z, alpha := 1, and the start freezes as
+ * "converged" if the largest projected |G_p| <= gtol.  Rejected: alpha := alpha / 2, below 2^-40 the start freezes,
+ * "stalled".  The start with the largest final F wins (ties: the first; dead starts never): out_theta (P), *out_value,
+ * *out_best -- -1 and NaN if every start is dead, which is not an error.  Per start, nullable: out_final (n_starts x P),
+ * out_values, out_status (0 ran out of iterations, 1 converged, 2 stalled or no direction, 3 dead).
+ * out_trace (nullable): (n_iters + 1) x n_starts x (2 P + 3) = [trial theta | F | G | the alpha it was made with | code],
+ * code 1 accepted, 0 rejected, 2 frozen earlier (the entry repeats the start's point), 3 trial invalid (F -inf, G NaN).
+ * Fixed summation orders: two calls return the same bits.  ROBO_BAD_SHAPE if the starts do not fit the workspace
+ * (ws_bytes) in one pass.  One synchronisation; state is kept with gp between calls of one (n_starts, P); leaves the GP
+ * unfitted.                                                                                                                  */
+int32_t robo_gp_optimize_hypers(robo_gp* gp, double mean_c, int32_t prior_kind, const double* prior_par,
+                                const double* lower, const double* upper, const double* starts, int32_t n_starts,
+                                int32_t n_iters, int32_t history, double step0, double c1, double gtol,
+                                double* out_theta, double* out_value, int32_t* out_best, double* out_final,
+                                double* out_values, int32_t* out_status, double* out_trace);
+
 /* The hyper-parameter chain of GaussianProcessMCMC.train, resident on the device: replaces
  *     sampler = emcee.EnsembleSampler(n_hypers, ndim, self.loglikelihood); sampler.run_mcmc(p0, n_steps, rstate0=rng)
  * (robo/models/gaussian_process_mcmc.py:114-142) INCLUDING emcee 2's stretch move, the prior and the accept test -- one

@@ -39,7 +39,8 @@ SYMBOLS = [
     "robo_last_error_string", "robo_version_string",
     "robo_gp_create", "robo_gp_destroy", "robo_gp_set_data", "robo_gp_set_output_transform",
     "robo_gp_set_precision", "robo_theta_size",
-    "robo_gp_fit", "robo_gp_loglik_batch", "robo_gp_mcmc_run", "robo_mcmc_draws", "robo_gp_fit_batch", "robo_gp_grad_loglik", "robo_gp_get_factor", "robo_gp_get_gram", "robo_gp_factor_cond", "robo_gp_prefetch_inverse",
+    "robo_gp_fit", "robo_gp_loglik_batch", "robo_gp_mcmc_run", "robo_mcmc_draws", "robo_gp_fit_batch", "robo_gp_grad_loglik", "robo_gp_grad_loglik_batch",
+    "robo_gp_optimize_hypers", "robo_gp_get_factor", "robo_gp_get_gram", "robo_gp_factor_cond", "robo_gp_prefetch_inverse",
     "robo_cand_create", "robo_cand_destroy", "robo_cand_set_points", "robo_cand_create_uniform", "robo_cand_get_points",
     "robo_cand_create_random", "robo_cand_create_sobol", "robo_cand_get_point", "robo_cand_workspace_chunk", "robo_cand_last_solve_kernel",
     "robo_gp_predict_cand", "robo_gp_predict", "robo_gp_predict_cov", "robo_gp_predict_grad", "robo_gp_predict_mixture_cand",
@@ -180,6 +181,9 @@ def lib():
         "robo_gp_mcmc_run": [vp, dbl, i32, _dp, i32, i32, dbl, _dp, C.POINTER(i32), _dp, i32, _dp, _dp, _dp, _dp,
                              C.POINTER(i64)],
         "robo_gp_grad_loglik": [vp, _dp, dbl, _dp, _dp, C.POINTER(i32)],
+        "robo_gp_grad_loglik_batch": [vp, _dp, i32, dbl, _dp, _dp, C.POINTER(i32)],
+        "robo_gp_optimize_hypers": [vp, dbl, i32, _dp, _dp, _dp, _dp, i32, i32, i32, dbl, dbl, dbl, _dp, _dp,
+                                    C.POINTER(i32), _dp, _dp, C.POINTER(i32), _dp],
         "robo_gp_get_factor": [vp, _dp],
         "robo_gp_get_gram": [vp, _dp, _dp],
         "robo_gp_factor_cond": [vp, _dp],
@@ -680,6 +684,48 @@ class DeviceGP(object):
                                          st.ctypes.data_as(C.POINTER(C.c_int32))))
         return ll, st
 
+    def grad_loglik_batch(self, thetas, mean_c):
+        """S (log likelihood, gradient) pairs in one batched pass (robo_gp_grad_loglik_batch) -> (ll (S), grad (S, P),
+        status (S)); per sample :meth:`grad_loglik`'s bits.  The GP is left unfitted."""
+        thetas = _f64(_full_theta(self, np.atleast_2d(thetas)))
+        assert thetas.ndim == 2 and thetas.shape[1] == self.n_theta
+        S = thetas.shape[0]
+        ll = np.empty(S)
+        grad = np.empty((S, self.n_theta))
+        st = np.empty(S, dtype=np.int32)
+        check(lib().robo_gp_grad_loglik_batch(self._h, _arr(thetas), S, float(mean_c), _arr(ll), _arr(grad),
+                                              st.ctypes.data_as(C.POINTER(C.c_int32))))
+        return ll, grad[:, len(self.fixed_head):], st
+
+    def optimize_hypers(self, mean_c, prior, lower, upper, starts, n_iters=60, history=8, step0=0.5, c1=1e-4, gtol=1e-5,
+                        diagnostics=False):
+        """Multi-start MAP optimisation of the hyper-parameters on the device (robo_gp_optimize_hypers): prior as in
+        :meth:`mcmc_run`; lower / upper (P) the box; starts (n_starts, P).  -> HyperOptResult"""
+        assert not self.fixed_head, "the device optimiser moves every library hyper-parameter: use the host optimiser"
+        P = self.n_theta
+        starts = _f64(np.atleast_2d(starts))
+        K = starts.shape[0]
+        assert starts.shape == (K, P)
+        lower, upper = _f64(np.broadcast_to(lower, (P,))), _f64(np.broadcast_to(upper, (P,)))
+        if prior is None:
+            kind, par = 0, np.zeros(9)
+        else:                                    # (kind, 5 parameters) DefaultPrior / (kind, 9 parameters) EnvPrior
+            kind = int(prior[0])
+            par = np.zeros(9)
+            given = _f64(prior[1]).reshape(-1)
+            assert given.size == (9 if kind == 2 else 5)
+            par[:given.size] = given
+        n_iters = int(n_iters)
+        theta, value, best = np.empty(P), C.c_double(), C.c_int32()
+        final, values, status = np.empty((K, P)), np.empty(K), np.empty(K, dtype=np.int32)
+        trace = np.empty((max(n_iters, 0) + 1, K, 2 * P + 3)) if diagnostics else None
+        check(lib().robo_gp_optimize_hypers(self._h, float(mean_c), kind, _arr(par), _arr(lower), _arr(upper), _arr(starts),
+                                            K, n_iters, int(history), float(step0), float(c1), float(gtol), _arr(theta),
+                                            C.byref(value), C.byref(best), _arr(final), _arr(values),
+                                            status.ctypes.data_as(C.POINTER(C.c_int32)),
+                                            _arr(trace) if diagnostics else None))
+        return HyperOptResult(theta, value.value, best.value, final, values, status, trace)
+
     def mcmc_run(self, mean_c, prior, pos, lnp, n_steps, u_stretch, partner, u_accept, a=2.0):
         """emcee 2's EnsembleSampler.run_mcmc on the device (robo_gp_mcmc_run): prior = None, (1, 5 parameters) DefaultPrior or
         (2, 9 parameters) EnvPrior;
@@ -800,6 +846,16 @@ class DeviceGP(object):
         """max-value entropy search over ``cand`` with the caller's uniforms u (K,) (robo_mes_eval_cand) -> MESResult;
         see :func:`mes_marginal`"""
         return mes_marginal([self], eta, cand, u, clamp, want_values, diagnostics, marginal=False)
+
+
+class HyperOptResult(object):
+    """robo_gp_optimize_hypers: theta / value / best of the winning start (best -1, NaN: every start was dead); per start
+    final (n_starts, P), values, status (0 ran out of iterations, 1 converged, 2 stalled or no direction, 3 dead);
+    trace (n_iters + 1, n_starts, 2 P + 3) = [trial theta | F | G | alpha | code] with diagnostics"""
+
+    def __init__(self, theta, value, best, final, values, status, trace=None):
+        self.theta, self.value, self.best = theta, value, best
+        self.final, self.values, self.status, self.trace = final, values, status, trace
 
 
 class MESResult(object):

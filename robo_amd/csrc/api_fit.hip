@@ -62,6 +62,7 @@ int32_t robo_gp_destroy(robo_gp* g) {
     batch_free(g->batch);
     mes_free(g->mes);
     rep_free(g->rep);
+    hyper_free(g->hyper);
     hipFree(g->d_X);
     hipFree(g->d_Xs);
     hipFree(g->d_y);
@@ -140,8 +141,11 @@ int32_t robo_gp_set_output_transform(robo_gp* g, double y_mean, double y_std) {
     return ROBO_OK;
 }
 
+}  // extern "C"
+
+namespace robo {
 // theta -> (FitSample, 1/sqrt(metric_d)); returns BAD_ARGUMENT for non-finite entries
-static int theta_to_sample(const robo_gp* g, const double* theta, double mean_c, FitSample* sp, double* ism) {
+int theta_to_sample(const robo_gp* g, const double* theta, double mean_c, FitSample* sp, double* ism) {
     const int D = g->dim, P = robo_theta_size(g->kind, D);
     for (int p = 0; p < P; ++p)
         if (!std::isfinite(theta[p])) {
@@ -161,6 +165,9 @@ static int theta_to_sample(const robo_gp* g, const double* theta, double mean_c,
     sp->mean_c = mean_c;
     return ROBO_OK;
 }
+}  // namespace robo
+
+extern "C" {
 
 static unsigned long long next_fit_gen() {
     static std::atomic<unsigned long long> gen{0};   // contexts of several devices fit on their own threads (multi.hip)
@@ -270,8 +277,11 @@ int32_t robo_gp_grad_loglik(robo_gp* g, const double* theta, double mean_c, doub
     return ROBO_OK;
 }
 
+}  // extern "C"
+
+namespace robo {
 // grow the batch workspace to hold S samples at the current n_pad
-static int batch_ensure(robo_gp* g, int S) {
+int batch_ensure(robo_gp* g, int S) {
     if (g->b_cap >= S && g->b_npad == g->n_pad) return ROBO_OK;
     hipFree(g->d_bK); hipFree(g->d_bLinv); hipFree(g->d_bXs); hipFree(g->d_bout);
     hipFree(g->d_bsp); hipFree(g->d_bfail); hipFree(g->d_bllpart); hipFree(g->d_bkeep);   // d_bism lives in d_bsp's block
@@ -304,6 +314,9 @@ static int batch_ensure(robo_gp* g, int S) {
     g->b_npad = g->n_pad;
     return ROBO_OK;
 }
+}  // namespace robo
+
+extern "C" {
 
 // S thetas on the training data of g, factorised by ONE sequence of launches per workspace chunk.  After each
 // chunk `keep(s0, ns, status)` may copy the chunk's factors out of the strided batch workspace (it runs before

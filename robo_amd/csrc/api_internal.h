@@ -1,5 +1,5 @@
-// Host helpers shared by the files that hold C ABI entry points (api_*.hip, refine.hip, batch.hip, mes.hip, comm.hip,
-// multi.hip): each is declared here once and defined in the file named above its group.  An ensemble driver reads as
+// Host helpers shared by the files that hold C ABI entry points (api_*.hip, refine.hip, batch.hip, mes.hip, hyperopt.hip,
+// comm.hip, multi.hip): each is declared here once and defined in the file named above its group.  An ensemble driver reads as
 // "ensemble_check, acq_sweep, its own kernels, finish_call".
 #pragma once
 #include <functional>
@@ -16,6 +16,11 @@ inline int dev_alloc(T** p, size_t count) {
     ROBO_HIP_CHECK(hipMalloc((void**)p, (count ? count : 1) * sizeof(T)));
     return ROBO_OK;
 }
+
+// ---- api_fit.hip: the batch workspace -----------------------------------------------------------------------------------------
+// theta -> (FitSample, 1/sqrt(metric_d)); ROBO_BAD_ARGUMENT for non-finite entries
+int theta_to_sample(const robo_gp* g, const double* theta, double mean_c, FitSample* sp, double* ism);
+int batch_ensure(robo_gp* g, int S);       // grow the batch workspace to hold S samples at the current n_pad
 
 // ---- api_predict.hip: candidate handles and the posterior ---------------------------------------------------------------------
 int cand_alloc(robo_ctx* ctx, int64_t m, int32_t dim, robo_cand** out);       // an empty handle (points not uploaded)

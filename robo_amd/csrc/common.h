@@ -309,6 +309,37 @@ struct RepWork {
     size_t trace_cap;               // doubles
 };
 void rep_free(RepWork* w);
+
+// ---- multi-start MAP optimisation of the hyper-parameters (hyperopt.hip) ------------------------------------------------------
+constexpr int HYPER_MAX_STARTS = 64, HYPER_MAX_HISTORY = 16;
+// everything a start carries between two launches; all arrays [K], [K][P] or [K][hist][P], device memory of one block
+struct HyperState {
+    int K, P, D, kind, n, hist, n_iters, prior_kind;
+    double mean_c, step0, c1, gtol;
+    double prior_par[9];            // mcmc_dev.h PRIOR_PAR
+    const double *lower, *upper;    // [P] the box
+    double *x, *f, *g, *alpha;      // accepted point, F and G there, current step length
+    double *z, *aused;              // pending trial point and the step length it was made with
+    double *sh, *yh;                // the (s, y) pairs, oldest first
+    int *npairs, *state, *pending;  // pairs held; 0 live / 1 converged / 2 stalled or no direction / 3 dead; the propose kernel's verdict
+    int* err;                       // bit 0: a factorisation hand-off timed out
+    double* out;                    // [P + 2]: winner's theta, value, index
+    double* trace;                  // (n_iters + 1) x K x (2 P + 3), or nullptr
+    FitSample* d_sp;                // the batched fit's inputs / outputs (api_fit.hip batch_ensure)
+    double* d_ism;
+    const double *d_out, *d_grad;   // (K x 2) z.z and log det; (K x P) likelihood gradient
+    const int* d_fail;
+};
+// the gradient workspace of a group of samples and the optimiser's state, kept with the GP between calls
+struct HyperWork {
+    int g_cap, g_npad, g_P;         // samples, n_pad and theta size the gradient workspace was sized for
+    double *d_V, *d_A, *d_alpha, *d_part, *d_out;
+    int K, P, hist;                 // what d_block was sized for
+    char* d_block;
+    double* d_trace;
+    size_t trace_cap;               // doubles
+};
+void hyper_free(HyperWork* w);
 int launch_rep_propose(robo_ctx* ctx, const RepState& st, int start, int h, int it);
 int launch_rep_accept(robo_ctx* ctx, const RepState& st, int acq_kind, double par, int start, int h, int it);
 }  // namespace robo
@@ -405,6 +436,7 @@ struct robo_gp {
     robo::BatchWork* batch;         // state of robo_acq_batch_* (batch.hip), kept between calls of one (m, S)
     robo::MesWork* mes;             // state of robo_mes_eval_* (mes.hip), kept between calls of one (m, S, K)
     robo::RepWork* rep;             // state of robo_rep_sample* (represent.hip), kept with gps[0] between calls
+    robo::HyperWork* hyper;         // workspace of robo_gp_grad_loglik_batch / robo_gp_optimize_hypers (hyperopt.hip)
 };
 
 struct robo_cand {
@@ -520,6 +552,23 @@ int launch_pack_linv(robo_gp* gp);
 int launch_grad_loglik(robo_gp* gp, double* d_V, double* d_A, double* d_alpha, double* d_part, double* d_out,
                        double* h_out);
 int launch_triinv(robo_gp* gp, double* d_W, double* d_V);   // W = L^-1 (and V = W^T) of the current factor
+// gradient.hip, S samples per launch: the factors of a batched fit (launch_potrf with want_inverse) -> out (S x P)
+struct GradBatch {
+    const double* K; size_t k_stride;        // the batched fit's factors, inverse diagonal blocks, scaled inputs and samples
+    const double* Linv; size_t linv_stride;
+    const double* Xs; size_t xs_stride;
+    const FitSample* sp;
+    double *V, *A;                           // S x (n_pad x n_pad) each; A doubles as W during the inversion
+    double *alpha, *part, *out;              // S x n_pad, S x P x tiles64, S x P
+    int S;
+};
+int launch_grad_loglik_batch(robo_gp* gp, const GradBatch& gb);
+// hyperopt.hip: the trial points of all starts (direction, projection, FitSample, scaled inputs); the accept test behind
+// the batched fit and gradient; the winner
+int launch_hyper_propose(robo_ctx* ctx, const HyperState& st, int t, const double* d_X, double* d_Xs, int64_t rows_real,
+                         int64_t rows_pad, size_t xs_stride);
+int launch_hyper_accept(robo_ctx* ctx, const HyperState& st, int t);
+int launch_hyper_result(robo_ctx* ctx, const HyperState& st);
 int launch_post(robo_gp* gp, robo_cand* cand, int64_t c0, int64_t cn);
 int launch_cross_grad(robo_gp* gp, const double* d_Xcs, double* d_V, int64_t c_first, int64_t c_count, int64_t rows_pad);
 int launch_predgrad_post(robo_gp* gp, const double* d_V, const double* d_q, const double* d_mu, const double* d_Xcs,

@@ -32,9 +32,8 @@ constexpr int RLD = RT + 2;
 
 // base of the recursion: W_ii = Linv_i, V_ii = Linv_i^T (columns >= n of V zeroed: the augmented row
 // and the identity padding of the factor take no part in K^-1)
-__global__ __launch_bounds__(256) void triinv_base_kernel(const double* __restrict__ Linv, int n,
-                                                          double* __restrict__ W, double* __restrict__ V, int ld) {
-    const int b = blockIdx.x;
+__device__ __forceinline__ void triinv_base_body(int b, const double* __restrict__ Linv, int n, double* __restrict__ W,
+                                                 double* __restrict__ V, int ld) {
     const double* src = Linv + (size_t)b * NB * NB;
     for (int e = threadIdx.x; e < NB * NB; e += 256) {
         const int r = e >> 7, c = e & 127;
@@ -42,6 +41,10 @@ __global__ __launch_bounds__(256) void triinv_base_kernel(const double* __restri
         W[(size_t)(b * NB + r) * ld + b * NB + c] = v;
         V[(size_t)(b * NB + c) * ld + b * NB + r] = (b * NB + r) < n ? v : 0.0;
     }
+}
+__global__ __launch_bounds__(256) void triinv_base_kernel(const double* __restrict__ Linv, int n,
+                                                          double* __restrict__ W, double* __restrict__ V, int ld) {
+    triinv_base_body(blockIdx.x, Linv, n, W, V, ld);
 }
 
 // one level of the merge, sb = 128-blocks per already inverted diagonal block.  Pair p: A = blocks
@@ -55,16 +58,14 @@ __global__ __launch_bounds__(256) void triinv_base_kernel(const double* __restri
 // phase with half of the matrix pipes idle): 32-row sub-tiles give the dispatcher 4x the workgroups to balance
 // (r03: W = L^-1 at N = 4096 1.23 -> ms).  Same k-order per entry, hence the same bits for every TM.
 template <int TM>
-__global__ __launch_bounds__(256, 2) void triinv_kernel(int phase, int sb, int nbk, int n,
-                                                        const double* __restrict__ L, double* __restrict__ W,
-                                                        double* __restrict__ V, int ld) {
-    __shared__ double smem[gemm_smem_doubles<TM>()];
+__device__ __forceinline__ void triinv_body(int bx, int by, int phase, int sb, int nbk, int n, const double* __restrict__ L,
+                                            double* __restrict__ W, double* __restrict__ V, int ld, double* smem) {
     constexpr int SPLIT = 4 / TM;
-    const int a0 = 2 * (int)blockIdx.y * sb, c0 = a0 + sb;
+    const int a0 = 2 * by * sb, c0 = a0 + sb;
     int nc = nbk - c0;
     nc = nc > sb ? sb : nc;
     if (nc <= 0) return;
-    const int tile = (int)blockIdx.x / SPLIT, h = (int)blockIdx.x % SPLIT;
+    const int tile = bx / SPLIT, h = bx % SPLIT;
     const int tj = tile % sb, ti = tile / sb;   // block inside A, block inside C
     if (ti >= nc) return;
     const size_t rowA = (size_t)(a0 + tj) * NB, rowC = (size_t)(c0 + ti) * NB;
@@ -97,11 +98,18 @@ __global__ __launch_bounds__(256, 2) void triinv_kernel(int phase, int sb, int n
                 }
     }
 }
+template <int TM>
+__global__ __launch_bounds__(256, 2) void triinv_kernel(int phase, int sb, int nbk, int n,
+                                                        const double* __restrict__ L, double* __restrict__ W,
+                                                        double* __restrict__ V, int ld) {
+    __shared__ double smem[gemm_smem_doubles<TM>()];
+    triinv_body<TM>((int)blockIdx.x, (int)blockIdx.y, phase, sb, nbk, n, L, W, V, ld, smem);
+}
 
 // alpha[c] = sum_{k < n} V[c][k] z[k]  (= (W^T z)_c = (K^-1 (y - mean))_c), one wavefront per row
-__global__ __launch_bounds__(256) void alpha_kernel(const double* __restrict__ V, int ld, const double* __restrict__ z,
-                                                    int n, int rows, double* __restrict__ alpha) {
-    const int lane = threadIdx.x & 63, c = blockIdx.x * 4 + (threadIdx.x >> 6);
+__device__ __forceinline__ void alpha_body(int bx, const double* __restrict__ V, int ld, const double* __restrict__ z,
+                                           int n, int rows, double* __restrict__ alpha) {
+    const int lane = threadIdx.x & 63, c = bx * 4 + (threadIdx.x >> 6);
     if (c >= rows) return;
     const double* v = V + (size_t)c * ld;
     double s = 0.0;
@@ -110,14 +118,17 @@ __global__ __launch_bounds__(256) void alpha_kernel(const double* __restrict__ V
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
     if (lane == 0) alpha[c] = c < n ? s : 0.0;
 }
+__global__ __launch_bounds__(256) void alpha_kernel(const double* __restrict__ V, int ld, const double* __restrict__ z,
+                                                    int n, int rows, double* __restrict__ alpha) {
+    alpha_body(blockIdx.x, V, ld, z, n, rows, alpha);
+}
 
 // A[i][j] = alpha_i alpha_j - sum_k V[i][k] V[j][k]   (V[c][k] = (L^-1)[k][c], zero for k < c)
-__global__ __launch_bounds__(256, 2) void kinv_tile_kernel(const double* __restrict__ V, int ldv, int kend,
-                                                           const double* __restrict__ alpha,
-                                                           double* __restrict__ A, int lda) {
-    __shared__ double smem[GEMM_SMEM_DOUBLES];
+__device__ __forceinline__ void kinv_tile_body(int bx, const double* __restrict__ V, int ldv, int kend,
+                                               const double* __restrict__ alpha, double* __restrict__ A, int lda,
+                                               double* smem) {
     int ta, tb;
-    tri_tile(blockIdx.x, ta, tb);
+    tri_tile(bx, ta, tb);
     Acc acc;
     acc_zero(acc);
     gemm_nt_128<false>(V + (size_t)ta * NB * ldv, ldv, V + (size_t)tb * NB * ldv, ldv, ta * NB, kend, acc, smem);
@@ -133,6 +144,12 @@ __global__ __launch_bounds__(256, 2) void kinv_tile_kernel(const double* __restr
                 A[(size_t)i * lda + j] = ai * alpha[j] - acc.t[tm][tn][r];
             }
         }
+}
+__global__ __launch_bounds__(256, 2) void kinv_tile_kernel(const double* __restrict__ V, int ldv, int kend,
+                                                           const double* __restrict__ alpha,
+                                                           double* __restrict__ A, int lda) {
+    __shared__ double smem[GEMM_SMEM_DOUBLES];
+    kinv_tile_body(blockIdx.x, V, ldv, kend, alpha, A, lda, smem);
 }
 
 // sum over the workgroup of up to RD per-thread values; result to out[idx(d)] by threads 0 .. cnt-1
@@ -158,15 +175,12 @@ __device__ __forceinline__ void block_sum_store(const double (&v)[RD], int cnt, 
 // block diagonal (only lower tiles are visited).  theta layout: [log amp, log m_d ..., (log a,
 // log b for the Fabolas kernel), log sigma^2].
 template <int KIND>
-__global__ __launch_bounds__(256) void grad_reduce_kernel(const double* __restrict__ Xs, const double* __restrict__ A,
-                                                          int lda, int n, CovParams cp, double* __restrict__ part,
-                                                          int ntiles) {
-    __shared__ double sI[RD * RLD];
-    __shared__ double sJ[RD * RLD];
-    __shared__ double sred[4 * RD];
+__device__ __forceinline__ void grad_reduce_body(int bx, const double* __restrict__ Xs, const double* __restrict__ A, int lda,
+                                                 int n, const CovParams cp, double* __restrict__ part, int ntiles, double* sI,
+                                                 double* sJ, double* sred) {
     const bool fab = KIND == ROBO_KERNEL_FABOLAS;
     int bi, bj;
-    tri_tile(blockIdx.x, bi, bj);
+    tri_tile(bx, bi, bj);
     const long long i0 = (long long)bi * RT, j0 = (long long)bj * RT;
     const int t = threadIdx.x, tx = t & 15, ty = t >> 4, dim = cp.dim;
     const int P = fab ? dim + 3 : dim + 2;
@@ -268,7 +282,7 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(const double* __restri
         const int n_metric = fab ? dim - 1 : dim;
         int cnt = n_metric - d0;
         cnt = cnt < 0 ? 0 : (cnt > RD ? RD : cnt);
-        block_sum_store(gd, cnt, sred, part + (size_t)(1 + d0) * ntiles, (size_t)ntiles, blockIdx.x);
+        block_sum_store(gd, cnt, sred, part + (size_t)(1 + d0) * ntiles, (size_t)ntiles, bx);
     }
     // scalars: amp -> 0, noise -> P - 1, Fabolas log a / log b -> dim, dim + 1
     __syncthreads();
@@ -289,16 +303,24 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(const double* __restri
             if (d == 0) p = 0;
             else if (d == 1) p = P - 1;
             else if (fab) p = dim + (d - 2);
-            if (p >= 0) part[(size_t)p * ntiles + blockIdx.x] = s;
+            if (p >= 0) part[(size_t)p * ntiles + bx] = s;
         }
     }
 }
+template <int KIND>
+__global__ __launch_bounds__(256) void grad_reduce_kernel(const double* __restrict__ Xs, const double* __restrict__ A,
+                                                          int lda, int n, CovParams cp, double* __restrict__ part,
+                                                          int ntiles) {
+    __shared__ double sI[RD * RLD];
+    __shared__ double sJ[RD * RLD];
+    __shared__ double sred[4 * RD];
+    grad_reduce_body<KIND>(blockIdx.x, Xs, A, lda, n, cp, part, ntiles, sI, sJ, sred);
+}
 
 // out[p] = 0.5 sum_tiles part[p][tile]   (fixed order: strided per thread, then a tree)
-__global__ __launch_bounds__(256) void grad_final_kernel(const double* __restrict__ part, int ntiles,
-                                                         double* __restrict__ out, double* __restrict__ out_host) {
-    __shared__ double s[256];
-    const double* row = part + (size_t)blockIdx.x * ntiles;
+__device__ __forceinline__ void grad_final_body(int bx, const double* __restrict__ part, int ntiles, double* __restrict__ out,
+                                                double* __restrict__ out_host, double* s) {
+    const double* row = part + (size_t)bx * ntiles;
     double a = 0.0;
     for (int i = threadIdx.x; i < ntiles; i += 256) a += row[i];
     s[threadIdx.x] = a;
@@ -308,9 +330,14 @@ __global__ __launch_bounds__(256) void grad_final_kernel(const double* __restric
         __syncthreads();
     }
     if (threadIdx.x == 0) {
-        out[blockIdx.x] = 0.5 * s[0];
-        if (out_host) out_host[blockIdx.x] = 0.5 * s[0];   // pinned, device-visible: no copy launch for P doubles
+        out[bx] = 0.5 * s[0];
+        if (out_host) out_host[bx] = 0.5 * s[0];   // pinned, device-visible: no copy launch for P doubles
     }
+}
+__global__ __launch_bounds__(256) void grad_final_kernel(const double* __restrict__ part, int ntiles,
+                                                         double* __restrict__ out, double* __restrict__ out_host) {
+    __shared__ double s[256];
+    grad_final_body(blockIdx.x, part, ntiles, out, out_host, s);
 }
 
 // d_V, d_A: (n_pad x n_pad) workspaces (d_A doubles as W during the inversion); d_alpha: n_pad;
@@ -359,6 +386,104 @@ int launch_grad_loglik(robo_gp* gp, double* d_V, double* d_A, double* d_alpha, d
     else ROBO_GRAD_CALL(ROBO_KERNEL_FABOLAS);
 #undef ROBO_GRAD_CALL
     hipLaunchKernelGGL(grad_final_kernel, dim3(P), dim3(256), 0, st, (const double*)d_part, ntiles, d_out, h_out);
+    ROBO_LAUNCH_CHECK();
+    return ROBO_OK;
+}
+
+// ---- S samples per launch (robo_gp_grad_loglik_batch, the optimiser of hyperopt.hip) ----------------------------------------
+// The same bodies with the sample as the last grid coordinate and per-sample pointers from the strides of GradBatch; the
+// covariance parameters come from the device-resident FitSample[s] (the optimiser forms theta on the device).  Every entry is
+// accumulated in the single-theta order, so a sample's gradient equals robo_gp_grad_loglik's bit for bit.  At BO sizes
+// (N <= 1024) a single-theta level of the merge or the reduction has far fewer workgroups than the chip has CUs.
+__global__ __launch_bounds__(256) void triinv_base_batch_kernel(const double* __restrict__ Linv, size_t linv_stride, int n,
+                                                                double* __restrict__ W, double* __restrict__ V, size_t stride,
+                                                                int ld) {
+    const size_t s = blockIdx.y;
+    triinv_base_body(blockIdx.x, Linv + s * linv_stride, n, W + s * stride, V + s * stride, ld);
+}
+
+template <int TM>
+__global__ __launch_bounds__(256, 2) void triinv_batch_kernel(int phase, int sb, int nbk, int n, const double* __restrict__ L,
+                                                              size_t l_stride, double* __restrict__ W, double* __restrict__ V,
+                                                              size_t stride, int ld) {
+    __shared__ double smem[gemm_smem_doubles<TM>()];
+    const size_t s = blockIdx.z;
+    triinv_body<TM>((int)blockIdx.x, (int)blockIdx.y, phase, sb, nbk, n, L + s * l_stride, W + s * stride, V + s * stride, ld,
+                    smem);
+}
+
+__global__ __launch_bounds__(256) void alpha_batch_kernel(const double* __restrict__ V, size_t stride, int ld,
+                                                          const double* __restrict__ L, size_t l_stride, int n, int rows,
+                                                          double* __restrict__ alpha, size_t alpha_stride) {
+    const size_t s = blockIdx.y;
+    alpha_body(blockIdx.x, V + s * stride, ld, L + s * l_stride + (size_t)n * ld, n, rows, alpha + s * alpha_stride);
+}
+
+__global__ __launch_bounds__(256, 2) void kinv_tile_batch_kernel(const double* __restrict__ V, double* __restrict__ A,
+                                                                 size_t stride, int ld, int kend,
+                                                                 const double* __restrict__ alpha, size_t alpha_stride) {
+    __shared__ double smem[GEMM_SMEM_DOUBLES];
+    const size_t s = blockIdx.y;
+    kinv_tile_body(blockIdx.x, V + s * stride, ld, kend, alpha + s * alpha_stride, A + s * stride, ld, smem);
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void grad_reduce_batch_kernel(const double* __restrict__ Xs, size_t xs_stride,
+                                                                const double* __restrict__ A, size_t stride, int lda, int n,
+                                                                const FitSample* __restrict__ sp, double* __restrict__ part,
+                                                                size_t part_stride, int ntiles) {
+    __shared__ double sI[RD * RLD];
+    __shared__ double sJ[RD * RLD];
+    __shared__ double sred[4 * RD];
+    const size_t s = blockIdx.y;
+    grad_reduce_body<KIND>(blockIdx.x, Xs + s * xs_stride, A + s * stride, lda, n, sp[s].cov, part + s * part_stride, ntiles,
+                           sI, sJ, sred);
+}
+
+__global__ __launch_bounds__(256) void grad_final_batch_kernel(const double* __restrict__ part, size_t part_stride, int ntiles,
+                                                               double* __restrict__ out, int P) {
+    __shared__ double sm[256];
+    const size_t s = blockIdx.y;
+    grad_final_body(blockIdx.x, part + s * part_stride, ntiles, out + s * P, nullptr, sm);
+}
+
+// gb.S factors of the batch workspace -> gb.out (S x P).  Asynchronous on the context's stream; allocates nothing.
+int launch_grad_loglik_batch(robo_gp* gp, const GradBatch& gb) {
+    hipStream_t st = gp->ctx->stream;
+    const int n = gp->n, n_pad = gp->n_pad, nbk = (n + NB - 1) / NB;
+    const unsigned S = (unsigned)gb.S;
+    const size_t stride = (size_t)n_pad * n_pad;
+    double* W = gb.A;   // dead before kinv_tile_batch_kernel writes A
+    hipLaunchKernelGGL(triinv_base_batch_kernel, dim3(nbk, S), dim3(256), 0, st, gb.Linv, gb.linv_stride, n, W, gb.V, stride,
+                       n_pad);
+    for (int sb = 1; sb < nbk; sb *= 2) {
+        const unsigned pairs = (unsigned)((nbk + 2 * sb - 1) / (2 * sb));
+        const bool narrow = (long long)sb * sb * pairs * S <= 2LL * gp->ctx->num_cu;   // (same bits for either TM)
+        for (int phase = 0; phase < 2; ++phase) {
+            if (narrow)
+                hipLaunchKernelGGL(triinv_batch_kernel<1>, dim3((unsigned)(sb * sb * 4), pairs, S), dim3(256), 0, st, phase, sb,
+                                   nbk, n, gb.K, gb.k_stride, W, gb.V, stride, n_pad);
+            else
+                hipLaunchKernelGGL(triinv_batch_kernel<4>, dim3((unsigned)(sb * sb), pairs, S), dim3(256), 0, st, phase, sb, nbk,
+                                   n, gb.K, gb.k_stride, W, gb.V, stride, n_pad);
+        }
+    }
+    hipLaunchKernelGGL(alpha_batch_kernel, dim3((nbk * NB + 3) / 4, S), dim3(256), 0, st, (const double*)gb.V, stride, n_pad,
+                       gb.K, gb.k_stride, n, nbk * NB, gb.alpha, (size_t)n_pad);
+    hipLaunchKernelGGL(kinv_tile_batch_kernel, dim3(nbk * (nbk + 1) / 2, S), dim3(256), 0, st, (const double*)gb.V, gb.A, stride,
+                       n_pad, nbk * NB, (const double*)gb.alpha, (size_t)n_pad);
+    const int t64 = (n + RT - 1) / RT, ntiles = t64 * (t64 + 1) / 2;
+    const int P = gp->kind == ROBO_KERNEL_FABOLAS ? gp->dim + 3 : gp->dim + 2;
+    const size_t part_stride = (size_t)P * ntiles;
+#define ROBO_GRAD_CALL(KIND)                                                                                             \
+    hipLaunchKernelGGL(grad_reduce_batch_kernel<KIND>, dim3(ntiles, S), dim3(256), 0, st, gb.Xs, gb.xs_stride,         \
+                       (const double*)gb.A, stride, n_pad, n, gb.sp, gb.part, part_stride, ntiles)
+    if (gp->kind == ROBO_KERNEL_MATERN52_ARD) ROBO_GRAD_CALL(ROBO_KERNEL_MATERN52_ARD);
+    else if (gp->kind == ROBO_KERNEL_RBF_ARD) ROBO_GRAD_CALL(ROBO_KERNEL_RBF_ARD);
+    else ROBO_GRAD_CALL(ROBO_KERNEL_FABOLAS);
+#undef ROBO_GRAD_CALL
+    hipLaunchKernelGGL(grad_final_batch_kernel, dim3(P, S), dim3(256), 0, st, (const double*)gb.part, part_stride, ntiles,
+                       gb.out, P);
     ROBO_LAUNCH_CHECK();
     return ROBO_OK;
 }

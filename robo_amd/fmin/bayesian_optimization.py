@@ -33,7 +33,8 @@ logger = logging.getLogger(__name__)
 def bayesian_optimization(objective_function, lower, upper, num_iterations=30, X_init=None, Y_init=None,
                           maximizer="random", acquisition_func="log_ei", model_type="gp_mcmc", n_init=3, rng=None,
                           output_path=None, n_candidates=500, chain_length=200, burnin_steps=100, n_gpus=None,
-                          devices=None, batch_size=1, fantasy="kriging_believer", liar="min", evaluate_batch=None):
+                          devices=None, batch_size=1, fantasy="kriging_believer", liar="min", evaluate_batch=None,
+                          hyper_optimizer="host", n_restarts=8):
     """Minimise ``objective_function`` over the box [lower, upper] -> dict with x_opt, f_opt,
     incumbents, incumbent_values, runtime, overhead, X, y (same keys as the reference).
 
@@ -62,9 +63,13 @@ def bayesian_optimization(objective_function, lower, upper, num_iterations=30, X
 
     from robo_amd import _lib
     devices = _lib.resolve_devices(devices, n_gpus)
+    if hyper_optimizer != "host" and model_type == "gp_mcmc":
+        raise ValueError("hyper_optimizer='{}' applies to model_type='gp'; 'gp_mcmc' samples its hyper-parameters"
+                         .format(hyper_optimizer))
     if model_type == "gp":
         model = GaussianProcess(kernel, prior=prior, rng=rng, normalize_output=False, normalize_input=True,
-                                lower=lower, upper=upper, devices=devices)
+                                lower=lower, upper=upper, devices=devices, optimizer=hyper_optimizer,
+                                n_restarts=n_restarts)
     elif model_type == "gp_mcmc":
         model = GaussianProcessMCMC(kernel, prior=prior, n_hypers=n_hypers, chain_length=chain_length,
                                     burnin_steps=burnin_steps, normalize_input=True, normalize_output=False,
