@@ -37,6 +37,16 @@ int32_t robo_microbench_gemm_f64(robo_ctx* ctx, int32_t variant, int32_t wgs, in
 int32_t robo_selftest_stretch_move(robo_ctx* ctx, const double* c, const double* s, const double* u, double a, int32_t P,
                                    int32_t n, double* out_z, double* out_q, double* out_lnpdiff);
 
+/* The covariance entries that no product entry point returns, through the product's own code:
+ * _cross_gram: the posterior's cross-gram kernel (launch_cross_gram, in the GP's precision) of the training inputs
+ *   at theta against m candidates (raw inputs, scaled on the device by theta's metrics as a prediction does);
+ *   out (m x n) row-major.  The GP needs data, not a fit; it is left unfitted.
+ * _cov_rows: the scalar device function cov_rows on n_pairs prescribed pairs of ALREADY SCALED rows xi, xj
+ *   (n_pairs x dim each); kind / amp / blr_a / blr_b as in the covariance parameters of a theta.               */
+int32_t robo_diag_cross_gram(robo_gp* gp, const double* theta, const double* Xc, int32_t m, double* out);
+int32_t robo_diag_cov_rows(robo_ctx* ctx, int32_t kind, int32_t dim, double amp, double blr_a, double blr_b,
+                           const double* xi, const double* xj, int64_t n_pairs, double* out);
+
 /* Shader clock while other work runs: _begin launches eight one-wave sampler workgroups on a private stream; each
  * sleeps through window_us of the 100 MHz wall clock and records the shader cycles that passed.  _end waits for them:
  * out3 = {mean, min, max} shader MHz.  bench.py brackets one posterior step with it, so that the roofline block can

@@ -63,7 +63,7 @@ COMM_ID_BYTES = 128
 DIAG_SYMBOLS = [
     "robo_selftest_mfma_layout", "robo_microbench_mfma_f64", "robo_microbench_mfma_f64_detail", "robo_microbench_gemm_f64",
     "robo_selftest_diag_timeline", "robo_diag_clock_sample_begin", "robo_diag_clock_sample_end",
-    "robo_selftest_stretch_move",
+    "robo_selftest_stretch_move", "robo_diag_cross_gram", "robo_diag_cov_rows",
 ]
 
 
@@ -297,7 +297,10 @@ def diag():
                        "robo_microbench_gemm_f64": [vp, i32, i32, i32, i32, _dp],
                        "robo_selftest_diag_timeline": [vp, _dp, _dp],
                        "robo_diag_clock_sample_begin": [vp, i32], "robo_diag_clock_sample_end": [vp, _dp],
-                       "robo_selftest_stretch_move": [vp, _dp, _dp, _dp, C.c_double, i32, i32, _dp, _dp, _dp]}.items():
+                       "robo_selftest_stretch_move": [vp, _dp, _dp, _dp, C.c_double, i32, i32, _dp, _dp, _dp],
+                       "robo_diag_cross_gram": [vp, _dp, _dp, i32, _dp],
+                       "robo_diag_cov_rows": [vp, i32, i32, C.c_double, C.c_double, C.c_double, _dp, _dp, C.c_int64,
+                                              _dp]}.items():
         fn = getattr(D, name)
         fn.argtypes = args
         fn.restype = i32
@@ -419,6 +422,15 @@ class Context(object):
         check(diag().robo_selftest_stretch_move(self._h, _arr(c), _arr(s), _arr(u), float(a), int(P), c.size,
                                                 _arr(z), _arr(q), _arr(d)))
         return z, q, d
+
+    def cov_rows(self, kind, xi, xj, amp=1.0, blr_a=0.0, blr_b=0.0):
+        """-> the device function cov_rows on pairs of already scaled rows xi, xj (n, dim) (include/robo_hip_diag.h)"""
+        xi, xj = _f64(xi), _f64(xj)
+        assert xi.ndim == 2 and xi.shape == xj.shape
+        out = np.empty(xi.shape[0])
+        check(diag().robo_diag_cov_rows(self._h, KERNEL_KINDS[kind], xi.shape[1], float(amp), float(blr_a), float(blr_b),
+                                        _arr(xi), _arr(xj), xi.shape[0], _arr(out)))
+        return out
 
     def microbench_mfma_f64_detail(self, iters=2000):
         """-> dict(full-chip tflops, issue interval of one lone wave in shader cycles, MHz under load)"""
@@ -776,6 +788,15 @@ class DeviceGP(object):
         theta = _f64(_full_theta(self, theta), (self.n_theta,))
         out = np.empty((self.n, self.n))
         check(lib().robo_gp_get_gram(self._h, _arr(theta), _arr(out)))
+        return out
+
+    def cross_gram(self, theta, Xc):
+        """-> (m, n) the posterior's cross-gram kernel at theta against candidates Xc (include/robo_hip_diag.h)"""
+        theta = _f64(_full_theta(self, theta), (self.n_theta,))
+        Xc = _f64(Xc)
+        assert Xc.ndim == 2 and Xc.shape[1] == self.dim
+        out = np.empty((Xc.shape[0], self.n))
+        check(diag().robo_diag_cross_gram(self._h, _arr(theta), _arr(Xc), Xc.shape[0], _arr(out)))
         return out
 
     def diag_timeline(self, theta):

@@ -43,8 +43,9 @@ int32_t robo_gp_create(robo_ctx* ctx, int32_t kind, int32_t n_max, int32_t dim, 
     ROBO_TRY(dev_alloc(&g->d_LinvP, (np / NB) * WP_BLOCK));
     ROBO_HIP_CHECK(hipMemset(g->d_LinvP, 0, (np / NB) * WP_BLOCK * sizeof(double)));
     ROBO_TRY(dev_alloc(&g->d_llpart, (np / NB) * 4));
-    ROBO_TRY(dev_alloc(&g->d_theta, (size_t)dim + 8 + sizeof(FitSample) / sizeof(double)));
+    ROBO_TRY(dev_alloc(&g->d_theta, (size_t)dim + 8 + sizeof(FitSample) / sizeof(double) + (size_t)dim));
     g->d_sp = reinterpret_cast<FitSample*>(g->d_theta + dim + 8);
+    g->d_x2max = g->d_theta + dim + 8 + sizeof(FitSample) / sizeof(double);
     ctx_retain(ctx);
     *out = g;
     return ROBO_OK;
@@ -110,6 +111,14 @@ int32_t robo_gp_set_data(robo_gp* g, const double* X, const double* y, int32_t n
     ROBO_HIP_CHECK(hipSetDevice(c->device));
     ROBO_HIP_CHECK(hipMemcpyAsync(g->d_X, X, (size_t)n * g->dim * sizeof(double), hipMemcpyHostToDevice, c->stream));
     ROBO_HIP_CHECK(hipMemcpyAsync(g->d_y, y, (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    // the data extents that decide between the two fp64 gram tiles (common.h gram_needs_direct)
+    for (int d = 0; d < g->dim; ++d) g->x2max[d] = 0.0;
+    for (int i = 0; i < n; ++i)
+        for (int d = 0; d < g->dim; ++d) {
+            const double x = X[(size_t)i * g->dim + d], x2 = x * x;
+            if (x2 > g->x2max[d]) g->x2max[d] = x2;
+        }
+    ROBO_HIP_CHECK(hipMemcpyAsync(g->d_x2max, g->x2max, (size_t)g->dim * sizeof(double), hipMemcpyHostToDevice, c->stream));
     if (n % NB == 0) {
         // the augmented row's own block (block n / NB) is never factored nor inverted (launch_potrf): its inverse slots
         // must not carry a former data set's entries -- the pack / keep kernels copy every block of the padded range
@@ -163,6 +172,7 @@ int theta_to_sample(const robo_gp* g, const double* theta, double mean_c, FitSam
     sp->cov.blr_b = fab ? std::exp(theta[D + 1]) : 0.0;
     sp->noise = std::exp(theta[P - 1]) + JITTER;
     sp->mean_c = mean_c;
+    sp->direct = gram_needs_direct(g->kind, ism, g->x2max, D);
     return ROBO_OK;
 }
 }  // namespace robo
@@ -206,7 +216,9 @@ static int gp_build_gram(robo_gp* g, const double* theta, double mean_c) {
     // theta travels as kernel arguments; block 0 of the scaling kernel leaves d_theta (metrics) and d_sp behind
     ROBO_TRY(launch_scale_inputs_theta(c, g->d_X, g->d_Xs, ta, g->n, g->n_pad, D, g->d_theta, g->d_sp));
     if (c->phase_events) ROBO_HIP_CHECK(hipEventRecord(c->events[19], c->stream));   // slot 19 -> 21: the gram kernel alone (K1)
-    ROBO_TRY(launch_gram(g, own_buffers(g)));
+    FitBuffers fb = own_buffers(g);
+    fb.gram_mixed = ta.sp.direct != 0;
+    ROBO_TRY(launch_gram(g, fb));
     return ROBO_OK;
 }
 
@@ -341,6 +353,7 @@ static int fit_batch_core(robo_gp* g, const double* thetas, int32_t S, double me
         double* hism = reinterpret_cast<double*>(hsp + cap);
         double* hout = hism + (size_t)cap * D;             // [ns][5]: z.z, log det, failure flag, min / max L_ii
         std::vector<int> status(ns, ROBO_OK);
+        bool any_direct = false;
         for (int s = 0; s < ns; ++s) {
             const int st = theta_to_sample(g, thetas + (size_t)(s0 + s) * P, mean_c, hsp + s, hism + (size_t)s * D);
             status[s] = st;
@@ -348,6 +361,7 @@ static int fit_batch_core(robo_gp* g, const double* thetas, int32_t S, double me
                 static const double zeros[MAX_DIM + 8] = {0};
                 theta_to_sample(g, zeros, mean_c, hsp + s, hism + (size_t)s * D);
             }
+            if (hsp[s].direct) any_direct = true;
         }
         ROBO_HIP_CHECK(hipMemcpyAsync(g->d_bsp, hsp, (size_t)cap * sizeof(FitSample) + (size_t)ns * D * sizeof(double),
                                       hipMemcpyHostToDevice, c->stream));
@@ -364,6 +378,7 @@ static int fit_batch_core(robo_gp* g, const double* thetas, int32_t S, double me
         fb.host_out = hout;
         fb.want_inverse = (bool)keep;      // likelihoods only: the posterior's inverse blocks are not formed
         fb.skip_tail = false;
+        fb.gram_mixed = any_direct;
         fb.S = ns;
         ROBO_TRY(launch_scale_inputs(c, g->d_X, g->d_bXs, g->d_bism, g->n, g->n_pad, D, ns, np * D, (size_t)D));
         ROBO_TRY(launch_potrf(g, fb, true));   // gram + factorisation; its tail kernel also reduces the log-likelihood terms into fb.out
@@ -466,6 +481,7 @@ int32_t robo_gp_mcmc_run(robo_gp* g, double mean_c, int32_t prior_kind, const do
     st.prior_kind = prior_kind; st.a = a; st.mean_c = mean_c;
     if (prior_kind != 0) for (int i = 0; i < (prior_kind == 2 ? 9 : 5); ++i) st.prior_par[i] = prior_par[i];
     st.d_sp = g->d_bsp; st.d_ism = g->d_bism; st.d_out = g->d_bout; st.d_fail = g->d_bfail;
+    st.d_x2max = g->d_x2max;
     hipStream_t s = c->stream;
     ROBO_HIP_CHECK(hipMemcpyAsync(st.d_pos, pos, (size_t)k * P * sizeof(double), hipMemcpyHostToDevice, s));
     if (!eval_start) ROBO_HIP_CHECK(hipMemcpyAsync(st.d_lnp, lnp, (size_t)k * sizeof(double), hipMemcpyHostToDevice, s));
@@ -486,6 +502,7 @@ int32_t robo_gp_mcmc_run(robo_gp* g, double mean_c, int32_t prior_kind, const do
     fb.ll_part = g->d_bllpart;
     fb.LinvP = nullptr;
     fb.host_out = nullptr;             // the likelihood terms are consumed on the device
+    fb.gram_mixed = true;              // the proposals are formed on the device: each carries its own FitSample::direct
     fb.want_inverse = false;
     fb.skip_tail = c->tune.mcmc_fused_tail != 0 && g->n_pad > NB;     // (one-block factors reduce inside their diagonal kernel)
     fb.S = half;
@@ -599,6 +616,8 @@ int32_t robo_gp_fit_batch(robo_gp* const* gps, int32_t S, const double* thetas, 
                 g->n_pad = g0->n_pad;
                 g->has_data = true;
                 g->fp32_gram = g0->fp32_gram;
+                memcpy(g->x2max, g0->x2max, sizeof(g->x2max));
+                ROBO_HIP_CHECK(hipMemcpyAsync(g->d_x2max, g->x2max, (size_t)D * sizeof(double), hipMemcpyHostToDevice, c->stream));
             }
             FitSample sp;
             double ism[MAX_DIM];

@@ -85,7 +85,30 @@ struct FitSample {
     CovParams cov;
     double noise;    // exp(theta[P-1]) + JITTER, added to the diagonal
     double mean_c;   // constant prior mean
+    int direct;      // fp64 stationary kernels: K from direct differences instead of the dot form (gram_needs_direct)
 };
+
+// Which of the two fp64 tiles of a stationary kernel builds K (gram_tile.h): the dot form  r2 = |xi|^2 + |xj|^2 - 2 xi.xj
+// carries an absolute error of about (D + 3) eps (|xi|^2 + |xj|^2) in r2, which is harmless while the SCALED coordinates
+// are O(1) and is not at short length scales or for data far from the origin.  The bound below uses the data extents
+// x2max[d] = max_i x_id^2 of the raw inputs (robo_gp_set_data) and the inverse square-root metrics of the theta:
+//     (D + 3) eps 2 sum_d ism_d^2 x2max_d  >  GRAM_DIRECT_BOUND   ->   direct differences.
+// ONE function for the host (theta_to_sample) and the device (the chain and optimiser kernels form theta themselves), every
+// operation rounded once and never contracted, so that every path takes the same tile for the same theta.
+constexpr double GRAM_DIRECT_BOUND = 1e-12;
+__host__ __device__ inline int gram_needs_direct(int kind, const double* ism, const double* x2max, int D) {
+#pragma clang fp contract(off)
+    if (kind == ROBO_KERNEL_FABOLAS) return 0;      // the product kernel has no dot form
+    double s = 0.0;
+    for (int d = 0; d < D; ++d) {
+        const double m2 = ism[d] * ism[d];
+        const double t = m2 * x2max[d];
+        s = s + t;
+    }
+    const double c = (double)(D + 3) * 4.44089209850062616e-16;     // (D + 3) * 2 * 2^-52
+    const double b = c * s;
+    return b > GRAM_DIRECT_BOUND ? 1 : 0;           // (a NaN extent -- non-finite data -- stays on the dot form)
+}
 
 // one theta as kernel arguments (single-sample fits, gram.hip)
 struct ThetaArgs {
@@ -327,6 +350,7 @@ struct HyperState {
     double* trace;                  // (n_iters + 1) x K x (2 P + 3), or nullptr
     FitSample* d_sp;                // the batched fit's inputs / outputs (api_fit.hip batch_ensure)
     double* d_ism;
+    const double* d_x2max;          // [D] data extents (robo_gp::d_x2max) for gram_needs_direct
     const double *d_out, *d_grad;   // (K x 2) z.z and log det; (K x P) likelihood gradient
     const int* d_fail;
 };
@@ -406,6 +430,8 @@ struct robo_gp {
     double* d_LinvP;    // the same inverses as packed MFMA A-operand fragments (WP_BLOCK doubles per block, predict.hip)
     double* d_theta;    // inverse sqrt metric (dim) of the current theta
     robo::FitSample* d_sp;   // device copy of the current FitSample
+    double x2max[robo::MAX_DIM];   // max_i x_id^2 of the raw training inputs per dimension (robo_gp_set_data)
+    double* d_x2max;         // device copy (inside d_theta's block)
     // batch workspace for robo_gp_loglik_batch (lazy, b_cap samples)
     int b_cap, b_npad;
     double *d_bK, *d_bLinv, *d_bXs, *d_bism, *d_bout, *h_bstage;
@@ -497,6 +523,9 @@ struct FitBuffers {
     double* host_out;                    // pinned host [S][5]: z.z, 2 sum log diag, failure flag, min / max L_ii -- or nullptr
     bool want_inverse;                   // false: log-likelihood only (no explicit inverse blocks, no fragments)
     bool skip_tail;                      // the caller reduces the likelihood terms itself (mcmc.hip mcmc_tail_kernel)
+    // launch_gram: a sample of this launch may carry FitSample::direct, so the kernel with both fp64 tiles is launched.  A
+    // caller that formed every theta on the host and found none clears it and gets the dot tile's kernel alone.
+    bool gram_mixed = true;
     int S;
 };
 int launch_scale_inputs_theta(robo_ctx* ctx, const double* d_in, double* d_out, const ThetaArgs& ta, int64_t rows_real,
@@ -523,6 +552,7 @@ struct McmcState {
     double *d_chain, *d_lnprob;                       // (k x n_steps x P), (k x n_steps); nullable
     FitSample* d_sp;                                  // the batched fit's inputs / outputs (api_fit.hip batch_ensure)
     double* d_ism;
+    const double* d_x2max;                            // [D] data extents (robo_gp::d_x2max) for gram_needs_direct
     const double* d_out;
     const int* d_fail;
 };
@@ -607,6 +637,8 @@ int launch_uniform(robo_ctx* ctx, double* d_out, int64_t m, int64_t m_pad, int d
 int launch_sobol(robo_ctx* ctx, double* d_out, int64_t m, int64_t m_pad, int dim, const unsigned long long* d_sv,
                  const unsigned long long* d_shift, int bits, uint64_t first);
 int launch_mfma_selftest(robo_ctx* ctx, double* out_err);
+int launch_cov_rows_probe(robo_ctx* ctx, const CovParams& cp, const double* h_xi, const double* h_xj, long long n,
+                          double* h_out);
 int launch_stretch_probe(robo_ctx* ctx, const double* h_c, const double* h_s, const double* h_u, double a, int P, int n,
                          double* h_z, double* h_q, double* h_d);
 int launch_gemm_microbench(robo_ctx* ctx, int variant, int wgs, int K, int reps, double* out_tflops);

@@ -66,6 +66,44 @@ int32_t robo_selftest_stretch_move(robo_ctx* ctx, const double* c, const double*
     return launch_stretch_probe(ctx, c, s, u, a, P, n, out_z, out_q, out_lnpdiff);
 }
 
+int32_t robo_diag_cross_gram(robo_gp* g, const double* theta, const double* Xc, int32_t m, double* out) {
+    if (!g || !theta || !Xc || !out || m < 1) return ROBO_BAD_ARGUMENT;
+    if (!g->has_data) return ROBO_NOT_FITTED;
+    {   // theta, the scaled training inputs and the metrics into the GP's own buffers (public entry point; K is discarded)
+        std::vector<double> tmp((size_t)g->n * g->n);
+        const int st = robo_gp_get_gram(g, theta, tmp.data());
+        if (st != ROBO_OK) return st;
+    }
+    robo_cand* k = nullptr;
+    { const int st = robo_cand_create(g->ctx, Xc, m, g->dim, &k); if (st != ROBO_OK) return st; }
+    const size_t np = (size_t)g->n_pad, mp = (size_t)k->m_pad;
+    double* d = nullptr;
+    int st = hipMalloc((void**)&d, mp * np * sizeof(double)) == hipSuccess ? ROBO_OK : ROBO_RUNTIME_ERROR;
+    // the posterior's own sequence: candidates scaled by the fitted metrics, then the cross-gram kernel per chunk
+    if (st == ROBO_OK) st = launch_scale_inputs(g->ctx, k->d_Xc, k->d_Xcs, g->d_theta, k->m, k->m_pad, g->dim);
+    if (st == ROBO_OK) st = launch_cross_gram(g, k, 0, k->m_pad, d);
+    std::vector<double> h(mp * np);
+    if (st == ROBO_OK && hipMemcpyAsync(h.data(), d, mp * np * sizeof(double), hipMemcpyDeviceToHost, g->ctx->stream) != hipSuccess)
+        st = ROBO_RUNTIME_ERROR;
+    if (hipStreamSynchronize(g->ctx->stream) != hipSuccess) st = ROBO_RUNTIME_ERROR;
+    if (d) hipFree(d);
+    robo_cand_destroy(k);
+    if (st != ROBO_OK) return st;
+    for (int i = 0; i < m; ++i)
+        for (int j = 0; j < g->n; ++j) out[(size_t)i * g->n + j] = h[(size_t)i * np + j];
+    return ROBO_OK;
+}
+
+int32_t robo_diag_cov_rows(robo_ctx* ctx, int32_t kind, int32_t dim, double amp, double blr_a, double blr_b,
+                           const double* xi, const double* xj, int64_t n_pairs, double* out) {
+    if (!ctx || !xi || !xj || !out || n_pairs < 1 || dim < 1 || dim > MAX_DIM) return ROBO_BAD_ARGUMENT;
+    if (kind != ROBO_KERNEL_MATERN52_ARD && kind != ROBO_KERNEL_RBF_ARD && kind != ROBO_KERNEL_FABOLAS) return ROBO_BAD_ARGUMENT;
+    ROBO_HIP_CHECK(hipSetDevice(ctx->device));
+    CovParams cp;
+    cp.kind = kind; cp.dim = dim; cp.amp = amp; cp.blr_a = blr_a; cp.blr_b = blr_b;
+    return launch_cov_rows_probe(ctx, cp, xi, xj, (long long)n_pairs, out);
+}
+
 int32_t robo_diag_clock_sample_begin(robo_ctx* ctx, int32_t window_us) {
     if (!ctx) return ROBO_BAD_ARGUMENT;
     ROBO_HIP_CHECK(hipSetDevice(ctx->device));

@@ -5,6 +5,7 @@
 //     on (the local microarchitecture guide lists no fp64 MFMA peak; the datasheet figure is
 //     78.6 TFLOP/s).
 #include "../common.h"
+#include "../kern_math.h"
 #include "../mcmc_dev.h"
 
 namespace robo {
@@ -108,6 +109,35 @@ int launch_stretch_probe(robo_ctx* ctx, const double* h_c, const double* h_s, co
     ROBO_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     ROBO_HIP_CHECK(hipFree(d));
     return ROBO_OK;
+}
+
+// cov_rows (kern_math.h: the scalar covariance of the posterior's self terms, the batch proposals and entropy search) on
+// prescribed pairs of already scaled rows: out[p] = cov_rows(cp, xi[p], xj[p])
+__global__ __launch_bounds__(256) void cov_rows_probe_kernel(CovParams cp, const double* __restrict__ xi,
+                                                             const double* __restrict__ xj, double* __restrict__ out,
+                                                             long long n) {
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < n) out[p] = cov_rows(cp, xi + p * cp.dim, xj + p * cp.dim);
+}
+
+int launch_cov_rows_probe(robo_ctx* ctx, const CovParams& cp, const double* h_xi, const double* h_xj, long long n,
+                          double* h_out) {
+    const size_t rows = (size_t)n * cp.dim * sizeof(double), bytes = 2 * rows + (size_t)n * sizeof(double);
+    double* d = nullptr;
+    ROBO_HIP_CHECK(hipMalloc((void**)&d, bytes));
+    double *dxi = d, *dxj = d + (size_t)n * cp.dim, *dout = dxj + (size_t)n * cp.dim;
+    const int st = [&]() -> int {          // (d is freed on every path)
+        ROBO_HIP_CHECK(hipMemcpyAsync(dxi, h_xi, rows, hipMemcpyHostToDevice, ctx->stream));
+        ROBO_HIP_CHECK(hipMemcpyAsync(dxj, h_xj, rows, hipMemcpyHostToDevice, ctx->stream));
+        hipLaunchKernelGGL(cov_rows_probe_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, cp,
+                           (const double*)dxi, (const double*)dxj, dout, n);
+        ROBO_LAUNCH_CHECK();
+        ROBO_HIP_CHECK(hipMemcpyAsync(h_out, dout, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        ROBO_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        return ROBO_OK;
+    }();
+    hipFree(d);
+    return st;
 }
 
 int launch_mfma_selftest(robo_ctx* ctx, double* out_err) {

@@ -78,6 +78,12 @@ __device__ __forceinline__ void pair_cov(const CovParams& cp, const double* __re
     constexpr bool fab = KIND == ROBO_KERNEL_FABOLAS;
     T acc[4][4], uu[4][4];
     T ss[fab ? 4 : 1][fab ? 4 : 1];      // Fabolas: sum of the per-dimension exponents (matern52_1d_split)
+    // ... folded into the product every FOLD dimensions: at the short end of the prior (ln metric = -10) one polynomial
+    // factor reaches (1 + s + s^2 / 3) = 3.7e4 at s = sqrt(5) e^5, and the bare product overflowed (fp32 from 9 such
+    // dimensions, fp64 from 68) while the one closing exponential had underflowed: inf * 0 = NaN for a true value of 0.
+    // FOLD keeps 3.7e4^FOLD finite: 4 in fp32 (1.9e18), one 16-dimension LDS pass in fp64 (1e73) -- so fp64 problems of
+    // up to 17 columns (one pass and the fidelity column) see exactly one exponential.
+    constexpr int FOLD = sizeof(T) == 4 ? 4 : GD;
 #pragma unroll
     for (int a = 0; a < 4; ++a)
 #pragma unroll
@@ -109,6 +115,15 @@ __device__ __forceinline__ void pair_cov(const CovParams& cp, const double* __re
                 for (int a = 0; a < 4; ++a)
 #pragma unroll
                     for (int b = 0; b < 4; ++b) matern52_1d_split(xi[a] - xj[b], acc[a][b], ss[fab ? a : 0][fab ? b : 0]);
+                if ((d0 + d) % FOLD == FOLD - 1 && d0 + d + 1 < dim - 1) {      // (the last fold is the closing one below)
+#pragma unroll
+                    for (int a = 0; a < 4; ++a)
+#pragma unroll
+                        for (int b = 0; b < 4; ++b) {
+                            acc[a][b] = matern52_split_close(acc[a][b], ss[fab ? a : 0][fab ? b : 0]);
+                            ss[fab ? a : 0][fab ? b : 0] = T(0);
+                        }
+                }
             } else {
 #pragma unroll
                 for (int a = 0; a < 4; ++a)
@@ -122,7 +137,7 @@ __device__ __forceinline__ void pair_cov(const CovParams& cp, const double* __re
     for (int a = 0; a < 4; ++a)
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
-            if (fab) acc[a][b] *= exp_np(-ss[fab ? a : 0][fab ? b : 0]);
+            if (fab) acc[a][b] = matern52_split_close(acc[a][b], ss[fab ? a : 0][fab ? b : 0]);
             cov[a][b] = cov_finish<T, KIND>(cp, acc[a][b], uu[a][b]);
         }
 }
@@ -133,7 +148,9 @@ __device__ __forceinline__ void pair_cov(const CovParams& cp, const double* __re
 // (six workgroups per CU = 80 VGPRs; the Fabolas product kernel needs more live values -- one Matern factor per pair and
 // dimension -- and spilled 92 registers under that cap: three per CU for it)
 // WPC: workgroups per CU the register allocation is asked to allow (0: the default, six -- three for the Fabolas kernel)
-template <class T, int KIND>
+// MIXED (fp64 stationary kernels only): samples of this launch may ask for the direct-difference tile (FitSample::direct,
+// a workgroup-uniform branch); false: the dot tile alone (launches whose thetas the host formed and found none that asks)
+template <class T, int KIND, bool MIXED>
 __global__ __launch_bounds__(256, KIND == ROBO_KERNEL_FABOLAS ? 3 : 6) void gram_kernel(const double* __restrict__ Xs, size_t xs_stride,
                                                    const double* __restrict__ y, double* __restrict__ K,
                                                    size_t k_stride, int n, int n_pad,
@@ -162,8 +179,12 @@ __global__ __launch_bounds__(256, KIND == ROBO_KERNEL_FABOLAS ? 3 : 6) void gram
     tri_tile(blockIdx.x, bi, bj);
     const long long i0 = (long long)bi * GT, j0 = (long long)bj * GT;
     double cov[4][4];
-    if constexpr (sizeof(T) == 8 && KIND != ROBO_KERNEL_FABOLAS) pair_cov_dot<KIND>(cp, Xs, i0, j0, sI, sJ, sN, cov);
-    else pair_cov<T, KIND>(cp, Xs, Xs, i0, j0, sI, sJ, cov);
+    if constexpr (sizeof(T) == 8 && KIND != ROBO_KERNEL_FABOLAS) {
+        if (MIXED && sp[blockIdx.y].direct) pair_cov_direct<KIND>(cp, Xs, i0, j0, sI, sJ, cov);
+        else pair_cov_dot<KIND>(cp, Xs, i0, j0, sI, sJ, sN, cov);
+    } else {
+        pair_cov<T, KIND>(cp, Xs, Xs, i0, j0, sI, sJ, cov);
+    }
     const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
     // which columns of the tile this thread's four entries per row are (gram_tile.h: the fp64 stationary kernels' tiles use
     // gram_col, the others four consecutive columns); c0 / c2: first column of the entry pairs (0, 1) and (2, 3)
@@ -275,14 +296,19 @@ int launch_gram(robo_gp* gp, const FitBuffers& fb, hipStream_t stream, int s0, i
     const int nb = gp->n_pad / NB, nbf = (gp->n % NB == 0 && nb > 1) ? nb - 1 : nb;     // factored panels (launch_potrf)
     if (!stream) stream = gp->ctx->stream;
     if (ns < 0) ns = fb.S - s0;
+    // the direct-difference tile is compiled into the launch only when a sample may ask for it (FitBuffers::gram_mixed)
+    const bool mixed = fb.gram_mixed && !gp->fp32_gram && gp->kind != ROBO_KERNEL_FABOLAS;
 #define ROBO_GRAM_CALL(TYPE, KIND)                                                                              \
-    hipLaunchKernelGGL((gram_kernel<TYPE, KIND>), dim3(tiles, ns), dim3(256), 0, stream,                        \
+    if (mixed) ROBO_GRAM_CALL_(TYPE, KIND, true); else ROBO_GRAM_CALL_(TYPE, KIND, false)
+#define ROBO_GRAM_CALL_(TYPE, KIND, MIXED)                                                                      \
+    hipLaunchKernelGGL((gram_kernel<TYPE, KIND, MIXED>), dim3(tiles, ns), dim3(256), 0, stream,                 \
                        fb.Xs + (size_t)s0 * fb.xs_stride, fb.xs_stride, (const double*)gp->d_y,                 \
                        fb.K + (size_t)s0 * fb.k_stride, fb.k_stride, gp->n, gp->n_pad, fb.sp + s0, fb.fail + s0,           \
                        fb.prog ? fb.prog + (size_t)s0 * PROG_STRIDE : (unsigned*)nullptr,                                \
                        fb.Linv + (size_t)s0 * fb.linv_stride, fb.linv_stride, nbf)
     ROBO_DISPATCH_COV(gp->fp32_gram, gp->kind, ROBO_GRAM_CALL);
 #undef ROBO_GRAM_CALL
+#undef ROBO_GRAM_CALL_
     ROBO_LAUNCH_CHECK();
     return ROBO_OK;
 }

@@ -183,6 +183,7 @@ __global__ __launch_bounds__(256) void hyper_propose_kernel(HyperState st, int t
             sp.cov.blr_b = fab ? exp(ok ? sz[D + 1] : 0.0) : 0.0;
             sp.noise = exp(ok ? sz[P - 1] : 0.0) + JITTER;
             sp.mean_c = st.mean_c;
+            sp.direct = gram_needs_direct(st.kind, sism, st.d_x2max, D);
             st.d_sp[k] = sp;
         }
     }
@@ -490,18 +491,22 @@ int32_t robo_gp_grad_loglik_batch(robo_gp* g, const double* thetas, int32_t S, d
         double* hism = reinterpret_cast<double*>(hsp + cap);
         double* hout = hism + (size_t)cap * D;             // [ns][5]: z.z, log det, failure flag, min / max L_ii
         std::vector<int> status(ns, ROBO_OK);
+        bool any_direct = false;
         for (int s = 0; s < ns; ++s) {
             status[s] = theta_to_sample(g, thetas + (size_t)(s0 + s) * P, mean_c, hsp + s, hism + (size_t)s * D);
             if (status[s] != ROBO_OK) {   // keep the slot numerically harmless: unit kernel
                 static const double zeros[MAX_DIM + 8] = {0};
                 theta_to_sample(g, zeros, mean_c, hsp + s, hism + (size_t)s * D);
             }
+            if (hsp[s].direct) any_direct = true;
         }
         ROBO_HIP_CHECK(hipMemcpyAsync(g->d_bsp, hsp, (size_t)cap * sizeof(FitSample) + (size_t)ns * D * sizeof(double),
                                       hipMemcpyHostToDevice, c->stream));
         const size_t np = (size_t)g->n_pad;
         ROBO_TRY(launch_scale_inputs(c, g->d_X, g->d_bXs, g->d_bism, g->n, g->n_pad, D, ns, np * D, (size_t)D));
-        ROBO_TRY(launch_potrf(g, batch_buffers(g, ns, hout), true));
+        FitBuffers fb = batch_buffers(g, ns, hout);
+        fb.gram_mixed = any_direct;
+        ROBO_TRY(launch_potrf(g, fb, true));
         ROBO_TRY(launch_grad_loglik_batch(g, grad_buffers(g, ns)));
         ROBO_HIP_CHECK(hipMemcpyAsync(out_grad + (size_t)s0 * P, g->hyper->d_out, (size_t)ns * P * sizeof(double),
                                       hipMemcpyDeviceToHost, c->stream));
@@ -609,11 +614,13 @@ int32_t robo_gp_optimize_hypers(robo_gp* g, double mean_c, int32_t prior_kind, c
     if (prior_kind != 0) for (int i = 0; i < (prior_kind == 2 ? 9 : 5); ++i) st.prior_par[i] = prior_par[i];
     st.trace = out_trace ? w->d_trace : nullptr;
     st.d_sp = g->d_bsp; st.d_ism = g->d_bism; st.d_out = g->d_bout; st.d_fail = g->d_bfail; st.d_grad = w->d_out;
+    st.d_x2max = g->d_x2max;
     hipStream_t s = c->stream;
     ROBO_HIP_CHECK(hipMemcpyAsync(d_lower, lower, (size_t)P * sizeof(double), hipMemcpyHostToDevice, s));
     ROBO_HIP_CHECK(hipMemcpyAsync(d_upper, upper, (size_t)P * sizeof(double), hipMemcpyHostToDevice, s));
     ROBO_HIP_CHECK(hipMemcpyAsync(st.x, starts, KP * sizeof(double), hipMemcpyHostToDevice, s));
     ROBO_HIP_CHECK(hipMemsetAsync(di, 0, (3 * (size_t)K + 1) * sizeof(int), s));
+    // (fb.gram_mixed stays set: the trial points are formed on the device, each carries its own FitSample::direct)
     const FitBuffers fb = batch_buffers(g, K, nullptr);     // the likelihood terms are consumed on the device
     const GradBatch gb = grad_buffers(g, K);
     for (int t = 0; t <= n_iters; ++t) {

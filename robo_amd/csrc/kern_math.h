@@ -17,7 +17,9 @@ namespace robo {
 template <class T>
 __device__ __forceinline__ T matern52_unit(T r2) {
     const T s = sqrt(T(5) * r2);
-    return (T(1) + s + T(5) * r2 / T(3)) * exp(-s);
+    const T e = exp(-s);
+    // (beyond the type's range -- fp32: scaled distances above 8e18 -- the polynomial is inf and the exponential 0: the entry is 0)
+    return e > T(0) ? (T(1) + s + T(5) * r2 / T(3)) * e : T(0);
 }
 
 // fp64 specialisation.  K1 (gram_kernel) is bound by fp64 VALU issue, not by HBM (r02i PMC: 111 VALU instructions per
@@ -89,13 +91,21 @@ constexpr double SQRT5 = 2.23606797749978969641;
 template <class T>
 __device__ __forceinline__ T matern52_1d(T df) {
     const T s = T(SQRT5) * fabs(df);
-    return (T(1) + s + s * s * T(1.0 / 3.0)) * exp_np(-s);
+    const T e = exp_np(-s);
+    return e > T(0) ? (T(1) + s + s * s * T(1.0 / 3.0)) * e : T(0);      // (s * s may be inf where e is 0)
 }
 template <class T>
 __device__ __forceinline__ void matern52_1d_split(T df, T& poly, T& expo) {
     const T s = T(SQRT5) * fabs(df);
     poly *= T(1) + s + s * s * T(1.0 / 3.0);
     expo += s;
+}
+// ... and the product closed (or folded) with the exponential of the summed exponents: 0 where that has underflowed, whatever
+// the polynomial product has grown to
+template <class T>
+__device__ __forceinline__ T matern52_split_close(T poly, T expo) {
+    const T e = exp_np(-expo);
+    return e > T(0) ? poly * e : T(0);
 }
 
 // KIND < 0: decided at run time from p.kind (cold paths); otherwise compiled in (the tiled

@@ -92,7 +92,7 @@ __device__ __forceinline__ bool mcmc_block_proposal(const McmcState& st, int sta
 }
 
 // the batch fit's per-sample inputs of proposal q (api_fit.hip theta_to_sample)
-__device__ __forceinline__ FitSample mcmc_fit_sample(const McmcState& st, const double* sq, bool ok) {
+__device__ __forceinline__ FitSample mcmc_fit_sample(const McmcState& st, const double* sq, const double* sism, bool ok) {
     const bool fab = st.kind == ROBO_KERNEL_FABOLAS;
     FitSample sp;
     sp.cov.kind = st.kind;
@@ -102,6 +102,7 @@ __device__ __forceinline__ FitSample mcmc_fit_sample(const McmcState& st, const 
     sp.cov.blr_b = fab ? exp(ok ? sq[st.D + 1] : 0.0) : 0.0;
     sp.noise = exp(ok ? sq[st.P - 1] : 0.0) + JITTER;
     sp.mean_c = st.mean_c;
+    sp.direct = gram_needs_direct(st.kind, sism, st.d_x2max, st.D);
     return sp;
 }
 

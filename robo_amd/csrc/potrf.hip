@@ -741,7 +741,7 @@ __global__ __launch_bounds__(256 * NG) void mcmc_block_step_kernel(McmcState st,
     double* sN = sJ + GD * GLD;
     static_assert(MAX_DIM + 8 + MAX_DIM + 2 + 3 * (2 * GD * GLD + 2 * GT) <= NBLK * BLK, "staging fits the W image");
     const bool ok = mcmc_block_proposal(st, start, first, h, it, w, sq, sism, sz, sflag);
-    const FitSample sp = mcmc_fit_sample(st, sq, ok);            // uniform, in every thread's registers
+    const FitSample sp = mcmc_fit_sample(st, sq, sism, ok);            // uniform, in every thread's registers
     const double z = *sz;
     double prior = 0.0;
     if (threadIdx.x == 0) {
@@ -755,7 +755,10 @@ __global__ __launch_bounds__(256 * NG) void mcmc_block_step_kernel(McmcState st,
         const int bi = grp == 0 ? 0 : 1, bj = grp == 2 ? 1 : 0;
         const int tx = tid & 15, ty = tid >> 4;
         double cov[4][4];
-        pair_cov_dot<KIND>(sp.cov, X, (long long)bi * GT, (long long)bj * GT, sI, sJ, sN, cov, sism, (long long)n, tid);
+        if (sp.direct)      // workgroup-uniform (gram_tile.h: which tile builds K for this theta)
+            pair_cov_direct<KIND>(sp.cov, X, (long long)bi * GT, (long long)bj * GT, sI, sJ, cov, sism, (long long)n, tid);
+        else
+            pair_cov_dot<KIND>(sp.cov, X, (long long)bi * GT, (long long)bj * GT, sI, sJ, sN, cov, sism, (long long)n, tid);
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
             const int gi = bi * GT + ty * 4 + a;
@@ -1776,7 +1779,7 @@ __global__ __launch_bounds__(256 * NG) void mcmc_block2_step_kernel(McmcState st
     double* sJ = sI + GD * GLD;
     double* sN = sJ + GD * GLD;
     const bool ok = mcmc_block_proposal(st, start, first, h, it, w, sq, sism, sz, sflag);
-    const FitSample sp = mcmc_fit_sample(st, sq, ok);
+    const FitSample sp = mcmc_fit_sample(st, sq, sism, ok);
     const double z = *sz;
     double prior = 0.0;
     if (threadIdx.x == 0) {
@@ -1796,7 +1799,10 @@ __global__ __launch_bounds__(256 * NG) void mcmc_block2_step_kernel(McmcState st
         tri_tile(t < 10 ? t : 9, bi, bj);
         const int tx = tid & 15, ty = tid >> 4;
         double cov[4][4];
-        pair_cov_dot<KIND>(sp.cov, X, (long long)bi * GT, (long long)bj * GT, sI, sJ, sN, cov, sism, (long long)n, tid);
+        if (sp.direct)      // workgroup-uniform (gram_tile.h: which tile builds K for this theta)
+            pair_cov_direct<KIND>(sp.cov, X, (long long)bi * GT, (long long)bj * GT, sI, sJ, cov, sism, (long long)n, tid);
+        else
+            pair_cov_dot<KIND>(sp.cov, X, (long long)bi * GT, (long long)bj * GT, sI, sJ, sN, cov, sism, (long long)n, tid);
         if (t < 10) {
 #pragma unroll
             for (int a = 0; a < 4; ++a) {

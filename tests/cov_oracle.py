@@ -1,0 +1,133 @@
+"""Extended-precision oracle of the covariance functions for tests/cov_checks.py.
+
+Scalars in mpmath (50 digits), matrices / Cholesky / substitution in np.longdouble (x87 80-bit: 64-bit significand).  The
+inputs are scaled in fp64 exactly as the device scales them -- x * ism_d with ism_d = exp(-0.5 ln m_d), one rounding --
+so that oracle and device differ only in what follows the scaling (robo_amd/csrc/gram.hip scale_inputs_kernel)."""
+import mpmath as mp
+import numpy as np
+
+L = np.longdouble
+JITTER = 1.25e-12           # robo_amd/csrc/common.h
+mp.mp.dps = 50
+
+
+def inv_sqrt_metric(ln_m):
+    return np.exp(-0.5 * np.asarray(ln_m, dtype=np.float64))
+
+
+def scale(X, ln_m, n_scaled=None):
+    """the device's scaled inputs (fp64); n_scaled: only the first columns carry a metric (Fabolas: all but the last)"""
+    X = np.asarray(X, dtype=np.float64)
+    ism = np.ones(X.shape[1])
+    ln_m = np.broadcast_to(np.asarray(ln_m, dtype=np.float64), (X.shape[1] if n_scaled is None else n_scaled,))
+    ism[:ln_m.size] = inv_sqrt_metric(ln_m)
+    return X * ism[None, :]
+
+
+# ---- scalars (mpmath) ---------------------------------------------------------------------------------------------------
+def k_scalar(kind, r2):
+    """matern52 / rbf at the squared scaled distance r2 (an exact mpf), unit amplitude"""
+    r2 = mp.mpf(r2)
+    if kind == "matern52":
+        s = mp.sqrt(5 * r2)
+        return (1 + s + 5 * r2 / 3) * mp.exp(-s)
+    if kind == "rbf":
+        return mp.exp(-r2 / 2)
+    raise ValueError(kind)
+
+
+def k_argument(kind, r2):
+    """|argument of the exponential| at r2: what an error of the argument is amplified by"""
+    r2 = np.asarray(r2, dtype=np.float64)
+    with np.errstate(over="ignore"):
+        return np.sqrt(5.0 * r2) if kind in ("matern52", "fabolas") else 0.5 * r2
+
+
+def scalar_column(kind, x):
+    """k(x_i, 0) for scalars x (exact doubles) -> (float64 nearest values, mpf list); fabolas: the one-dimensional factor"""
+    vals = [k_scalar("matern52" if kind == "fabolas" else kind, mp.mpf(float(v)) ** 2) for v in x]
+    return np.array([float(v) for v in vals]), vals
+
+
+# ---- matrices (long double) -----------------------------------------------------------------------------------------------
+def _matern_unit(r2):
+    T = r2.dtype.type
+    s = np.sqrt(T(5) * r2)
+    return (T(1) + s + T(5) * r2 / T(3)) * np.exp(-s)
+
+
+def kernel(kind, amp, A, B=None, blr=(1.0, 1.0), dtype=L):
+    """k(A, B) on ALREADY SCALED rows by direct differences in `dtype` (np.longdouble: the oracle; np.float64: the fp64
+    direct-difference model whose own deviation from the oracle the tolerances of check_feeds are built on).
+    fabolas: the last column is the unscaled fidelity coordinate; blr = (a, b)."""
+    A = np.asarray(A).astype(dtype)
+    B = A if B is None else np.asarray(B).astype(dtype)
+    T = np.dtype(dtype).type
+    if kind == "fabolas":
+        prod = np.ones((A.shape[0], B.shape[0]), dtype=dtype)
+        for d in range(A.shape[1] - 1):
+            diff = A[:, d][:, None] - B[:, d][None, :]
+            prod *= _matern_unit(diff * diff)
+        uu = A[:, -1][:, None] * B[:, -1][None, :]
+        return T(amp) * prod * (T(blr[0]) + T(blr[1]) * uu)
+    r2 = np.zeros((A.shape[0], B.shape[0]), dtype=dtype)
+    for d in range(A.shape[1]):
+        diff = A[:, d][:, None] - B[:, d][None, :]
+        r2 += diff * diff
+    if kind == "matern52":
+        return T(amp) * _matern_unit(r2)
+    if kind == "rbf":
+        return T(amp) * np.exp(T(-0.5) * r2)
+    raise ValueError(kind)
+
+
+def cholesky(K):
+    """lower Cholesky factor in K's own precision (row-oriented, vectorised over the finished columns)"""
+    K = np.array(K)
+    n = K.shape[0]
+    Lf = np.zeros_like(K)
+    for j in range(n):
+        d = K[j, j] - Lf[j, :j] @ Lf[j, :j]
+        if not d > 0:
+            raise np.linalg.LinAlgError("not positive definite at column %d" % j)
+        Lf[j, j] = np.sqrt(d)
+        if j + 1 < n:
+            Lf[j + 1:, j] = (K[j + 1:, j] - Lf[j + 1:, :j] @ Lf[j, :j]) / Lf[j, j]
+    return Lf
+
+
+def solve_lower(Lf, B):
+    """L^-1 B by forward substitution in L's precision"""
+    B = np.array(B, dtype=Lf.dtype)
+    X = np.zeros_like(B)
+    for i in range(Lf.shape[0]):
+        X[i] = (B[i] - Lf[i, :i] @ X[:i]) / Lf[i, i]
+    return X
+
+
+class Posterior(object):
+    """fit + predict of one theta in one precision, from the scaled rows"""
+
+    def __init__(self, kind, amp, noise, Xs, y, mean, blr=(1.0, 1.0), dtype=L):
+        T = np.dtype(dtype).type
+        self.kind, self.amp, self.blr, self.dtype, self.Xs, self.mean = kind, amp, blr, dtype, Xs, mean
+        K = kernel(kind, amp, Xs, blr=blr, dtype=dtype)
+        K[np.diag_indices_from(K)] += T(noise) + T(JITTER)
+        self.K = K
+        self.Lf = cholesky(K)
+        self.z = solve_lower(self.Lf, (np.asarray(y, dtype=np.float64) - mean).astype(dtype))
+        n = K.shape[0]
+        self.loglik = -T(0.5) * (self.z @ self.z + T(2) * np.sum(np.log(np.diag(self.Lf))) + T(n) * np.log(T(2) * T(np.pi)))
+
+    def predict(self, Xcs):
+        """(mean, variance) at scaled candidate rows; the variance is NOT floored"""
+        Ks = kernel(self.kind, self.amp, Xcs, self.Xs, blr=self.blr, dtype=self.dtype)
+        V = solve_lower(self.Lf, Ks.T)
+        mu = V.T @ self.z + np.dtype(self.dtype).type(self.mean)
+        T = np.dtype(self.dtype).type
+        if self.kind == "fabolas":
+            u = np.asarray(Xcs)[:, -1].astype(self.dtype)
+            self_k = T(self.amp) * (T(self.blr[0]) + T(self.blr[1]) * u * u)
+        else:
+            self_k = np.full(Ks.shape[0], T(self.amp))
+        return mu, self_k - np.sum(V * V, axis=0)
