@@ -450,6 +450,54 @@ int32_t robo_mes_sample_min_moments(robo_ctx* ctx, const double* mean, const dou
 int32_t robo_mes_eval_moments(robo_ctx* ctx, const double* mean, const double* var, int64_t m, const double* ystar,
                               int32_t K, double* out_acq, double* out_max, int64_t* out_argmax, uint32_t* out_flags);
 
+/* ---- knowledge gradient over a discretisation (Frazier, Powell & Dayanik 2009; no counterpart in the reference), for
+ * minimisation: how much the MINIMUM OF THE POSTERIOR MEAN is expected to drop after one more noisy observation at x.
+ * The discretisation A = {z_0 .. z_{nb-1}} is a candidate handle `rep` in the model's normalised input space,
+ * 1 <= nb <= 64: the representer handle of robo_ig_eval_cand, its solve cached across calls in the same way (while the
+ * factor and the points stay the same).  For a candidate x:
+ *   a_j     = mu(z_j), the transformed posterior mean of the discretisation (what robo_gp_predict_cand returns for rep),
+ *             computed on the device by the call
+ *   v       = var(x), the sweep's transformed variance, floored at DBL_EPSILON as it stands
+ *   s_j     = y_std^2 (k(x, z_j) - v_x . v_zj), the posterior covariance, SIGNED and not floored (robo_gp_cross_cov clips
+ *             at DBL_EPSILON because the reference does; the knowledge gradient needs the sign)
+ *   sigma~  = sqrt(v + sn2), sn2 >= 0 in the scale of the returned variances, as robo_ig_eval_cand takes it
+ *   b_j     = s_j / sigma~, the slopes;  include_self != 0: one more line for x itself, a_nb = mu(x), b_nb = v / sigma~,
+ *             n = nb + 1 <= 65 lines, otherwise n = nb
+ *   KG(x)   = min_j a_j - E_Z[ min_j (a_j + b_j Z) ],  Z ~ N(0, 1),  KG(x) >= 0.
+ * Evaluated in the envelope form, in which every term is non-negative (the direct form sum_j a_j (Phi(hi_j) - Phi(lo_j))
+ * + ... subtracts numbers of size |a| to obtain a result that may be 1e-12 |a|; it is not used):
+ *   1. A_j = -a_j, B_j = -b_j.
+ *   2. The lines are ordered by (B ascending, A descending, index ascending).
+ *   3. Of lines with equal B only the first is kept.
+ *   4. Upper-envelope stack scan: for the next line i and the stack top t, c = (A_t - A_i) / (B_i - B_t); while c <= the
+ *      breakpoint stored with t, t is popped; then i is pushed with breakpoint c.  The bottom line's breakpoint is -inf.
+ *   5. KG = sum_k (B_k - B_{k-1}) f(-|c_k|) over consecutive survivors, in ascending k, with
+ *      f(-t) = phi(t) (1 - t sqrt(pi/2) erfcx(t / sqrt 2)).  A term with |c_k| > 36 counts as exactly 0 (its true size is
+ *      below 1e-283 (B_k - B_{k-1}); phi is subnormal from about 37.6).  A term's own conditioning is eps (t^2 + 1).
+ * A NaN among v, mu(x), any s_j or any a_j: KG = NaN and ROBO_FLAG_NAN.  A single surviving line: exactly 0.0.  Every sum
+ * and the sort have a fixed order: two calls on the same inputs, and the same candidate at any batch position, give the
+ * same bits.  argmax follows np.argmax (first index, NaN maximal) through the sweep's own reduction.
+ * out_kg (m) and out_disc_mean (nb: the a_j) are nullable; out_trace, nullable, m x (nb + 2): per candidate
+ * s_0 .. s_{nb-1}, v, mu(x) as the kernel read them -- the inputs from which an oracle can recompute the value.
+ * nb outside 1 .. 64, sn2 < 0 or NaN, a NULL required pointer, a GP with fp32 covariance entries: ROBO_BAD_ARGUMENT; a GP
+ * that is not fitted: ROBO_NOT_FITTED; cand and rep on different contexts or of different dim: ROBO_BAD_SHAPE.
+ * One synchronisation per call.  Event slots 30 and 31 bracket the envelope kernel of the last sample, under the
+ * condition of slots 24..27.                                                                                        */
+int32_t robo_kg_eval_cand(robo_gp* gp, robo_cand* cand, robo_cand* rep, double sn2, int32_t include_self, double* out_kg,
+                          double* out_max, int64_t* out_argmax, uint32_t* out_flags, double* out_disc_mean,
+                          double* out_trace);
+/* the mean over S fitted GPs: sample s is taken against gps[s] and sn2s[s] with the shared rep, re-solved per sample;
+ * KG = (sum_s KG_s) / S accumulated in sample order, as robo_acq_eval_marginal_cand.  out_disc_mean S x nb, out_trace
+ * S x m x (nb + 2).  S = 1 equals the single form bit for bit.                                                      */
+int32_t robo_kg_eval_marginal_cand(robo_gp* const* gps, int32_t S, robo_cand* cand, robo_cand* rep, const double* sn2s,
+                                   int32_t include_self, double* out_kg, double* out_max, int64_t* out_argmax,
+                                   uint32_t* out_flags, double* out_disc_mean, double* out_trace);
+/* the envelope kernel alone for any model's moments (as robo_ig_eval_moments): s (m, nb) signed covariances, v (m),
+ * mean (m), disc_mean (nb).  Equals the fused call bit for bit when fed the fused call's own trace.                  */
+int32_t robo_kg_eval_moments(robo_ctx* ctx, int64_t m, int32_t nb, double sn2, int32_t include_self, const double* s,
+                             const double* v, const double* mean, const double* disc_mean, double* out_kg,
+                             double* out_max, int64_t* out_argmax, uint32_t* out_flags);
+
 /* ---- entropy search: replaces InformationGain.innovations/_dh_fun/compute ---------------
  * (robo/acquisition_functions/information_gain.py:87-125,169-203,253-272), batched over candidates.
  * rep: the Nb <= 64 representer points as a candidate batch (same normalised space).  The EP

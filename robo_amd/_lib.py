@@ -28,6 +28,7 @@ ACQ_KINDS = {"ei": 0, "log_ei": 1, "pi": 2, "lcb": 3}
 FLAG_ZERO_SIGMA, FLAG_NEGATIVE_EI, FLAG_NAN, FLAG_NOT_FACTORED, FLAG_FROZEN = 1, 2, 4, 8, 16
 FANTASY_KINDS = {"kriging_believer": 0, "constant_liar": 1}   # robo_acq_batch_*: how a pick's fantasy target is chosen
 MES_MAX_K = 128                                  # robo_mes_*: cap on the sampled minima per model
+KG_MAX_DISC = 64                                 # robo_kg_*: cap on the discretisation points of the knowledge gradient
 REFINE_MAX_STARTS = 1024                         # robo_acq_refine_*: cap on n_starts
 MC_MAX_NB, MC_MAX_NP, MC_MAX_NF = 64, 512, 65535   # limits of the Monte-Carlo p_min entry points (robo_pmin_mc, robo_igmc_*)
 
@@ -49,6 +50,7 @@ SYMBOLS = [
     "robo_rep_sample", "robo_rep_sample_batch",
     "robo_acq_batch_cand", "robo_acq_batch_marginal_cand",
     "robo_mes_eval_cand", "robo_mes_eval_marginal_cand", "robo_mes_sample_min_moments", "robo_mes_eval_moments",
+    "robo_kg_eval_cand", "robo_kg_eval_marginal_cand", "robo_kg_eval_moments",
     "robo_ig_eval_cand", "robo_ig_eval_per_cost_cand", "robo_ig_eval_moments", "robo_gp_cross_cov",
     "robo_ep_joint_min", "robo_pmin_mc", "robo_igmc_eval_cand", "robo_igmc_eval_moments",
     "robo_comm_create_id", "robo_comm_init", "robo_comm_destroy", "robo_comm_info", "robo_comm_allgather",
@@ -226,6 +228,10 @@ def lib():
                                         _dp, _dp, _dp],
         "robo_mes_sample_min_moments": [vp, _dp, _dp, i64, _dp, i32, i32, dbl, _dp, _dp],
         "robo_mes_eval_moments": [vp, _dp, _dp, i64, _dp, i32, _dp, _dp, C.POINTER(i64), C.POINTER(C.c_uint32)],
+        "robo_kg_eval_cand": [vp, vp, vp, dbl, i32, _dp, _dp, C.POINTER(i64), C.POINTER(C.c_uint32), _dp, _dp],
+        "robo_kg_eval_marginal_cand": [pp, i32, vp, vp, _dp, i32, _dp, _dp, C.POINTER(i64), C.POINTER(C.c_uint32), _dp, _dp],
+        "robo_kg_eval_moments": [vp, i64, i32, dbl, i32, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(i64),
+                                 C.POINTER(C.c_uint32)],
         "robo_ig_eval_cand": [vp, vp, vp, i32, dbl, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(i64)],
         "robo_ig_eval_per_cost_cand": [vp, vp, vp, i32, dbl, _dp, _dp, _dp, _dp, _dp, _dp, vp, vp, dbl, _dp, _dp,
                                        C.POINTER(i64)],
@@ -869,6 +875,12 @@ class DeviceGP(object):
         return mes_marginal([self], eta, cand, u, clamp, want_values, diagnostics, marginal=False)
 
 
+    def kg(self, cand, rep, sn2, include_self=True, want_values=True, diagnostics=False):
+        """knowledge gradient of ``cand`` over the discretisation ``rep`` (robo_kg_eval_cand) -> KGResult; see
+        :func:`kg_marginal`"""
+        return kg_marginal([self], cand, rep, sn2, include_self, want_values, diagnostics, marginal=False)
+
+
 class HyperOptResult(object):
     """robo_gp_optimize_hypers: theta / value / best of the winning start (best -1, NaN: every start was dead); per start
     final (n_starts, P), values, status (0 ran out of iterations, 1 converged, 2 stalled or no direction, 3 dead);
@@ -933,6 +945,51 @@ def mes_from_moments(ctx, mean, var, ystar):
     best = _Best()
     check(lib().robo_mes_eval_moments(ctx._h, _arr(mean), _arr(var), mean.shape[0], _arr(ystar), ystar.shape[0], _arr(out),
                                       *best.refs))
+    return (out,) + best.values()
+
+
+class KGResult(object):
+    """values (m,) or None, max, argmax, flags, disc_mean (nb,) the posterior mean of the discretisation ((S, nb) in the
+    marginal form); with diagnostics: trace (m, nb + 2) / (S, m, nb + 2) = per candidate s_0 .. s_{nb-1}, v, mu(x) as the
+    kernel read them (include/robo_hip.h)"""
+
+    def __init__(self, values, max, argmax, flags, disc_mean, trace=None):
+        self.values, self.max, self.argmax, self.flags = values, float(max), int(argmax), int(flags)
+        self.disc_mean, self.trace = disc_mean, trace
+
+
+def kg_marginal(gps, cand, rep, sn2s, include_self=True, want_values=True, diagnostics=False, marginal=True):
+    """knowledge gradient over device GPs (one: robo_kg_eval_cand; the mean over several hyper-parameter samples, each
+    against its own posterior of the shared discretisation ``rep``: robo_kg_eval_marginal_cand).  sn2s: one noise variance
+    (in the scale of the returned variances), or one per sample."""
+    S = len(gps)
+    sn2s = _etas(sn2s, S)
+    nb = rep.m
+    ok = 1 <= nb <= KG_MAX_DISC
+    shape = (S,) if marginal else ()
+    out = np.empty(cand.m) if want_values else None
+    disc = np.full(shape + (max(nb, 1),), np.nan)
+    trace = np.empty(shape + (cand.m, nb + 2)) if (diagnostics and ok) else None
+    best = _Best()
+    tail = (int(bool(include_self)), _arr(out) if want_values else None) + best.refs + \
+        (_arr(disc), _arr(trace) if trace is not None else None)
+    if marginal:
+        check(lib().robo_kg_eval_marginal_cand(_handles(gps), S, cand._h, rep._h, _arr(sn2s), *tail))
+    else:
+        check(lib().robo_kg_eval_cand(gps[0]._h, cand._h, rep._h, float(sn2s[0]), *tail))
+    return KGResult(out, *best.values(), disc, trace)
+
+
+def kg_from_moments(ctx, s, v, mean, disc_mean, sn2, include_self=True):
+    """the envelope kernel alone on the device for the moments of any model (robo_kg_eval_moments): s (m, nb) signed
+    posterior covariances between the candidates and the discretisation, v (m,), mean (m,), disc_mean (nb,)
+    -> (values, max, argmax, flags)"""
+    s, v, mean, disc_mean = _f64(s), _f64(v), _f64(mean), _f64(disc_mean)
+    assert s.ndim == 2 and v.shape == (s.shape[0],) and mean.shape == v.shape and disc_mean.shape == (s.shape[1],)
+    out = np.empty(s.shape[0])
+    best = _Best()
+    check(lib().robo_kg_eval_moments(ctx._h, s.shape[0], s.shape[1], float(sn2), int(bool(include_self)), _arr(s), _arr(v),
+                                     _arr(mean), _arr(disc_mean), _arr(out), *best.refs))
     return (out,) + best.values()
 
 

@@ -41,6 +41,7 @@ class MarginalizationGPMCMC(BaseAcquisitionFunction):
         # evaluates only ITS hyper-parameter samples on all candidates; the per-rank partial sums are exchanged
         # and added in rank order (robo_amd.sharding.allgather_ordered_sum)
         self.sample_shard = False
+        self._kg_rep = None         # knowledge gradient: the shared discretisation as a device handle, per update()
 
     def _build_estimators(self):
         for i in range(len(self.model.models)):
@@ -58,6 +59,7 @@ class MarginalizationGPMCMC(BaseAcquisitionFunction):
 
     def update(self, model, cost_model=None, **kwargs):
         self.model = model
+        self._kg_drop()
         if cost_model is not None:
             self.cost_model = cost_model
         if len(self.estimators) != len(self.model.models):
@@ -361,7 +363,66 @@ class MarginalizationGPMCMC(BaseAcquisitionFunction):
         self.last_ystar = np.array([e._ystar for e in est])
         return vals
 
+    # ---- knowledge gradient: one discretisation for all hyper-parameter samples, re-solved per sample ------------------------
+    def _is_kg(self):
+        from robo_amd.acquisition_functions.knowledge_gradient import KnowledgeGradient
+        return isinstance(self.acquisition_func, KnowledgeGradient)
+
+    def _kg_drop(self):
+        if getattr(self, "_kg_rep", None) is not None:
+            self._kg_rep.close()
+        self._kg_rep = None
+
+    def _kg_native(self):
+        """all sub-models are trained device GPs on one context -> the marginal entry point (robo_kg_eval_marginal_cand)"""
+        from robo_amd.acquisition_functions.knowledge_gradient import kg_refuse_sharded
+        kg_refuse_sharded(self.model, "MarginalizationGPMCMC(KnowledgeGradient)")
+        if self.sample_shard:
+            raise NotImplementedError("MarginalizationGPMCMC(KnowledgeGradient) has no sample shard: multi-device and "
+                                      "sharded forms of the knowledge gradient are not implemented")
+        if not self.estimators:
+            return False
+        for e in self.estimators:
+            kg_refuse_sharded(e.model, "MarginalizationGPMCMC(KnowledgeGradient)")
+            if not (hasattr(e.model, "acquisition") and hasattr(e.model, "gp")) or hasattr(e.model, "normalize") \
+                    or not getattr(e.model, "is_trained", False):
+                return False
+            e.model._materialise()
+        gps = [e.model.gp for e in self.estimators]
+        return all(isinstance(g, _lib.DeviceGP) for g in gps) and len({id(g.ctx) for g in gps}) == 1
+
+    def _kg_marginal(self, X, want_values, diagnostics=False):
+        """the fused marginal call; the discretisation comes from the first sample's model (as _mes_compute takes its
+        grid) and is shared by every estimator for this update()"""
+        from robo_amd.acquisition_functions.knowledge_gradient import kg_discretisation
+        f, est = self.acquisition_func, self.estimators
+        gps = [e.model.gp for e in est]
+        if self._kg_rep is None:
+            Z = est[0]._disc
+            if Z is None:
+                Z = kg_discretisation(est[0].model, f.rng, f.n_disc, f.n_grid, f.discretisation)
+            for e in est:
+                e._disc = Z
+                e._drop_rep()
+            self._kg_rep = _lib.Candidates(gps[0].ctx, est[0].model._normalised(Z))
+        sn2s = np.array([e._sn2() for e in est])
+        cand = X if isinstance(X, _lib.Candidates) else _lib.Candidates(gps[0].ctx, est[0].model._normalised(np.asarray(X)))
+        try:
+            res = _lib.kg_marginal(gps, cand, self._kg_rep, sn2s, f.include_self, want_values, diagnostics)
+        finally:
+            if cand is not X:
+                cand.close()
+        self.last_max, self.last_argmax = res.max, res.argmax
+        return res
+
     def compute(self, X_test, derivative=False):
+        if self._is_kg():
+            if derivative:
+                raise NotImplementedError("KnowledgeGradient has no derivative")
+            if self._kg_native():
+                if isinstance(X_test, _lib.Candidates):
+                    self.estimators[0]._host_points(X_test)        # the condition a device batch comes under
+                return self._kg_marginal(X_test, True).values
         if self._is_mes():
             if derivative:
                 raise NotImplementedError("MES has no derivative")
@@ -478,6 +539,8 @@ class MarginalizationGPMCMC(BaseAcquisitionFunction):
                 cand.close()
 
     def argmax(self, X_test):
+        if self._is_kg() and self._kg_native():
+            return int(self._kg_marginal(X_test, False).argmax)
         if self._is_mes() and self._mes_native():
             res = self._mes_marginal(X_test, False)
             self.last_max, self.last_argmax, self.last_ystar = res.max, res.argmax, res.ystar

@@ -345,6 +345,7 @@ int32_t robo_cand_destroy(robo_cand* k) {
     hipFree(k->d_Q);
     hipFree(k->d_G);
     hipFree(k->d_igc);
+    hipFree(k->d_kg);
     free(k->h_igkey);
     hipFree(k->d_Ks);
     hipFree(k->d_P);

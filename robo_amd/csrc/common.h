@@ -489,6 +489,8 @@ struct robo_cand {
     // features / outputs, EP tensors
     double *d_S, *d_F, *d_Q, *d_G, *d_igc;
     size_t f_cap, q_cap, g_cap;
+    double* d_kg;       // knowledge gradient (lazy, grows): [S x 64 discretisation means | S x m x (nb + 2) trace]
+    size_t kg_cap;
     double* h_igkey;    // host copy of the EP state whose device form d_G / d_igc hold (compared in full before an upload
     size_t igkey_len;   // is skipped: compute() is called many times per update(), information_gain.py:87-125 / :153-167)
     double* d_mu_all;   // (s_cap, m_pad) per-sample means/variances for the GP-MCMC mixture (lazy)
@@ -622,7 +624,12 @@ int launch_argmax(robo_cand* cand, const double* d_vals, double scale);
 int launch_report_best(robo_cand* cand, double* h_pinned);
 int launch_cov(robo_gp* gp, robo_cand* cand, double* d_cov);
 int launch_mixture(robo_cand* cand, int S);
-int launch_cross_cov(robo_gp* gp, robo_cand* cand, robo_cand* rep, int64_t c0, int64_t cn, double* d_S);
+// clip: floored at DBL_EPSILON as the reference's predict(full_cov=True) (entropy search); false: signed (kg.hip)
+int launch_cross_cov(robo_gp* gp, robo_cand* cand, robo_cand* rep, int64_t c0, int64_t cn, double* d_S, bool clip = true);
+// kg.hip: the knowledge gradient of candidates c < m from their signed covariance rows d_S (m x NB), d_var, d_mean and the
+// nb discretisation means; first: acq_sum[c] = KG, else acq_sum[c] += KG; d_trace (m x (nb + 2)) nullable
+int launch_kg(robo_ctx* ctx, const double* d_S, const double* d_var, const double* d_mean, const double* d_disc, int64_t m,
+              int nb, double sn2, int include_self, bool first, double* d_acq_sum, unsigned* d_flags, double* d_trace);
 int launch_ig_dh(robo_ctx* ctx, const double* d_S, const double* d_var, double* d_F, double* d_Q, const double* d_G,
                  const double* d_consts, int64_t c0, int64_t cn, int64_t m, int nb, int npts, int kf, double sn2,
                  double H, double* d_out);

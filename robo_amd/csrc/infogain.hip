@@ -28,7 +28,8 @@ constexpr int IG_Q2_OFF = 64;   // column offset of the q2 block in the 128-wide
 //  off-diagonals included, gaussian_process.py:290-294, and predict_variance reads it back)
 // TM: 32 TM candidates per workgroup -- a batch of 8192 is only 64 tiles of 128 (0.75 ms of a config-4 step with
 // three quarters of the chip idle, r03e); the k-order of every entry's products is the same, hence the same bits
-template <int TM>
+// CLIP = false: the signed covariance, not floored (the knowledge gradient's slopes need the sign, kg.hip)
+template <int TM, bool CLIP>
 __global__ __launch_bounds__(256) void cross_cov_kernel(const double* __restrict__ Vc, int ldv,
                                                         const double* __restrict__ Vr, int ldr, int kend,
                                                         const double* __restrict__ Xcs, long long c0,
@@ -52,7 +53,7 @@ __global__ __launch_bounds__(256) void cross_cov_kernel(const double* __restrict
                 if (b < nb) {
                     v = (cov_rows(cp, Xcs + (size_t)(c0 + a) * cp.dim, Xrs + (size_t)b * cp.dim) - acc.t[tm][tn][r]) *
                         (y_std * y_std);
-                    v = v < eps ? eps : v;
+                    if (CLIP) v = v < eps ? eps : v;
                 }
                 S[(size_t)(c0 + a) * NB + b] = v;
             }
@@ -178,14 +179,17 @@ __global__ __launch_bounds__(256) void ig_dh_kernel(const double* __restrict__ S
     }
 }
 
-int launch_cross_cov(robo_gp* gp, robo_cand* cand, robo_cand* rep, int64_t c0, int64_t cn, double* d_S) {
-#define ROBO_CC_CALL(TM)                                                                                         \
-    hipLaunchKernelGGL(cross_cov_kernel<TM>, dim3((unsigned)(cn / (32 * TM))), dim3(256), 0, gp->ctx->stream,  \
-                       (const double*)cand->d_V, gp->n_pad, (const double*)rep->d_V, gp->n_pad,                 \
-                       (gp->n + NB - 1) / NB * NB, (const double*)cand->d_Xcs, (long long)c0,                   \
+int launch_cross_cov(robo_gp* gp, robo_cand* cand, robo_cand* rep, int64_t c0, int64_t cn, double* d_S, bool clip) {
+#define ROBO_CC_CALL(TM, CLIP)                                                                                            \
+    hipLaunchKernelGGL((cross_cov_kernel<TM, CLIP>), dim3((unsigned)(cn / (32 * TM))), dim3(256), 0,                       \
+                       gp->ctx->stream, (const double*)cand->d_V, gp->n_pad, (const double*)rep->d_V, gp->n_pad,         \
+                       (gp->n + NB - 1) / NB * NB, (const double*)cand->d_Xcs, (long long)c0,                            \
                        (const double*)rep->d_Xcs, (int)rep->m, gp->cov, gp->y_std, d_S)
-    if (cn / NB >= 2 * gp->ctx->num_cu) ROBO_CC_CALL(4);
-    else ROBO_CC_CALL(1);
+    const bool wide = cn / NB >= 2 * gp->ctx->num_cu;
+    if (wide && clip) ROBO_CC_CALL(4, true);
+    else if (wide) ROBO_CC_CALL(4, false);
+    else if (clip) ROBO_CC_CALL(1, true);
+    else ROBO_CC_CALL(1, false);
 #undef ROBO_CC_CALL
     ROBO_LAUNCH_CHECK();
     return ROBO_OK;

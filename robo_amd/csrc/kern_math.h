@@ -176,6 +176,16 @@ __device__ __forceinline__ double norm_logcdf(double z) {
     return log1p(-0.5 * erfc(z * SQRT1_2));
 }
 
+// f(-t) = phi(t) - t Phi(-t) = E[(Z - t)^+] for t >= 0: one segment of the knowledge gradient's envelope sum (kg.hip).
+// erfcx form: the bracket tends to 1 / t^2, so the value carries its own conditioning eps (t^2 + 1) and no more (measured
+// against 60-digit arithmetic: 3.6 of those units on [0, 36]; the plain difference phi(t) - t Phi(-t) loses above 1000).
+// Beyond t = 36 the term counts as exactly 0 (phi is subnormal from about 37.6).  NaN stays NaN.
+constexpr double SQRT_PI_2 = 1.25331413731550025121;
+__device__ __forceinline__ double norm_tail_mean(double t) {
+    if (t > 36.0) return 0.0;
+    return norm_pdf(t) * (1.0 - t * SQRT_PI_2 * erfcx(t * SQRT1_2));
+}
+
 // robo/acquisition_functions/ei.py:70-78 (the batch-level guards are applied by the host shim
 // from the flags word)
 __device__ __forceinline__ double acq_ei(double m, double v, double eta, double par) {

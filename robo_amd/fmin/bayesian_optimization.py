@@ -7,6 +7,7 @@ without george, pybnn and pyrfr: :2,5,8,11), wired to the MI355X GP path:
     n_hypers 3 * len(kernel), made even                      (:85-87)
     model    GaussianProcess | GaussianProcessMCMC(chain_length=200, burnin_steps=100)  (:89-100)
     acq      EI | LogEI | PI | LCB, wrapped in MarginalizationGPMCMC for gp_mcmc       (:114-129)
+             | MES | KnowledgeGradient (not in the reference)
 
     maximiser RandomSampling | SciPyOptimizer | DifferentialEvolution                    (:131-139)
               | DeviceRandomSampling | DeviceGradientAscent (not in the reference)
@@ -18,7 +19,7 @@ import logging
 
 import numpy as np
 
-from robo_amd.acquisition_functions import EI, LCB, MES, PI, LogEI, MarginalizationGPMCMC
+from robo_amd.acquisition_functions import EI, LCB, MES, PI, KnowledgeGradient, LogEI, MarginalizationGPMCMC
 from robo_amd.initial_design import init_latin_hypercube_sampling
 from robo_amd.kernels import Matern52Kernel
 from robo_amd.maximizers import (DeviceGradientAscent, DeviceRandomSampling, DifferentialEvolution, RandomSampling,
@@ -78,7 +79,9 @@ def bayesian_optimization(objective_function, lower, upper, num_iterations=30, X
         raise ValueError("'{}' is not a valid model (robo_amd provides 'gp' and 'gp_mcmc')".format(model_type))
 
     # "mes": max-value entropy search; its draws (discretisation, uniforms) come from this call's rng
-    acq_classes = {"ei": EI, "log_ei": LogEI, "pi": PI, "lcb": LCB, "mes": lambda m: MES(m, rng=rng)}
+    # "kg": knowledge gradient over a discretisation drawn from this call's rng as well
+    acq_classes = {"ei": EI, "log_ei": LogEI, "pi": PI, "lcb": LCB, "mes": lambda m: MES(m, rng=rng),
+                   "kg": lambda m: KnowledgeGradient(m, rng=rng)}
     if acquisition_func not in acq_classes:
         raise ValueError("'{}' is not a valid acquisition function".format(acquisition_func))
     a = acq_classes[acquisition_func](model)
