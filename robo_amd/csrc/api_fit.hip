@@ -506,17 +506,13 @@ int32_t robo_gp_mcmc_run(robo_gp* g, double mean_c, int32_t prior_kind, const do
     fb.want_inverse = false;
     fb.skip_tail = c->tune.mcmc_fused_tail != 0 && g->n_pad > NB;     // (one-block factors reduce inside their diagonal kernel)
     fb.S = half;
-    // one-block problems: the whole half-step in one launch (potrf.hip mcmc_block_step_kernel; tuning: 0 never,
-    // 1 only below 64 points, 2 = default: every one-block problem)
+    // one-block problems: the whole half-step in one launch (mcmc_block.hip mcmc_block_step_kernel; tuning: 0 never,
+    // 1 only below 64 points, 2 or more = default: every one-block problem)
     const int bs = c->tune.mcmc_block_step;
     const bool one_block = (bs >= 2 ? g->n_pad == NB : (bs == 1 && g->n + 1 <= 64)) && !g->fp32_gram &&
                            g->kind != ROBO_KERNEL_FABOLAS;
-    // two-block problems (128 <= N <= 254): likewise one launch, block row 1 through the batch workspace -- tuning value 3,
-    // NOT the default: measured slower than the launch path (r06i: 122 vs 91 us per half-step at N = 200; potrf.hip)
-    const bool two_block = bs >= 3 && g->n_pad == 2 * NB && g->n >= NB && !g->fp32_gram && g->kind != ROBO_KERNEL_FABOLAS;
     auto half_step = [&](int start, int first, int h, int it) -> int {
         if (one_block) return launch_mcmc_block_step(g, st, start, first, h, it);
-        if (two_block) return launch_mcmc_block2_step(g, st, start, first, h, it, g->d_bK, np * np);
         ROBO_TRY(launch_mcmc_propose_scale(c, st, start, first, h, it, g->d_X, g->d_bXs, g->n, g->n_pad, np * D));
         ROBO_TRY(launch_potrf(g, fb, true));        // gram + factorisation
         if (fb.skip_tail) {                          // likelihood terms + accept test + chain record: one launch
@@ -590,7 +586,7 @@ int32_t robo_gp_fit_batch(robo_gp* const* gps, int32_t S, const double* thetas, 
     auto keep = [&](int s0, int ns, const int* status) -> int {
         const double* hout = reinterpret_cast<const double*>(reinterpret_cast<const FitSample*>(g0->h_bstage) + g0->b_cap) +
                              (size_t)g0->b_cap * D;      // the batch's [ns][5] result block (fit_batch_core)
-        // every kept factor goes to its handle in ONE launch (potrf.hip batch_keep_kernel)
+        // every kept factor goes to its handle in ONE launch (fit_keep.hip batch_keep_kernel)
         std::vector<KeepDst> dst((size_t)ns);
         for (int s = 0; s < ns; ++s) {
             KeepDst& d = dst[(size_t)s];

@@ -187,8 +187,8 @@ struct Tuning {
     int potrf_batch_roll;        // ... with the diagonal workgroup's 80-KB rolling layout (two workgroups per CU); 0: the 150-KB image
     int potrf_batch_follow;      // batched fits: diagonal block + panel of a step in one launch, the panel following (-1 = default: up to 17 panels; 0 / 1)
     int mcmc_fused_tail;         // device chain, multi-block factors: likelihood terms + accept test in one launch (1)
-    int mcmc_block_step;         // ensemble half-step in ONE launch: 2 (default) every one-block problem, 1 only N <= 63, 0 never;
-                                 // 3: two-block problems (N <= 254) too -- built in r06, measured SLOWER than the launch path
+    int mcmc_block_step;         // ensemble half-step in ONE launch: 2 (default) every one-block problem, 1 only N <= 63, 0 never
+                                 // (a larger value means 2: the two-block form that 3 selected was measured slower and removed)
 };
 void tuning_from_env(Tuning* t);
 }  // namespace robo
@@ -532,7 +532,7 @@ struct FitBuffers {
 };
 int launch_scale_inputs_theta(robo_ctx* ctx, const double* d_in, double* d_out, const ThetaArgs& ta, int64_t rows_real,
                               int64_t rows_pad, int dim, double* d_ism_out, FitSample* d_sp_out);
-// destination of one sample of a batched fit that keeps its factors (potrf.hip batch_keep_kernel)
+// destination of one sample of a batched fit that keeps its factors (fit_keep.hip batch_keep_kernel)
 struct KeepDst {
     double *K, *Linv, *LinvP, *Xs, *theta;
     double *X, *y;            // nullptr for gps[0] (owns the training data already)
@@ -564,7 +564,6 @@ int launch_mcmc_accept(robo_ctx* ctx, const McmcState& st, int start, int first,
 int launch_mcmc_tail(robo_ctx* ctx, const McmcState& st, int start, int first, int h, int it, const double* d_K, size_t k_stride,
                      int ld, int nbf, const int* d_fail);
 int launch_mcmc_block_step(robo_gp* gp, const McmcState& st, int start, int first, int h, int it);
-int launch_mcmc_block2_step(robo_gp* gp, const McmcState& st, int start, int first, int h, int it, double* d_K, size_t k_stride);
 // with_gram: the gram matrices are built here too, every sub-batch's on the stream its factorisation runs on
 int launch_potrf(robo_gp* gp, const FitBuffers& fb, bool with_gram = false);
 int launch_diag_timeline(robo_gp* gp, long long* d_stamps);

@@ -12,7 +12,7 @@
 // HBM traffic per launch: gram   8 * n_pad*(n_pad+64)/2 bytes written, 8*n*D read
 //                         cross  8 * rows*n_pad written, 8*(rows+n)*D read
 #include "common.h"
-#include "gram_tile.h"      // GT, GD, GLD, pair_cov_dot
+#include "gram_tile.h"      // GT, GD, GLD, pair_cov_dot, gram_aug_entry
 #include "kern_math.h"
 
 namespace robo {
@@ -208,20 +208,7 @@ __global__ __launch_bounds__(256, KIND == ROBO_KERNEL_FABOLAS ? 3 : 6) void gram
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
             const int gj = (int)j0 + (b < 2 ? c0 + b : c2 + b - 2);
-            double val;
-            if (gi < n && gj < n) {
-                val = cov[a][b];
-                if (gi == gj) val += noise;
-            } else if (gi == gj) {
-                val = 1.0;
-            } else if (gi == n && gj < n) {
-                val = y[gj] - mean_c;
-            } else if (gj == n && gi < n) {
-                val = y[gi] - mean_c;
-            } else {
-                val = 0.0;
-            }
-            v[b] = val;
+            v[b] = gram_aug_entry(gi, gj, n, cov[a][b], noise, y, mean_c);
         }
         double* row = K + (size_t)gi * n_pad + j0;
         *reinterpret_cast<double2*>(row + c0) = make_double2(v[0], v[1]);

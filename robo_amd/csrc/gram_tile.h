@@ -1,4 +1,4 @@
-// The 64 x 64 tile of the fp64 gram matrix (K1), shared by gram.hip and the fused ensemble step of small problems (potrf.hip).
+// The 64 x 64 tile of the fp64 gram matrix (K1), shared by gram.hip and the fused ensemble step of small problems (mcmc_block.hip).
 #pragma once
 #include "common.h"
 #include "kern_math.h"
@@ -23,6 +23,27 @@ __host__ __device__ constexpr int gram_col(int tx, int b) {
 #else
     return 4 * tx + b;
 #endif
+}
+
+// Entry (gi, gj) of the AUGMENTED gram matrix (DESIGN.md "augmented row"): the covariance plus the noise on the diagonal
+// among the n training points; row / column n is the right-hand side y - mean, so that one Cholesky also yields
+// z = L^-1 (y - mean) as row n of the factor; everything else is identity padding.  cov: k(x_gi, x_gj), read for gi, gj < n only.
+__device__ __forceinline__ double gram_aug_entry(int gi, int gj, int n, double cov, double noise, const double* __restrict__ y,
+                                                 double mean_c) {
+    double val;
+    if (gi < n && gj < n) {
+        val = cov;
+        if (gi == gj) val += noise;
+    } else if (gi == gj) {
+        val = 1.0;
+    } else if (gi == n && gj < n) {
+        val = y[gj] - mean_c;
+    } else if (gj == n && gi < n) {
+        val = y[gi] - mean_c;
+    } else {
+        val = 0.0;
+    }
+    return val;
 }
 
 // One 16-dimension pass of both row blocks of a tile into LDS, transposed to [d][row] (thread t of the tile's 256).

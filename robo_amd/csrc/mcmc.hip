@@ -15,12 +15,13 @@
 //                         log u, walker / log-probability / acceptance-count update, chain record after the second half
 // One-block problems (N <= 126, a Bayesian-optimisation run's own sizes) take all of that in ONE launch per half-step,
 // one workgroup per walker with the gram tiles written straight into the factorisation's LDS image
-// (potrf.hip: mcmc_block_step_kernel; same decisions, likelihoods within an ulp of this file's form).
+// (mcmc_block.hip: mcmc_block_step_kernel; same decisions, likelihoods within an ulp of this file's form).
 // The random numbers do not depend on the chain, so the caller draws them up front in emcee 2's order (per half-step:
 // rand for z, randint for the partners, rand for the accept test) -- same stream, same chain as the reference's sampler
 // up to the rounding of exp / log on the device.  z and q are formed by the rn_* operations of common.h: the compiler
 // may not contract them into fused multiply-adds (numpy has none; round 5's q was a v_fma_f64, tests/test_isa.py).
 #include "common.h"
+#include "loglik_dev.h"
 #include "mcmc_dev.h"
 
 namespace robo {
@@ -99,9 +100,10 @@ __global__ __launch_bounds__(256) void mcmc_accept_kernel(McmcState st, int star
 }
 
 // Tail of a multi-block ensemble half-step in ONE launch, one workgroup per walker (r06): the likelihood terms of the
-// factorisation's tail -- potrf_inverse_kernel's per-block shares added block by block as loglik_finish_kernel adds them, the
-// same operations in the same order, hence the same bits -- and then mcmc_accept_kernel's test, walker update and chain record
-// for THIS walker.  Three launches (shares, finish, accept: ~14 us of an 83-us half-step at N = 200) become one.
+// factorisation's tail -- potrf_inverse_kernel's per-block shares (loglik_dev.h) added block by block as loglik_finish_kernel
+// adds them, the same operations in the same order, hence the same bits -- and then mcmc_accept_kernel's test, walker update
+// and chain record for THIS walker (mcmc_dev.h: mcmc_accept_walker).  Three launches (shares, finish, accept: ~14 us of
+// an 83-us half-step at N = 200) become one.
 __global__ __launch_bounds__(256) void mcmc_tail_kernel(McmcState st, int start, int first, int h, int it,
                                                         const double* __restrict__ K, size_t k_stride, int ld, int nbf,
                                                         const int* __restrict__ fail) {
@@ -112,46 +114,21 @@ __global__ __launch_bounds__(256) void mcmc_tail_kernel(McmcState st, int start,
     double sq = 0.0, sl = 0.0;
     for (int kb = 0; kb < nbf; ++kb) {
         const int r = kb * NB + tid;
-        double q = 0.0, lg = 0.0;
-        if (tid < NB && r < n) {
-            const double zi = Ks[(size_t)n * ld + r];
-            q = zi * zi;
-            lg = log(Ks[(size_t)r * ld + r]);
+        const bool valid = tid < NB && r < n;
+        double zi = 0.0, d = 0.0;
+        if (valid) {
+            zi = Ks[(size_t)n * ld + r];
+            d = Ks[(size_t)r * ld + r];
         }
-        for (int o = 32; o > 0; o >>= 1) {
-            q += __shfl_xor(q, o);
-            lg += __shfl_xor(lg, o);
-        }
-        if ((tid & 63) == 0 && tid < NB) {
-            red[tid >> 6] = q;
-            red[2 + (tid >> 6)] = lg;
-        }
-        __syncthreads();
-        sq += red[0] + red[1];
-        sl += red[2] + red[3];
+        const LlShare s = block_ll_share<false, false>(tid, valid, zi, d, red);
+        sq += s.quad;
+        sl += s.logdiag;
         __syncthreads();
     }
     const int half = st.k / 2, sw = start ? first + w : h * half + w;
     if (tid == 0) {
         const int f = fail[w];
-        const double lp = mcmc_lnprob(st.d_prior[w], f, sq, 2.0 * sl, n);
-        if (lp != lp) atomicOr(st.d_err, 1);       // emcee: "lnprob returned NaN."
-        if (f < 0) atomicOr(st.d_err, 4);          // a panel follower's hand-off timed out (potrf.hip)
-        int acc = 0;
-        if (start) {
-            if (lp == __builtin_huge_val()) atomicOr(st.d_err, 2);   // "The initial lnprob was +inf."
-            st.d_lnp[sw] = lp;
-        } else {
-            const size_t r = ((size_t)it * 2 + h) * half + w;
-            const double lnpdiff = mcmc_lnpdiff(P, log(st.d_z[w]), lp, st.d_lnp[sw]);
-            if (lnpdiff > log(st.d_ua[r])) {
-                acc = 1;
-                st.d_lnp[sw] = lp;
-                st.d_nacc[sw] += 1;
-            }
-            if (st.d_lnprob) st.d_lnprob[(size_t)sw * st.n_steps + it] = st.d_lnp[sw];
-        }
-        sacc = acc;
+        sacc = mcmc_accept_walker(st, start, h, it, w, sw, st.d_prior[w], f, f < 0, sq, 2.0 * sl, st.d_z + w);
     }
     __syncthreads();
     if (start) return;

@@ -1,4 +1,4 @@
-// Device-side pieces of the hyper-parameter chain shared by mcmc.hip and the fused one-block step (potrf.hip).
+// Device-side pieces of the hyper-parameter chain shared by mcmc.hip and the fused one-block step (mcmc_block.hip).
 #pragma once
 #include "common.h"
 
@@ -119,6 +119,34 @@ __device__ __forceinline__ double mcmc_lnprob(double prior, int fail, double qua
 // emcee 2's accept statistic  lnpdiff = (ndim - 1) log z + lnp(q) - lnp(s)  in its order of operations, unfused
 __device__ __forceinline__ double mcmc_lnpdiff(int P, double log_z, double lp_new, double lp_old) {
     return rn_sub(rn_add(rn_mul((double)P - 1.0, log_z), lp_new), lp_old);
+}
+
+// The accept decision and chain record of ONE walker, by one thread of the walker's workgroup (the per-walker kernels:
+// mcmc_block_step_kernel, mcmc_tail_kernel): lnp(q) from the prior term and the fit's (z.z, log det, failure flag), the
+// error bits for a NaN and a +inf start (and a timed-out follower hand-off), emcee's accept test lnpdiff > log u, and the
+// walker's log-probability, acceptance count and log-probability record.  w: walker within the half (index of its random
+// numbers), sw: its index in the ensemble.  *z is read only when a move is tested.  Returns whether the move was accepted
+// (0 at the start evaluation); the caller moves the walker and records its position.
+__device__ __forceinline__ int mcmc_accept_walker(const McmcState& st, int start, int h, int it, int w, int sw, double prior,
+                                                  int fail, bool timed_out, double quad, double logdet, const double* z) {
+    const double lp = mcmc_lnprob(prior, fail, quad, logdet, st.n);
+    if (lp != lp) atomicOr(st.d_err, 1);       // emcee: "lnprob returned NaN."
+    if (timed_out) atomicOr(st.d_err, 4);      // a panel follower's hand-off timed out (potrf.hip): not a rejection
+    int acc = 0;
+    if (start) {
+        if (lp == __builtin_huge_val()) atomicOr(st.d_err, 2);   // "The initial lnprob was +inf."
+        st.d_lnp[sw] = lp;
+    } else {
+        const size_t r = ((size_t)it * 2 + h) * (st.k / 2) + w;
+        const double lnpdiff = mcmc_lnpdiff(st.P, log(*z), lp, st.d_lnp[sw]);
+        if (lnpdiff > log(st.d_ua[r])) {
+            acc = 1;
+            st.d_lnp[sw] = lp;
+            st.d_nacc[sw] += 1;
+        }
+        if (st.d_lnprob) st.d_lnprob[(size_t)sw * st.n_steps + it] = st.d_lnp[sw];
+    }
+    return acc;
 }
 
 }  // namespace robo

@@ -70,6 +70,10 @@ def test_device_resident_chain(emu_ctx):
     P.check_device_chain(emu_ctx, cases=(("matern52", 150, 3, 10, 4), ("rbf", 40, 2, 8, 5),
                                                ("fabolas", 50, 3, 12, 4), ("fabolas", 60, 3, 12, 3, "env"),
                                                ("fabolas", 150, 4, 14, 2, "env")))
+    # the one-launch half-step at the tile-group boundary and the last one-block size; the fused tail where the augmented
+    # row is alone in (128) or first in (129) its block
+    P.check_device_chain(emu_ctx, cases=(("matern52", 63, 3, 10, 2), ("rbf", 64, 3, 10, 2), ("matern52", 126, 3, 10, 2),
+                                         ("rbf", 128, 3, 10, 2), ("matern52", 129, 3, 10, 2)), model_classes=False)
 
 
 def test_elementwise_and_degenerate_branches(emu_ctx):
@@ -99,6 +103,8 @@ def test_fit_batch_keeps_factors(emu_ctx):
 
 def test_batched_likelihoods(emu_ctx):
     P.check_batched_likelihoods(emu_ctx)
+    # one-block sizes at the 16-row sub-block, 64-row tile-group and block boundaries (bit for bit here)
+    P.check_batched_likelihoods(emu_ctx, sizes=tuple((N, 3) for N in (15, 16, 17, 63, 64, 126, 127)))
 
 
 def test_batched_split_streams(emu_ctx):

@@ -159,6 +159,9 @@ def test_fit_batch_keeps_factors(ctx):
 
 def test_batched_likelihoods(ctx):
     P.check_batched_likelihoods(ctx, sizes=((60, 3), (300, 4), (1500, 8)))
+    # one-block sizes at the 16-row sub-block, 64-row tile-group and block boundaries: the likelihood that leaves the
+    # diagonal kernel (loglik_batch) == the one of the factorisation's tail (fit), the same 128-row share either way
+    P.check_batched_likelihoods(ctx, sizes=tuple((N, 3) for N in (15, 16, 17, 63, 64, 126, 127)))
 
 
 def test_batched_fit_multiple_of_128(ctx):
@@ -579,6 +582,10 @@ def test_host_array_handle_reuse(ctx):
 def test_device_resident_chain(ctx):
     P.check_device_chain(ctx)
     P.check_device_chain(ctx, cases=(("matern52", 300, 16, 36, 20),))
+    # the one-launch half-step at the tile-group boundary and the last one-block size; the fused tail where the augmented
+    # row is alone in (128) or first in (129) its block
+    P.check_device_chain(ctx, cases=(("matern52", 63, 3, 10, 3), ("rbf", 64, 3, 10, 3), ("matern52", 126, 3, 10, 3),
+                                     ("rbf", 128, 3, 10, 3), ("matern52", 129, 3, 10, 3)), model_classes=False)
 
 
 def test_device_chain_fused_batches_beyond_residency(ctx):

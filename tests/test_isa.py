@@ -5,7 +5,7 @@ the plain operators, and hipcc's default -ffp-contract=fast-honor-pragmas compil
 (emcee) rounds z (c - s) first; the one-ulp seeds grew along the chain and the walkers left the reference's after a few
 hundred steps on the MI355X only (the g++ interpreter never fuses).  These tests read what the compiler emits:
 
-* LLVM IR of every kernel that inlines the proposal (mcmc.hip, potrf.hip): the three operations of q, the five of z and
+* LLVM IR of every kernel that inlines the proposal (mcmc.hip, mcmc_block.hip): the three operations of q, the five of z and
   the three of the accept statistic carry no `contract` flag -- the only thing the AMDGPU backend may fuse under
   fast-honor-pragmas -- and no fma / fmuladd intrinsic sits on those paths.
 * machine code of the probe kernels of the diagnostics library (the same device functions on arrays): no v_fma_f64.
@@ -107,14 +107,14 @@ def _no_fusable(flag_lists):
 @pytest.fixture(scope="module")
 def ir(tmp_path_factory):
     tmp = tmp_path_factory.mktemp("isa")
-    return {src: _ir_functions(_emit(src, "ll", tmp)) for src in ("mcmc.hip", "potrf.hip")}
+    return {src: _ir_functions(_emit(src, "ll", tmp)) for src in ("mcmc.hip", "mcmc_block.hip")}
 
 
 def test_stretch_move_is_not_contractable_in_the_chain_kernels(ir):
     kernels = {k: v for src in ir.values() for k, v in src.items()
-               if "mcmc_propose_scale_kernel" in k or "mcmc_block_step_kernel" in k or "mcmc_block2_step_kernel" in k}
-    # the launch-per-phase proposal + four one-block instantiations + two two-block ones
-    assert len(kernels) == 7, sorted(kernels)
+               if "mcmc_propose_scale_kernel" in k or "mcmc_block_step_kernel" in k}
+    # the launch-per-phase proposal + four one-block instantiations
+    assert len(kernels) == 5, sorted(kernels)
     for name, lines in kernels.items():
         q = _stretch_q_sites(lines)
         z = _stretch_z_sites(lines)
@@ -149,8 +149,8 @@ def test_the_check_sees_a_contractable_proposal(tmp_path):
 
 
 def test_accept_statistic_is_not_contractable(ir):
-    for src, name in (("mcmc.hip", "mcmc_accept_kernel"), ("mcmc.hip", "mcmc_tail_kernel"), ("potrf.hip", "mcmc_block_step_kernel"),
-                      ("potrf.hip", "mcmc_block2_step_kernel")):
+    for src, name in (("mcmc.hip", "mcmc_accept_kernel"), ("mcmc.hip", "mcmc_tail_kernel"),
+                      ("mcmc_block.hip", "mcmc_block_step_kernel")):
         for k, lines in ir[src].items():
             if name not in k:
                 continue

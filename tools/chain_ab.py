@@ -1,6 +1,7 @@
 """Device-resident hyper-parameter chain (robo_gp_mcmc_run): time per ensemble half-step at BO-typical sizes, the fused
-one-launch half-step (mcmc_block_step = 3: one- and two-block problems) against the launch-per-phase form (0), same session;
-chains compared.       python tools/chain_ab.py [D] [walkers] [steps]"""
+one-launch half-step of one-block problems (mcmc_block_step = 2, the default) against the launch-per-phase form (0), same
+session; chains compared.  CHAIN_KNOB / CHAIN_VALUES pick another tuning key and its two values (e.g. mcmc_fused_tail, 1,0
+for the multi-block sizes).       python tools/chain_ab.py [D] [walkers] [steps]"""
 import os
 import sys
 import time
@@ -15,7 +16,7 @@ K = int(sys.argv[2]) if len(sys.argv) > 2 else 52
 STEPS = int(sys.argv[3]) if len(sys.argv) > 3 else 200
 ctx = _lib.Context(0)
 KNOB = os.environ.get("CHAIN_KNOB", "mcmc_block_step")          # which tuning key the two columns differ in
-A_VAL, B_VAL = (int(v) for v in os.environ.get("CHAIN_VALUES", "3,0").split(","))
+A_VAL, B_VAL = (int(v) for v in os.environ.get("CHAIN_VALUES", "2,0").split(","))
 for N in (int(v) for v in os.environ.get("CHAIN_N", "100,127,150,200,254,255,300").split(",")):
     rs = np.random.RandomState(3)
     X = rs.rand(N, D)
