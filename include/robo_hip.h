@@ -103,7 +103,11 @@ int32_t robo_ctx_set_phase_events(robo_ctx* ctx, int32_t on);
  * trsm_small_deep, trsm_rows, predict_stepwise, mcmc_block_step (the chain's one-launch half-step of one-block problems:
  * 0 never, 1 up to 63 points, 2 = default: all of them; a larger value means 2), potrf_fused, potrf_tm4_min,
  * potrf_max_wg, potrf_group, potrf_split (sub-batches of a batched factorisation on their own streams, default 3, from
- * potrf_split_min = 12 panels on), potrf_lead, potrf_thin_last (kernel-variant selection; A/B runs and tests).         */
+ * potrf_split_min = 12 panels on), potrf_lead, potrf_thin_last (kernel-variant selection; A/B runs and tests),
+ * acq_screen (1 = default: an argmax-only acquisition call skips the candidates that cannot win, see robo_acq_eval_cand;
+ * 0 never), acq_screen_min (batches above this many candidates are screened; -1 = default: winv_max, the size above which
+ * the unscreened call is the block-row substitution; tests lower it), acq_screen_keep_max (percent of the batch that may
+ * survive the screen, default 25: more than that and the call falls back to the plain sweep).                          */
 int32_t robo_ctx_set_tuning(robo_ctx* ctx, const char* key, int64_t value);
 const char* robo_last_error_string(void);
 const char* robo_version_string(void);
@@ -299,11 +303,31 @@ int32_t robo_gp_predict_cov(robo_gp* gp, const double* Xc, int64_t m, double* ou
  * RandomSampling.maximize (robo/maximizers/random_sampling.py:48-50) ------------------ */
 /* out_acq (m,) may be NULL when only the maximiser is wanted.  argmax follows np.argmax:
  * first index of the maximum, NaN counts as maximal.  par = xi (EI/LogEI/PI) or kappa (LCB);
- * eta = incumbent value (ignored by LCB).                                                     */
+ * eta = incumbent value (ignored by LCB).
+ * Argmax-only calls (out_acq == NULL, also of the sharded and multi-device forms) on a large batch are SCREENED: one
+ * O(N) pass per candidate gives the posterior mean through alpha = L^-T z and, with the prior variance and the variance
+ * floor, an upper and a lower bound of the acquisition value; only candidates whose upper bound reaches the best lower
+ * bound are solved, by the block-row substitution the unscreened call runs, so (max, argmax, flags) are the unscreened
+ * call's bit for bit.  Screened: EI, LogEI, PI, LCB with kappa >= 0, finite eta / par, one fitted GP with fp64
+ * covariance entries, batches above `acq_screen_min`, max L_ii / min L_ii <= 1e4.  When more than `acq_screen_keep_max`
+ * percent survive, the call runs the plain sweep and the factor is not screened again for 1, 2, 4, ... calls (until the
+ * next fit).  After a screened call the handle holds no posterior of the whole batch.                               */
 int32_t robo_acq_eval_cand(robo_gp* gp, int32_t acq_kind, double par, double eta, robo_cand* cand, double* out_acq,
                            double* out_max, int64_t* out_argmax, uint32_t* out_flags);
 int32_t robo_acq_eval(robo_gp* gp, int32_t acq_kind, double par, double eta, const double* Xc, int64_t m,
                       double* out_acq, double* out_max, int64_t* out_argmax, uint32_t* out_flags);
+/* What the last argmax-only acquisition call on this handle did.  *out_outcome: */
+#define ROBO_SCREEN_NOT_ELIGIBLE 0 /* the plain sweep ran: not an eligible call, or the factor is in its back-off   */
+#define ROBO_SCREEN_SCREENED 1     /* out_n_survivors of out_n_screened candidates were solved                      */
+#define ROBO_SCREEN_PROBE_USED 2   /* ... after the incumbent was taken from the exact values of the 128 candidates with the largest upper bounds */
+#define ROBO_SCREEN_FELL_BACK 3    /* too many survivors (or none below the bound): the plain sweep ran on the whole batch */
+int32_t robo_cand_last_screen(robo_cand* cand, int64_t* out_n_screened, int64_t* out_n_survivors, int32_t* out_outcome);
+/* The screen's bounds themselves (soundness tests, A/B tools): out_upper / out_lower (m,) with
+ * lower <= the value robo_acq_eval_cand returns for the candidate <= upper; NaN coordinates give NaN bounds.  Needs a
+ * (kind, par) the screen handles (LCB: kappa >= 0) and fp64 covariance entries; batch size, tuning keys and the
+ * conditioning guard are not consulted.                                                                            */
+int32_t robo_acq_screen_bounds(robo_gp* gp, int32_t acq_kind, double par, double eta, robo_cand* cand, double* out_upper,
+                               double* out_lower);
 /* the element-wise half alone, for (mean, var) produced by any other BaseModel plugin
  * (the reference's acquisition classes accept every model, e.g. test/dummy_model.py)          */
 int32_t robo_acq_eval_moments(robo_ctx* ctx, int32_t acq_kind, double par, double eta, const double* mean,

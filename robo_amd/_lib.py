@@ -26,6 +26,7 @@ EP_NAN_MESSAGE = ("an error occurs while running expectation propagation in entr
 KERNEL_KINDS = {"matern52": 0, "rbf": 1, "fabolas": 2}
 ACQ_KINDS = {"ei": 0, "log_ei": 1, "pi": 2, "lcb": 3}
 FLAG_ZERO_SIGMA, FLAG_NEGATIVE_EI, FLAG_NAN, FLAG_NOT_FACTORED, FLAG_FROZEN = 1, 2, 4, 8, 16
+SCREEN_NOT_ELIGIBLE, SCREEN_SCREENED, SCREEN_PROBE_USED, SCREEN_FELL_BACK = 0, 1, 2, 3     # robo_cand_last_screen's outcome
 FANTASY_KINDS = {"kriging_believer": 0, "constant_liar": 1}   # robo_acq_batch_*: how a pick's fantasy target is chosen
 MES_MAX_K = 128                                  # robo_mes_*: cap on the sampled minima per model
 KG_MAX_DISC = 64                                 # robo_kg_*: cap on the discretisation points of the knowledge gradient
@@ -46,6 +47,7 @@ SYMBOLS = [
     "robo_cand_create_random", "robo_cand_create_sobol", "robo_cand_get_point", "robo_cand_workspace_chunk", "robo_cand_last_solve_kernel",
     "robo_gp_predict_cand", "robo_gp_predict", "robo_gp_predict_cov", "robo_gp_predict_grad", "robo_gp_predict_mixture_cand",
     "robo_acq_eval_cand", "robo_acq_eval", "robo_acq_eval_moments", "robo_acq_eval_marginal_cand", "robo_acq_eval_sum_cand",
+    "robo_cand_last_screen", "robo_acq_screen_bounds",
     "robo_acq_refine_cand", "robo_acq_refine_marginal_cand",
     "robo_rep_sample", "robo_rep_sample_batch",
     "robo_acq_batch_cand", "robo_acq_batch_marginal_cand",
@@ -207,6 +209,8 @@ def lib():
         "robo_gp_predict_mixture_cand": [pp, i32, vp, _dp, _dp],
         "robo_acq_eval_cand": [vp, i32, dbl, dbl, vp, _dp, _dp, C.POINTER(i64), C.POINTER(C.c_uint32)],
         "robo_acq_eval": [vp, i32, dbl, dbl, _dp, i64, _dp, _dp, C.POINTER(i64), C.POINTER(C.c_uint32)],
+        "robo_cand_last_screen": [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i32)],
+        "robo_acq_screen_bounds": [vp, i32, dbl, dbl, vp, _dp, _dp],
         "robo_acq_eval_moments": [vp, i32, dbl, dbl, _dp, _dp, i64, _dp, _dp, C.POINTER(i64), C.POINTER(C.c_uint32)],
         "robo_acq_eval_marginal_cand": [pp, i32, i32, dbl, _dp, vp, _dp, _dp, C.POINTER(i64),
                                         C.POINTER(C.c_uint32)],
@@ -609,6 +613,12 @@ class Candidates(object):
         check(lib().robo_cand_last_solve_kernel(self._h, buf, 64))
         return buf.value.decode()
 
+    def last_screen(self):
+        """what the last argmax-only acquisition call on this handle did -> (candidates screened, survivors, SCREEN_* outcome)"""
+        n, kept, outcome = C.c_int64(0), C.c_int64(0), C.c_int32(0)
+        check(lib().robo_cand_last_screen(self._h, C.byref(n), C.byref(kept), C.byref(outcome)))
+        return int(n.value), int(kept.value), int(outcome.value)
+
     def points(self):
         out = np.empty((self.m, self.dim))
         check(lib().robo_cand_get_points(self._h, _arr(out)))
@@ -856,6 +866,11 @@ class DeviceGP(object):
                                       _arr(out) if want_values else None, *best.refs))
         return (out,) + best.values()
 
+    def screen_bounds(self, kind, par, eta, cand):
+        """-> (upper, lower) bounds of the acquisition value of every candidate, as the screen of argmax-only calls forms them"""
+        up, lo = np.empty(cand.m), np.empty(cand.m)
+        check(lib().robo_acq_screen_bounds(self._h, ACQ_KINDS[kind], float(par), float(eta), cand._h, _arr(up), _arr(lo)))
+        return up, lo
 
     def refine(self, kind, par, eta, cand, n_starts=256, n_steps=50, step0=0.05, diagnostics=False):
         """sweep over ``cand`` + multi-start projected gradient ascent on the device (robo_acq_refine_cand)

@@ -293,7 +293,7 @@ extern "C" {
 
 int32_t robo_acq_eval_cand(robo_gp* g, int32_t acq_kind, double par, double eta, robo_cand* k, double* out_acq,
                            double* out_max, int64_t* out_argmax, uint32_t* out_flags) {
-    ROBO_TRY(acq_sweep(&g, 1, false, acq_kind, par, &eta, k));
+    ROBO_TRY(acq_sweep_best(g, acq_kind, par, eta, k, out_acq != nullptr));
     return clear_flags_on_error(k, acq_read_back(k, k->d_acq, out_acq, out_max, out_argmax, out_flags));
 }
 

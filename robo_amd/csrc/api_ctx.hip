@@ -61,6 +61,9 @@ static const TuneKey TUNE_KEYS[] = {
     {"potrf_lead", nullptr, &Tuning::potrf_lead, -1},
     {"mcmc_block_step", nullptr, &Tuning::mcmc_block_step, 2},
     {"mcmc_fused_tail", nullptr, &Tuning::mcmc_fused_tail, 1},
+    {"acq_screen", nullptr, &Tuning::acq_screen, 1},
+    {"acq_screen_min", &Tuning::acq_screen_min, nullptr, -1},
+    {"acq_screen_keep_max", nullptr, &Tuning::acq_screen_keep_max, 25},
 };
 
 static void tune_set(Tuning* t, const TuneKey& k, long long v) {

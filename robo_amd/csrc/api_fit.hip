@@ -75,6 +75,7 @@ int32_t robo_gp_destroy(robo_gp* g) {
     hipFree(g->d_bkeep);
     hipFree(g->d_theta);
     hipFree(g->d_Winv);
+    hipFree(g->d_alpha);
     hipFree(g->d_wnorm);
     if (g->h_wnorm) hipHostFree(g->h_wnorm);
     hipFree(g->d_mcmc);

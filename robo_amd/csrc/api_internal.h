@@ -32,8 +32,10 @@ int predict_core(robo_gp* g, robo_cand* k, bool single_chunk = false,
                  const std::function<int(int64_t, int64_t)>& after_chunk = nullptr, bool need_v = false);
 // the rest of predict_core for points whose scaled rows are in k->d_Xcs already, the solve decided (decide_winv) and the
 // workspace sized: launches only
+// events: record the phase events 24..27 whatever the batch size (the survivors of a screened large batch)
 int predict_scaled(robo_gp* g, robo_cand* k, bool winv, const std::function<int(int64_t, int64_t)>& after_chunk = nullptr,
-                   bool need_v = false);
+                   bool need_v = false, bool events = false);
+bool winv_candidate(const robo_gp* g, const robo_cand* k);     // the batch and the factor qualify for the explicit inverse
 int predict_samples(robo_gp* const* gps, int32_t S, robo_cand* k, int cap);   // -> rows of k->d_mu_all / d_var_all
 int host_cand(robo_gp* g, const double* Xc, int64_t m, robo_cand** out, bool* kept);   // the handle behind host arrays
 int host_cand_rows(robo_gp* g, int64_t m, robo_cand** out);     // ... kept and sized for m points, nothing uploaded (m <= 16384)
@@ -48,6 +50,10 @@ int acq_read_back(robo_cand* k, const double* d_vec, double* out_vec, double* ou
 int acq_accumulate(robo_gp* const* gps, int32_t S, int32_t acq_kind, double par, const double* etas, robo_cand* k);
 // the sweep into k->d_acq and the argmax partials (asynchronous): gps[0]'s acquisition, or (marginal) the mean over S samples
 int acq_sweep(robo_gp* const* gps, int32_t S, bool marginal, int32_t acq_kind, double par, const double* etas, robo_cand* k);
+// screen.hip: what robo_acq_eval_cand and its sharded / multi-device forms run.  want_values = false (the caller takes
+// (max, argmax, flags) only): an eligible call screens the batch and solves the survivors alone, leaving the winner in k's
+// argmax slots exactly as acq_sweep does; every other call is acq_sweep.
+int acq_sweep_best(robo_gp* g, int32_t acq_kind, double par, double eta, robo_cand* k, bool want_values);
 // the samples of an ensemble call against the candidates, then hipSetDevice.  `label` opens the messages.
 constexpr unsigned ENSEMBLE_MES_VERDICTS = 1;      // an unfitted sample is ROBO_BAD_ARGUMENT naming the sample; no shape checks
 constexpr unsigned ENSEMBLE_ONE_KIND_FP64 = 2;     // every sample has the first one's kernel kind and fp64 covariance entries

@@ -85,7 +85,7 @@ static int winv_min_blocks_for(const robo_gp* g, long long m) {
     return (m <= 8 && t.winv_gemv != 0 && t.winv_min_blocks > 3) ? 3 : t.winv_min_blocks;
 }
 
-static bool winv_candidate(const robo_gp* g, const robo_cand* k) {
+bool winv_candidate(const robo_gp* g, const robo_cand* k) {
     if (k->m_pad > g->ctx->tune.winv_max) return false;
     return winv_factor_ok(g, winv_min_blocks_for(g, k->m));
 }
@@ -120,14 +120,15 @@ int predict_core(robo_gp* g, robo_cand* k, bool single_chunk, const std::functio
     return predict_scaled(g, k, winv, after_chunk, need_v);
 }
 
-int predict_scaled(robo_gp* g, robo_cand* k, bool winv, const std::function<int(int64_t, int64_t)>& after_chunk, bool need_v) {
+int predict_scaled(robo_gp* g, robo_cand* k, bool winv, const std::function<int(int64_t, int64_t)>& after_chunk, bool need_v,
+                   bool events) {
     k->solved_gen = 0;
     // event slots 24..27 bracket the phases of the LAST chunk (bench.py reads them after a sync):
     //   24 -> 25 cross-gram, 25 -> 26 triangular solve (the MFMA kernel), 26 -> 27 post
     // (small batches are latency-bound and four event packets cost several microseconds: recorded for them only when
     // the phase events are switched on, robo_ctx_set_phase_events)
     hipStream_t st = g->ctx->stream;
-    const bool ev = g->ctx->phase_events || k->m_pad > 16384;
+    const bool ev = g->ctx->phase_events || events || k->m_pad > 16384;
     for (int64_t c0 = 0; c0 < k->m_pad; c0 += k->chunk) {
         const int64_t cn = k->m_pad - c0 < k->chunk ? k->m_pad - c0 : k->chunk;
         if (ev) ROBO_HIP_CHECK(hipEventRecord(g->ctx->events[24], st));
@@ -353,6 +354,12 @@ int32_t robo_cand_destroy(robo_cand* k) {
     hipFree(k->d_part_val);
     hipFree(k->d_part_idx);
     hipFree(k->d_flags);
+    hipFree(k->d_scr_up);
+    hipFree(k->d_scr_lo);
+    hipFree(k->d_scr_cnt);
+    hipFree(k->d_scr_map);
+    robo_cand_destroy(k->scr_sub);
+    refine_free(k->scr_probe);
     robo_ctx* ctx = k->ctx;
     delete k;
     ctx_release(ctx);

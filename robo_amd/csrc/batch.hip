@@ -168,7 +168,7 @@ __global__ __launch_bounds__(256) void batch_bwd_kernel(const double* __restrict
                                                         double* __restrict__ v, double* __restrict__ beta, int i, int n,
                                                         const int* __restrict__ stop) {
     __shared__ double sv[NB], sb[NB], sp[NB];
-    if (*stop) return;
+    if (stop && *stop) return;
     const int tid = threadIdx.x, c = tid & (NB - 1), half = tid >> 7;
     const int nv = n - i * NB < NB ? n - i * NB : NB;
     if (tid < NB) sv[tid] = tid < nv ? v[i * NB + tid] : 0.0;
@@ -420,6 +420,15 @@ int launch_batch_record(robo_ctx* ctx, const BatchState& st, const robo_cand* ca
     return ROBO_OK;
 }
 
+int launch_bwd_rows(robo_gp* gp, double* d_v, double* d_beta, const int* d_stop) {
+    const int n = gp->n, n_pad = gp->n_pad, nbk = (n + NB - 1) / NB;
+    for (int i = nbk - 1; i >= 0; --i)
+        hipLaunchKernelGGL(batch_bwd_kernel, dim3((unsigned)(i > 1 ? i : 1)), dim3(256), 0, gp->ctx->stream,
+                           (const double*)gp->d_K, n_pad, (const double*)gp->d_Linv, d_v, d_beta, i, n, d_stop);
+    ROBO_LAUNCH_CHECK();
+    return ROBO_OK;
+}
+
 // one conditioning step of sample s for pick j >= 1: k_*(x_j) and the scalars, beta, the pass over the candidates
 int launch_batch_condition(robo_gp* gp, const BatchState& st, const robo_cand* cand, int s, int j, int acq_kind, double par,
                            int fantasy_kind, double liar) {
@@ -436,9 +445,7 @@ int launch_batch_condition(robo_gp* gp, const BatchState& st, const robo_cand* c
     for (int i = 0; i < nbk; ++i)
         hipLaunchKernelGGL(batch_fwd_kernel, dim3((unsigned)(nbk - 1 - i > 1 ? nbk - 1 - i : 1)), dim3(256), 0, stream,
                            (const double*)gp->d_K, n_pad, (const double*)gp->d_Linv, w, v, i, n, (const int*)st.stop);
-    for (int i = nbk - 1; i >= 0; --i)
-        hipLaunchKernelGGL(batch_bwd_kernel, dim3((unsigned)(i > 1 ? i : 1)), dim3(256), 0, stream, (const double*)gp->d_K,
-                           n_pad, (const double*)gp->d_Linv, v, beta, i, n, (const int*)st.stop);
+    ROBO_TRY(launch_bwd_rows(gp, v, beta, st.stop));
     const dim3 grid((unsigned)((st.m + BC_CAND - 1) / BC_CAND));
 #define ROBO_COND_CALL(KIND)                                                                                              \
     do {                                                                                                                  \

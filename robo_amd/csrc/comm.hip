@@ -350,7 +350,7 @@ int32_t robo_acq_eval_cand_sharded(robo_comm* c, robo_gp* g, int32_t acq_kind, d
         return ROBO_BAD_ARGUMENT;
     }
     ROBO_HIP_CHECK(hipSetDevice(c->ctx->device));
-    const int status = acq_sweep(&g, 1, false, acq_kind, par, &eta, k);
+    const int status = acq_sweep_best(g, acq_kind, par, eta, k, out_acq != nullptr);
     return exchange_best(c, k, status, global_offset, "robo_acq_eval_cand_sharded", out_acq, out_max, out_argmax,
                          out_owner_rank, out_flags);
 }

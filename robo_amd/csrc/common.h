@@ -189,6 +189,10 @@ struct Tuning {
     int mcmc_fused_tail;         // device chain, multi-block factors: likelihood terms + accept test in one launch (1)
     int mcmc_block_step;         // ensemble half-step in ONE launch: 2 (default) every one-block problem, 1 only N <= 63, 0 never
                                  // (a larger value means 2: the two-block form that 3 selected was measured slower and removed)
+    int acq_screen;              // argmax-only acquisition calls skip the candidates that cannot win (screen.hip): 1 (default), 0 never
+    long long acq_screen_min;    // ... for batches above this many candidates (-1 = default: winv_max, above which the unscreened
+                                 // call is the block-row substitution; tests lower it so that the interpreter reaches the screen)
+    int acq_screen_keep_max;     // ... while at most this percentage of the batch survives (25); beyond it the plain sweep runs
 };
 void tuning_from_env(Tuning* t);
 }  // namespace robo
@@ -463,6 +467,11 @@ struct robo_gp {
     robo::MesWork* mes;             // state of robo_mes_eval_* (mes.hip), kept between calls of one (m, S, K)
     robo::RepWork* rep;             // state of robo_rep_sample* (represent.hip), kept with gps[0] between calls
     robo::HyperWork* hyper;         // workspace of robo_gp_grad_loglik_batch / robo_gp_optimize_hypers (hyperopt.hip)
+    // the acquisition screen (screen.hip), lazy: [scratch (n_pad_max) | alpha = L^-T z (n_pad_max) | sum_j |alpha_j| sqrt(k_jj)]
+    double* d_alpha;
+    unsigned long long alpha_gen;   // fit_gen alpha was computed for (0: none)
+    unsigned long long screen_gen;  // fit_gen the back-off below belongs to
+    int screen_skip, screen_backoff;   // eligible calls still to pass unscreened after a failed screen; length of the next pause
 };
 
 struct robo_cand {
@@ -504,6 +513,16 @@ struct robo_cand {
     long long* d_part_idx;
     unsigned* d_flags;
     int n_part;
+    // the acquisition screen (screen.hip), lazy: bounds (m_pad each), survivor counts / offsets per 256 candidates, the
+    // survivors' original indices, and the sub-handle that holds their scaled rows and runs their exact solve
+    double *d_scr_up, *d_scr_lo;
+    int* d_scr_cnt;                 // [n_part + 1] counts -> exclusive offsets, total last
+    long long* d_scr_map;           // [scr_sub's capacity]
+    struct robo_cand* scr_sub;      // owned; m / m_pad / n_part are set per call to the survivors at hand
+    robo::RefineWork* scr_probe;    // the selection state of the probe (refine.hip's top-K), lazy
+    int64_t scr_cap;                // rows scr_sub was allocated for
+    int64_t scr_n, scr_kept;        // robo_cand_last_screen: candidates screened, survivors
+    int scr_outcome;
 };
 
 // ---- launchers implemented in the .hip files (all asynchronous on ctx->stream) ------------
@@ -621,6 +640,8 @@ int launch_batch_condition(robo_gp* gp, const BatchState& st, const robo_cand* c
 int launch_acq(robo_ctx* ctx, robo_cand* cand, int acq_kind, double par, double eta, bool accumulate, bool first);
 int launch_argmax(robo_cand* cand, const double* d_vals, double scale);
 int launch_report_best(robo_cand* cand, double* h_pinned);
+// batch.hip: beta = L^-T v for ONE right-hand side by backward block rows with the fit's inverted diagonal blocks (v is consumed)
+int launch_bwd_rows(robo_gp* gp, double* d_v, double* d_beta, const int* d_stop = nullptr);   // *d_stop != 0: no-op
 int launch_cov(robo_gp* gp, robo_cand* cand, double* d_cov);
 int launch_mixture(robo_cand* cand, int S);
 // clip: floored at DBL_EPSILON as the reference's predict(full_cov=True) (entropy search); false: signed (kg.hip)

@@ -1,0 +1,552 @@
+// The acquisition screen: argmax-only sweeps (robo_acq_eval_cand and its sharded / multi-device forms with out_acq == NULL)
+// solve only the candidates that can still be the argmax.
+//
+// The block-row substitution costs O(N^2) per candidate and the caller of an argmax-only sweep sees one winner.  Two facts
+// that cost O(N) per candidate decide for almost all of the others that they are not it:
+//   * the posterior mean is  mu = k_* . alpha  with  alpha = K^-1 (y - c) = L^-T z,  z = row n of the factor: alpha belongs to
+//     the FIT (computed once per fit_gen, by the backward block rows of batch.hip, never from the explicit inverse);
+//   * post_kernel forms  v = (k** - q) y_std^2  with q a sum of squares, so  v <= k** y_std^2  holds in floating point too, and
+//     v >= DBL_EPSILON by the floor.
+// EI, LogEI and LCB (kappa >= 0) increase in sigma and decrease in the mean; PI increases in sigma where its numerator
+// eta - mu - xi is negative and decreases where it is positive.  So
+//     U_c = acq(mean - delta, prior variance (1 + rho)) (1 + rho)        L_c = acq(mean + delta, floor) (1 - rho)
+// bracket the value the sweep would return for candidate c (PI: U = 1 where the numerator can be >= 0, the lower bound at the
+// prior variance there).  b = max_c L_c is a value SOME candidate reaches, so a candidate with U_c < b cannot be the argmax
+// and cannot tie with it.  The others -- every candidate with a NaN in its screening quantities among them, `U_c < b` is
+// false for it -- are gathered in ascending original index and run through the path the unscreened call runs for the whole
+// batch (predict_scaled without the explicit inverse, post_kernel, acq_kernel, the argmax).  Block-row results do not depend
+// on tile shape or position (tests/test_gpu_parity.py test_small_and_large_candidate_tiles_agree), the gather keeps the index
+// order, so (max, argmax, flags) are the unscreened call's bit for bit.
+//
+// Margins (measured: DESIGN.md "The acquisition screen", tests/test_acq_screen.py):
+//   delta = SCREEN_DELTA_REL (|y_mean| + y_std (|mean_c| + sqrt(k_cc) sum_j |alpha_j| sqrt(k_jj)))  -- the scale of the mean's
+//           rounding in either route: every product of either sum is bounded by sqrt(k_cc k_jj) |alpha_j|;
+//   rho   = SCREEN_RHO relative, on the prior variance and on the value of EI, PI and LogEI (LogEI: of |value| + 1).
+// Guard: max L_ii / min L_ii <= SCREEN_DIAG_RATIO_MAX, in the style of winv_factor_ok.
+//
+// Flags: acq_kernel ORs them over the candidates it sees, here the survivors.  A pruned candidate cannot raise one: NAN needs a
+// NaN value, and a NaN in the screening quantities makes a survivor; ZERO_SIGMA needs sqrt(v) == 0 and post_kernel floors v at
+// DBL_EPSILON; NEGATIVE_EI needs EI < -DBL_MIN, but z Phi(z) + phi(z) is rounded to a negative number only where both terms
+// have underflowed below DBL_MIN (|z| > 37.5 with sigma >= 1.5e-8: the clamp of acq_kernel returns +0 there).
+//
+// The probe.  Where eta lies below every mean, L_c is the value at the variance floor -- essentially 0 for every candidate --
+// and b = max L_c prunes nothing.  When more than the cap survive, the SCREEN_PROBE candidates with the largest U_c (the
+// radix selection of refine.hip) are evaluated exactly by the block-row path and b is raised to their best value less rho:
+// again a value some candidate reaches.  The probe supplies that bound alone: its values and flags are dropped, the
+// survivors (the probed ones among them) are solved afresh.
+//
+// When more than acq_screen_keep_max percent still survive (eta below every mean: L_c is the value at the variance floor,
+// essentially 0 everywhere, and nothing is pruned) the call runs the plain sweep on everything and the factor is not
+// screened for the next 1, 2, 4, ... eligible calls: a regime that never prunes pays for the screen a vanishing number of
+// times.  A new fit starts afresh.
+#include <cmath>
+
+#include "api_internal.h"
+#include "kern_math.h"
+
+namespace robo {
+
+constexpr double SCREEN_DELTA_REL = 1e-11;
+constexpr double SCREEN_RHO = 1e-5;
+constexpr double SCREEN_DIAG_RATIO_MAX = 1e4;
+constexpr int SCREEN_PROBE = NB;     // candidates of the probe: one tile
+
+constexpr int SC_CAND = 64;          // candidates per workgroup of the bounds pass (one per lane; the 4 waves split the rows)
+constexpr int SC_ROWS = 32;          // training rows per wave and tile
+constexpr int SC_LD = NB + 2;
+
+// ---- alpha's scale: sum_j |alpha_j| sqrt(k_jj) -> out[0] ---------------------------------------------------------------
+__global__ __launch_bounds__(256) void screen_alpha_norm_kernel(const double* __restrict__ alpha, const double* __restrict__ Xs,
+                                                                CovParams cp, int n, double* __restrict__ out) {
+    __shared__ double sh[256];
+    double a = 0.0;
+    for (int j = threadIdx.x; j < n; j += 256)
+        a += fabs(alpha[j]) * sqrt(fabs(cov_self(cp, Xs[(size_t)j * cp.dim + cp.dim - 1])));
+    sh[threadIdx.x] = a;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[0] = sh[0];
+}
+
+// x moved outwards by rho (|x| + abs_term); infinities and NaN stay what they are
+__device__ __forceinline__ double screen_widen(double x, double sign, double abs_term) {
+    return isfinite(x) ? x + sign * SCREEN_RHO * (fabs(x) + abs_term) : x;
+}
+
+// the two bounds of one candidate from its transformed mean m (+- delta), the transformed prior variance and the floor
+__device__ __forceinline__ void screen_bounds(int kind, double par, double eta, double m, double delta, double v_prior,
+                                              double& up, double& lo) {
+    const double eps = 2.220446049250313e-16;
+    double v_hi = v_prior < eps ? eps : v_prior;     // the floor of post_kernel; NaN propagates
+    v_hi = v_hi * (1.0 + SCREEN_RHO);
+    const double v_lo = eps;
+    const double m_lo = m - delta, m_hi = m + delta;
+    if (kind == ROBO_ACQ_EI) {
+        up = acq_ei(m_lo, v_hi, eta, par);
+        lo = acq_ei(m_hi, v_lo, eta, par);
+        if (up < 0.0 && up > -2.2250738585072014e-308) up = 0.0;     // as acq_kernel
+        if (lo < 0.0 && lo > -2.2250738585072014e-308) lo = 0.0;
+        up = screen_widen(up, 1.0, 0.0);
+        lo = screen_widen(lo, -1.0, 0.0);
+    } else if (kind == ROBO_ACQ_LOG_EI) {
+        up = screen_widen(acq_log_ei(m_lo, v_hi, eta, par), 1.0, 1.0);
+        lo = screen_widen(acq_log_ei(m_hi, v_lo, eta, par), -1.0, 1.0);
+    } else if (kind == ROBO_ACQ_PI) {
+        // Phi(num / sigma) falls in sigma where num > 0: no bound from the prior variance above, the lower one from it
+        up = (eta - m_lo - par >= 0.0) ? 1.0 : screen_widen(acq_pi(m_lo, v_hi, eta, par), 1.0, 0.0);
+        lo = screen_widen(acq_pi(m_hi, (eta - m_hi - par >= 0.0) ? v_hi : v_lo, eta, par), -1.0, 0.0);
+    } else {
+        // a plain sum: its rounding is eps (|m| + kappa sigma), far inside delta (|m| <= the scale delta is taken from)
+        up = acq_lcb(m_lo, v_hi, par);
+        lo = acq_lcb(m_hi, v_lo, par);
+    }
+}
+
+// ---- the bounds pass -------------------------------------------------------------------------------------------------------
+// SIBLING of batch_cond_kernel (batch.hip): the same staging, SMALLD split and pair loop -- change the two together.  A
+// workgroup owns 64 candidates, one per lane; its four waves split every
+// tile of 128 training points (32 rows each, staged as [dimension][row]: a broadcast read).  Per pair the covariance is
+// accumulated dimension by dimension with direct differences, as the cross-gram generators of predict.hip do, and
+// multiplied into the lane's running k_* . alpha.  No V, no workspace.
+template <int KIND, bool SMALLD>
+__global__ __launch_bounds__(256) void screen_bounds_kernel(const double* __restrict__ Xcs, const double* __restrict__ Xs,
+                                                            const double* __restrict__ alpha,
+                                                            const double* __restrict__ alpha_norm, CovParams cp, int n,
+                                                            long long m, double mean_c, double y_mean, double y_std,
+                                                            int acq_kind, double par, double eta, double* __restrict__ up,
+                                                            double* __restrict__ lo) {
+    __shared__ double sX[16 * SC_LD];
+    __shared__ double sA[NB];
+    __shared__ double sP[4][SC_CAND];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, D = cp.dim;
+    const long long i = (long long)blockIdx.x * SC_CAND + lane;
+    const bool live = i < m;
+    const long long ii = live ? i : 0;
+    double xc[16];
+    if (SMALLD) {
+#pragma unroll
+        for (int d = 0; d < 16; ++d) xc[d] = d < D ? Xcs[ii * D + d] : 0.0;
+    }
+    const int nbk = (n + NB - 1) / NB;
+    double dot = 0.0;
+    for (int tile = 0; tile < nbk; ++tile) {
+        double acc[SC_ROWS], uu[SC_ROWS];
+#pragma unroll
+        for (int r = 0; r < SC_ROWS; ++r) cov_init<double, KIND>(cp, acc[r], uu[r]);
+        for (int d0 = 0; d0 < D; d0 += 16) {
+            __syncthreads();
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const int idx = tid + e * 256, row = idx >> 4, d = idx & 15;
+                const int rg = tile * NB + row;
+                sX[d * SC_LD + row] = (d0 + d < D && rg < n) ? Xs[(size_t)rg * D + d0 + d] : 0.0;
+            }
+            if (d0 == 0 && tid < NB) sA[tid] = tile * NB + tid < n ? alpha[tile * NB + tid] : 0.0;
+            __syncthreads();
+            const int dn = D - d0 < 16 ? D - d0 : 16;
+            const double* sx = sX + wave * SC_ROWS;
+            if (SMALLD) {
+#pragma unroll
+                for (int d = 0; d < 16; ++d) {
+                    if (d < dn) {
+#pragma unroll
+                        for (int r = 0; r < SC_ROWS; ++r)
+                            cov_step<double, KIND>(cp, d, xc[d], sx[d * SC_LD + r], acc[r], uu[r]);
+                    }
+                }
+            } else {
+                for (int d = 0; d < dn; ++d) {
+                    const double xi = Xcs[ii * D + d0 + d];
+#pragma unroll
+                    for (int r = 0; r < SC_ROWS; ++r)
+                        cov_step<double, KIND>(cp, d0 + d, xi, sx[d * SC_LD + r], acc[r], uu[r]);
+                }
+            }
+        }
+        // rows >= n (the augmented row, the padding) take no part
+#pragma unroll
+        for (int r = 0; r < SC_ROWS; ++r) {
+            const double kv = cov_finish<double, KIND>(cp, acc[r], uu[r]);
+            if (tile * NB + wave * SC_ROWS + r < n) dot = fma(kv, sA[wave * SC_ROWS + r], dot);
+        }
+    }
+    sP[wave][lane] = dot;
+    __syncthreads();
+    if (wave != 0 || !live) return;
+    const double mu = (sP[0][lane] + sP[1][lane]) + (sP[2][lane] + sP[3][lane]);
+    const double kself = cov_self(cp, Xcs[i * D + D - 1]);
+    double mt = mu + mean_c;
+    mt = mt * y_std + y_mean;
+    const double v_prior = kself * (y_std * y_std);
+    const double delta = SCREEN_DELTA_REL * (fabs(y_mean) + fabs(y_std) * (fabs(mean_c) + sqrt(fabs(kself)) * alpha_norm[0]));
+    double u, l;
+    screen_bounds(acq_kind, par, eta, mt, delta, v_prior, u, l);
+    up[i] = u;
+    lo[i] = l;
+}
+
+// ---- b = max_c L_c (NaN ignored; -inf when there is none) ---------------------------------------------------------------------
+__device__ __forceinline__ double screen_block_max(double x, double* sh) {
+    for (int o = 32; o > 0; o >>= 1) {
+        const double y = __shfl_xor(x, o);
+        x = y > x ? y : x;
+    }
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = x;
+    __syncthreads();
+    double r = sh[0];
+    for (int w = 1; w < 4; ++w) r = sh[w] > r ? sh[w] : r;
+    return r;
+}
+
+__global__ __launch_bounds__(256) void screen_maxlo_kernel(const double* __restrict__ lo, long long m, double* __restrict__ part) {
+    __shared__ double sh[4];
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    double x = -__builtin_huge_val();
+    if (i < m && !isnan(lo[i])) x = lo[i];
+    const double r = screen_block_max(x, sh);
+    if (threadIdx.x == 0) part[blockIdx.x] = r;
+}
+
+__global__ __launch_bounds__(256) void screen_maxlo_final_kernel(double* __restrict__ part, int n_part) {
+    __shared__ double sh[4];
+    double x = -__builtin_huge_val();
+    for (int p = threadIdx.x; p < n_part; p += 256) x = part[p] > x ? part[p] : x;
+    const double r = screen_block_max(x, sh);
+    if (threadIdx.x == 0) part[n_part] = r;
+}
+
+// ---- survivors: count per 256 candidates, offsets, ordered gather ---------------------------------------------------------------
+// candidate c is pruned only if `U_c < b` evaluates true
+__device__ __forceinline__ bool screen_survives(const double* __restrict__ up, long long c, long long m, double b) {
+    return c < m && !(up[c] < b);
+}
+
+__global__ __launch_bounds__(256) void screen_count_kernel(const double* __restrict__ up, long long m,
+                                                           const double* __restrict__ b, int* __restrict__ cnt) {
+    __shared__ int sw[4];
+    const long long c = (long long)blockIdx.x * 256 + threadIdx.x;
+    const unsigned long long mask = __ballot(screen_survives(up, c, m, *b) ? 1 : 0);
+    if ((threadIdx.x & 63) == 0) sw[threadIdx.x >> 6] = __builtin_popcountll(mask);
+    __syncthreads();
+    if (threadIdx.x == 0) cnt[blockIdx.x] = (sw[0] + sw[1]) + (sw[2] + sw[3]);
+}
+
+// one workgroup: cnt[0 .. n_part) -> exclusive offsets, cnt[n_part] = the total; (total, b) -> pinned host memory
+__global__ __launch_bounds__(256) void screen_scan_kernel(int* __restrict__ cnt, int n_part, const double* __restrict__ b,
+                                                          double* __restrict__ host) {
+    __shared__ int s[256];
+    __shared__ int carry;
+    const int t = threadIdx.x;
+    if (t == 0) carry = 0;
+    __syncthreads();
+    for (int base = 0; base < n_part; base += 256) {
+        const int x = base + t < n_part ? cnt[base + t] : 0;
+        s[t] = x;
+        __syncthreads();
+        for (int o = 1; o < 256; o <<= 1) {
+            const int y = t >= o ? s[t - o] : 0;
+            __syncthreads();
+            s[t] += y;
+            __syncthreads();
+        }
+        const int c0 = carry;
+        if (base + t < n_part) cnt[base + t] = c0 + s[t] - x;
+        __syncthreads();
+        if (t == 255) carry = c0 + s[255];
+        __syncthreads();
+    }
+    if (t == 0) {
+        cnt[n_part] = carry;
+        host[0] = (double)carry;
+        host[1] = *b;
+    }
+}
+
+// the survivors' scaled rows in ascending original index -> sub_Xcs, their indices -> map
+__global__ __launch_bounds__(256) void screen_gather_kernel(const double* __restrict__ up, long long m,
+                                                            const double* __restrict__ b, const int* __restrict__ cnt,
+                                                            const double* __restrict__ Xcs, int dim, long long cap,
+                                                            double* __restrict__ sub_Xcs, long long* __restrict__ map) {
+    __shared__ int sw[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long c = (long long)blockIdx.x * 256 + threadIdx.x;
+    const bool keep = screen_survives(up, c, m, *b);
+    const unsigned long long mask = __ballot(keep ? 1 : 0);
+    if (lane == 0) sw[wave] = __builtin_popcountll(mask);
+    __syncthreads();
+    if (!keep) return;
+    int before = __builtin_popcountll(mask & ((1ull << lane) - 1ull));
+    for (int w = 0; w < wave; ++w) before += sw[w];
+    const long long dst = (long long)cnt[blockIdx.x] + before;
+    if (dst >= cap) return;
+    map[dst] = c;
+    for (int d = 0; d < dim; ++d) sub_Xcs[dst * dim + d] = Xcs[c * dim + d];
+}
+
+// pad rows replicate row 0, as in every candidate handle
+__global__ __launch_bounds__(256) void screen_pad_kernel(double* __restrict__ sub_Xcs, int dim, long long rows, long long rows_pad) {
+    const long long total = (rows_pad - rows) * dim;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256)
+        sub_Xcs[rows * dim + e] = sub_Xcs[e % dim];
+}
+
+// the survivors' winner under its original index into the batch's own argmax slots; their flags into the batch's word.
+// The gather is ascending, so the first index among equal values in the sub-batch is the first in the batch.
+__global__ void screen_map_best_kernel(const double* __restrict__ sub_val, const long long* __restrict__ sub_idx,
+                                       unsigned* __restrict__ sub_flags, const long long* __restrict__ map,
+                                       double* __restrict__ best_val, long long* __restrict__ best_idx,
+                                       unsigned* __restrict__ flags) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    *best_val = *sub_val;
+    *best_idx = *sub_idx < 0 ? *sub_idx : map[*sub_idx];
+    *flags |= *sub_flags;
+    *sub_flags = 0u;
+}
+
+// b := max(b, best exact value of the probed candidates less rho); the probe's flags are dropped
+__global__ void screen_probe_bound_kernel(const double* __restrict__ vals, const RefineSel* __restrict__ sel, int kind,
+                                          double* __restrict__ b, unsigned* __restrict__ probe_flags) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    double best = -__builtin_huge_val();
+    const int keff = (int)sel->keff;             // slots beyond the candidates with a bound hold no candidate
+    for (int i = 0; i < keff; ++i)
+        if (vals[i] > best) best = vals[i];
+    if (kind != ROBO_ACQ_LCB) best = screen_widen(best, -1.0, kind == ROBO_ACQ_LOG_EI ? 1.0 : 0.0);
+    if (best > *b) *b = best;
+    *probe_flags = 0u;
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------------------
+static bool screen_kind_ok(int kind, double par, double eta) {
+    if (!std::isfinite(par)) return false;
+    if (kind == ROBO_ACQ_LCB) return par >= 0.0;
+    return (kind == ROBO_ACQ_EI || kind == ROBO_ACQ_LOG_EI || kind == ROBO_ACQ_PI) && std::isfinite(eta);
+}
+
+// alpha = L^-T z of the factor the handle holds: once per fit_gen
+static int alpha_ensure(robo_gp* g) {
+    const size_t np = (size_t)g->n_pad_max;
+    if (!g->d_alpha) ROBO_TRY(dev_alloc(&g->d_alpha, 2 * np + 8));
+    if (g->alpha_gen == g->fit_gen) return ROBO_OK;
+    hipStream_t st = g->ctx->stream;
+    double* v = g->d_alpha;
+    double* a = g->d_alpha + np;
+    ROBO_HIP_CHECK(hipMemcpyAsync(v, g->d_K + (size_t)g->n * g->n_pad, (size_t)g->n * sizeof(double), hipMemcpyDeviceToDevice, st));
+    ROBO_TRY(launch_bwd_rows(g, v, a));
+    hipLaunchKernelGGL(screen_alpha_norm_kernel, dim3(1), dim3(256), 0, st, (const double*)a, (const double*)g->d_Xs, g->cov,
+                       g->n, g->d_alpha + 2 * np);
+    ROBO_LAUNCH_CHECK();
+    g->alpha_gen = g->fit_gen;
+    return ROBO_OK;
+}
+
+static int screen_buffers(robo_cand* k) {
+    const size_t mp = (size_t)k->m_pad;
+    if (!k->d_scr_up) ROBO_TRY(dev_alloc(&k->d_scr_up, mp));
+    if (!k->d_scr_lo) ROBO_TRY(dev_alloc(&k->d_scr_lo, mp + (size_t)k->n_part + 2));    // bounds | partial maxima | b
+    if (!k->d_scr_cnt) ROBO_TRY(dev_alloc(&k->d_scr_cnt, (size_t)k->n_part + 2));
+    return ROBO_OK;
+}
+
+// scaled rows of k and the bounds of every candidate into k->d_scr_up / d_scr_lo (asynchronous)
+static int launch_screen_bounds(robo_gp* g, robo_cand* k, int kind, double par, double eta) {
+    robo_ctx* c = g->ctx;
+    ROBO_TRY(alpha_ensure(g));
+    ROBO_TRY(screen_buffers(k));
+    ROBO_TRY(launch_scale_inputs(c, k->d_Xc, k->d_Xcs, g->d_theta, k->m, k->m_pad, g->dim));
+    const dim3 grid((unsigned)((k->m + SC_CAND - 1) / SC_CAND));
+    const double* alpha = g->d_alpha + (size_t)g->n_pad_max;
+    const double* anorm = g->d_alpha + 2 * (size_t)g->n_pad_max;
+#define ROBO_SCREEN_CALL(KIND)                                                                                            \
+    do {                                                                                                                  \
+        if (g->dim <= 16)                                                                                                 \
+            hipLaunchKernelGGL((screen_bounds_kernel<KIND, true>), grid, dim3(256), 0, c->stream, (const double*)k->d_Xcs, \
+                               (const double*)g->d_Xs, alpha, anorm, g->cov, g->n, (long long)k->m, g->mean_c, g->y_mean, \
+                               g->y_std, kind, par, eta, k->d_scr_up, k->d_scr_lo);                                       \
+        else                                                                                                              \
+            hipLaunchKernelGGL((screen_bounds_kernel<KIND, false>), grid, dim3(256), 0, c->stream, (const double*)k->d_Xcs, \
+                               (const double*)g->d_Xs, alpha, anorm, g->cov, g->n, (long long)k->m, g->mean_c, g->y_mean, \
+                               g->y_std, kind, par, eta, k->d_scr_up, k->d_scr_lo);                                       \
+    } while (0)
+    if (g->kind == ROBO_KERNEL_MATERN52_ARD) ROBO_SCREEN_CALL(ROBO_KERNEL_MATERN52_ARD);
+    else if (g->kind == ROBO_KERNEL_RBF_ARD) ROBO_SCREEN_CALL(ROBO_KERNEL_RBF_ARD);
+    else ROBO_SCREEN_CALL(ROBO_KERNEL_FABOLAS);
+#undef ROBO_SCREEN_CALL
+    ROBO_LAUNCH_CHECK();
+    return ROBO_OK;
+}
+
+// everything acq_sweep would check is in order, and the call is one the screen handles
+static bool screen_eligible(const robo_gp* g, const robo_cand* k, int kind, double par, double eta) {
+    if (!g || !k || !g->fitted || k->dim != g->dim || k->ctx != g->ctx) return false;
+    const Tuning& t = g->ctx->tune;
+    if (t.acq_screen == 0 || !screen_kind_ok(kind, par, eta)) return false;
+    if (k->m <= (t.acq_screen_min >= 0 ? t.acq_screen_min : t.winv_max)) return false;
+    // the unscreened call must be the fused block-row substitution: its results do not depend on the tile a candidate is in
+    if (g->fp32_gram || t.predict_stepwise || winv_candidate(g, k)) return false;
+    return g->diag_min > 0.0 && g->diag_max <= SCREEN_DIAG_RATIO_MAX * g->diag_min;
+}
+
+// the sub-handle of the survivors, sized once for the most the cap lets through
+static int screen_sub(robo_cand* k, int64_t cap) {
+    if (cap < SCREEN_PROBE) cap = SCREEN_PROBE;       // the probe's tile goes through the same sub-handle
+    if (k->scr_sub && k->scr_cap >= cap) return ROBO_OK;
+    robo_cand_destroy(k->scr_sub);
+    hipFree(k->d_scr_map);
+    k->scr_sub = nullptr;
+    k->d_scr_map = nullptr;
+    k->scr_cap = 0;
+    ROBO_TRY(cand_alloc(k->ctx, cap, k->dim, &k->scr_sub));
+    ROBO_TRY(dev_alloc(&k->d_scr_map, (size_t)k->scr_sub->m_pad));
+    k->scr_cap = cap;
+    return ROBO_OK;
+}
+
+int acq_sweep_best(robo_gp* g, int32_t kind, double par, double eta, robo_cand* k, bool want_values) {
+    if (k) {
+        k->scr_outcome = ROBO_SCREEN_NOT_ELIGIBLE;
+        k->scr_n = k->scr_kept = 0;
+    }
+    if (want_values || !screen_eligible(g, k, kind, par, eta)) return acq_sweep(&g, 1, false, kind, par, &eta, k);
+    if (g->screen_gen != g->fit_gen) {
+        g->screen_gen = g->fit_gen;
+        g->screen_skip = 0;
+        g->screen_backoff = 1;
+    }
+    if (g->screen_skip > 0) {
+        --g->screen_skip;
+        return acq_sweep(&g, 1, false, kind, par, &eta, k);
+    }
+    robo_ctx* c = g->ctx;
+    hipStream_t st = c->stream;
+    ROBO_HIP_CHECK(hipSetDevice(c->device));
+    k->solved_gen = 0;
+    ROBO_TRY(launch_screen_bounds(g, k, kind, par, eta));
+    double* part = k->d_scr_lo + k->m_pad;
+    double* b = part + k->n_part;
+    double* hp = c->h_pinned + 8;
+    const dim3 blocks((unsigned)k->n_part);
+    hipLaunchKernelGGL(screen_maxlo_kernel, blocks, dim3(256), 0, st, (const double*)k->d_scr_lo, (long long)k->m, part);
+    hipLaunchKernelGGL(screen_maxlo_final_kernel, dim3(1), dim3(256), 0, st, part, k->n_part);
+    // survivors of the current b: counts, offsets, the total into pinned memory (one synchronisation)
+    int64_t kept = 0;
+    auto count_survivors = [&]() -> int {
+        hipLaunchKernelGGL(screen_count_kernel, blocks, dim3(256), 0, st, (const double*)k->d_scr_up, (long long)k->m,
+                           (const double*)b, k->d_scr_cnt);
+        hipLaunchKernelGGL(screen_scan_kernel, dim3(1), dim3(256), 0, st, k->d_scr_cnt, k->n_part, (const double*)b, hp);
+        ROBO_LAUNCH_CHECK();
+        ROBO_HIP_CHECK(hipStreamSynchronize(st));
+        kept = (int64_t)hp[0];
+        return ROBO_OK;
+    };
+    ROBO_TRY(count_survivors());
+    int64_t cap = k->m / 100 * c->tune.acq_screen_keep_max + k->m % 100 * c->tune.acq_screen_keep_max / 100;
+    if (cap > k->m) cap = k->m;
+    if (cap < 1) cap = 1;
+    k->scr_n = k->m;
+    k->scr_kept = kept;
+    bool probed = false;
+    if (kept > cap) {
+        // the incumbent from the exact values of the candidates with the largest upper bounds
+        ROBO_TRY(screen_sub(k, cap));
+        if (!k->scr_probe) ROBO_TRY(refine_alloc(c, SCREEN_PROBE, k->dim, &k->scr_probe));
+        const RefineState& ps = k->scr_probe->st;
+        robo_cand* s = k->scr_sub;
+        ROBO_TRY(launch_refine_select(c, ps, k->d_scr_up, k->m, k->d_Xcs, 0.0));
+        s->m = s->m_pad = SCREEN_PROBE;
+        s->n_part = 1;
+        s->solved_gen = 0;
+        ROBO_HIP_CHECK(hipMemcpyAsync(s->d_Xcs, ps.x, (size_t)SCREEN_PROBE * k->dim * sizeof(double), hipMemcpyDeviceToDevice, st));
+        ROBO_TRY(cand_ensure_workspace(s, g->n_pad, false));
+        ROBO_TRY(predict_scaled(g, s, false));
+        ROBO_TRY(clear_flags_on_error(s, launch_acq(c, s, kind, par, eta, false, false)));
+        hipLaunchKernelGGL(screen_probe_bound_kernel, dim3(1), dim3(64), 0, st, (const double*)s->d_acq,
+                           (const RefineSel*)ps.sel, kind, part + k->n_part, s->d_flags);
+        ROBO_LAUNCH_CHECK();
+        ROBO_TRY(count_survivors());
+        k->scr_kept = kept;
+        probed = true;
+    }
+    if (kept < 1 || kept > cap) {
+        // nothing to gain on this factor for now: the plain sweep, and a pause that doubles with every failed screen
+        k->scr_outcome = ROBO_SCREEN_FELL_BACK;
+        g->screen_skip = g->screen_backoff;
+        if (g->screen_backoff < (1 << 20)) g->screen_backoff *= 2;
+        return acq_sweep(&g, 1, false, kind, par, &eta, k);
+    }
+    g->screen_backoff = 1;
+    k->scr_outcome = probed ? ROBO_SCREEN_PROBE_USED : ROBO_SCREEN_SCREENED;
+    ROBO_TRY(screen_sub(k, cap));
+    robo_cand* s = k->scr_sub;
+    s->m = kept;
+    s->m_pad = round_up64(kept, NB);
+    s->n_part = (int)((kept + 255) / 256);
+    s->solved_gen = 0;
+    hipLaunchKernelGGL(screen_gather_kernel, blocks, dim3(256), 0, st, (const double*)k->d_scr_up, (long long)k->m, b,
+                       (const int*)k->d_scr_cnt, (const double*)k->d_Xcs, k->dim, (long long)s->m_pad, s->d_Xcs, k->d_scr_map);
+    if (s->m_pad > kept)
+        hipLaunchKernelGGL(screen_pad_kernel, dim3((unsigned)(((s->m_pad - kept) * k->dim + 255) / 256)), dim3(256), 0, st,
+                           s->d_Xcs, k->dim, (long long)kept, (long long)s->m_pad);
+    ROBO_LAUNCH_CHECK();
+    // the path the unscreened call runs for the whole batch; its event pair 25 -> 26 is the batch's (bench.py reads it)
+    ROBO_TRY(cand_ensure_workspace(s, g->n_pad, false));
+    ROBO_TRY(predict_scaled(g, s, false, nullptr, false, k->m_pad > 16384));
+    int status = launch_acq(c, s, kind, par, eta, false, false);
+    if (status == ROBO_OK) {
+        hipLaunchKernelGGL(screen_map_best_kernel, dim3(1), dim3(64), 0, st, (const double*)(s->d_part_val + s->n_part),
+                           (const long long*)(s->d_part_idx + s->n_part), s->d_flags, (const long long*)k->d_scr_map,
+                           k->d_part_val + k->n_part, k->d_part_idx + k->n_part, k->d_flags);
+        if (hipGetLastError() != hipSuccess) status = ROBO_RUNTIME_ERROR;
+    }
+    if (status != ROBO_OK) clear_flags_on_error(s, status);
+    k->solve_kernel = s->solve_kernel;
+    return clear_flags_on_error(k, status);
+}
+
+}  // namespace robo
+
+using namespace robo;
+
+extern "C" {
+
+int32_t robo_cand_last_screen(robo_cand* k, int64_t* out_n_screened, int64_t* out_n_survivors, int32_t* out_outcome) {
+    if (!k) return ROBO_BAD_ARGUMENT;
+    if (out_n_screened) *out_n_screened = k->scr_n;
+    if (out_n_survivors) *out_n_survivors = k->scr_kept;
+    if (out_outcome) *out_outcome = k->scr_outcome;
+    return ROBO_OK;
+}
+
+int32_t robo_acq_screen_bounds(robo_gp* g, int32_t acq_kind, double par, double eta, robo_cand* k, double* out_upper,
+                               double* out_lower) {
+    if (!g || !k) return ROBO_BAD_ARGUMENT;
+    ROBO_TRY(check_acq_kind(acq_kind));
+    if (!g->fitted) {
+        set_error("Model has to be trained first!");
+        return ROBO_NOT_FITTED;
+    }
+    if (k->dim != g->dim || k->ctx != g->ctx) {
+        set_error("candidate batch (dim %d) does not match the GP (dim %d) or lives on another context", k->dim, g->dim);
+        return ROBO_BAD_SHAPE;
+    }
+    if (g->fp32_gram || !screen_kind_ok(acq_kind, par, eta)) {
+        set_error("robo_acq_screen_bounds: no bound for this call (LCB needs kappa >= 0; finite eta / par; fp64 covariance "
+                  "entries)");
+        return ROBO_BAD_ARGUMENT;
+    }
+    hipStream_t st = g->ctx->stream;
+    ROBO_HIP_CHECK(hipSetDevice(g->ctx->device));
+    k->solved_gen = 0;
+    ROBO_TRY(launch_screen_bounds(g, k, acq_kind, par, eta));
+    if (out_upper)
+        ROBO_HIP_CHECK(hipMemcpyAsync(out_upper, k->d_scr_up, (size_t)k->m * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (out_lower)
+        ROBO_HIP_CHECK(hipMemcpyAsync(out_lower, k->d_scr_lo, (size_t)k->m * sizeof(double), hipMemcpyDeviceToHost, st));
+    ROBO_HIP_CHECK(hipStreamSynchronize(st));
+    return ROBO_OK;
+}
+
+}  // extern "C"
