@@ -107,7 +107,14 @@ int32_t robo_ctx_set_phase_events(robo_ctx* ctx, int32_t on);
  * acq_screen (1 = default: an argmax-only acquisition call skips the candidates that cannot win, see robo_acq_eval_cand;
  * 0 never), acq_screen_min (batches above this many candidates are screened; -1 = default: winv_max, the size above which
  * the unscreened call is the block-row substitution; tests lower it), acq_screen_keep_max (percent of the batch that may
- * survive the screen, default 25: more than that and the call falls back to the plain sweep).                          */
+ * survive the screen, default 25: more than that and the call falls back to the plain sweep),
+ * trsm_chain (small batches on two or more block rows, solved by ONE launch whose block rows hand their tiles to each
+ * other instead of one launch per block row, trsm_chain.hip: -1 = default: automatic (from three block rows on, while the
+ * launch stays within trsm_chain_max_wg), 0 never, 1 wherever legal (from two block rows on); taken by
+ * robo_gp_predict[_cand], robo_gp_predict_cov, robo_acq_eval[_cand] and robo_acq_eval_marginal_cand, bit-identical
+ * results; a launch whose hand-off times out is repeated by launches, the context stays off the chain until this key is
+ * set again, and robo_last_error_string says so although the call succeeds), trsm_chain_max_wg (the automatic rule:
+ * while 16-candidate tiles x block rows <= this many times the CU count), trsm_chain_spin_limit (tests only).           */
 int32_t robo_ctx_set_tuning(robo_ctx* ctx, const char* key, int64_t value);
 const char* robo_last_error_string(void);
 const char* robo_version_string(void);

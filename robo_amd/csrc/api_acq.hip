@@ -48,24 +48,26 @@ int acq_read_back(robo_cand* k, const double* d_vec, double* out_vec, double* ou
     return ROBO_OK;
 }
 
-int acq_accumulate(robo_gp* const* gps, int32_t S, int32_t acq_kind, double par, const double* etas, robo_cand* k) {
+int acq_accumulate(robo_gp* const* gps, int32_t S, int32_t acq_kind, double par, const double* etas, robo_cand* k,
+                   bool allow_chain) {
     if (!gps || S < 1 || !k || !etas) return ROBO_BAD_ARGUMENT;
     ROBO_TRY(check_acq_kind(acq_kind));
     ROBO_HIP_CHECK(hipSetDevice(k->ctx->device));
     for (int s = 0; s < S; ++s) {
-        ROBO_TRY(clear_flags_on_error(k, predict_core(gps[s], k)));
+        ROBO_TRY(clear_flags_on_error(k, predict_core(gps[s], k, false, nullptr, false, allow_chain)));
         ROBO_TRY(clear_flags_on_error(k, launch_acq(k->ctx, k, acq_kind, par, etas[s], true, s == 0)));
     }
     return ROBO_OK;
 }
 
-int acq_sweep(robo_gp* const* gps, int32_t S, bool marginal, int32_t acq_kind, double par, const double* etas, robo_cand* k) {
+int acq_sweep(robo_gp* const* gps, int32_t S, bool marginal, int32_t acq_kind, double par, const double* etas, robo_cand* k,
+              bool allow_chain) {
     if (marginal) {
-        ROBO_TRY(acq_accumulate(gps, S, acq_kind, par, etas, k));
+        ROBO_TRY(acq_accumulate(gps, S, acq_kind, par, etas, k, allow_chain));
         return clear_flags_on_error(k, launch_argmax(k, k->d_acq_sum, (double)S));
     }
     ROBO_TRY(check_acq_kind(acq_kind));
-    ROBO_TRY(predict_core(gps[0], k));
+    ROBO_TRY(predict_core(gps[0], k, false, nullptr, false, allow_chain));
     return clear_flags_on_error(k, launch_acq(gps[0]->ctx, k, acq_kind, par, etas[0], false, false));
 }
 
@@ -293,8 +295,16 @@ extern "C" {
 
 int32_t robo_acq_eval_cand(robo_gp* g, int32_t acq_kind, double par, double eta, robo_cand* k, double* out_acq,
                            double* out_max, int64_t* out_argmax, uint32_t* out_flags) {
-    ROBO_TRY(acq_sweep_best(g, acq_kind, par, eta, k, out_acq != nullptr));
-    return clear_flags_on_error(k, acq_read_back(k, k->d_acq, out_acq, out_max, out_argmax, out_flags));
+    // the chained solve's time-out word is looked at behind the read-back's synchronisation: a launch that gave up (it never
+    // should) turns the chain off for the context, and the second pass runs the launches
+    for (int pass = 0;; ++pass) {
+        int st = acq_sweep_best(g, acq_kind, par, eta, k, out_acq != nullptr, true);
+        if (st == ROBO_CHAIN_RETRY && pass == 0) continue;
+        ROBO_TRY(st);
+        st = acq_read_back(k, k->d_acq, out_acq, out_max, out_argmax, out_flags);
+        if (st == ROBO_OK && chain_timed_out(k->ctx) && pass == 0) continue;
+        return clear_flags_on_error(k, st);
+    }
 }
 
 int32_t robo_acq_eval(robo_gp* g, int32_t acq_kind, double par, double eta, const double* Xc, int64_t m,
@@ -315,8 +325,12 @@ int32_t robo_acq_eval(robo_gp* g, int32_t acq_kind, double par, double eta, cons
 int32_t robo_acq_eval_marginal_cand(robo_gp* const* gps, int32_t S, int32_t acq_kind, double par, const double* etas,
                                     robo_cand* k, double* out_acq, double* out_max, int64_t* out_argmax,
                                     uint32_t* out_flags) {
-    ROBO_TRY(acq_sweep(gps, S, true, acq_kind, par, etas, k));
-    return clear_flags_on_error(k, acq_read_back(k, k->d_acq, out_acq, out_max, out_argmax, out_flags));
+    for (int pass = 0;; ++pass) {          // (the second pass: after a time-out of the chained solve, robo_acq_eval_cand)
+        ROBO_TRY(acq_sweep(gps, S, true, acq_kind, par, etas, k, true));
+        const int st = acq_read_back(k, k->d_acq, out_acq, out_max, out_argmax, out_flags);
+        if (st == ROBO_OK && chain_timed_out(k->ctx) && pass == 0) continue;
+        return clear_flags_on_error(k, st);
+    }
 }
 
 int32_t robo_acq_eval_sum_cand(robo_gp* const* gps, int32_t S, int32_t acq_kind, double par, const double* etas,

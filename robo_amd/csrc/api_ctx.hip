@@ -64,6 +64,9 @@ static const TuneKey TUNE_KEYS[] = {
     {"acq_screen", nullptr, &Tuning::acq_screen, 1},
     {"acq_screen_min", &Tuning::acq_screen_min, nullptr, -1},
     {"acq_screen_keep_max", nullptr, &Tuning::acq_screen_keep_max, 25},
+    {"trsm_chain", nullptr, &Tuning::trsm_chain, -1},
+    {"trsm_chain_max_wg", nullptr, &Tuning::trsm_chain_max_wg, 4},
+    {"trsm_chain_spin_limit", &Tuning::trsm_chain_spin_limit, nullptr, -1},
 };
 
 static void tune_set(Tuning* t, const TuneKey& k, long long v) {
@@ -102,6 +105,7 @@ static void ctx_free(robo_ctx* c) {
     hipFree(c->d_fail);
     hipFree(c->d_prog);
     hipHostFree(c->h_pinned);
+    if (c->h_chain) hipHostFree(c->h_chain);
     ep_release(c);
     mc_release(c);
     if (c->own_stream) hipStreamDestroy(c->stream);
@@ -237,6 +241,7 @@ int32_t robo_ctx_set_tuning(robo_ctx* c, const char* key, int64_t value) {
         if (strcmp(key, k.name) == 0) {
             tune_set(&c->tune, k, value == INT64_MIN ? k.dflt : (long long)value);
             if (c->tune.ws_bytes < 1) c->tune.ws_bytes = (long long)6 << 30;
+            if (strcmp(key, "trsm_chain") == 0) c->chain_off = false;     // re-arms a context that a time-out took off the chain
             return ROBO_OK;
         }
     set_error("robo_ctx_set_tuning: unknown key '%s'", key);

@@ -28,13 +28,16 @@ int cand_ensure_workspace(robo_cand* k, int n_pad, bool single_chunk);        //
 int decide_winv(robo_gp* g, const robo_cand* k, bool* use);                   // the solve goes through W = L^-1 (built here)
 // fills k->d_mean / d_var (asynchronous); after_chunk(c0, cn) runs while the chunk's V = L^-1 K*^T is in the workspace;
 // need_v: the caller consumes V itself, not only its reductions
+// allow_chain: small batches may take the chained one-launch solve (trsm_chain.hip).  Only for callers that END IN A
+// SYNCHRONISATION OF THEIR OWN and call chain_timed_out behind it (true: repeat the call once -- it runs the launches now)
 int predict_core(robo_gp* g, robo_cand* k, bool single_chunk = false,
-                 const std::function<int(int64_t, int64_t)>& after_chunk = nullptr, bool need_v = false);
+                 const std::function<int(int64_t, int64_t)>& after_chunk = nullptr, bool need_v = false,
+                 bool allow_chain = false);
 // the rest of predict_core for points whose scaled rows are in k->d_Xcs already, the solve decided (decide_winv) and the
 // workspace sized: launches only
 // events: record the phase events 24..27 whatever the batch size (the survivors of a screened large batch)
 int predict_scaled(robo_gp* g, robo_cand* k, bool winv, const std::function<int(int64_t, int64_t)>& after_chunk = nullptr,
-                   bool need_v = false, bool events = false);
+                   bool need_v = false, bool events = false, bool allow_chain = false);
 bool winv_candidate(const robo_gp* g, const robo_cand* k);     // the batch and the factor qualify for the explicit inverse
 int predict_samples(robo_gp* const* gps, int32_t S, robo_cand* k, int cap);   // -> rows of k->d_mu_all / d_var_all
 int host_cand(robo_gp* g, const double* Xc, int64_t m, robo_cand** out, bool* kept);   // the handle behind host arrays
@@ -47,13 +50,19 @@ int clear_flags_on_error(robo_cand* k, int status);        // -> status; a faile
 int acq_read_back(robo_cand* k, const double* d_vec, double* out_vec, double* out_max, int64_t* out_argmax,
                   uint32_t* out_flags);
 // sum over the samples of the acquisition into k->d_acq_sum (asynchronous)
-int acq_accumulate(robo_gp* const* gps, int32_t S, int32_t acq_kind, double par, const double* etas, robo_cand* k);
+int acq_accumulate(robo_gp* const* gps, int32_t S, int32_t acq_kind, double par, const double* etas, robo_cand* k,
+                   bool allow_chain = false);
 // the sweep into k->d_acq and the argmax partials (asynchronous): gps[0]'s acquisition, or (marginal) the mean over S samples
-int acq_sweep(robo_gp* const* gps, int32_t S, bool marginal, int32_t acq_kind, double par, const double* etas, robo_cand* k);
+int acq_sweep(robo_gp* const* gps, int32_t S, bool marginal, int32_t acq_kind, double par, const double* etas, robo_cand* k,
+              bool allow_chain = false);
 // screen.hip: what robo_acq_eval_cand and its sharded / multi-device forms run.  want_values = false (the caller takes
 // (max, argmax, flags) only): an eligible call screens the batch and solves the survivors alone, leaving the winner in k's
 // argmax slots exactly as acq_sweep does; every other call is acq_sweep.
-int acq_sweep_best(robo_gp* g, int32_t acq_kind, double par, double eta, robo_cand* k, bool want_values);
+// allow_chain (see predict_core): also for the survivors and the probe.  ROBO_CHAIN_RETRY: the probe's solve gave up at the
+// synchronisation behind it -- the caller repeats the call.
+constexpr int ROBO_CHAIN_RETRY = 0x7C01;     // internal: never leaves the library
+int acq_sweep_best(robo_gp* g, int32_t acq_kind, double par, double eta, robo_cand* k, bool want_values,
+                   bool allow_chain = false);
 // the samples of an ensemble call against the candidates, then hipSetDevice.  `label` opens the messages.
 constexpr unsigned ENSEMBLE_MES_VERDICTS = 1;      // an unfitted sample is ROBO_BAD_ARGUMENT naming the sample; no shape checks
 constexpr unsigned ENSEMBLE_ONE_KIND_FP64 = 2;     // every sample has the first one's kernel kind and fp64 covariance entries

@@ -100,7 +100,7 @@ int decide_winv(robo_gp* g, const robo_cand* k, bool* use) {
 
 // need_v: the caller consumes V = L^-1 K_*^T itself (cross-covariances, full covariance), not only its reductions
 int predict_core(robo_gp* g, robo_cand* k, bool single_chunk, const std::function<int(int64_t, int64_t)>& after_chunk,
-                 bool need_v) {
+                 bool need_v, bool allow_chain) {
     if (!g || !k) return ROBO_BAD_ARGUMENT;
     if (!g->fitted) {
         set_error("Model has to be trained first!");
@@ -117,11 +117,11 @@ int predict_core(robo_gp* g, robo_cand* k, bool single_chunk, const std::functio
     bool winv = false;
     ROBO_TRY(decide_winv(g, k, &winv));
     ROBO_TRY(launch_scale_inputs(g->ctx, k->d_Xc, k->d_Xcs, g->d_theta, k->m, k->m_pad, g->dim));
-    return predict_scaled(g, k, winv, after_chunk, need_v);
+    return predict_scaled(g, k, winv, after_chunk, need_v, false, allow_chain);
 }
 
 int predict_scaled(robo_gp* g, robo_cand* k, bool winv, const std::function<int(int64_t, int64_t)>& after_chunk, bool need_v,
-                   bool events) {
+                   bool events, bool allow_chain) {
     k->solved_gen = 0;
     // event slots 24..27 bracket the phases of the LAST chunk (bench.py reads them after a sync):
     //   24 -> 25 cross-gram, 25 -> 26 triangular solve (the MFMA kernel), 26 -> 27 post
@@ -142,7 +142,10 @@ int predict_scaled(robo_gp* g, robo_cand* k, bool winv, const std::function<int(
             ROBO_TRY(launch_trsm(g, k, c0, cn));
         } else {
             if (ev) ROBO_HIP_CHECK(hipEventRecord(g->ctx->events[25], st));
-            ROBO_TRY(launch_predict_fused(g, k, c0, cn));
+            // small batches on two or more block rows: one launch chained by hand-offs, where the caller looks at its
+            // time-out word at the synchronisation it ends in (allow_chain)
+            if (allow_chain && chain_wanted(g, cn)) ROBO_TRY(launch_predict_chain(g, k, c0, cn));
+            else ROBO_TRY(launch_predict_fused(g, k, c0, cn));
         }
         if (ev) ROBO_HIP_CHECK(hipEventRecord(g->ctx->events[26], st));
         if (after_chunk) ROBO_TRY(after_chunk(c0, cn));
@@ -358,6 +361,7 @@ int32_t robo_cand_destroy(robo_cand* k) {
     hipFree(k->d_scr_lo);
     hipFree(k->d_scr_cnt);
     hipFree(k->d_scr_map);
+    hipFree(k->d_chain);
     robo_cand_destroy(k->scr_sub);
     refine_free(k->scr_probe);
     robo_ctx* ctx = k->ctx;
@@ -397,14 +401,18 @@ int32_t robo_gp_factor_cond(robo_gp* g, double* out) {
 }
 
 int32_t robo_gp_predict_cand(robo_gp* g, robo_cand* k, double* out_mean, double* out_var) {
-    ROBO_TRY(predict_core(g, k));
-    hipStream_t st = g->ctx->stream;
-    if (out_mean)
-        ROBO_HIP_CHECK(hipMemcpyAsync(out_mean, k->d_mean, (size_t)k->m * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (out_var)
-        ROBO_HIP_CHECK(hipMemcpyAsync(out_var, k->d_var, (size_t)k->m * sizeof(double), hipMemcpyDeviceToHost, st));
-    ROBO_HIP_CHECK(hipStreamSynchronize(st));
-    return ROBO_OK;
+    // the chained solve's time-out word is looked at behind the call's own synchronisation; a launch that gave up (it never
+    // should) turns the chain off for the context, and the second pass runs the launches
+    for (int pass = 0;; ++pass) {
+        ROBO_TRY(predict_core(g, k, false, nullptr, false, true));
+        hipStream_t st = g->ctx->stream;
+        if (out_mean)
+            ROBO_HIP_CHECK(hipMemcpyAsync(out_mean, k->d_mean, (size_t)k->m * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (out_var)
+            ROBO_HIP_CHECK(hipMemcpyAsync(out_var, k->d_var, (size_t)k->m * sizeof(double), hipMemcpyDeviceToHost, st));
+        ROBO_HIP_CHECK(hipStreamSynchronize(st));
+        if (!chain_timed_out(g->ctx) || pass > 0) return ROBO_OK;
+    }
 }
 
 int32_t robo_gp_predict_mixture_cand(robo_gp* const* gps, int32_t S, robo_cand* k, double* out_mean,
@@ -504,14 +512,16 @@ int32_t robo_gp_predict_cov(robo_gp* g, const double* Xc, int64_t m, double* out
     }
     robo_cand* k = nullptr;
     ROBO_TRY(robo_cand_create(g->ctx, Xc, m, g->dim, &k));
-    int st = predict_core(g, k, true, nullptr, true);
     double* d_cov = nullptr;
-    if (st == ROBO_OK && hipMalloc((void**)&d_cov, (size_t)m * m * sizeof(double)) != hipSuccess) {
+    int st = ROBO_OK;
+    if (hipMalloc((void**)&d_cov, (size_t)m * m * sizeof(double)) != hipSuccess) {
         set_error("hipMalloc of the %lld x %lld covariance failed", (long long)m, (long long)m);
         st = ROBO_RUNTIME_ERROR;
     }
-    if (st == ROBO_OK) st = launch_cov(g, k, d_cov);
-    if (st == ROBO_OK) {
+    for (int pass = 0; st == ROBO_OK; ++pass) {      // (the second pass: after a time-out of the chained solve, robo_gp_predict_cand)
+        st = predict_core(g, k, true, nullptr, true, true);
+        if (st == ROBO_OK) st = launch_cov(g, k, d_cov);
+        if (st != ROBO_OK) break;
         hipStream_t s = g->ctx->stream;
         hipError_t e = hipMemcpyAsync(out_cov, d_cov, (size_t)m * m * sizeof(double), hipMemcpyDeviceToHost, s);
         if (e == hipSuccess && out_mean)
@@ -521,6 +531,7 @@ int32_t robo_gp_predict_cov(robo_gp* g, const double* Xc, int64_t m, double* out
             set_error("predict_cov copy-out failed: %s", hipGetErrorString(e));
             st = ROBO_RUNTIME_ERROR;
         }
+        if (st != ROBO_OK || !chain_timed_out(g->ctx) || pass > 0) break;
     }
     if (d_cov) hipFree(d_cov);
     robo_cand_destroy(k);

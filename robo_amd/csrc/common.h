@@ -193,6 +193,12 @@ struct Tuning {
     long long acq_screen_min;    // ... for batches above this many candidates (-1 = default: winv_max, above which the unscreened
                                  // call is the block-row substitution; tests lower it so that the interpreter reaches the screen)
     int acq_screen_keep_max;     // ... while at most this percentage of the batch survives (25); beyond it the plain sweep runs
+    int trsm_chain;              // small batches on >= 2 block rows: all block rows in ONE launch chained by hand-offs (trsm_chain.hip)
+                                 // from the entry points that look at its time-out word: -1 auto (>= 3 block rows, within
+                                 // trsm_chain_max_wg), 0 never, 1 wherever legal
+    int trsm_chain_max_wg;       // ... auto: while (16-candidate tiles x block rows) <= this many times the CU count (4: measured)
+    long long trsm_chain_spin_limit;   // TEST ONLY: polls before a consumer gives up (-1 = PROG_SPIN_LIMIT); 0 also keeps the
+                                 // producers from publishing, so that the first wait of a launch fails at its first poll
 };
 void tuning_from_env(Tuning* t);
 }  // namespace robo
@@ -373,6 +379,7 @@ int launch_rep_accept(robo_ctx* ctx, const RepState& st, int acq_kind, double pa
 }  // namespace robo
 
 constexpr int ROBO_AUX_STREAMS = 3;
+constexpr int ROBO_CHAIN_SLOTS = 16;    // chained solves whose time-out words may be in flight between two synchronisations
 struct robo_ctx {
     int device;
     hipStream_t stream;
@@ -399,6 +406,11 @@ struct robo_ctx {
     double* h_pinned;    // small pinned staging (64 doubles)
     robo::EpWork* ep;    // robo_ep_joint_min's buffers (ep.hip), allocated on first use, grown, never shrunk
     robo::McWork* mc;    // the Monte-Carlo p_min's buffers (igmc.hip), likewise
+    // the chained solve (trsm_chain.hip): pinned copies of the time-out words of the launches since the last synchronisation
+    // that looked at them (chain_timed_out), how many, and "a launch gave up once: this context stays on the launch path"
+    unsigned* h_chain;
+    int chain_pending;
+    bool chain_off;
 };
 
 namespace robo {
@@ -523,6 +535,10 @@ struct robo_cand {
     int64_t scr_cap;                // rows scr_sub was allocated for
     int64_t scr_n, scr_kept;        // robo_cand_last_screen: candidates screened, survivors
     int scr_outcome;
+    // the chained solve (trsm_chain.hip), lazy, grows: [ticket | time-out | progress words] zeroed per launch, then the
+    // per-(tile, block row) partial sums
+    char* d_chain;
+    size_t chain_bytes;
 };
 
 // ---- launchers implemented in the .hip files (all asynchronous on ctx->stream) ------------
@@ -598,6 +614,11 @@ int winv_rows_buffer(robo_gp* gp, robo_cand* cand, int64_t rows, double** out);
 int launch_winv_rows(robo_gp* gp, robo_cand* cand, int64_t rows);
 int launch_trsm(robo_gp* gp, robo_cand* cand, int64_t c0, int64_t cn);
 int launch_predict_fused(robo_gp* gp, robo_cand* cand, int64_t c0, int64_t cn);
+// trsm_chain.hip: the small-batch block-row solve of a chunk in one launch; whether a chunk takes it; the look at the time-out
+// words after a synchronisation of the stream (true: a launch gave up -- the caller repeats its call, which runs the launches)
+bool chain_wanted(const robo_gp* gp, int64_t cn);
+int launch_predict_chain(robo_gp* gp, robo_cand* cand, int64_t c0, int64_t cn);
+bool chain_timed_out(robo_ctx* ctx);
 int launch_pack_linv(robo_gp* gp);
 int launch_grad_loglik(robo_gp* gp, double* d_V, double* d_A, double* d_alpha, double* d_part, double* d_out,
                        double* h_out);

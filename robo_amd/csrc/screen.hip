@@ -405,12 +405,12 @@ static int screen_sub(robo_cand* k, int64_t cap) {
     return ROBO_OK;
 }
 
-int acq_sweep_best(robo_gp* g, int32_t kind, double par, double eta, robo_cand* k, bool want_values) {
+int acq_sweep_best(robo_gp* g, int32_t kind, double par, double eta, robo_cand* k, bool want_values, bool allow_chain) {
     if (k) {
         k->scr_outcome = ROBO_SCREEN_NOT_ELIGIBLE;
         k->scr_n = k->scr_kept = 0;
     }
-    if (want_values || !screen_eligible(g, k, kind, par, eta)) return acq_sweep(&g, 1, false, kind, par, &eta, k);
+    if (want_values || !screen_eligible(g, k, kind, par, eta)) return acq_sweep(&g, 1, false, kind, par, &eta, k, allow_chain);
     if (g->screen_gen != g->fit_gen) {
         g->screen_gen = g->fit_gen;
         g->screen_skip = 0;
@@ -418,7 +418,7 @@ int acq_sweep_best(robo_gp* g, int32_t kind, double par, double eta, robo_cand* 
     }
     if (g->screen_skip > 0) {
         --g->screen_skip;
-        return acq_sweep(&g, 1, false, kind, par, &eta, k);
+        return acq_sweep(&g, 1, false, kind, par, &eta, k, allow_chain);
     }
     robo_ctx* c = g->ctx;
     hipStream_t st = c->stream;
@@ -461,12 +461,14 @@ int acq_sweep_best(robo_gp* g, int32_t kind, double par, double eta, robo_cand* 
         s->solved_gen = 0;
         ROBO_HIP_CHECK(hipMemcpyAsync(s->d_Xcs, ps.x, (size_t)SCREEN_PROBE * k->dim * sizeof(double), hipMemcpyDeviceToDevice, st));
         ROBO_TRY(cand_ensure_workspace(s, g->n_pad, false));
-        ROBO_TRY(predict_scaled(g, s, false));
+        ROBO_TRY(predict_scaled(g, s, false, nullptr, false, false, allow_chain));
         ROBO_TRY(clear_flags_on_error(s, launch_acq(c, s, kind, par, eta, false, false)));
         hipLaunchKernelGGL(screen_probe_bound_kernel, dim3(1), dim3(64), 0, st, (const double*)s->d_acq,
                            (const RefineSel*)ps.sel, kind, part + k->n_part, s->d_flags);
         ROBO_LAUNCH_CHECK();
         ROBO_TRY(count_survivors());
+        // (a probe whose chained solve gave up has produced no incumbent: the caller starts over, on launches)
+        if (allow_chain && chain_timed_out(c)) return clear_flags_on_error(s, ROBO_CHAIN_RETRY);
         k->scr_kept = kept;
         probed = true;
     }
@@ -475,7 +477,7 @@ int acq_sweep_best(robo_gp* g, int32_t kind, double par, double eta, robo_cand* 
         k->scr_outcome = ROBO_SCREEN_FELL_BACK;
         g->screen_skip = g->screen_backoff;
         if (g->screen_backoff < (1 << 20)) g->screen_backoff *= 2;
-        return acq_sweep(&g, 1, false, kind, par, &eta, k);
+        return acq_sweep(&g, 1, false, kind, par, &eta, k, allow_chain);
     }
     g->screen_backoff = 1;
     k->scr_outcome = probed ? ROBO_SCREEN_PROBE_USED : ROBO_SCREEN_SCREENED;
@@ -493,7 +495,7 @@ int acq_sweep_best(robo_gp* g, int32_t kind, double par, double eta, robo_cand* 
     ROBO_LAUNCH_CHECK();
     // the path the unscreened call runs for the whole batch; its event pair 25 -> 26 is the batch's (bench.py reads it)
     ROBO_TRY(cand_ensure_workspace(s, g->n_pad, false));
-    ROBO_TRY(predict_scaled(g, s, false, nullptr, false, k->m_pad > 16384));
+    ROBO_TRY(predict_scaled(g, s, false, nullptr, false, k->m_pad > 16384, allow_chain));
     int status = launch_acq(c, s, kind, par, eta, false, false);
     if (status == ROBO_OK) {
         hipLaunchKernelGGL(screen_map_best_kernel, dim3(1), dim3(64), 0, st, (const double*)(s->d_part_val + s->n_part),
