@@ -530,6 +530,43 @@ int32_t robo_kg_eval_moments(robo_ctx* ctx, int64_t m, int32_t nb, double sn2, i
                              const double* v, const double* mean, const double* disc_mean, double* out_kg,
                              double* out_max, int64_t* out_argmax, uint32_t* out_flags);
 
+/* ---- two-objective expected hypervolume improvement (Emmerich, Deutz & Klinkenberg 2011, for minimisation; not in the
+ * reference): the expected gain in dominated hypervolume of one more observation whose two objectives have independent
+ * normal posteriors.  ref = (r1, r2) is the reference point; front (P x 2, row-major) holds 0 <= P <= ROBO_EHVI_MAX_FRONT
+ * mutually non-dominated points (a_i, b_i), i = 1 .. P, every one strictly below ref in both coordinates, sorted with a
+ * strictly ascending, hence b strictly descending.  With the sentinels a_0 = -inf, a_{P+1} = r1, b_0 = r2 the region inside
+ * ref that the front does not dominate is the union of the strips [a_i, a_{i+1}) x (-inf, b_i), i = 0 .. P, and for
+ * y1 ~ N(mu1, s1^2), y2 ~ N(mu2, s2^2):
+ *   g(b; mu, s) = E[(b - y)^+] = s f((b - mu) / s),  f(z) = phi(z) + z Phi(z),  g(-inf) = 0;  s == 0: max(b - mu, 0)
+ *   EHVI        = sum_{i=0}^{P} [ g(a_{i+1}; mu1, s1) - g(a_i; mu1, s1) ] g(b_i; mu2, s2),  every term >= 0.
+ * f is taken as f(z) = max(z, 0) + f(-|z|) with the knowledge gradient's erfcx form of f(-t) above: it carries only its own
+ * conditioning eps (z^2 + 1) and is exactly 0 for z < -36.  The strips are summed in index order i = 0 .. P, the boundary
+ * value g(a_i) carried from strip to strip (P + 2 evaluations of g for objective 1, P + 1 for objective 2), by a
+ * compensated (Kahan) sum, so that the accumulation costs 2 eps of the sum whatever P is; a difference of two rounded g
+ * values that comes out negative counts as 0.  Every operation is rounded once and never contracted, and the order depends
+ * on nothing but the front: the same four moments give the same bits at any batch position, for any m, any chunking and
+ * in either entry point.
+ * A NaN among the four moments (or a negative variance): EHVI = NaN and ROBO_FLAG_NAN.  s1 == 0 or s2 == 0: ROBO_FLAG_ZERO_SIGMA, the value by the
+ * max branch (not zeroed).  argmax follows np.argmax (first index, NaN maximal) through the sweep's own reduction.
+ * The fused form runs the sweep of gp1 over cand, keeps its moments, runs the sweep of gp2, then the strip kernel and the
+ * reduction, with one synchronisation; both sweeps are chunked by the candidate workspace.  The moments are what
+ * robo_gp_predict_cand returns (output transform applied, variance floored at DBL_EPSILON), so the two GPs may differ in
+ * kernel, hyper-parameters, N and output normalisation.  out_ehvi (m) is nullable; out_trace, nullable, m x 4: per candidate
+ * mean1, var1, mean2, var2 as the kernel read them.  Later calls on the same handles return what they return on fresh ones.
+ * P outside 0 .. ROBO_EHVI_MAX_FRONT, a non-finite ref or front entry, a front that is not sorted as above or has a point
+ * not strictly below ref, a NULL required pointer, GPs or cand on different contexts: ROBO_BAD_ARGUMENT; a GP whose dim
+ * is not cand's: ROBO_BAD_SHAPE; a GP that is not fitted: ROBO_NOT_FITTED -- all before anything is launched.
+ * Event slots 30 and 31 bracket the strip kernel, under the condition of slots 24..27.                              */
+#define ROBO_EHVI_MAX_FRONT 4096
+int32_t robo_ehvi_eval_cand(robo_gp* gp1, robo_gp* gp2, robo_cand* cand, const double* front, int32_t P, const double* ref,
+                            double* out_ehvi, double* out_max, int64_t* out_argmax, uint32_t* out_flags,
+                            double* out_trace);
+/* the strip kernel alone for any model's moments: mean1, var1, mean2, var2 (m each).  Equals the fused call bit for bit
+ * when fed the fused call's own trace.                                                                              */
+int32_t robo_ehvi_eval_moments(robo_ctx* ctx, int64_t m, const double* mean1, const double* var1, const double* mean2,
+                               const double* var2, const double* front, int32_t P, const double* ref, double* out_ehvi,
+                               double* out_max, int64_t* out_argmax, uint32_t* out_flags);
+
 /* ---- entropy search: replaces InformationGain.innovations/_dh_fun/compute ---------------
  * (robo/acquisition_functions/information_gain.py:87-125,169-203,253-272), batched over candidates.
  * rep: the Nb <= 64 representer points as a candidate batch (same normalised space).  The EP

@@ -30,6 +30,7 @@ SCREEN_NOT_ELIGIBLE, SCREEN_SCREENED, SCREEN_PROBE_USED, SCREEN_FELL_BACK = 0, 1
 FANTASY_KINDS = {"kriging_believer": 0, "constant_liar": 1}   # robo_acq_batch_*: how a pick's fantasy target is chosen
 MES_MAX_K = 128                                  # robo_mes_*: cap on the sampled minima per model
 KG_MAX_DISC = 64                                 # robo_kg_*: cap on the discretisation points of the knowledge gradient
+EHVI_MAX_FRONT = 4096                            # robo_ehvi_*: cap on the points of the Pareto front
 REFINE_MAX_STARTS = 1024                         # robo_acq_refine_*: cap on n_starts
 MC_MAX_NB, MC_MAX_NP, MC_MAX_NF = 64, 512, 65535   # limits of the Monte-Carlo p_min entry points (robo_pmin_mc, robo_igmc_*)
 
@@ -53,6 +54,7 @@ SYMBOLS = [
     "robo_acq_batch_cand", "robo_acq_batch_marginal_cand",
     "robo_mes_eval_cand", "robo_mes_eval_marginal_cand", "robo_mes_sample_min_moments", "robo_mes_eval_moments",
     "robo_kg_eval_cand", "robo_kg_eval_marginal_cand", "robo_kg_eval_moments",
+    "robo_ehvi_eval_cand", "robo_ehvi_eval_moments",
     "robo_ig_eval_cand", "robo_ig_eval_per_cost_cand", "robo_ig_eval_moments", "robo_gp_cross_cov",
     "robo_ep_joint_min", "robo_pmin_mc", "robo_igmc_eval_cand", "robo_igmc_eval_moments",
     "robo_comm_create_id", "robo_comm_init", "robo_comm_destroy", "robo_comm_info", "robo_comm_allgather",
@@ -236,6 +238,9 @@ def lib():
         "robo_kg_eval_marginal_cand": [pp, i32, vp, vp, _dp, i32, _dp, _dp, C.POINTER(i64), C.POINTER(C.c_uint32), _dp, _dp],
         "robo_kg_eval_moments": [vp, i64, i32, dbl, i32, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(i64),
                                  C.POINTER(C.c_uint32)],
+        "robo_ehvi_eval_cand": [vp, vp, vp, _dp, i32, _dp, _dp, _dp, C.POINTER(i64), C.POINTER(C.c_uint32), _dp],
+        "robo_ehvi_eval_moments": [vp, i64, _dp, _dp, _dp, _dp, _dp, i32, _dp, _dp, _dp, C.POINTER(i64),
+                                   C.POINTER(C.c_uint32)],
         "robo_ig_eval_cand": [vp, vp, vp, i32, dbl, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(i64)],
         "robo_ig_eval_per_cost_cand": [vp, vp, vp, i32, dbl, _dp, _dp, _dp, _dp, _dp, _dp, vp, vp, dbl, _dp, _dp,
                                        C.POINTER(i64)],
@@ -896,6 +901,20 @@ class DeviceGP(object):
         return kg_marginal([self], cand, rep, sn2, include_self, want_values, diagnostics, marginal=False)
 
 
+    def ehvi(self, other, cand, front, ref, want_values=True, diagnostics=False):
+        """two-objective expected hypervolume improvement of ``cand`` with this GP as the first objective and ``other``
+        as the second, over the sorted front (P, 2) and the reference point (robo_ehvi_eval_cand) -> EHVIResult"""
+        front, ref = _ehvi_front(front, ref)
+        P = front.shape[0]
+        out = np.empty(cand.m) if want_values else None
+        trace = np.empty((cand.m, 4)) if (diagnostics and P <= EHVI_MAX_FRONT) else None
+        best = _Best()
+        check(lib().robo_ehvi_eval_cand(self._h, other._h, cand._h, _arr(front), P, _arr(ref),
+                                        _arr(out) if want_values else None, *best.refs,
+                                        _arr(trace) if trace is not None else None))
+        return EHVIResult(out, *best.values(), trace)
+
+
 class HyperOptResult(object):
     """robo_gp_optimize_hypers: theta / value / best of the winning start (best -1, NaN: every start was dead); per start
     final (n_starts, P), values, status (0 ran out of iterations, 1 converged, 2 stalled or no direction, 3 dead);
@@ -1005,6 +1024,38 @@ def kg_from_moments(ctx, s, v, mean, disc_mean, sn2, include_self=True):
     best = _Best()
     check(lib().robo_kg_eval_moments(ctx._h, s.shape[0], s.shape[1], float(sn2), int(bool(include_self)), _arr(s), _arr(v),
                                      _arr(mean), _arr(disc_mean), _arr(out), *best.refs))
+    return (out,) + best.values()
+
+
+class EHVIResult(object):
+    """values (m,) or None, max, argmax, flags; with diagnostics: trace (m, 4) = per candidate mean1, var1, mean2, var2 as
+    the kernel read them (include/robo_hip.h)"""
+
+    def __init__(self, values, max, argmax, flags, trace=None):
+        self.values, self.max, self.argmax, self.flags, self.trace = values, float(max), int(argmax), int(flags), trace
+
+
+def _ehvi_front(front, ref):
+    """(front (P, 2), ref (2,)) contiguous fp64; an empty front in any shape is (0, 2)"""
+    front, ref = _f64(front), _f64(ref, (2,))
+    if front.size == 0:
+        front = np.zeros((0, 2))
+    if front.ndim != 2 or front.shape[1] != 2:
+        raise ValueError("front must be (P, 2), got %r" % (front.shape,))
+    return front, ref
+
+
+def ehvi_from_moments(ctx, mean1, var1, mean2, var2, front, ref):
+    """the strip kernel of the two-objective expected hypervolume improvement alone on the device for the moments of any
+    pair of models (robo_ehvi_eval_moments): four (m,) arrays, the sorted front (P, 2), the reference point
+    -> (values, max, argmax, flags)"""
+    mean1, var1, mean2, var2 = _f64(mean1), _f64(var1), _f64(mean2), _f64(var2)
+    assert mean1.ndim == 1 and var1.shape == mean1.shape and mean2.shape == mean1.shape and var2.shape == mean1.shape
+    front, ref = _ehvi_front(front, ref)
+    out = np.empty(mean1.shape[0])
+    best = _Best()
+    check(lib().robo_ehvi_eval_moments(ctx._h, mean1.shape[0], _arr(mean1), _arr(var1), _arr(mean2), _arr(var2), _arr(front),
+                                       front.shape[0], _arr(ref), _arr(out), *best.refs))
     return (out,) + best.values()
 
 

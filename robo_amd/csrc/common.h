@@ -510,7 +510,8 @@ struct robo_cand {
     // features / outputs, EP tensors
     double *d_S, *d_F, *d_Q, *d_G, *d_igc;
     size_t f_cap, q_cap, g_cap;
-    double* d_kg;       // knowledge gradient (lazy, grows): [S x 64 discretisation means | S x m x (nb + 2) trace]
+    double* d_kg;       // knowledge gradient (lazy, grows): [S x 64 discretisation means | S x m x (nb + 2) trace]; the expected
+                        // hypervolume improvement's [front (4096 x 2) | m x 4 trace] (api_ehvi.hip)
     size_t kg_cap;
     double* h_igkey;    // host copy of the EP state whose device form d_G / d_igc hold (compared in full before an upload
     size_t igkey_len;   // is skipped: compute() is called many times per update(), information_gain.py:87-125 / :153-167)
@@ -671,6 +672,11 @@ int launch_cross_cov(robo_gp* gp, robo_cand* cand, robo_cand* rep, int64_t c0, i
 // nb discretisation means; first: acq_sum[c] = KG, else acq_sum[c] += KG; d_trace (m x (nb + 2)) nullable
 int launch_kg(robo_ctx* ctx, const double* d_S, const double* d_var, const double* d_mean, const double* d_disc, int64_t m,
               int nb, double sn2, int include_self, bool first, double* d_acq_sum, unsigned* d_flags, double* d_trace);
+// ehvi.hip: the two-objective expected hypervolume improvement of candidates c < m from their four moments over the sorted
+// front d_front (P x 2) and the reference point into d_out; d_trace (m x 4: mean1, var1, mean2, var2) nullable
+int launch_ehvi(robo_ctx* ctx, const double* d_mean1, const double* d_var1, const double* d_mean2, const double* d_var2,
+                const double* d_front, int P, double r1, double r2, int64_t m, double* d_out, unsigned* d_flags,
+                double* d_trace);
 int launch_ig_dh(robo_ctx* ctx, const double* d_S, const double* d_var, double* d_F, double* d_Q, const double* d_G,
                  const double* d_consts, int64_t c0, int64_t cn, int64_t m, int nb, int npts, int kf, double sn2,
                  double H, double* d_out);
