@@ -131,3 +131,55 @@ class Posterior(object):
         else:
             self_k = np.full(Ks.shape[0], T(self.amp))
         return mu, self_k - np.sum(V * V, axis=0)
+
+    def covariance(self, Xa_s, Xb_s=None):
+        """posterior covariance k(a, b) - v_a . v_b between scaled rows (Xb_s None: Xa_s with itself); signed, NOT floored"""
+        Va = solve_lower(self.Lf, kernel(self.kind, self.amp, Xa_s, self.Xs, blr=self.blr, dtype=self.dtype).T)
+        Vb = Va if Xb_s is None else \
+            solve_lower(self.Lf, kernel(self.kind, self.amp, Xb_s, self.Xs, blr=self.blr, dtype=self.dtype).T)
+        return kernel(self.kind, self.amp, Xa_s, Xb_s, blr=self.blr, dtype=self.dtype) - Va.T @ Vb
+
+    def gradients(self, Xcs, inv_sqrt_metric):
+        """(d mean / d x, d variance / d x), each (M, D), at scaled candidate rows, in the UNSCALED input space:
+        inv_sqrt_metric (D,) = d xs_d / d x_d (1 for the Fabolas fidelity column).  With v = L^-1 k_*, w_d = L^-1 d k_* / d xs_d:
+            d mean / d xs_d = w_d . z,      d var / d xs_d = d k(x, x) / d xs_d - 2 v . w_d
+        (robo_amd/csrc/predgrad.hip).  Stationary kernels k = amp f(r2): d k / d xs_d = amp f'(r2) 2 (xs_d - xs'_d), f' =
+        -(5/6)(1 + t) e^-t (Matern 5/2, t = sqrt(5 r2)) or -f / 2 (RBF); k(x, x) is constant.  Fabolas k = amp prod_d m(df_d^2)
+        (a + b u u'): the same with the one-dimensional factor, d k / d u = amp prod b u' and d k(x, x) / d u = 2 amp b u."""
+        T = np.dtype(self.dtype).type
+        A, B = np.asarray(Xcs).astype(self.dtype), np.asarray(self.Xs).astype(self.dtype)
+        M, D = A.shape
+        diff = A[:, None, :] - B[None, :, :]                                # (M, N, D)
+        dK = np.empty((D,) + diff.shape[:2], dtype=self.dtype)
+        dself = np.zeros((M, D), dtype=self.dtype)
+        if self.kind == "fabolas":
+            a, b = T(self.blr[0]), T(self.blr[1])
+            s2 = diff[:, :, :-1] ** 2
+            t = np.sqrt(T(5) * s2)
+            fac = (T(1) + t + T(5) * s2 / T(3)) * np.exp(-t)               # the factors m(df_d^2)
+            dfac = -(T(5) / T(6)) * (T(1) + t) * np.exp(-t) * T(2) * diff[:, :, :-1]
+            uu = A[:, -1][:, None] * B[:, -1][None, :]
+            for d in range(D - 1):
+                others = np.prod(np.delete(fac, d, axis=2), axis=2)
+                dK[d] = T(self.amp) * others * dfac[:, :, d] * (a + b * uu)
+            dK[D - 1] = T(self.amp) * np.prod(fac, axis=2) * b * B[:, -1][None, :]
+            dself[:, D - 1] = T(2) * T(self.amp) * b * A[:, -1]
+        else:
+            r2 = np.sum(diff * diff, axis=2)
+            if self.kind == "matern52":
+                t = np.sqrt(T(5) * r2)
+                df = -(T(5) / T(6)) * (T(1) + t) * np.exp(-t)
+            elif self.kind == "rbf":
+                df = T(-0.5) * np.exp(T(-0.5) * r2)
+            else:
+                raise ValueError(self.kind)
+            for d in range(D):
+                dK[d] = T(self.amp) * df * T(2) * diff[:, :, d]
+        V = solve_lower(self.Lf, kernel(self.kind, self.amp, Xcs, self.Xs, blr=self.blr, dtype=self.dtype).T)
+        dm, dv = np.empty((M, D), dtype=self.dtype), np.empty((M, D), dtype=self.dtype)
+        ism = np.asarray(inv_sqrt_metric, dtype=np.float64).astype(self.dtype)
+        for d in range(D):
+            Wd = solve_lower(self.Lf, dK[d].T)
+            dm[:, d] = (Wd.T @ self.z) * ism[d]
+            dv[:, d] = (dself[:, d] - T(2) * np.sum(V * Wd, axis=0)) * ism[d]
+        return dm, dv

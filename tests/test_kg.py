@@ -2,8 +2,9 @@
 robo_kg_eval_moments; the KnowledgeGradient class and the "kg" front end) against tests/kg_oracle.py.
 
 CPU: through the interpreter (tests/hipemu).  -m gpu: the same checks at the same small shapes on the MI355X, plus the
-fused form at N = 256, D = 4, m = 32 773, nb = 50, where a chunk holds at least 2 x num_cu x 64 candidates and the
-cross-covariance takes its 128-row tile.
+fused form at N = 256, D = 4, m = 256 num_cu + 5 (65 541 on the 256-CU part), nb = 50: the cross-covariance takes its
+128-row tile when a workspace pass holds at least 2 x num_cu tiles of 128 candidates (infogain.hip launch_cross_cov), and
+the test asserts that rule's own inputs.
 
 The oracle is the envelope rule in np.longdouble, itself checked against plain quadrature (test_oracle_against_quadrature).
 
@@ -15,7 +16,7 @@ or the inputs of the moments form); per candidate
 16 = [3.6 (f in fp64, measured against 60-digit arithmetic) + 3 (the breakpoint: two rounded differences and a quotient,
 each amplified by the term's conditioning t^2)], doubled.  Largest observed error / (eps sum_k term_k (c_k^2 + 1)):
     interpreter:   2.23 (moments cases), 3.55 (fused cases)
-    MI355X:        2.23 (moments cases), 4.41 (fused cases), 2.17 (fused large)
+    MI355X:        2.23 (moments cases), 4.41 (fused cases), 2.14 (fused large)
 """
 import os
 import sys
@@ -35,7 +36,7 @@ from oracle import gp_oracle as O  # noqa: E402
 LD = KO.LD
 BOUND_FACTOR = 16           # KO.bound
 SMALL = dict(N=80, D=3, Ms=(400, 401), nbs=(1, 2, 37, 64), kinds=("matern52", "rbf"))
-LARGE = dict(N=256, D=4, M=32768 + 5, nb=50)
+LARGE = dict(N=256, D=4, nb=50)              # M = 256 num_cu + 5: sized from the device in test_fused_large_gpu
 
 
 @pytest.fixture(scope="module")
@@ -668,8 +669,12 @@ def test_classes_and_front_end_gpu(gpu_ctx):
 
 @pytest.mark.gpu
 def test_fused_large_gpu(gpu_ctx):
-    """a chunk of at least 2 x num_cu x 64 candidates: the cross-covariance's 128-row tile, signed"""
-    sz = LARGE
+    """a chunk of at least 2 x num_cu tiles of 128 candidates (2 num_cu + 1 of them, the last one ragged): the
+    cross-covariance's 128-row tile, signed.  num_cu is the device's multiprocessor count, the number the library reads
+    (torch's device properties, asked in a child process: vcons_checks.device_cu_count)."""
+    from vcons_checks import device_cu_count
+    num_cu = device_cu_count()
+    sz = dict(LARGE, M=256 * num_cu + 5)
     worst = _Worst()
     rs, X, y = _data(sz["N"], sz["D"], 4)
     theta = _theta(sz["D"], _ls2(sz["D"]))
@@ -679,7 +684,7 @@ def test_fused_large_gpu(gpu_ctx):
     try:
         rows = np.concatenate((np.arange(0, sz["M"], 97), np.arange(sz["M"] - 6, sz["M"])))
         r = _check_fused_one(gpu_ctx, g, cand, rep, 1e-2, True, "fused large", worst, rows)
-        assert cand.chunk() >= 32768, cand.chunk()                              # the 128-row tile was really taken
+        assert cand.chunk() // 128 >= 2 * num_cu, (cand.chunk(), num_cu)        # launch_cross_cov's rule for the 128-row tile
         orc = _oracle_posterior("matern52", theta, X, y, Xc[rows], Z, "large")
         _check_trace(r, orc, 1.0, "fused large", rows)
         assert orc["s"].min() < -1e-6 and r.trace[:, :sz["nb"]].min() < -1e-6

@@ -239,6 +239,10 @@ def test_refstub_kernels_equal_oracle_kernels():
         import george
     finally:
         sys.path.remove(stub)
+        # the stand-in must not stay importable: a later test of the same process that installs robo_amd.compat without
+        # `force` (tests/test_infogain_mc.py) refuses to shadow a `george` it finds (the local name keeps the module alive)
+        for name in [m for m in sys.modules if m == "george" or m.startswith("george.")]:
+            del sys.modules[name]
     rs = np.random.RandomState(0)
     D = 4
     X1, X2 = rs.rand(23, D), rs.rand(17, D)
