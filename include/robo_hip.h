@@ -567,6 +567,52 @@ int32_t robo_ehvi_eval_moments(robo_ctx* ctx, int64_t m, const double* mean1, co
                                const double* var2, const double* front, int32_t P, const double* ref, double* out_ehvi,
                                double* out_max, int64_t* out_argmax, uint32_t* out_flags);
 
+/* ---- pathwise posterior samples (Matheron's rule; Wilson et al. 2020, "Efficiently sampling functions from Gaussian
+ * process posteriors"; not in the reference): S whole functions drawn from the posterior of one fitted GP, evaluated and
+ * minimised over candidate batches of any size -- Thompson sampling, and S parallel proposals from one call.
+ *   f_s(x) = c + phi(x) . w_s + k(x, X) . alpha_s,     alpha_s = (K + noise I)^-1 (y - c - Phi_X w_s - sqrt(noise) eps_s)
+ * All inputs are in the GP's scaled space: x~ = x (.) ism with ism the inverse square-root metric scale_inputs_kernel
+ * applies.  Kernel kinds ROBO_KERNEL_MATERN52_ARD and ROBO_KERNEL_RBF_ARD only.
+ *   Features.   phi_f(x) = sqrt(2 amp / F) cos(x~ . omega_f + b_f), f = 0 .. F - 1.  The caller gives omega (F x D,
+ *               row-major), phase b (F) and the standard-normal draws w (S x F) and eps (S x N).  The library draws nothing:
+ *               the result is a deterministic function of its arguments.
+ *   Right-hand side.  r_s = (y - c) - Phi_X w_s - sqrt(noise + JITTER) eps_s, with y, c and the noise exactly what the fit
+ *               used (y after the output normalisation, noise + JITTER the fit's diagonal addition); Phi_X is phi at the
+ *               training rows, evaluated by the kernel that later evaluates candidates.
+ *   Weights.    alpha_s = L^-T L^-1 r_s with the factor the GP holds, by forward and backward block rows with the fit's
+ *               inverted diagonal blocks, followed by ONE step of iterative refinement against K itself with the same factor:
+ *               rho_s = r_s - (K alpha_s + (noise + JITTER) alpha_s), alpha_s += L^-T L^-1 rho_s, K alpha_s at the training
+ *               rows formed by the path kernel (diagonal entries exactly amp).  alpha is large where the noise is small
+ *               (like sqrt(N) / noise against values of O(1)), so the few ulps by which the factor's K differs from the
+ *               kernel's own entries would otherwise reach the values.  A path's weights are formed by the same
+ *               operations whatever S is.
+ *   Value.      f_s(x) = c + sum_f phi_f(x) w_sf + sum_j k(x~, X~_j) alpha_sj, then the output transform of
+ *               robo_gp_predict_cand (f y_std + y_mean).  One accumulator per (x, s) takes the training points in tiles of 64 in
+ *               index order, then the features in tiles of 64 in index order, each product on the fp64 matrix pipe; k is
+ *               formed from |x~|^2 + |X~_j|^2 - 2 x~ . X~_j (clamped at 0).  Consequently the bits of f_s(x) depend only on x,
+ *               the GP and path s's own draws: not on the candidate's position in the batch, on m, on the chunking, on S or
+ *               on the other paths' draws.
+ *   Pick.       Per path np.argmax(-f_s): first index, NaN maximal; out_min[s] is f_s at the pick.
+ *   NaN.        A NaN coordinate of a candidate gives NaN in every path at that candidate and ROBO_FLAG_NAN.
+ * robo_paths_create is one call with one synchronisation.  The object is a SNAPSHOT: it keeps the scaled training rows, the
+ * metric, alpha, omega, b, w, the amplitude, the kind, c and the output transform.  Later fits, robo_gp_set_data or the
+ * destruction of the GP do not change a paths object.  Kind ROBO_KERNEL_FABOLAS (the kernel is not stationary), F outside
+ * 1 .. ROBO_PATHS_MAX_FEATURES, S outside 1 .. ROBO_PATHS_MAX, a NULL pointer, a non-finite entry of omega, phase, w or
+ * eps: ROBO_BAD_ARGUMENT; a GP that is not fitted: ROBO_NOT_FITTED -- all before anything is launched.
+ * robo_paths_eval_cand is one call with one synchronisation, chunked by the candidate workspace (S x chunk values) when the
+ * values are asked for, a per-path best carried across the chunks.  out_values (S x m, row-major) is nullable, out_min (S),
+ * out_argmin (S) and out_flags are not.  cand's dim is not the GP's: ROBO_BAD_SHAPE; cand on another context or a NULL
+ * pointer: ROBO_BAD_ARGUMENT.  robo_paths_destroy(NULL) is harmless.  Event slots 30 and 31 bracket the passes of the path
+ * kernel (with the values' copies in between when they are asked for), under the condition of slots 24..27.               */
+#define ROBO_PATHS_MAX 64             /* S */
+#define ROBO_PATHS_MAX_FEATURES 4096  /* F */
+typedef struct robo_paths robo_paths; /* S posterior sample paths of one fitted GP (a snapshot) */
+int32_t robo_paths_create(robo_gp* gp, int32_t F, int32_t S, const double* omega, const double* phase,
+                          const double* w, const double* eps, robo_paths** out);
+int32_t robo_paths_eval_cand(robo_paths* p, robo_cand* cand, double* out_values /* S x m, nullable */,
+                             double* out_min /* S */, int64_t* out_argmin /* S */, uint32_t* out_flags);
+int32_t robo_paths_destroy(robo_paths* p);
+
 /* ---- entropy search: replaces InformationGain.innovations/_dh_fun/compute ---------------
  * (robo/acquisition_functions/information_gain.py:87-125,169-203,253-272), batched over candidates.
  * rep: the Nb <= 64 representer points as a candidate batch (same normalised space).  The EP

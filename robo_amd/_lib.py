@@ -31,6 +31,8 @@ FANTASY_KINDS = {"kriging_believer": 0, "constant_liar": 1}   # robo_acq_batch_*
 MES_MAX_K = 128                                  # robo_mes_*: cap on the sampled minima per model
 KG_MAX_DISC = 64                                 # robo_kg_*: cap on the discretisation points of the knowledge gradient
 EHVI_MAX_FRONT = 4096                            # robo_ehvi_*: cap on the points of the Pareto front
+PATHS_MAX = 64                                   # robo_paths_*: cap on the sample paths of one object
+PATHS_MAX_FEATURES = 4096                        # ... and on its random Fourier features
 REFINE_MAX_STARTS = 1024                         # robo_acq_refine_*: cap on n_starts
 MC_MAX_NB, MC_MAX_NP, MC_MAX_NF = 64, 512, 65535   # limits of the Monte-Carlo p_min entry points (robo_pmin_mc, robo_igmc_*)
 
@@ -55,6 +57,7 @@ SYMBOLS = [
     "robo_mes_eval_cand", "robo_mes_eval_marginal_cand", "robo_mes_sample_min_moments", "robo_mes_eval_moments",
     "robo_kg_eval_cand", "robo_kg_eval_marginal_cand", "robo_kg_eval_moments",
     "robo_ehvi_eval_cand", "robo_ehvi_eval_moments",
+    "robo_paths_create", "robo_paths_eval_cand", "robo_paths_destroy",
     "robo_ig_eval_cand", "robo_ig_eval_per_cost_cand", "robo_ig_eval_moments", "robo_gp_cross_cov",
     "robo_ep_joint_min", "robo_pmin_mc", "robo_igmc_eval_cand", "robo_igmc_eval_moments",
     "robo_comm_create_id", "robo_comm_init", "robo_comm_destroy", "robo_comm_info", "robo_comm_allgather",
@@ -241,6 +244,9 @@ def lib():
         "robo_ehvi_eval_cand": [vp, vp, vp, _dp, i32, _dp, _dp, _dp, C.POINTER(i64), C.POINTER(C.c_uint32), _dp],
         "robo_ehvi_eval_moments": [vp, i64, _dp, _dp, _dp, _dp, _dp, i32, _dp, _dp, _dp, C.POINTER(i64),
                                    C.POINTER(C.c_uint32)],
+        "robo_paths_create": [vp, i32, i32, _dp, _dp, _dp, _dp, pp],
+        "robo_paths_eval_cand": [vp, vp, _dp, _dp, C.POINTER(i64), C.POINTER(C.c_uint32)],
+        "robo_paths_destroy": [vp],
         "robo_ig_eval_cand": [vp, vp, vp, i32, dbl, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(i64)],
         "robo_ig_eval_per_cost_cand": [vp, vp, vp, i32, dbl, _dp, _dp, _dp, _dp, _dp, _dp, vp, vp, dbl, _dp, _dp,
                                        C.POINTER(i64)],
@@ -914,6 +920,11 @@ class DeviceGP(object):
                                         _arr(trace) if trace is not None else None))
         return EHVIResult(out, *best.values(), trace)
 
+    def sample_paths(self, omega, phase, w, eps):
+        """S posterior sample paths of the fitted GP from the caller's draws: omega (F, D) and phase (F,) in the scaled
+        space (util/spectral.py draw_features), w (S, F) and eps (S, N) standard normal (robo_paths_create) -> PosteriorPaths"""
+        return PosteriorPaths(self, omega, phase, w, eps)
+
 
 class HyperOptResult(object):
     """robo_gp_optimize_hypers: theta / value / best of the winning start (best -1, NaN: every start was dead); per start
@@ -1057,6 +1068,59 @@ def ehvi_from_moments(ctx, mean1, var1, mean2, var2, front, ref):
     check(lib().robo_ehvi_eval_moments(ctx._h, mean1.shape[0], _arr(mean1), _arr(var1), _arr(mean2), _arr(var2), _arr(front),
                                        front.shape[0], _arr(ref), _arr(out), *best.refs))
     return (out,) + best.values()
+
+
+class PathsResult(object):
+    """values (S, m) or None, min (S,), argmin (S,) -- per path np.argmax(-f): first index, NaN maximal --, flags"""
+
+    def __init__(self, values, min, argmin, flags):
+        self.values, self.min, self.argmin, self.flags = values, min, argmin, int(flags)
+
+
+class PosteriorPaths(object):
+    """robo_paths: S posterior sample paths of one fitted GP (Matheron's rule, include/robo_hip.h).  A snapshot: later fits
+    of the GP do not change it."""
+
+    def __init__(self, gp, omega, phase, w, eps):
+        self._h = None
+        omega, phase, w, eps = _f64(omega), _f64(phase), _f64(w), _f64(eps)
+        if omega.ndim != 2 or omega.shape[1] != gp.dim:
+            raise RoboBadShape("omega must be (F, %d), got %r" % (gp.dim, omega.shape))
+        F = omega.shape[0]
+        if phase.shape != (F,) or w.ndim != 2 or w.shape[1] != F or eps.shape != (w.shape[0], gp.n):
+            raise RoboBadShape("phase must be (F,), w (S, F) and eps (S, N = %d): got %r, %r, %r"
+                               % (gp.n, phase.shape, w.shape, eps.shape))
+        self.ctx, self.dim, self.n_features, self.n_paths = gp.ctx, gp.dim, F, w.shape[0]
+        self._owner = lib()
+        h = C.c_void_p()
+        check(self._owner.robo_paths_create(gp._h, F, self.n_paths, _arr(omega), _arr(phase), _arr(w), _arr(eps), C.byref(h)))
+        self._h = h
+
+    def evaluate(self, Xc, want_values=True):
+        """the paths over a Candidates handle or an (m, D) array in the GP's input space -> PathsResult"""
+        own = not isinstance(Xc, Candidates)
+        cand = Candidates(self.ctx, Xc) if own else Xc
+        try:
+            S = self.n_paths
+            out = np.empty((S, cand.m)) if want_values else None
+            mn, am, fl = np.empty(S), np.empty(S, dtype=np.int64), C.c_uint32(0)
+            check(lib().robo_paths_eval_cand(self._h, cand._h, _arr(out) if want_values else None, _arr(mn),
+                                             am.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(fl)))
+            return PathsResult(out, mn, am, fl.value)
+        finally:
+            if own:
+                cand.close()
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            self._owner.robo_paths_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class BatchResult(object):

@@ -1,0 +1,187 @@
+"""Thompson sampling by pathwise posterior samples (Matheron's rule; Wilson et al. 2020) -- no counterpart in the reference.
+
+EI, PI, LCB, MES, KG and EHVI score a candidate from its posterior moments.  Thompson sampling draws a whole function from
+the posterior and minimises it; q paths give q proposals from one call, without fantasies.  A path is
+
+    f_s(x) = c + phi(x) . w_s + k(x, X) . alpha_s,     alpha_s = (K + noise I)^-1 (y - c - Phi_X w_s - sqrt(noise) eps_s)
+
+with phi the random Fourier features of the prior (util/spectral.py) and w_s, eps_s standard normal.  The draws are made
+here from ``rng``; all arithmetic runs on the device (robo_amd/csrc/paths.hip; the rule is stated in include/robo_hip.h).
+
+* ``GaussianProcess``: all paths come from the one fitted GP.
+* ``GaussianProcessMCMC``: every path first draws one hyper-parameter sample uniformly -- this is how Thompson sampling
+  marginalises, so the class is NOT wrapped in ``MarginalizationGPMCMC``.  One paths object per distinct sample.
+
+The acquisition value is -f_0(x) (path 0), so that the maximisers' argmax is the path's minimiser.
+"""
+import numpy as np
+
+from robo_amd import _lib
+from robo_amd.acquisition_functions.base_acquisition import BaseAcquisitionFunction
+from robo_amd.util.spectral import draw_features
+
+
+class ThompsonSampling(BaseAcquisitionFunction):
+
+    # a path's minimiser over a slice of the candidates is not the batch's: no candidate shard
+    # (maximizers/random_sampling.py _check_candidate_shard)
+    candidate_shard = False
+
+    def __init__(self, model, n_paths=1, n_features=1024, rng=None):
+        super(ThompsonSampling, self).__init__(model)
+        self.n_paths, self.n_features = int(n_paths), int(n_features)
+        if not 1 <= self.n_paths <= _lib.PATHS_MAX:
+            raise ValueError("n_paths = %d, must be in [1, %d]" % (self.n_paths, _lib.PATHS_MAX))
+        if not 1 <= self.n_features <= _lib.PATHS_MAX_FEATURES:
+            raise ValueError("n_features = %d, must be in [1, %d]" % (self.n_features, _lib.PATHS_MAX_FEATURES))
+        self.rng = np.random.RandomState(np.random.randint(0, 10000)) if rng is None else rng
+        self.last_max = None
+        self.last_argmax = None
+        self.hyper_index = None          # (n_paths,) the hyper-parameter sample behind every path (all 0 for a GaussianProcess)
+        self._groups = []                # [(PosteriorPaths, path numbers it holds in order)]
+        self._stale = True               # paths are drawn on the first use after update(): the model may not be trained yet
+
+    # ---- the draws ----------------------------------------------------------------------------------------------------------
+    def _sub_models(self):
+        model = self.model
+        subs = list(model.models) if hasattr(model, "models") else [model]
+        if getattr(model, "devices", None) or any(getattr(m, "devices", None) for m in subs):
+            raise NotImplementedError("ThompsonSampling runs on one device: multi-device models are not implemented "
+                                      "(devices=%r)" % (getattr(model, "devices", None),))
+        for m in subs:
+            if not (hasattr(m, "acquisition") and hasattr(m, "gp") and hasattr(m, "_normalised")) or hasattr(m, "normalize"):
+                raise TypeError("ThompsonSampling needs a robo_amd GaussianProcess or GaussianProcessMCMC model (got %s)"
+                                % type(m).__name__)
+        if not subs or not getattr(model, "is_trained", False):
+            raise Exception('Model has to be trained first!')
+        return subs
+
+    def _close(self):
+        for paths, _ in self._groups:
+            paths.close()
+        self._groups = []
+
+    def update(self, model):
+        """the retrained model: new features and new paths (drawn when first used)"""
+        self.model = model
+        self._stale = True
+
+    def _draw(self, n_paths=None):
+        """Per path, in path order: the hyper-parameter sample (``rng.randint(len(models))``, GaussianProcessMCMC only).
+        Then per distinct sample in ascending order: (omega, phase) = draw_features, w = standard_normal((S_i, F)),
+        eps = standard_normal((S_i, N))."""
+        subs = self._sub_models()
+        self._close()
+        if n_paths is not None:
+            self.n_paths = int(n_paths)
+        S, F = self.n_paths, self.n_features
+        if len(subs) > 1:
+            self.hyper_index = np.array([int(self.rng.randint(len(subs))) for _ in range(S)], dtype=np.int64)
+        else:
+            self.hyper_index = np.zeros(S, dtype=np.int64)
+        for i in sorted(set(self.hyper_index.tolist())):
+            m = subs[i]
+            m._materialise()
+            members = np.flatnonzero(self.hyper_index == i)
+            omega, phase = draw_features(m.kernel.kind, m.gp.dim, F, self.rng)
+            w = self.rng.standard_normal((len(members), F))
+            eps = self.rng.standard_normal((len(members), m.gp.n))
+            self._groups.append((m.gp.sample_paths(omega, phase, w, eps), members))
+        self._stale = False
+
+    def _ready(self):
+        if self._stale or not self._groups:
+            self._draw()
+        return self._sub_models()[0]
+
+    # ---- evaluation ---------------------------------------------------------------------------------------------------------
+    def _candidates(self, X, sub):
+        if isinstance(X, _lib.CandidateShards):
+            raise NotImplementedError("ThompsonSampling runs on one device: candidate shards are not implemented")
+        if isinstance(X, _lib.Candidates):
+            if not sub.normalize_input:
+                raise TypeError("ThompsonSampling on a device candidate batch needs a model with normalize_input=True")
+            return X
+        return _lib.Candidates(sub.gp.ctx, sub._normalised(np.asarray(X, dtype=np.float64)))
+
+    def _evaluate(self, X, want_values, paths=None):
+        """-> (values (S, m) or None, min (S,), argmin (S,)) in path order; ``paths``: only the groups that hold one of them"""
+        sub = self._ready()
+        cand = self._candidates(X, sub)
+        try:
+            S = self.n_paths
+            vals = np.empty((S, cand.m)) if want_values else None
+            mn, am = np.full(S, np.nan), np.full(S, -1, dtype=np.int64)
+            for group, members in self._groups:
+                if paths is not None and not np.intersect1d(members, paths).size:
+                    continue
+                r = group.evaluate(cand, want_values=want_values)
+                mn[members], am[members] = r.min, r.argmin
+                if want_values:
+                    vals[members] = r.values
+            return vals, mn, am
+        finally:
+            if cand is not X:
+                cand.close()
+
+    def compute(self, X, derivative=False, **kwargs):
+        """-f_0(X): the negated first path, (M,)"""
+        if derivative:
+            raise NotImplementedError("ThompsonSampling has no derivative")
+        vals, mn, am = self._evaluate(X, True, paths=[0])
+        self.last_max, self.last_argmax = -float(mn[0]), int(am[0])
+        return -vals[0]
+
+    def argmax(self, X):
+        """Index of the first path's minimiser among X ((M, D) in the caller's input space, or a device batch
+        ``_lib.Candidates`` in the normalised one): only the pick comes back."""
+        _, mn, am = self._evaluate(X, False, paths=[0])
+        self.last_max, self.last_argmax = -float(mn[0]), int(am[0])
+        return int(am[0])
+
+    def argmax_sharded(self, comm, X_slice, global_offset):
+        raise NotImplementedError("ThompsonSampling has no candidate shard: multi-device and sharded forms are not "
+                                  "implemented (use shard=False)")
+
+    def select_batch(self, X, q, **unused):
+        """q distinct rows of X, one per path -> (q, D) points in the caller's input space; ``last_batch`` keeps the row
+        indices.  Path j takes its minimiser; when that row is taken already it takes its best row not yet taken (one
+        read-back of that path's values).  With fewer than q paths, q paths are redrawn.  The fantasy arguments of the
+        greedy selections are ignored: a path needs none."""
+        q = int(q)
+        sub = self._sub_models()[0]
+        if self._stale or not self._groups or self.n_paths < q:
+            self._draw(max(q, self.n_paths) if self.n_paths < q else None)
+        cand = self._candidates(X, sub)
+        try:
+            if q < 1 or q > cand.m:
+                raise ValueError("select_batch: q = %d outside 1 .. m = %d" % (q, cand.m))
+            _, mn, am = self._evaluate(cand, False, paths=np.arange(q))
+            picks = []
+            for j in range(q):
+                i = int(am[j])
+                if i in picks:
+                    vals, _, _ = self._evaluate(cand, True, paths=[j])
+                    neg = -vals[j]
+                    neg[picks] = -np.inf                   # (NaN stays maximal among the rows not yet taken)
+                    i = int(np.argmax(neg))
+                picks.append(i)
+            self.last_batch = np.array(picks, dtype=np.int64)
+            self.last_max, self.last_argmax = -float(mn[0]), int(am[0])
+            pts = np.array([cand.point(i) for i in picks]).reshape(q, cand.dim)
+        finally:
+            if cand is not X:
+                cand.close()
+        if not sub.normalize_input:
+            return pts
+        lower, upper = np.asarray(sub.lower, dtype=np.float64), np.asarray(sub.upper, dtype=np.float64)
+        return lower + (upper - lower) * pts
+
+    def __deepcopy__(self, memo):
+        import copy
+        dup = ThompsonSampling.__new__(ThompsonSampling)
+        memo[id(self)] = dup
+        for k, v in self.__dict__.items():
+            dup.__dict__[k] = [] if k == "_groups" else copy.deepcopy(v, memo)
+        dup._stale = True
+        return dup

@@ -7,7 +7,8 @@ without george, pybnn and pyrfr: :2,5,8,11), wired to the MI355X GP path:
     n_hypers 3 * len(kernel), made even                      (:85-87)
     model    GaussianProcess | GaussianProcessMCMC(chain_length=200, burnin_steps=100)  (:89-100)
     acq      EI | LogEI | PI | LCB, wrapped in MarginalizationGPMCMC for gp_mcmc       (:114-129)
-             | MES | KnowledgeGradient (not in the reference)
+             | MES | KnowledgeGradient | ThompsonSampling (not in the reference; Thompson sampling marginalises over
+             the hyper-parameter samples itself and is not wrapped)
 
     maximiser RandomSampling | SciPyOptimizer | DifferentialEvolution                    (:131-139)
               | DeviceRandomSampling | DeviceGradientAscent (not in the reference)
@@ -19,7 +20,8 @@ import logging
 
 import numpy as np
 
-from robo_amd.acquisition_functions import EI, LCB, MES, PI, KnowledgeGradient, LogEI, MarginalizationGPMCMC
+from robo_amd.acquisition_functions import (EI, LCB, MES, PI, KnowledgeGradient, LogEI, MarginalizationGPMCMC,
+                                            ThompsonSampling)
 from robo_amd.initial_design import init_latin_hypercube_sampling
 from robo_amd.kernels import Matern52Kernel
 from robo_amd.maximizers import (DeviceGradientAscent, DeviceRandomSampling, DifferentialEvolution, RandomSampling,
@@ -35,7 +37,7 @@ def bayesian_optimization(objective_function, lower, upper, num_iterations=30, X
                           maximizer="random", acquisition_func="log_ei", model_type="gp_mcmc", n_init=3, rng=None,
                           output_path=None, n_candidates=500, chain_length=200, burnin_steps=100, n_gpus=None,
                           devices=None, batch_size=1, fantasy="kriging_believer", liar="min", evaluate_batch=None,
-                          hyper_optimizer="host", n_restarts=8):
+                          hyper_optimizer="host", n_restarts=8, n_features=1024):
     """Minimise ``objective_function`` over the box [lower, upper] -> dict with x_opt, f_opt,
     incumbents, incumbent_values, runtime, overhead, X, y (same keys as the reference).
 
@@ -47,6 +49,12 @@ def bayesian_optimization(objective_function, lower, upper, num_iterations=30, X
     (robo/solver/bayesian_optimization.py:156-203).  ``model_type="gp"``: the fitted model is replicated on every
     device and the candidate batch of each maximisation is split over them; ``"gp_mcmc"``: the hyper-parameter samples
     (and, for large N, the walkers of the chain) are split over the devices.  Same chosen points as on one device.
+
+    ``acquisition_func="thompson"``: Thompson sampling by pathwise posterior samples with ``n_features`` random Fourier
+    features (acquisition_functions/thompson_sampling.py); its draws come from this call's rng.  Every proposal is the
+    minimiser of one posterior sample path over the candidates, so ``batch_size=q`` proposes one point per path from one
+    call: ``fantasy`` and ``liar`` are ignored (a path needs no fantasies).  With ``model_type="gp_mcmc"`` every path
+    draws its own hyper-parameter sample.  One device only.
     """
     assert upper.shape[0] == lower.shape[0], "Dimension miss match"
     assert np.all(lower < upper), "Lower bound >= upper bound"
@@ -81,11 +89,13 @@ def bayesian_optimization(objective_function, lower, upper, num_iterations=30, X
     # "mes": max-value entropy search; its draws (discretisation, uniforms) come from this call's rng
     # "kg": knowledge gradient over a discretisation drawn from this call's rng as well
     acq_classes = {"ei": EI, "log_ei": LogEI, "pi": PI, "lcb": LCB, "mes": lambda m: MES(m, rng=rng),
-                   "kg": lambda m: KnowledgeGradient(m, rng=rng)}
+                   "kg": lambda m: KnowledgeGradient(m, rng=rng),
+                   "thompson": lambda m: ThompsonSampling(m, n_paths=max(int(batch_size), 1), n_features=n_features, rng=rng)}
     if acquisition_func not in acq_classes:
         raise ValueError("'{}' is not a valid acquisition function".format(acquisition_func))
     a = acq_classes[acquisition_func](model)
-    acq = MarginalizationGPMCMC(a) if model_type == "gp_mcmc" else a
+    # (Thompson sampling draws a hyper-parameter sample per path: that is its marginalisation)
+    acq = MarginalizationGPMCMC(a) if model_type == "gp_mcmc" and acquisition_func != "thompson" else a
 
     if maximizer == "random":
         max_func = RandomSampling(acq, lower, upper, n_samples=n_candidates, rng=rng)
