@@ -111,16 +111,6 @@ int finish_call(robo_cand* k, const char* label, int status, std::initializer_li
     return clear_flags_on_error(k, status);
 }
 
-int grow_trace(double** d_buf, size_t* cap, size_t doubles) {
-    if (doubles <= *cap) return ROBO_OK;
-    if (*d_buf) ROBO_HIP_CHECK(hipFree(*d_buf));
-    *d_buf = nullptr;
-    *cap = 0;
-    ROBO_HIP_CHECK(hipMalloc((void**)d_buf, doubles * sizeof(double)));
-    *cap = doubles;
-    return ROBO_OK;
-}
-
 int moments_handle(robo_ctx* ctx, const double* mean, const double* var, int64_t m, const char* what, robo_cand** out) {
     robo_cand* k = nullptr;
     ROBO_TRY(cand_alloc(ctx, m, 1, &k));

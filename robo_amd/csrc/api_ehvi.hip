@@ -39,7 +39,7 @@ static int ehvi_check(const double* front, int64_t P, const double* ref) {
 // [front (ROBO_EHVI_MAX_FRONT x 2) | trace (m x 4)] on the handle (the diagnostics buffer the knowledge gradient uses),
 // the front uploaded (asynchronous: the caller's array outlives the call's synchronisation)
 static int ehvi_stage_front(robo_cand* k, const double* front, int P, size_t trace_len) {
-    ROBO_TRY(grow_trace(&k->d_kg, &k->kg_cap, (size_t)2 * ROBO_EHVI_MAX_FRONT + trace_len));
+    ROBO_TRY(dev_grow(k->ctx->stream, &k->d_kg, &k->kg_cap, (size_t)2 * ROBO_EHVI_MAX_FRONT + trace_len));
     if (P > 0)
         ROBO_HIP_CHECK(hipMemcpyAsync(k->d_kg, front, (size_t)2 * P * sizeof(double), hipMemcpyHostToDevice, k->ctx->stream));
     return ROBO_OK;

@@ -1,10 +1,13 @@
 // Host helpers shared by the files that hold C ABI entry points (api_*.hip, refine.hip, batch.hip, mes.hip, hyperopt.hip,
 // comm.hip, multi.hip): each is declared here once and defined in the file named above its group.  An ensemble driver reads as
-// "ensemble_check, acq_sweep, its own kernels, finish_call".
+// "ensemble_check, acq_sweep, its own kernels, finish_call".  A driver that keeps device state between its launches lays its
+// arrays out in one allocation with BlockLayout (block_layout.h); its diagnostics trace and every other buffer that only grows
+// go through dev_grow.
 #pragma once
 #include <functional>
 #include <initializer_list>
 
+#include "block_layout.h"
 #include "common.h"
 
 namespace robo {
@@ -14,6 +17,20 @@ inline size_t workspace_bytes(const robo_ctx* c) { return (size_t)c->tune.ws_byt
 template <class T>
 inline int dev_alloc(T** p, size_t count) {
     ROBO_HIP_CHECK(hipMalloc((void**)p, (count ? count : 1) * sizeof(T)));
+    return ROBO_OK;
+}
+
+// A grow-once buffer (diagnostics traces, per-context scratch, a state block that only grows): room for `count` elements,
+// never shrinks.  A regrow waits for the work `st` holds before it frees; a failed allocation leaves (nullptr, 0).
+template <class T>
+inline int dev_grow(hipStream_t st, T** p, size_t* cap, size_t count) {
+    if (count <= *cap) return ROBO_OK;
+    ROBO_HIP_CHECK(hipStreamSynchronize(st));
+    if (*p) ROBO_HIP_CHECK(hipFree(*p));
+    *p = nullptr;
+    *cap = 0;
+    ROBO_HIP_CHECK(hipMalloc((void**)p, count * sizeof(T)));
+    *cap = count;
     return ROBO_OK;
 }
 
@@ -75,7 +92,6 @@ struct ReadBack {
     size_t bytes;
 };
 int finish_call(robo_cand* k, const char* label, int status, std::initializer_list<ReadBack> copies, bool sync = true);
-int grow_trace(double** d_buf, size_t* cap, size_t doubles);                  // a diagnostics buffer: grows, never shrinks
 // a one-dimensional candidate handle holding (mean, var) of any model; failure reads "<what> failed: <hip error>"
 int moments_handle(robo_ctx* ctx, const double* mean, const double* var, int64_t m, const char* what, robo_cand** out);
 // dH / (exp(log-cost mean) + overhead) of every candidate into k->d_acq and the argmax partials (asynchronous)

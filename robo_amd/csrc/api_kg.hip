@@ -27,7 +27,7 @@ static int kg_check(int64_t nb, const double* sn2s, int S) {
 // S x m x (nb + 2) trace] on the handle
 static int kg_ensure(robo_cand* k, int S, size_t trace_len) {
     if (!k->d_S) ROBO_TRY(dev_alloc(&k->d_S, (size_t)k->m_pad * NB));
-    return grow_trace(&k->d_kg, &k->kg_cap, (size_t)S * KG_MAX_DISC + trace_len);
+    return dev_grow(k->ctx->stream, &k->d_kg, &k->kg_cap, (size_t)S * KG_MAX_DISC + trace_len);
 }
 
 // sum over the samples of KG into k->d_acq_sum, the discretisation means and the trace into k->d_kg (asynchronous)

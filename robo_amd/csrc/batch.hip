@@ -325,65 +325,49 @@ __global__ __launch_bounds__(256) void batch_cond_kernel(BatchState st, int s, i
 // ---- host side ------------------------------------------------------------------------------------------------------------
 int batch_alloc(robo_ctx* ctx, int64_t m, int64_t m_pad, int S, int n_pad, int q, BatchWork** out) {
     BatchWork* w = new BatchWork();
-    memset(w, 0, sizeof(*w));
     w->m = m;
     w->S = S;
     w->n_pad = n_pad;
     w->q = q;
-    size_t bytes = 0;
-    auto take = [&bytes](size_t n) {
-        const size_t at = bytes;
-        bytes += (n + 15) / 16 * 16;
-        return at;
-    };
-    const size_t sm = (size_t)S * m_pad * 8, sn = (size_t)S * n_pad * 8;
-    const size_t o_mu = take(sm), o_var = take(sm), o_mt = take(sm), o_w = take(sn), o_v = take(sn), o_beta = take(sn);
-    const size_t o_ch = take((size_t)S * q * m_pad * 8), o_dh = take((size_t)S * q * 8);
-    const size_t o_scal = take((size_t)2 * S * 8), o_eta = take((size_t)S * 8), o_val = take((size_t)q * 8);
-    const size_t o_fant = take((size_t)q * S * 8), o_idx = take((size_t)q * 8), o_flg = take((size_t)q * 4), o_int = take(16);
-    if (hipMalloc((void**)&w->d_block, bytes) != hipSuccess) {
-        set_error("hipMalloc of %zu bytes failed (batch selection state)", bytes);
+    BatchState& st = w->st;
+    const size_t sm = (size_t)S * m_pad, sn = (size_t)S * n_pad;
+    BlockLayout lay(16);
+    lay.add(&st.mu_lat, sm);
+    lay.add(&st.var_lat, sm);
+    lay.add(&st.mean_t, sm);
+    lay.add(&st.w, sn);
+    lay.add(&st.v, sn);
+    lay.add(&st.beta, sn);
+    lay.add(&st.chist, (size_t)S * q * m_pad);
+    lay.add(&st.dhist, (size_t)S * q);
+    lay.add(&st.scal, (size_t)2 * S);
+    lay.add(&st.eta, (size_t)S);
+    // everything a call reports (values, fantasies, indices, flags, picks made) is one contiguous range from `val` to the
+    // end of the block: ONE copy into pinned memory, as the sweep's own report
+    w->rep_off = lay.add(&st.val, (size_t)q);
+    w->off_fant = lay.add(&st.fant, (size_t)q * S) - w->rep_off;
+    w->off_idx = lay.add(&st.idx, (size_t)q) - w->rep_off;
+    w->off_flg = lay.add(&st.flg, (size_t)q) - w->rep_off;
+    w->off_int = lay.add(&st.n_made, 4) - w->rep_off;         // [n_made, stop] and padding
+    w->rep_bytes = lay.bytes() - w->rep_off;
+    if (hipMalloc((void**)&w->d_block, lay.bytes()) != hipSuccess) {
+        set_error("hipMalloc of %zu bytes failed (batch selection state)", lay.bytes());
         delete w;
         return ROBO_RUNTIME_ERROR;
     }
-    // everything a call reports (values, fantasies, indices, flags, picks made) is one contiguous range: ONE copy into
-    // pinned memory, as the sweep's own report
-    w->rep_off = o_val;
-    w->rep_bytes = bytes - o_val;
-    w->off_fant = o_fant - o_val;
-    w->off_idx = o_idx - o_val;
-    w->off_flg = o_flg - o_val;
-    w->off_int = o_int - o_val;
     if (hipHostMalloc((void**)&w->h_report, w->rep_bytes) != hipSuccess) {
         set_error("hipHostMalloc of %zu bytes failed (batch selection report)", w->rep_bytes);
         hipFree(w->d_block);
         delete w;
         return ROBO_RUNTIME_ERROR;
     }
-    char* b = w->d_block;
-    BatchState& st = w->st;
+    lay.bind(w->d_block);
+    st.stop = st.n_made + 1;
     st.S = S;
     st.q = q;
+    st.qcap = q;
     st.m = m;
     st.m_pad = m_pad;
-    st.mu_lat = (double*)(b + o_mu);
-    st.var_lat = (double*)(b + o_var);
-    st.mean_t = (double*)(b + o_mt);
-    st.w = (double*)(b + o_w);
-    st.v = (double*)(b + o_v);
-    st.beta = (double*)(b + o_beta);
-    st.chist = (double*)(b + o_ch);
-    st.dhist = (double*)(b + o_dh);
-    st.qcap = q;
-    st.scal = (double*)(b + o_scal);
-    st.eta = (double*)(b + o_eta);
-    st.val = (double*)(b + o_val);
-    st.fant = (double*)(b + o_fant);
-    st.idx = (long long*)(b + o_idx);
-    st.flg = (unsigned*)(b + o_flg);
-    st.n_made = (int*)(b + o_int);
-    st.stop = st.n_made + 1;
-    st.trace = nullptr;
     (void)ctx;
     *out = w;
     return ROBO_OK;
@@ -497,7 +481,7 @@ static int batch_core(robo_gp* const* gps, int32_t S, bool marginal, int32_t acq
     BatchWork* w = nullptr;
     ROBO_TRY(select_ensure(g0, k, S, q, &w));
     const size_t trace_len = (size_t)q * S * k->m * 2;
-    if (out_trace) ROBO_TRY(grow_trace(&w->d_trace, &w->trace_cap, trace_len));
+    if (out_trace) ROBO_TRY(dev_grow(c->stream, &w->d_trace, &w->trace_cap, trace_len));
     w->st.q = q;
     w->st.trace = out_trace ? w->d_trace : nullptr;
     const BatchState& st = w->st;

@@ -245,7 +245,7 @@ struct RefineState {
 struct RefineWork {
     int K, D;
     ::robo_cand* ws;                // the K (D + 1) pseudo-rows of the solve
-    char* d_block;                  // one allocation behind `st`
+    char* d_block;                  // one allocation behind `st`, laid out by refine_alloc's BlockLayout (block_layout.h)
     double* d_trace;
     size_t trace_cap;               // doubles
     RefineState st;
@@ -279,7 +279,8 @@ struct BatchWork {
     double* d_trace;
     size_t trace_cap;               // doubles
     char* h_report;                 // pinned copy of the block's tail [val | fant | idx | flg | n_made, stop]: one D2H per call
-    size_t rep_off, rep_bytes, off_fant, off_idx, off_flg, off_int;
+    size_t rep_off, rep_bytes, off_fant, off_idx, off_flg, off_int;   // the tail in the block; its arrays in the tail (from
+                                    // the offsets batch_alloc's BlockLayout returned)
     BatchState st;
 };
 int batch_alloc(robo_ctx* ctx, int64_t m, int64_t m_pad, int S, int n_pad, int q, BatchWork** out);
@@ -300,10 +301,10 @@ struct MesState {
 struct MesWork {
     int64_t m;
     int S, K;
-    double* d_block;
+    double* d_block;                // [ystar | gumbel | status] (ONE layout entry), u, brk, bpart, fpart, done
     double* d_trace;
     size_t trace_cap;               // doubles
-    double* h_stage;                // pinned: [ystar | gumbel | status] of the block's head (one D2H per call), then u
+    double* h_stage;               // pinned: [ystar | gumbel | status] of the block's head (one D2H per call), then u
     size_t rep_doubles;
     MesState st;
 };
@@ -336,8 +337,8 @@ struct RepState {
     double* trace;                  // [S][T][2][k/2][D + 2]: q, lnp(q), code -- or nullptr
 };
 struct RepWork {
-    size_t bytes;                   // of d_block (grows, never shrinks)
-    char* d_block;
+    size_t bytes;                   // of d_block (dev_grow: grows, never shrinks)
+    char* d_block;                  // laid out anew by every call (rep_core's BlockLayout)
     double* d_trace;
     size_t trace_cap;               // doubles
 };
@@ -369,7 +370,7 @@ struct HyperWork {
     int g_cap, g_npad, g_P;         // samples, n_pad and theta size the gradient workspace was sized for
     double *d_V, *d_A, *d_alpha, *d_part, *d_out;
     int K, P, hist;                 // what d_block was sized for
-    char* d_block;
+    char* d_block;                  // [lower | upper | HyperState's arrays]; the four int arrays are ONE layout entry
     double* d_trace;
     size_t trace_cap;               // doubles
 };

@@ -442,7 +442,6 @@ static int ep_ensure(robo_ctx* c, long long S, int nb) {
     ROBO_HIP_CHECK(hipStreamSynchronize(c->stream));
     ep_release(c);
     EpWork* w = new EpWork();
-    memset(w, 0, sizeof(*w));
     c->ep = w;
     const size_t n1 = (size_t)cs * cnb, n2 = n1 * cnb, n3 = n2 * cnb, nt = n1 * (cnb + 1) / 2 * cnb;
     ROBO_HIP_CHECK(hipMalloc((void**)&w->d_mu, n1 * sizeof(double)));

@@ -399,10 +399,7 @@ static size_t hyper_sample_bytes(const robo_gp* g) {
 
 // the gradient workspace for `cap` samples at the current n_pad: allocated here, before any launch
 static int hyper_grad_ensure(robo_gp* g, int cap) {
-    if (!g->hyper) {
-        g->hyper = new HyperWork();
-        memset(g->hyper, 0, sizeof(HyperWork));
-    }
+    if (!g->hyper) g->hyper = new HyperWork();
     HyperWork* w = g->hyper;
     const int P = robo_theta_size(g->kind, g->dim);
     if (w->g_cap >= cap && w->g_npad == g->n_pad && w->g_P == P) return ROBO_OK;
@@ -577,37 +574,34 @@ int32_t robo_gp_optimize_hypers(robo_gp* g, double mean_c, int32_t prior_kind, c
     ROBO_TRY(hyper_grad_ensure(g, K));
     HyperWork* w = g->hyper;
     // one state block: doubles first, then ints
-    const size_t KP = (size_t)K * P, pairs = KP * (size_t)history;
-    const size_t n_dbl = 2 * (size_t)P + 3 * KP + 3 * (size_t)K + 2 * pairs + (size_t)P + 2;
-    const size_t bytes = n_dbl * sizeof(double) + (3 * (size_t)K + 1) * sizeof(int);
+    const size_t KP = (size_t)K * P, pairs = KP * (size_t)history, n_int = 3 * (size_t)K + 1;
+    HyperState st;
+    memset(&st, 0, sizeof(st));
+    BlockLayout lay(sizeof(double));
+    lay.add(&st.lower, (size_t)P);
+    lay.add(&st.upper, (size_t)P);
+    lay.add(&st.x, KP);
+    lay.add(&st.g, KP);
+    lay.add(&st.z, KP);
+    lay.add(&st.f, (size_t)K);
+    lay.add(&st.alpha, (size_t)K);
+    lay.add(&st.aused, (size_t)K);
+    lay.add(&st.sh, pairs);
+    lay.add(&st.yh, pairs);
+    lay.add(&st.out, (size_t)P + 2);
+    lay.add(&st.npairs, n_int);         // [npairs | state | pending | err]: cleared and read back as one range, so one entry
     if (!w->d_block || w->K != K || w->P != P || w->hist != history) {
         if (w->d_block) ROBO_HIP_CHECK(hipFree(w->d_block));
         w->d_block = nullptr;
-        ROBO_HIP_CHECK(hipMalloc((void**)&w->d_block, bytes));
+        ROBO_HIP_CHECK(hipMalloc((void**)&w->d_block, lay.bytes()));
         w->K = K; w->P = P; w->hist = history;
     }
+    lay.bind(w->d_block);
+    st.state = st.npairs + K;
+    st.pending = st.npairs + 2 * K;
+    st.err = st.npairs + 3 * K;
     const size_t trace_doubles = (size_t)(n_iters + 1) * K * (2 * (size_t)P + 3);
-    if (out_trace) ROBO_TRY(grow_trace(&w->d_trace, &w->trace_cap, trace_doubles));
-    HyperState st;
-    memset(&st, 0, sizeof(st));
-    double* d = reinterpret_cast<double*>(w->d_block);
-    double* d_lower = d; d += P;
-    double* d_upper = d; d += P;
-    st.x = d; d += KP;
-    st.g = d; d += KP;
-    st.z = d; d += KP;
-    st.f = d; d += K;
-    st.alpha = d; d += K;
-    st.aused = d; d += K;
-    st.sh = d; d += pairs;
-    st.yh = d; d += pairs;
-    st.out = d; d += P + 2;
-    int* di = reinterpret_cast<int*>(d);
-    st.npairs = di;
-    st.state = di + K;
-    st.pending = di + 2 * K;
-    st.err = di + 3 * K;
-    st.lower = d_lower; st.upper = d_upper;
+    if (out_trace) ROBO_TRY(dev_grow(c->stream, &w->d_trace, &w->trace_cap, trace_doubles));
     st.K = K; st.P = P; st.D = D; st.kind = g->kind; st.n = g->n; st.hist = history; st.n_iters = n_iters;
     st.prior_kind = prior_kind;
     st.mean_c = mean_c; st.step0 = step0; st.c1 = c1; st.gtol = gtol;
@@ -616,10 +610,10 @@ int32_t robo_gp_optimize_hypers(robo_gp* g, double mean_c, int32_t prior_kind, c
     st.d_sp = g->d_bsp; st.d_ism = g->d_bism; st.d_out = g->d_bout; st.d_fail = g->d_bfail; st.d_grad = w->d_out;
     st.d_x2max = g->d_x2max;
     hipStream_t s = c->stream;
-    ROBO_HIP_CHECK(hipMemcpyAsync(d_lower, lower, (size_t)P * sizeof(double), hipMemcpyHostToDevice, s));
-    ROBO_HIP_CHECK(hipMemcpyAsync(d_upper, upper, (size_t)P * sizeof(double), hipMemcpyHostToDevice, s));
+    ROBO_HIP_CHECK(hipMemcpyAsync((void*)st.lower, lower, (size_t)P * sizeof(double), hipMemcpyHostToDevice, s));
+    ROBO_HIP_CHECK(hipMemcpyAsync((void*)st.upper, upper, (size_t)P * sizeof(double), hipMemcpyHostToDevice, s));
     ROBO_HIP_CHECK(hipMemcpyAsync(st.x, starts, KP * sizeof(double), hipMemcpyHostToDevice, s));
-    ROBO_HIP_CHECK(hipMemsetAsync(di, 0, (3 * (size_t)K + 1) * sizeof(int), s));
+    ROBO_HIP_CHECK(hipMemsetAsync(st.npairs, 0, n_int * sizeof(int), s));
     // (fb.gram_mixed stays set: the trial points are formed on the device, each carries its own FitSample::direct)
     const FitBuffers fb = batch_buffers(g, K, nullptr);     // the likelihood terms are consumed on the device
     const GradBatch gb = grad_buffers(g, K);
@@ -631,11 +625,11 @@ int32_t robo_gp_optimize_hypers(robo_gp* g, double mean_c, int32_t prior_kind, c
     }
     ROBO_TRY(launch_hyper_result(c, st));
     std::vector<double> hres((size_t)P + 2), hx(KP), hf((size_t)K);
-    std::vector<int> hint(3 * (size_t)K + 1);
+    std::vector<int> hint(n_int);
     ROBO_HIP_CHECK(hipMemcpyAsync(hres.data(), st.out, ((size_t)P + 2) * sizeof(double), hipMemcpyDeviceToHost, s));
     ROBO_HIP_CHECK(hipMemcpyAsync(hx.data(), st.x, KP * sizeof(double), hipMemcpyDeviceToHost, s));
     ROBO_HIP_CHECK(hipMemcpyAsync(hf.data(), st.f, (size_t)K * sizeof(double), hipMemcpyDeviceToHost, s));
-    ROBO_HIP_CHECK(hipMemcpyAsync(hint.data(), di, (3 * (size_t)K + 1) * sizeof(int), hipMemcpyDeviceToHost, s));
+    ROBO_HIP_CHECK(hipMemcpyAsync(hint.data(), st.npairs, n_int * sizeof(int), hipMemcpyDeviceToHost, s));
     if (out_trace)
         ROBO_HIP_CHECK(hipMemcpyAsync(out_trace, w->d_trace, trace_doubles * sizeof(double), hipMemcpyDeviceToHost, s));
     ROBO_HIP_CHECK(hipStreamSynchronize(s));

@@ -20,7 +20,7 @@
 #include <cmath>
 #include <vector>
 
-#include "common.h"
+#include "api_internal.h"
 
 namespace robo {
 
@@ -261,18 +261,6 @@ void mc_release(robo_ctx* c) {
     c->mc = nullptr;
 }
 
-template <class T>
-static int mc_grow(robo_ctx* c, T** p, size_t* cap, size_t n) {
-    if (*cap >= n) return ROBO_OK;
-    ROBO_HIP_CHECK(hipStreamSynchronize(c->stream));
-    hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    ROBO_HIP_CHECK(hipMalloc((void**)p, n * sizeof(T)));
-    *cap = n;
-    return ROBO_OK;
-}
-
 static McWork* mc_work(robo_ctx* c) {
     if (!c->mc) c->mc = new McWork();
     return c->mc;
@@ -295,7 +283,7 @@ static int mc_upload_z(robo_ctx* c, int nb, int nf, const double* z) {
         memcmp(w->zkey.data() + 2, z, n * sizeof(double)) == 0)
         return ROBO_OK;
     w->zkey.clear();
-    ROBO_TRY(mc_grow(c, &w->d_zt, &w->cap_zt, n));
+    ROBO_TRY(dev_grow(c->stream, &w->d_zt, &w->cap_zt, n));
     std::vector<double> zt(n);
     for (int f = 0; f < nf; ++f)
         for (int k = 0; k < nb; ++k) zt[(size_t)k * nf + f] = z[(size_t)f * nb + k];
@@ -308,7 +296,7 @@ static int mc_upload_z(robo_ctx* c, int nb, int nf, const double* z) {
 }
 
 static int mc_upload(robo_ctx* c, double** d, size_t* cap, const double* h, size_t n) {
-    ROBO_TRY(mc_grow(c, d, cap, n));
+    ROBO_TRY(dev_grow(c->stream, d, cap, n));
     ROBO_HIP_CHECK(hipMemcpyAsync(*d, h, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
     return ROBO_OK;
 }
@@ -356,9 +344,9 @@ extern "C" int32_t robo_pmin_mc(robo_ctx* ctx, int32_t S, int32_t nb, int32_t nf
     ROBO_TRY(mc_upload(ctx, &w->d_mb, &w->cap_mb, mu, n1));
     ROBO_TRY(mc_upload(ctx, &w->d_vb, &w->cap_vb, sigma, n1 * nb));
     ROBO_TRY(mc_upload(ctx, &w->d_w, &w->cap_w, &zero, 1));
-    ROBO_TRY(mc_grow(ctx, &w->d_counts, &w->cap_counts, n1));
-    ROBO_TRY(mc_grow(ctx, &w->d_jit, &w->cap_jit, (size_t)S));
-    ROBO_TRY(mc_grow(ctx, &w->d_status, &w->cap_status, (size_t)S));
+    ROBO_TRY(dev_grow(ctx->stream, &w->d_counts, &w->cap_counts, n1));
+    ROBO_TRY(dev_grow(ctx->stream, &w->d_jit, &w->cap_jit, (size_t)S));
+    ROBO_TRY(dev_grow(ctx->stream, &w->d_status, &w->cap_status, (size_t)S));
     McArgs a;
     memset(&a, 0, sizeof(a));
     a.nb = nb, a.np = 1, a.nf = nf, a.m = S;
@@ -392,9 +380,9 @@ extern "C" int32_t robo_igmc_eval_moments(robo_ctx* ctx, int64_t m, int32_t nb, 
     const size_t nc = out_counts ? (size_t)m * n_outcomes * nb : 0;
     ROBO_TRY(mc_upload(ctx, &w->d_s, &w->cap_s, s, (size_t)m * nb));
     ROBO_TRY(mc_upload(ctx, &w->d_v, &w->cap_v, v, (size_t)m));
-    ROBO_TRY(mc_grow(ctx, &w->d_gain, &w->cap_gain, (size_t)m));
-    if (out_counts) ROBO_TRY(mc_grow(ctx, &w->d_counts, &w->cap_counts, nc));
-    if (out_jitter) ROBO_TRY(mc_grow(ctx, &w->d_jit, &w->cap_jit, (size_t)m));
+    ROBO_TRY(dev_grow(ctx->stream, &w->d_gain, &w->cap_gain, (size_t)m));
+    if (out_counts) ROBO_TRY(dev_grow(ctx->stream, &w->d_counts, &w->cap_counts, nc));
+    if (out_jitter) ROBO_TRY(dev_grow(ctx->stream, &w->d_jit, &w->cap_jit, (size_t)m));
     ROBO_TRY(mc_eval_gains(ctx, m, nb, n_outcomes, nf, sn2, w->d_s, nb, w->d_v, Mb, Vb, logP, lmb, W, z, w->d_gain,
                            out_counts ? w->d_counts : nullptr, out_jitter ? w->d_jit : nullptr, nullptr));
     ROBO_HIP_CHECK(hipMemcpyAsync(out_dh, w->d_gain, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, st));

@@ -259,17 +259,22 @@ __global__ __launch_bounds__(256) void mes_value_kernel(const double* __restrict
 // ---- host side ------------------------------------------------------------------------------------------------------------
 int mes_alloc(int64_t m, int S, int K, MesWork** out) {
     MesWork* w = new MesWork();
-    memset(w, 0, sizeof(*w));
     w->m = m;
     w->S = S;
     w->K = K;
+    MesState& st = w->st;
     const int nblk = (int)((m + MES_CHUNK - 1) / MES_CHUNK);
-    // [ystar | gumbel | status] is what a call reports: ONE copy into pinned memory
+    // [ystar | gumbel | status] is what a call reports: ONE copy into pinned memory, so one entry
     w->rep_doubles = (size_t)S * K + (size_t)S * 7 + (size_t)S;
-    const size_t o_u = w->rep_doubles, o_brk = o_u + (size_t)S * K, o_bpart = o_brk + 8, o_fpart = o_bpart + (size_t)nblk * 3;
-    const size_t total = o_fpart + (size_t)nblk * MES_F_THREADS;
-    if (hipMalloc((void**)&w->d_block, total * sizeof(double) + 16) != hipSuccess) {
-        set_error("hipMalloc of %zu bytes failed (max-value entropy search state)", total * sizeof(double) + 16);
+    BlockLayout lay(sizeof(double));
+    lay.add(&st.ystar, w->rep_doubles);
+    lay.add(&st.u, (size_t)S * K);
+    lay.add(&st.brk, 8);
+    lay.add(&st.bpart, (size_t)nblk * 3);
+    lay.add(&st.fpart, (size_t)nblk * MES_F_THREADS);
+    lay.add(&st.done, 1);
+    if (hipMalloc((void**)&w->d_block, lay.bytes()) != hipSuccess) {
+        set_error("hipMalloc of %zu bytes failed (max-value entropy search state)", lay.bytes());
         delete w;
         return ROBO_RUNTIME_ERROR;
     }
@@ -279,19 +284,12 @@ int mes_alloc(int64_t m, int S, int K, MesWork** out) {
         delete w;
         return ROBO_RUNTIME_ERROR;
     }
-    double* b = w->d_block;
-    MesState& st = w->st;
+    lay.bind(w->d_block);
+    st.gumbel = st.ystar + (size_t)S * K;
+    st.status = st.gumbel + (size_t)S * 7;
     st.m = m;
     st.K = K;
     st.nblk = nblk;
-    st.ystar = b;
-    st.gumbel = b + (size_t)S * K;
-    st.status = st.gumbel + (size_t)S * 7;
-    st.u = b + o_u;
-    st.brk = b + o_brk;
-    st.bpart = b + o_bpart;
-    st.fpart = b + o_fpart;
-    st.done = reinterpret_cast<int*>(b + total);
     *out = w;
     return ROBO_OK;
 }
@@ -391,7 +389,7 @@ static int mes_core(robo_gp* const* gps, int32_t S, const double* etas, robo_can
     MesWork* w = nullptr;
     ROBO_TRY(mes_ensure(g0, k, S, K, &w));
     const size_t trace_len = (size_t)S * k->m * 2;
-    if (out_trace) ROBO_TRY(grow_trace(&w->d_trace, &w->trace_cap, trace_len));
+    if (out_trace) ROBO_TRY(dev_grow(c->stream, &w->d_trace, &w->trace_cap, trace_len));
     const MesState& st = w->st;
     ROBO_TRY(mes_upload_draws(c, w, u));
     // event slots 27 -> 30 -> 31 bracket the tail of the LAST sample: minimum sampling, element-wise half

@@ -380,23 +380,31 @@ __global__ void refine_result_kernel(RefineState st, unsigned* __restrict__ cand
 // ---- host side ---------------------------------------------------------------------------------------------------------------
 int refine_alloc(robo_ctx* ctx, int K, int D, RefineWork** out) {
     RefineWork* w = new RefineWork();
-    memset(w, 0, sizeof(*w));
     w->K = K;
     w->D = D;
+    RefineState& st = w->st;
     const size_t kd = (size_t)K * D, k8 = (size_t)round_up(K, 8);
-    // doubles first, then the 8-byte integers, then the 4-byte words (every array starts 16-byte aligned)
-    size_t bytes = 0;
-    auto take = [&bytes](size_t n) {
-        const size_t at = bytes;
-        bytes += (n + 15) / 16 * 16;
-        return at;
-    };
-    const size_t o_x = take(kd * 8), o_g = take(kd * 8), o_y = take(kd * 8), o_ys = take(kd * 8), o_gy = take(kd * 8);
-    const size_t o_f = take(k8 * 8), o_alpha = take(k8 * 8), o_aused = take(k8 * 8), o_fy = take(k8 * 8);
-    const size_t o_sval = take(2 * k8 * 8), o_out = take(((size_t)D + 4) * 8);
-    const size_t o_start = take(k8 * 8), o_sidx = take(2 * k8 * 8);
-    const size_t o_frozen = take(k8 * 4), o_bad = take(k8 * 4), o_hist = take(256 * 4), o_flags = take(16);
-    const size_t o_sel = take(sizeof(RefineSel));
+    // doubles first, then the 8-byte integers, then the 4-byte words
+    BlockLayout lay(16);
+    lay.add(&st.x, kd);
+    lay.add(&st.g, kd);
+    lay.add(&st.y, kd);
+    lay.add(&st.ys, kd);
+    lay.add(&st.gy, kd);
+    lay.add(&st.f, k8);
+    lay.add(&st.alpha, k8);
+    lay.add(&st.aused, k8);
+    lay.add(&st.fy, k8);
+    lay.add(&st.sel_val, 2 * k8);         // sel_val / sel_idx: [0, K) as collected, [K, 2 K) sorted
+    lay.add(&st.out, (size_t)D + 4);
+    lay.add(&st.start, k8);
+    lay.add(&st.sel_idx, 2 * k8);
+    lay.add(&st.frozen, k8);
+    lay.add(&st.bad, k8);
+    lay.add(&st.hist, 256);
+    lay.add(&st.flags, 4);
+    lay.add(&st.sel, 1);
+    const size_t bytes = lay.bytes();
     if (hipMalloc((void**)&w->d_block, bytes) != hipSuccess) {
         set_error("hipMalloc of %zu bytes failed (refinement state)", bytes);
         delete w;
@@ -408,30 +416,10 @@ int refine_alloc(robo_ctx* ctx, int K, int D, RefineWork** out) {
         delete w;
         return ROBO_RUNTIME_ERROR;
     }
-    char* b = w->d_block;
-    RefineState& st = w->st;
+    lay.bind(w->d_block);
     st.K = K;
     st.D = D;
-    st.x = (double*)(b + o_x);
-    st.g = (double*)(b + o_g);
-    st.y = (double*)(b + o_y);
-    st.ys = (double*)(b + o_ys);
-    st.gy = (double*)(b + o_gy);
-    st.f = (double*)(b + o_f);
-    st.alpha = (double*)(b + o_alpha);
-    st.aused = (double*)(b + o_aused);
-    st.fy = (double*)(b + o_fy);
-    st.sel_val = (double*)(b + o_sval);
-    st.out = (double*)(b + o_out);
-    st.start = (long long*)(b + o_start);
-    st.sel_idx = (long long*)(b + o_sidx);
-    st.frozen = (int*)(b + o_frozen);
-    st.bad = (int*)(b + o_bad);
-    st.hist = (unsigned*)(b + o_hist);
-    st.flags = (unsigned*)(b + o_flags);
-    st.sel = (RefineSel*)(b + o_sel);
-    st.trace = nullptr;
-    *out = w;             // sel_val / sel_idx: [0, K) as collected, [K, 2 K) sorted
+    *out = w;
     return ROBO_OK;
 }
 
@@ -524,7 +512,7 @@ static int refine_core(robo_gp* const* gps, int32_t S, bool marginal, int32_t ac
     ROBO_TRY(refine_ensure(g0, K, D, &w));
     ROBO_TRY(cand_ensure_workspace(w->ws, g0->n_pad, true));
     const size_t trace_len = (size_t)(T + 1) * K * (2 * D + 3);
-    if (out_trace) ROBO_TRY(grow_trace(&w->d_trace, &w->trace_cap, trace_len));
+    if (out_trace) ROBO_TRY(dev_grow(c->stream, &w->d_trace, &w->trace_cap, trace_len));
     w->st.trace = out_trace ? w->d_trace : nullptr;
     const RefineState& st = w->st;
 

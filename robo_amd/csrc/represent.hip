@@ -205,35 +205,29 @@ static int rep_core(robo_gp* const* gps, int32_t S, int32_t acq_kind, double par
         chains[s] = RepChain{g->d_theta, hs[s]->d_Xcs, hs[s]->d_mean, hs[s]->d_var, etas[s]};
     }
 
-    // one block: doubles first, then the 8-byte integers, then the 4-byte words (every array starts 16-byte aligned)
-    size_t bytes = 0;
-    auto take = [&bytes](size_t n) {
-        const size_t at = bytes;
-        bytes += (n + 15) / 16 * 16;
-        return at;
-    };
+    // one block: doubles first, then the 8-byte integers, then the 4-byte words
     const size_t nd = (size_t)S * T * 2 * half;
-    const size_t o_pos = take((size_t)S * k * D * 8), o_lnp = take((size_t)S * k * 8), o_q = take((size_t)S * half * D * 8);
-    const size_t o_z = take((size_t)S * half * 8), o_uz = take(nd * 8), o_ua = take(nd * 8), o_lo = take((size_t)D * 8);
-    const size_t o_up = take((size_t)D * 8), o_nacc = take((size_t)S * k * 8), o_chain = take((size_t)S * sizeof(RepChain));
-    const size_t o_pa = take(nd * 4), o_out = take((size_t)S * half * 4), o_flags = take((size_t)S * 4);
-    if (!g0->rep) {
-        g0->rep = new RepWork();
-        memset(g0->rep, 0, sizeof(RepWork));
-    }
-    RepWork* w = g0->rep;
-    if (w->bytes < bytes) {
-        ROBO_HIP_CHECK(hipStreamSynchronize(c->stream));
-        if (w->d_block) ROBO_HIP_CHECK(hipFree(w->d_block));
-        w->d_block = nullptr;
-        w->bytes = 0;
-        ROBO_HIP_CHECK(hipMalloc((void**)&w->d_block, bytes));
-        w->bytes = bytes;
-    }
-    const size_t trace_len = nd * ((size_t)D + 2);
-    if (out_trace && trace_len > 0) ROBO_TRY(grow_trace(&w->d_trace, &w->trace_cap, trace_len));
-    char* b = w->d_block;
     RepState st;
+    BlockLayout lay(16);
+    lay.add(&st.pos, (size_t)S * k * D);
+    lay.add(&st.lnp, (size_t)S * k);
+    lay.add(&st.q, (size_t)S * half * D);
+    lay.add(&st.z, (size_t)S * half);
+    lay.add(&st.uz, nd);
+    lay.add(&st.ua, nd);
+    lay.add(&st.lower, (size_t)D);
+    lay.add(&st.upper, (size_t)D);
+    lay.add(&st.nacc, (size_t)S * k);
+    lay.add(&st.chain, (size_t)S);
+    lay.add(&st.partner, nd);
+    lay.add(&st.outside, (size_t)S * half);
+    lay.add(&st.flags, (size_t)S);
+    if (!g0->rep) g0->rep = new RepWork();
+    RepWork* w = g0->rep;
+    ROBO_TRY(dev_grow(c->stream, &w->d_block, &w->bytes, lay.bytes()));
+    lay.bind(w->d_block);
+    const size_t trace_len = nd * ((size_t)D + 2);
+    if (out_trace && trace_len > 0) ROBO_TRY(dev_grow(c->stream, &w->d_trace, &w->trace_cap, trace_len));
     st.S = S;
     st.k = k;
     st.D = D;
@@ -241,35 +235,23 @@ static int rep_core(robo_gp* const* gps, int32_t S, int32_t acq_kind, double par
     st.normalize = normalize ? 1 : 0;
     st.m_pad = m_pad;
     st.a = a;
-    st.pos = (double*)(b + o_pos);
-    st.lnp = (double*)(b + o_lnp);
-    st.q = (double*)(b + o_q);
-    st.z = (double*)(b + o_z);
-    st.outside = (int*)(b + o_out);
-    st.nacc = (long long*)(b + o_nacc);
-    st.flags = (unsigned*)(b + o_flags);
-    st.uz = (const double*)(b + o_uz);
-    st.ua = (const double*)(b + o_ua);
-    st.partner = (const int*)(b + o_pa);
-    st.lower = (const double*)(b + o_lo);
-    st.upper = (const double*)(b + o_up);
-    st.chain = (const RepChain*)(b + o_chain);
     st.trace = (out_trace && trace_len > 0) ? w->d_trace : nullptr;
 
+    // (uz .. chain are const in RepState, the kernels only read them: the uploads cast that away)
     hipStream_t stream = c->stream;
     const hipMemcpyKind h2d = hipMemcpyHostToDevice;
-    ROBO_HIP_CHECK(hipMemcpyAsync(b + o_pos, pos, (size_t)S * k * D * 8, h2d, stream));
-    if (!eval_start) ROBO_HIP_CHECK(hipMemcpyAsync(b + o_lnp, lnp, (size_t)S * k * 8, h2d, stream));
+    ROBO_HIP_CHECK(hipMemcpyAsync(st.pos, pos, (size_t)S * k * D * 8, h2d, stream));
+    if (!eval_start) ROBO_HIP_CHECK(hipMemcpyAsync(st.lnp, lnp, (size_t)S * k * 8, h2d, stream));
     if (nd > 0) {
-        ROBO_HIP_CHECK(hipMemcpyAsync(b + o_uz, u_stretch, nd * 8, h2d, stream));
-        ROBO_HIP_CHECK(hipMemcpyAsync(b + o_ua, u_accept, nd * 8, h2d, stream));
-        ROBO_HIP_CHECK(hipMemcpyAsync(b + o_pa, partner, nd * 4, h2d, stream));
+        ROBO_HIP_CHECK(hipMemcpyAsync((void*)st.uz, u_stretch, nd * 8, h2d, stream));
+        ROBO_HIP_CHECK(hipMemcpyAsync((void*)st.ua, u_accept, nd * 8, h2d, stream));
+        ROBO_HIP_CHECK(hipMemcpyAsync((void*)st.partner, partner, nd * 4, h2d, stream));
     }
-    ROBO_HIP_CHECK(hipMemcpyAsync(b + o_lo, lower, (size_t)D * 8, h2d, stream));
-    ROBO_HIP_CHECK(hipMemcpyAsync(b + o_up, upper, (size_t)D * 8, h2d, stream));
-    ROBO_HIP_CHECK(hipMemcpyAsync(b + o_chain, chains.data(), (size_t)S * sizeof(RepChain), h2d, stream));
-    ROBO_HIP_CHECK(hipMemsetAsync(b + o_nacc, 0, (size_t)S * k * 8, stream));
-    ROBO_HIP_CHECK(hipMemsetAsync(b + o_flags, 0, (size_t)S * 4, stream));
+    ROBO_HIP_CHECK(hipMemcpyAsync((void*)st.lower, lower, (size_t)D * 8, h2d, stream));
+    ROBO_HIP_CHECK(hipMemcpyAsync((void*)st.upper, upper, (size_t)D * 8, h2d, stream));
+    ROBO_HIP_CHECK(hipMemcpyAsync((void*)st.chain, chains.data(), (size_t)S * sizeof(RepChain), h2d, stream));
+    ROBO_HIP_CHECK(hipMemsetAsync(st.nacc, 0, (size_t)S * k * 8, stream));
+    ROBO_HIP_CHECK(hipMemsetAsync(st.flags, 0, (size_t)S * 4, stream));
 
     // start evaluation and steps: launches only
     int status = ROBO_OK;

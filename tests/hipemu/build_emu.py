@@ -104,5 +104,19 @@ def _build_sched_selftest(force=False):
     return SCHED_SELFTEST
 
 
+LAYOUT_SELFTEST = os.path.join(HERE, "_build", "layout_selftest")
+
+
+def build_layout_selftest(force=False):
+    """layout_selftest.cpp: an executable on robo_amd/csrc/block_layout.h alone (no interpreter, no HIP)"""
+    with _build_lock():
+        deps = [os.path.join(HERE, "layout_selftest.cpp"), os.path.join(ROOT, "robo_amd", "csrc", "block_layout.h")]
+        if not force and os.path.exists(LAYOUT_SELFTEST) and \
+                all(os.path.getmtime(d) <= os.path.getmtime(LAYOUT_SELFTEST) for d in deps):
+            return LAYOUT_SELFTEST
+        subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", deps[0], "-o", LAYOUT_SELFTEST])
+        return LAYOUT_SELFTEST
+
+
 if __name__ == "__main__":
     print(build(force=True))

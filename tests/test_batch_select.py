@@ -365,6 +365,40 @@ def _edges_emu_small(emu_ctx):
         g.close()
 
 
+def _check_shape_change(ctx):
+    """one live handle through the state-block shapes q = 3 -> q = 5 -> two samples -> q = 3: every reallocation gives the
+    bits of a handle that never held another shape (N = 22, D = 2, 40 candidates: every array of the block is non-empty
+    and the odd q makes the 16-byte round-up between the arrays matter)"""
+    sz = dict(N=22, D=2, M=40)
+    live, fresh_one, fresh_two = gps = [_setup(ctx, sz, seed=7)[2] for _ in range(3)]      # the same data and theta
+    _, _, other, eta, Xc = _setup(ctx, sz, seed=7, noise=3e-2)        # the second sample of the marginal form
+    gps.append(other)
+    cand = _lib.Candidates(ctx, Xc)
+
+    def one(g, q):
+        return g.select_batch("ei", 0.0, eta, cand, q, "kriging_believer", diagnostics=True)
+
+    def two(g):
+        return _lib.acq_batch([g, other], "ei", 0.0, np.array([eta, eta - 0.01]), cand, 5, "constant_liar", eta,
+                              diagnostics=True)
+
+    try:
+        first, more, both, again = one(live, 3), one(live, 5), two(live), one(live, 3)
+        for a, b in ((first, again), (more, one(fresh_one, 5)), (both, two(fresh_two))):
+            assert a.n_made == b.n_made == len(a.indices)            # (every pick made: the whole report range is compared)
+            for x, y in ((a.indices, b.indices), (a.values, b.values), (a.fantasies, b.fantasies), (a.flags, b.flags),
+                         (a.trace, b.trace)):
+                assert x.tobytes() == y.tobytes()
+    finally:
+        cand.close()
+        for g in gps:
+            g.close()
+
+
+def _shape_change_emu_small(emu_ctx):
+    _check_shape_change(emu_ctx)
+
+
 def _check_chunked(ctx, N, D, M, ws_blocks, q):
     rs, og, g, eta, Xc = _setup(ctx, dict(N=N, D=D, M=M))
     try:
@@ -392,6 +426,7 @@ def _chunked_first_sweep_gives_the_same_bits_emu_small(emu_ctx):
 @pytest.mark.gpu
 def test_chunked_first_sweep_gives_the_same_bits_gpu(gpu_ctx):
     _check_chunked(gpu_ctx, 1000, 6, 5000, 16, 4)
+    _check_shape_change(gpu_ctx)
 
 
 # ---- 7. the marginal form ------------------------------------------------------------------------------------------------------
@@ -487,7 +522,7 @@ def test_device_checks_emu_small(emu_ctx):
     checks += [("output transform", _every_pick_with_output_transform_emu_small),
                ("D = 19", _every_pick_beyond_16_dimensions_emu),
                ("oracle's greedy choice", _picks_equal_the_oracles_greedy_choice_emu_small),
-               ("edges", _edges_emu_small), ("chunked first sweep", _chunked_first_sweep_gives_the_same_bits_emu_small),
+               ("edges", _edges_emu_small), ("shape change", _shape_change_emu_small), ("chunked first sweep", _chunked_first_sweep_gives_the_same_bits_emu_small),
                ("marginal", _marginal_emu_small)]
     failed = []
     for name, fn in checks:                      # every item runs and is reported, whatever the earlier ones did

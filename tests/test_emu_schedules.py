@@ -41,6 +41,16 @@ def test_schedules_expose_a_known_race():
     assert run(2, 0, 1) == 1.0 and run(1, 1, 0) == 1.0   # (each schedule is blind to the other's bug)
 
 
+def test_block_layout_selftest():
+    """the one rule every driver's device state block is laid out by (robo_amd/csrc/block_layout.h): offsets, total, bound
+    pointers, empty arrays and the const overload, checked by a stand-alone program (tests/hipemu/layout_selftest.cpp)"""
+    import subprocess
+    import build_emu
+    r = subprocess.run([build_emu.build_layout_selftest()], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "layout selftest ok" in r.stdout
+
+
 @pytest.fixture(scope="module")
 def emu():
     import build_emu

@@ -289,6 +289,34 @@ def _check_edges(ctx):
     g.close()
 
 
+def _check_shape_change(ctx):
+    """one live handle through the state-block shapes (3 starts, history 2) -> (4 starts, history 3) -> the first again:
+    every reallocation gives the bits of a handle that never held another shape (N = 22, D = 2, 2 iterations: every array
+    of the block is non-empty, and the int tail [npairs | state | pending | err] of 4 starts ends on half a double)"""
+    X, y = _sine_inputs(22, 2)
+    mean_c = float(y.mean())
+    prior, dev_prior = _default_prior(4)
+    starts = prior.sample_from_prior(4)
+    live, fresh = gps = [_lib.DeviceGP(ctx, "matern52", 22, 2) for _ in range(2)]
+
+    def run(g, k, history):
+        return g.optimize_hypers(mean_c, dev_prior, -20.0, 20.0, starts[:k], n_iters=2, diagnostics=True,
+                                 **dict(RULE, history=history))
+
+    try:
+        for g in gps:
+            g.set_data(X, y)
+        first, more, again = run(live, 3, 2), run(live, 4, 3), run(live, 3, 2)
+        for a, b in ((first, again), (more, run(fresh, 4, 3))):
+            assert a.best == b.best
+            for p, r in ((a.theta, b.theta), (np.float64(a.value), np.float64(b.value)), (a.final, b.final),
+                         (a.values, b.values), (a.status, b.status), (a.trace, b.trace)):
+                assert p.tobytes() == r.tobytes()
+    finally:
+        for g in gps:
+            g.close()
+
+
 def _check_fabolas_priors(ctx, N=150, D=4, T=8):
     """prior kinds 0 and 2 on the Fabolas kernel: F and G of every entry against the oracle, the steps against the rule"""
     from robo_amd.priors import EnvPrior
@@ -431,11 +459,13 @@ def test_trace_sine_gpu(gpu_ctx):
 
 def test_rule_edges(emu_ctx):
     _check_edges(emu_ctx)
+    _check_shape_change(emu_ctx)
 
 
 @pytest.mark.gpu
 def test_rule_edges_gpu(gpu_ctx):
     _check_edges(gpu_ctx)
+    _check_shape_change(gpu_ctx)
 
 
 def test_fabolas_priors(emu_ctx):

@@ -312,6 +312,34 @@ def _check_marginal(ctx, sz, label, S=3):
             g.close()
 
 
+def _check_shape_change(ctx):
+    """one live handle through the state-block shapes K = 3 -> K = 7 -> two samples -> K = 3: every reallocation gives the
+    bits of a handle that never held another shape (N = 22, D = 2, 40 candidates: every array of the block is non-empty,
+    the odd K puts every later array at an odd multiple of 8 bytes)"""
+    rs, X, y = _data(22, 2, 5)
+    live, fresh_one, fresh_two = gps = [_fit(ctx, "matern52", _theta(2, _ls2(2)), X, y) for _ in range(3)]
+    gps.append(_fit(ctx, "matern52", _theta(2, _ls2(2) * 1.2, noise=3e-2), X, y))      # the marginal form's second sample
+    cand = _lib.Candidates(ctx, rs.rand(40, 2))
+    eta, u = float(y.min()), rs.rand(2, 7)
+
+    def one(g, K):
+        return g.mes(eta, cand, u[0, :K], clamp=True, diagnostics=True)
+
+    def two(g):
+        return _lib.mes_marginal([g, gps[3]], np.array([eta, eta - 0.05]), cand, u, clamp=True, diagnostics=True)
+
+    try:
+        first, more, both, again = one(live, 3), one(live, 7), two(live), one(live, 3)
+        for a, b in ((first, again), (more, one(fresh_one, 7)), (both, two(fresh_two))):
+            for p, r in ((a.values, b.values), (a.ystar, b.ystar), (a.gumbel, b.gumbel), (a.trace, b.trace),
+                         ([a.max, a.argmax, a.flags], [b.max, b.argmax, b.flags])):
+                assert _bits(p, r)
+    finally:
+        cand.close()
+        for g in gps:
+            g.close()
+
+
 # ---- f. host classes and the front end ----------------------------------------------------------------------------------
 def _branin(x):
     a, b, c, r, s, t = 1.0, 5.1 / (4 * np.pi ** 2), 5.0 / np.pi, 6.0, 10.0, 1.0 / (8 * np.pi)
@@ -550,7 +578,8 @@ _DEVICE_CHECKS = [("a element-wise half", _check_elementwise),
                   ("b sampling half", lambda c: _check_sampling(c, "sampling")),
                   ("c fused", lambda c: _check_fused(c, SMALL, KINDS, "fused")),
                   ("c fused argument errors", _check_fused_errors),
-                  ("d marginal", lambda c: _check_marginal(c, SMALL, "marginal"))]
+                  ("d marginal", lambda c: _check_marginal(c, SMALL, "marginal")),
+                  ("shape change on a live handle", _check_shape_change)]
 _CLASS_CHECKS = [("f moments path", _check_class_moments_path), ("f GP model", _check_class_gp),
                  ("f marginalised", _check_class_marginal), ("f front end", _check_front_end)]
 

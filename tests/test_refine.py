@@ -585,14 +585,39 @@ def _check_independence(ctx, sz, ks):
         g.close()
 
 
+def _check_shape_change(ctx):
+    """one live handle through the state-block shapes 3 starts -> 8 starts -> 3 starts: every reallocation gives the bits
+    of a handle that never held another shape (N = 22, D = 2, 40 candidates, 2 steps: every array of the block is
+    non-empty and the odd counts make the 16-byte round-up between the arrays matter)"""
+    sz = dict(N=22, D=2, M=40)
+    (_, _, live, y, Xc), (_, _, fresh, _, _) = _setup(ctx, sz, seed=5), _setup(ctx, sz, seed=5)
+    cand = _lib.Candidates(ctx, Xc)
+
+    def run(g, k):
+        return g.refine("log_ei", 0.0, y.min(), cand, k, 2, 0.05, diagnostics=True)
+
+    try:
+        first, more, again = run(live, 3), run(live, 8), run(live, 3)
+        for a, b in ((first, again), (more, run(fresh, 8))):
+            assert (a.start_index, a.flags) == (b.start_index, b.flags)
+            for p, r in ((a.x, b.x), (np.float64(a.value), np.float64(b.value)), (a.starts, b.starts), (a.trace, b.trace)):
+                assert p.tobytes() == r.tobytes()
+    finally:
+        cand.close()
+        live.close()
+        fresh.close()
+
+
 def test_independence(emu_ctx):
     _check_independence(emu_ctx, SMALL, (4, 16))
+    _check_shape_change(emu_ctx)
 
 
 @pytest.mark.gpu
 def test_independence_gpu(gpu_ctx):
     _check_independence(gpu_ctx, LARGE, (4, 16))
     _check_independence(gpu_ctx, dict(LARGE, T=10), (64, 256))
+    _check_shape_change(gpu_ctx)
 
 
 # ---- 8. classes and front end --------------------------------------------------------------------------------------------------

@@ -244,6 +244,24 @@ def check_batch_equals_single(ctx, case):
             g.close()
 
 
+def check_shape_change(ctx):
+    """one live handle through the state-block shapes (4 walkers, 3 steps) -> (8 walkers, 2 steps) -> the first again: the
+    block grows once, and every call gives the bits of a handle that never held another shape (N = 22, D = 2: every
+    array of the block is non-empty and odd counts make the 16-byte round-up between the arrays matter)"""
+    kind, par = "log_ei", 0.0
+    small = _problem(dict(name="small", N=22, D=2, k=4, T=3, S=1), True, 0)
+    large = _problem(dict(name="large", N=22, D=2, k=8, T=2, S=1), True, 0)
+    assert np.array_equal(small["ogps"][0].X, large["ogps"][0].X)          # one model: the data are the seed's first draws
+    live, fresh = gps = _device_gps(ctx, small) + _device_gps(ctx, large)
+    try:
+        first, more, again = _run([live], small, kind, par), _run([live], large, kind, par), _run([live], small, kind, par)
+        for a, b in zip(first + more, again + _run([fresh], large, kind, par)):
+            assert a.tobytes() == b.tobytes()
+    finally:
+        for g in gps:
+            g.close()
+
+
 def _model(N, D, seed, ls2=0.3, noise=1e-3):
     """a trained robo_amd GaussianProcess on the library in use, inputs normalised from BOX"""
     from robo_amd.kernels import Matern52Kernel
@@ -530,6 +548,7 @@ def test_through_the_interpreter(emu_ctx):
         for sampling in ("log_ei", "ei"):
             step("equals host sampler", check_equals_host_sampler, case, sampling)
     step("batch equals single", check_batch_equals_single, emu_ctx, EMU3)
+    step("shape change on a live handle", check_shape_change, emu_ctx)
     step("protocol", check_protocol, emu_ctx, EMU3)
     step("declined call falls back", check_declined_call_falls_back, emu_ctx, EMU3)
     for mc in (False, True):
@@ -559,6 +578,7 @@ def test_gpu_equals_host_sampler(gpu_ctx, case, sampling):
 @pytest.mark.gpu
 def test_gpu_batch_equals_single(gpu_ctx):
     check_batch_equals_single(gpu_ctx, LARGE)
+    check_shape_change(gpu_ctx)
 
 
 @pytest.mark.gpu
