@@ -107,7 +107,11 @@ int32_t robo_ctx_set_phase_events(robo_ctx* ctx, int32_t on);
  * acq_screen (1 = default: an argmax-only acquisition call skips the candidates that cannot win, see robo_acq_eval_cand;
  * 0 never), acq_screen_min (batches above this many candidates are screened; -1 = default: winv_max, the size above which
  * the unscreened call is the block-row substitution; tests lower it), acq_screen_keep_max (percent of the batch that may
- * survive the screen, default 25: more than that and the call falls back to the plain sweep),
+ * survive the screen, default 25: more than that and the call falls back to the plain sweep), acq_screen_dot (which kernel
+ * forms the screen's bounds: -1 = default: the dot-form kernel, whose squared distances come from the fp64 matrix
+ * instruction on centred coordinates, for Matern-5/2 and RBF up to D = 32 where the fitted theta's worst-case distance
+ * error stays within 1e-12, the direct-difference kernel otherwise; 0 never the dot form; 1 wherever the kind and D permit,
+ * whatever the error: tests.  Both give rigorous bounds, so results do not depend on it),
  * trsm_chain (small batches on two or more block rows, solved by ONE launch whose block rows hand their tiles to each
  * other instead of one launch per block row, trsm_chain.hip: -1 = default: automatic (from three block rows on, while the
  * launch stays within trsm_chain_max_wg), 0 never, 1 wherever legal (from two block rows on); taken by
@@ -277,7 +281,9 @@ int32_t robo_cand_get_points(robo_cand* cand, double* out_Xc);
  * caller (tests) see that a batch was evaluated in several passes.                                              */
 int32_t robo_cand_workspace_chunk(robo_cand* cand, int64_t* out_chunk);
 /* name of the kernel that ran the solve of the last posterior on this handle ("" before the first): the library picks
- * it from the batch size and precision; bench.py labels its roofline block with it.  Diagnostics.                */
+ * it from the batch size and precision; bench.py labels its roofline block with it.  Diagnostics.  Where buf has room
+ * behind that string's terminator a second string follows it: the kernel that formed the bounds of the last acquisition
+ * screen on this handle ("screen_bounds_kernel", "screen_bounds_dot_kernel", "" before the first).                 */
 int32_t robo_cand_last_solve_kernel(robo_cand* cand, char* buf, int32_t buf_len);
 int32_t robo_cand_get_point(robo_cand* cand, int64_t index, double* out_x); /* one row: the winner */
 

@@ -624,6 +624,13 @@ class Candidates(object):
         check(lib().robo_cand_last_solve_kernel(self._h, buf, 64))
         return buf.value.decode()
 
+    def bounds_kernel(self):
+        """name of the kernel that ran the last bounds pass of the acquisition screen on this handle ("": none yet): the
+        second string robo_cand_last_solve_kernel leaves behind the first one's terminator"""
+        buf = C.create_string_buffer(128)
+        check(lib().robo_cand_last_solve_kernel(self._h, buf, 128))
+        return buf.raw.split(b"\0")[1].decode()
+
     def last_screen(self):
         """what the last argmax-only acquisition call on this handle did -> (candidates screened, survivors, SCREEN_* outcome)"""
         n, kept, outcome = C.c_int64(0), C.c_int64(0), C.c_int32(0)

@@ -316,7 +316,10 @@ int32_t robo_cand_workspace_chunk(robo_cand* k, int64_t* out_chunk) {
 
 int32_t robo_cand_last_solve_kernel(robo_cand* k, char* buf, int32_t buf_len) {
     if (!k || !buf || buf_len < 1) return ROBO_BAD_ARGUMENT;
-    snprintf(buf, (size_t)buf_len, "%s", k->solve_kernel ? k->solve_kernel : "");
+    const int used = snprintf(buf, (size_t)buf_len, "%s", k->solve_kernel ? k->solve_kernel : "");
+    // behind the terminator, where the buffer has room: the kernel of the last bounds pass of the acquisition screen
+    if (used >= 0 && used + 1 < buf_len)
+        snprintf(buf + used + 1, (size_t)(buf_len - used - 1), "%s", k->scr_bounds_kernel ? k->scr_bounds_kernel : "");
     return ROBO_OK;
 }
 

@@ -193,6 +193,9 @@ struct Tuning {
     long long acq_screen_min;    // ... for batches above this many candidates (-1 = default: winv_max, above which the unscreened
                                  // call is the block-row substitution; tests lower it so that the interpreter reaches the screen)
     int acq_screen_keep_max;     // ... while at most this percentage of the batch survives (25); beyond it the plain sweep runs
+    int acq_screen_dot;          // ... with the bounds pass's squared distances from the matrix pipe (screen_bounds_dot_kernel): -1
+                                 // (default) where the fitted theta's worst-case r2 error stays within SCREEN_DOT_BOUND, 0 never,
+                                 // 1 wherever the kind and D permit, whatever the bound (tests)
     int trsm_chain;              // small batches on >= 2 block rows: all block rows in ONE launch chained by hand-offs (trsm_chain.hip)
                                  // from the entry points that look at its time-out word: -1 auto (>= 3 block rows, within
                                  // trsm_chain_max_wg), 0 never, 1 wherever legal
@@ -480,8 +483,10 @@ struct robo_gp {
     robo::MesWork* mes;             // state of robo_mes_eval_* (mes.hip), kept between calls of one (m, S, K)
     robo::RepWork* rep;             // state of robo_rep_sample* (represent.hip), kept with gps[0] between calls
     robo::HyperWork* hyper;         // workspace of robo_gp_grad_loglik_batch / robo_gp_optimize_hypers (hyperopt.hip)
-    // the acquisition screen (screen.hip), lazy: [scratch (n_pad_max) | alpha = L^-T z (n_pad_max) | sum_j |alpha_j| sqrt(k_jj)]
+    // the acquisition screen (screen.hip), lazy: [scratch (n_pad_max) | alpha = L^-T z (n_pad_max) | sum_j |alpha_j| sqrt(k_jj),
+    // then, for the kinds and D the dot-form bounds kernel takes, its per-fit inputs (screen.hip "The dot form")]
     double* d_alpha;
+    double dot_extent;              // sum_d max_j (x_jd - centre_d)^2 of the scaled training rows alpha was computed for
     unsigned long long alpha_gen;   // fit_gen alpha was computed for (0: none)
     unsigned long long screen_gen;  // fit_gen the back-off below belongs to
     int screen_skip, screen_backoff;   // eligible calls still to pass unscreened after a failed screen; length of the next pause
@@ -537,6 +542,7 @@ struct robo_cand {
     int64_t scr_cap;                // rows scr_sub was allocated for
     int64_t scr_n, scr_kept;        // robo_cand_last_screen: candidates screened, survivors
     int scr_outcome;
+    const char* scr_bounds_kernel;  // name of the kernel that ran the last bounds pass on this handle (diagnostics: tests)
     // the chained solve (trsm_chain.hip), lazy, grows: [ticket | time-out | progress words] zeroed per launch, then the
     // per-(tile, block row) partial sums
     char* d_chain;

@@ -39,6 +39,42 @@
 // essentially 0 everywhere, and nothing is pruned) the call runs the plain sweep on everything and the factor is not
 // screened for the next 1, 2, 4, ... eligible calls: a regime that never prunes pays for the screen a vanishing number of
 // times.  A new fit starts afresh.
+//
+// The dot form.  Two kernels form the bounds.  screen_bounds_kernel accumulates r2 from direct differences on the VALU (32
+// of its ~100 fp64 instructions per pair at D = 16); screen_bounds_dot_kernel (Matern-5/2 and RBF, D <= SCREEN_DOT_MAX_D)
+// takes  r2 = |a|^2 + |b|^2 - 2 a.b  from v_mfma_f64_16x16x4_f64, which is idle in the first: training rows are the A operand
+// -2 b, candidates the B operand a, both CENTRED  (a = x_c - ctr, b = x_j - ctr, ctr the mid-range of the scaled training
+// rows per dimension: r2 does not move, the norms shrink to the data's half-extent), the contraction padded with zeros to
+// K = 4 KS >= D.  The norms cost no instruction of their own: |b|^2 is the accumulator's initial value (the C operand), |a|^2
+// the addend of the FMA that scales r2 for the covariance function anyway.  (Two extra K columns [|b|^2, 1] x [1, |a|^2]
+// were built first: 5 k-steps instead of 4 at D = 16 and 5 instead of 2 at D = 8, same VALU count, 0.90 against
+// 0.88 ms for the headline step.)  The rows, the norms, amp alpha and the scalars below are laid out once per fit_gen
+// (alpha_ensure), never per call.
+//   Error of that r2.  With u = 2^-53, eps = 2 u:
+//     centring   a_d, b_d carry a relative u each, so (a_d - b_d)^2 moves by <= 2 u (|a_d| + |b_d|)^2 <= 2 eps (a_d^2 + b_d^2):
+//                summed, 2 eps (|a|^2 + |b|^2);
+//     norms      |a|^2, |b|^2 by D FMAs: (D + 1) u each, <= (D + 1) eps (|a|^2 + |b|^2) / 2;
+//     product    K terms accumulated by the matrix pipe, one rounding per step; the terms' magnitudes sum to
+//                |a|^2 + |b|^2 + 2 sum_d |a_d b_d| <= 2 (|a|^2 + |b|^2):  K u 2 (|a|^2 + |b|^2) = K eps (|a|^2 + |b|^2);
+//                the factor -2 of the staged rows is exact;
+//     clamp      r2 >= 0 in exact arithmetic, so max(r2, SD_R2_MIN) moves the computed value towards the true one (or by 1e-290).
+//     finish     |a|^2 enters as fma(5, acc, 5 |a|^2) (RBF: -1/2): one rounding of the product 5 |a|^2 and one of the sum,
+//                <= 2 u (|a|^2 + |b|^2) in r2;
+//   Together < (K + 6) 2 eps (|a|^2 + |b|^2) / 2; the kernel uses (K + 6) 2 eps (|a|^2 + max_j |b_j|^2), twice that, as the
+//   bound |dr2| (gram_tile.h has the same analysis for the fit's tile, with (D + 3)).
+//   Effect on the mean.  |dk/dr2| <= amp c_KIND with c = 5/6 (Matern-5/2: dk/dr2 = -(5/6)(1 + s) e^-s, s = sqrt(5 r2), largest
+//   at s = 0) and c = 1/2 (RBF), so  |d mu~| <= y_std amp c_KIND |dr2| sum_j |alpha_j|.  Candidate c's delta gains
+//       SCREEN_DOT_SAFETY y_std amp c_KIND (K + 6) 2 eps (|x_c - ctr|^2 + max_j |x_j - ctr|^2) sum_j |alpha_j|
+//   evaluated in the kernel from its own centred norm: a candidate far outside the data box loosens its own bound only (a NaN
+//   or infinite coordinate makes the term, hence both bounds, NaN or vacuous: a survivor).  The sum's own rounding (four
+//   lane groups of 4 rows per tile, added in a fixed order) and amp folded into alpha are of the size SCREEN_DELTA_REL
+//   covers already.
+//   Selection (launch_screen_bounds).  The dot kernel runs where the kind and D permit, acq_screen_dot allows (-1 rule, 0
+//   never, 1 always) and, under the rule, gram_needs_direct's figure with centred extents,
+//       (D + 3) 2 eps sum_d max_j (x_jd - ctr_d)^2        (scaled rows; computed on the device with the centre),
+//   is at most SCREEN_DOT_BOUND = GRAM_DIRECT_BOUND = 1e-12.  Measured (tests/test_acq_screen_dot.py): at that bound the
+//   largest |mu~ - mu_sweep| stays below 1e-4 of the delta the kernel applies; the headline theta gives 8.4e-15.  The direct
+//   kernel keeps Fabolas, D above the limit and every theta beyond the bound (ln m = -10 at the prior's edge).
 #include <cmath>
 
 #include "api_internal.h"
@@ -50,6 +86,9 @@ constexpr double SCREEN_DELTA_REL = 1e-11;
 constexpr double SCREEN_RHO = 1e-5;
 constexpr double SCREEN_DIAG_RATIO_MAX = 1e4;
 constexpr int SCREEN_PROBE = NB;     // candidates of the probe: one tile
+constexpr int SCREEN_DOT_MAX_D = 32;          // the dot kernel's k-loop: KS = 1, 2, 4 (D <= 16, the tuned case) or 8 k-steps of 4
+constexpr double SCREEN_DOT_SAFETY = 4.0;
+constexpr double SCREEN_DOT_BOUND = GRAM_DIRECT_BOUND;     // worst-case r2 error a theta may carry into the dot kernel (measured: header)
 
 constexpr int SC_CAND = 64;          // candidates per workgroup of the bounds pass (one per lane; the 4 waves split the rows)
 constexpr int SC_ROWS = 32;          // training rows per wave and tile
@@ -182,6 +221,240 @@ __global__ __launch_bounds__(256) void screen_bounds_kernel(const double* __rest
     mt = mt * y_std + y_mean;
     const double v_prior = kself * (y_std * y_std);
     const double delta = SCREEN_DELTA_REL * (fabs(y_mean) + fabs(y_std) * (fabs(mean_c) + sqrt(fabs(kself)) * alpha_norm[0]));
+    double u, l;
+    screen_bounds(acq_kind, par, eta, mt, delta, v_prior, u, l);
+    up[i] = u;
+    lo[i] = l;
+}
+
+// ---- the bounds pass, dot form ------------------------------------------------------------------------------------------------
+// The same bounds from  r2 = |a|^2 + |b|^2 - 2 a.b  on the matrix pipe (header: "The dot form").  Once per fit_gen
+// screen_dot_prep_kernel finds the centre and the three scalars of the delta term, and screen_dot_pack_kernel lays the
+// centred training rows and amp alpha out in the order the bounds kernel consumes them:
+//     rows   [tile of 16 rows][k-step kk][lane l]  =  A[i = l & 15][k = 4 kk + (l >> 4)]  of the row  [-2 b_0 .. -2 b_{D-1}, 0 ..]
+//     alpha  [stage of 128 rows][0][tile of 16 rows][g = l >> 4][r]  =  amp alpha[16 tile + g + 4 r]   (the rows of lane l's D registers)
+//     norms  [stage of 128 rows][1][tile of 16 rows][g = l >> 4][r]  =  |b|^2 of the same rows: the accumulator's initial value
+// with zeros for rows >= n (they take no part: the FMA adds k * 0).
+template <int N>
+__device__ __forceinline__ double screen_block_reduce(double x, double* sh, int op) {     // op 0 sum, 1 max; N threads
+    __syncthreads();
+    sh[threadIdx.x] = x;
+    __syncthreads();
+    for (int o = N / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+            const double y = sh[threadIdx.x + o];
+            sh[threadIdx.x] = op == 0 ? sh[threadIdx.x] + y : (y > sh[threadIdx.x] ? y : sh[threadIdx.x]);
+        }
+        __syncthreads();
+    }
+    return sh[0];
+}
+
+// st[1] = sum_j |alpha_j|, st[2] = max_j |x_j - ctr|^2, st[3] = sum_d max_j (x_jd - ctr_d)^2, st[SD_CTR + d] = ctr_d (mid-range)
+constexpr int SD_CTR = 4;
+__global__ __launch_bounds__(256) void screen_dot_prep_kernel(const double* __restrict__ alpha, const double* __restrict__ Xs,
+                                                              int D, int n, double* __restrict__ st) {
+    __shared__ double sh[256];
+    __shared__ double sc[SCREEN_DOT_MAX_D];
+    const double inf = __builtin_huge_val();
+    double ext = 0.0;
+    for (int d = 0; d < D; ++d) {
+        double hi = -inf, nlo = -inf;
+        for (int j = threadIdx.x; j < n; j += 256) {
+            const double x = Xs[(size_t)j * D + d];
+            hi = x > hi ? x : hi;
+            nlo = -x > nlo ? -x : nlo;
+        }
+        hi = screen_block_reduce<256>(hi, sh, 1);
+        nlo = screen_block_reduce<256>(nlo, sh, 1);
+        const double c = 0.5 * (hi - nlo), h = hi - c, l = c + nlo;
+        ext += fmax(h * h, l * l);
+        if (threadIdx.x == 0) sc[d] = c;
+    }
+    __syncthreads();
+    double a = 0.0, r = 0.0;
+    for (int j = threadIdx.x; j < n; j += 256) {
+        a += fabs(alpha[j]);
+        double s = 0.0;
+        for (int d = 0; d < D; ++d) {
+            const double b = Xs[(size_t)j * D + d] - sc[d];
+            s = fma(b, b, s);
+        }
+        r = s > r ? s : r;
+    }
+    a = screen_block_reduce<256>(a, sh, 0);
+    r = screen_block_reduce<256>(r, sh, 1);
+    if (threadIdx.x == 0) {
+        st[1] = a;
+        st[2] = r;
+        st[3] = ext;
+    }
+    if ((int)threadIdx.x < D) st[SD_CTR + threadIdx.x] = sc[threadIdx.x];
+}
+
+// one workgroup per 64 rows (4 tiles of 16): thread -> (tile, lane) of every k-step
+__global__ __launch_bounds__(256) void screen_dot_pack_kernel(const double* __restrict__ alpha, const double* __restrict__ Xs,
+                                                              const double* __restrict__ st, double amp, int D, int ks, int n,
+                                                              double* __restrict__ rows, double* __restrict__ apack) {
+    const int tile = blockIdx.x * 4 + (threadIdx.x >> 6), l = threadIdx.x & 63, g = l >> 4;
+    const int row = tile * 16 + (l & 15);
+    const bool real = row < n;
+    double nb = 0.0;
+    if (real)
+        for (int d = 0; d < D; ++d) {
+            const double b = Xs[(size_t)row * D + d] - st[SD_CTR + d];
+            nb = fma(b, b, nb);
+        }
+    for (int kk = 0; kk < ks; ++kk) {
+        const int k = 4 * kk + g;
+        double v = 0.0;
+        if (real && k < D) v = -2.0 * (Xs[(size_t)row * D + k] - st[SD_CTR + k]);
+        rows[((size_t)tile * ks + kk) * 64 + l] = v;
+    }
+    // lane l < 16 holds row 16 tile + l: its norm and alpha go to slot (g, r) with l = g + 4 r
+    if (l < 16) {
+        const int slot = (tile >> 3) * 2 * NB + (tile & 7) * 16 + (l & 3) * 4 + (l >> 2);
+        apack[slot] = real ? amp * alpha[row] : 0.0;
+        apack[slot + NB] = nb;
+    }
+}
+
+// sqrt(5 r2) and exp(-s) as kern_math.h's pos_sqrt / exp_nonpos, less their two selects: r2 arrives clamped at SD_R2_MIN > 0
+// (rsq stays finite, s = 1e-145, k = 1 to the last bit), and 2^n underflows to 0 through v_ldexp_f64 by itself
+constexpr double SD_R2_MIN = 1e-290;
+template <int KIND>
+__device__ __forceinline__ void screen_dot_finish(const v4d acc, double nc, const double* __restrict__ al, double (&dot)[4]) {
+    double x[4], q[4];       // exp's argument (<= 0); the factor in front of it
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        // r2 = acc + |a|^2 inside the product that follows anyway (nc arrives times 5, times -1/2), the clamp behind it
+        if (KIND == ROBO_KERNEL_MATERN52_ARD) {
+            const double t = fmax(fma(5.0, acc[r], nc), 5.0 * SD_R2_MIN);
+            double y = __builtin_amdgcn_rsq(t);
+            const double e = fma(-t * y, y, 1.0);
+            y = fma(y * e, fma(e, 0.375, 0.5), y);
+            const double s0 = t * y;
+            const double s = fma(fma(-s0, s0, t), 0.5 * y, s0);
+            x[r] = -s;
+            q[r] = fma(t, 1.0 / 3.0, 1.0 + s);
+        } else {
+            x[r] = fmin(fma(-0.5, acc[r], nc), -0.5 * SD_R2_MIN);
+            q[r] = 1.0;
+        }
+    }
+    double nn[4], rr[4], p[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        nn[r] = rint(x[r] * 1.4426950408889634074);
+        rr[r] = fma(nn[r], -6.93147180369123816490e-01, x[r]);
+        rr[r] = fma(nn[r], -1.90821492927058770002e-10, rr[r]);
+        p[r] = 2.08767569878680989792e-09;
+    }
+    // Horner, one coefficient over the four rows: the constant is one scalar operand of four independent v_fma_f64
+#define ROBO_SD_HORNER(C)                                     \
+    _Pragma("unroll") for (int r = 0; r < 4; ++r) p[r] = fma(p[r], rr[r], C)
+    ROBO_SD_HORNER(2.50521083854417187751e-08);
+    ROBO_SD_HORNER(2.75573192239858906526e-07);
+    ROBO_SD_HORNER(2.75573192239858906526e-06);
+    ROBO_SD_HORNER(2.48015873015873015873e-05);
+    ROBO_SD_HORNER(1.98412698412698412698e-04);
+    ROBO_SD_HORNER(1.38888888888888888889e-03);
+    ROBO_SD_HORNER(8.33333333333333333333e-03);
+    ROBO_SD_HORNER(4.16666666666666666667e-02);
+    ROBO_SD_HORNER(1.66666666666666666667e-01);
+    ROBO_SD_HORNER(0.5);
+    ROBO_SD_HORNER(1.0);
+    ROBO_SD_HORNER(1.0);
+#undef ROBO_SD_HORNER
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        double kv = ldexp(p[r], (int)nn[r]);
+        if (KIND == ROBO_KERNEL_MATERN52_ARD) kv *= q[r];
+        dot[r] = fma(kv, al[r], dot[r]);
+    }
+}
+
+constexpr int SD_CAND = 64;          // candidates per workgroup: one MFMA column tile of 16 per wave
+constexpr int SD_STAGE = NB;         // training rows per LDS stage: 8 row tiles, swept by every wave
+
+// Same arguments as screen_bounds_kernel, read in the dot form's layout: Xs = the packed rows, alpha = the packed amp alpha
+// and norms, alpha_norm = the block [sum_j |alpha_j| sqrt(k_jj), sum_j |alpha_j|, max_j |b_j|^2, -, centre].  A wave holds its 16
+// candidates' centred coordinates as the B operand for the whole sweep; a lane owns 4 training rows x 1 candidate of every
+// 16 x 16 pair tile and finishes the tile while the matrix pipe forms the next one.
+template <int KIND, int KS>
+__global__ __launch_bounds__(256) void screen_bounds_dot_kernel(const double* __restrict__ Xcs, const double* __restrict__ Xs,
+                                                                const double* __restrict__ alpha,
+                                                                const double* __restrict__ alpha_norm, CovParams cp, int n,
+                                                                long long m, double mean_c, double y_mean, double y_std,
+                                                                int acq_kind, double par, double eta, double* __restrict__ up,
+                                                                double* __restrict__ lo) {
+    constexpr int TILES = SD_STAGE / 16, STAGE_DOUBLES = TILES * KS * 64, PER = STAGE_DOUBLES / 256;
+    __shared__ double sA[STAGE_DOUBLES];
+    __shared__ __attribute__((aligned(32))) double sAN[2 * SD_STAGE];      // amp alpha | norms of the stage's rows
+    const double *sAl = sAN, *sNj = sAN + SD_STAGE;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, D = cp.dim;
+    const long long i = (long long)blockIdx.x * SD_CAND + wave * 16 + (lane & 15);
+    const bool live = i < m;
+    const long long ii = live ? i : 0;
+    // B fragments: the centred candidate; its norm enters in the finish
+    double b[KS], nc = 0.0;
+#pragma unroll
+    for (int kk = 0; kk < KS; ++kk) {
+        const int k = 4 * kk + g;
+        b[kk] = k < D ? Xcs[ii * D + k] - alpha_norm[SD_CTR + k] : 0.0;
+        nc = fma(b[kk], b[kk], nc);
+    }
+    nc += __shfl_xor(nc, 16);
+    nc += __shfl_xor(nc, 32);
+    const double ncf = KIND == ROBO_KERNEL_MATERN52_ARD ? 5.0 * nc : -0.5 * nc;
+    const int nst = (n + SD_STAGE - 1) / SD_STAGE;
+    double pa[PER];
+#pragma unroll
+    for (int e = 0; e < PER; ++e) pa[e] = Xs[e * 256 + tid];
+    double pan = alpha[tid];
+    double dot[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int s = 0; s < nst; ++s) {
+        __syncthreads();
+#pragma unroll
+        for (int e = 0; e < PER; ++e) sA[e * 256 + tid] = pa[e];
+        sAN[tid] = pan;
+        __syncthreads();
+        if (s + 1 < nst) {
+            const double* nx = Xs + (size_t)(s + 1) * STAGE_DOUBLES;
+#pragma unroll
+            for (int e = 0; e < PER; ++e) pa[e] = nx[e * 256 + tid];
+            pan = alpha[(s + 1) * 2 * SD_STAGE + tid];
+        }
+        const double* nj = sNj + g * 4;
+        v4d acc = v4d{nj[0], nj[1], nj[2], nj[3]};
+#pragma unroll
+        for (int kk = 0; kk < KS; ++kk) acc = mfma_f64(sA[kk * 64 + lane], b[kk], acc);
+#pragma unroll
+        for (int t = 0; t < TILES; ++t) {
+            v4d nxt = acc;
+            if (t + 1 < TILES) {
+                nj += 16;
+                nxt = v4d{nj[0], nj[1], nj[2], nj[3]};
+#pragma unroll
+                for (int kk = 0; kk < KS; ++kk) nxt = mfma_f64(sA[((t + 1) * KS + kk) * 64 + lane], b[kk], nxt);
+            }
+            screen_dot_finish<KIND>(acc, ncf, sAl + t * 16 + g * 4, dot);
+            acc = nxt;
+        }
+    }
+    // the candidate's four row groups in a fixed order (every lane of the four ends with the same bits)
+    double mu = (dot[0] + dot[1]) + (dot[2] + dot[3]);
+    mu += __shfl_xor(mu, 16);
+    mu += __shfl_xor(mu, 32);
+    if (g != 0 || !live) return;
+    const double kself = cp.amp;
+    double mt = mu + mean_c;
+    mt = mt * y_std + y_mean;
+    const double v_prior = kself * (y_std * y_std);
+    const double ck = KIND == ROBO_KERNEL_MATERN52_ARD ? 5.0 / 6.0 : 0.5;
+    const double r2_err = (double)(4 * KS + 6) * 4.44089209850062616e-16 * (nc + alpha_norm[2]);
+    const double delta = SCREEN_DELTA_REL * (fabs(y_mean) + fabs(y_std) * (fabs(mean_c) + sqrt(fabs(kself)) * alpha_norm[0])) +
+                         SCREEN_DOT_SAFETY * fabs(y_std) * fabs(cp.amp) * ck * r2_err * alpha_norm[1];
     double u, l;
     screen_bounds(acq_kind, par, eta, mt, delta, v_prior, u, l);
     up[i] = u;
@@ -327,20 +600,55 @@ static bool screen_kind_ok(int kind, double par, double eta) {
 }
 
 // alpha = L^-T z of the factor the handle holds: once per fit_gen
+// the dot kernel's k-steps for this GP (0: not a kind or a D it takes); its per-fit block behind alpha's:
+// [scalars and centre (SD_CTR + SCREEN_DOT_MAX_D) | packed amp alpha and norms (2 n_pad_max) | packed rows (n_pad_max x 4 KS)]
+static int screen_dot_ks(const robo_gp* g) {
+    if ((g->kind != ROBO_KERNEL_MATERN52_ARD && g->kind != ROBO_KERNEL_RBF_ARD) || g->dim > SCREEN_DOT_MAX_D) return 0;
+    return g->dim <= 4 ? 1 : g->dim <= 8 ? 2 : g->dim <= 16 ? 4 : 8;
+}
+
 static int alpha_ensure(robo_gp* g) {
     const size_t np = (size_t)g->n_pad_max;
-    if (!g->d_alpha) ROBO_TRY(dev_alloc(&g->d_alpha, 2 * np + 8));
+    const int ks = screen_dot_ks(g);
+    const size_t dot_doubles = ks ? SD_CTR + SCREEN_DOT_MAX_D + 2 * np + np * 4 * (size_t)ks : 0;
+    if (!g->d_alpha) ROBO_TRY(dev_alloc(&g->d_alpha, 2 * np + 8 + dot_doubles));
     if (g->alpha_gen == g->fit_gen) return ROBO_OK;
-    hipStream_t st = g->ctx->stream;
+    robo_ctx* c = g->ctx;
+    hipStream_t st = c->stream;
     double* v = g->d_alpha;
     double* a = g->d_alpha + np;
     ROBO_HIP_CHECK(hipMemcpyAsync(v, g->d_K + (size_t)g->n * g->n_pad, (size_t)g->n * sizeof(double), hipMemcpyDeviceToDevice, st));
     ROBO_TRY(launch_bwd_rows(g, v, a));
+    double* stats = g->d_alpha + 2 * np;
     hipLaunchKernelGGL(screen_alpha_norm_kernel, dim3(1), dim3(256), 0, st, (const double*)a, (const double*)g->d_Xs, g->cov,
-                       g->n, g->d_alpha + 2 * np);
+                       g->n, stats);
+    g->dot_extent = 0.0;
+    if (ks) {
+        double* apack = stats + SD_CTR + SCREEN_DOT_MAX_D;
+        const int nst = (g->n + SD_STAGE - 1) / SD_STAGE;
+        hipLaunchKernelGGL(screen_dot_prep_kernel, dim3(1), dim3(256), 0, st, (const double*)a, (const double*)g->d_Xs, g->dim,
+                           g->n, stats);
+        hipLaunchKernelGGL(screen_dot_pack_kernel, dim3((unsigned)(nst * SD_STAGE / 64)), dim3(256), 0, st, (const double*)a,
+                           (const double*)g->d_Xs, (const double*)stats, g->cov.amp, g->dim, ks, g->n, apack + 2 * np, apack);
+        ROBO_LAUNCH_CHECK();
+        // the centred extent decides between the two kernels on the host: one small copy per fit_gen
+        double* hp = c->h_pinned + MAX_DIM + 16;
+        ROBO_HIP_CHECK(hipMemcpyAsync(hp, stats + 3, sizeof(double), hipMemcpyDeviceToHost, st));
+        ROBO_HIP_CHECK(hipStreamSynchronize(st));
+        g->dot_extent = hp[0];
+    }
     ROBO_LAUNCH_CHECK();
     g->alpha_gen = g->fit_gen;
     return ROBO_OK;
+}
+
+// whether the bounds of this factor come from the dot kernel (header: "Selection"); alpha_ensure has run
+static bool screen_dot_wanted(const robo_gp* g) {
+    const int t = g->ctx->tune.acq_screen_dot;
+    if (t == 0 || !screen_dot_ks(g)) return false;
+    if (t > 0) return true;
+    const double worst = (double)(g->dim + 3) * 4.44089209850062616e-16 * g->dot_extent;
+    return worst <= SCREEN_DOT_BOUND;            // (a NaN extent takes the direct kernel)
 }
 
 static int screen_buffers(robo_cand* k) {
@@ -360,7 +668,31 @@ static int launch_screen_bounds(robo_gp* g, robo_cand* k, int kind, double par, 
     const dim3 grid((unsigned)((k->m + SC_CAND - 1) / SC_CAND));
     const double* alpha = g->d_alpha + (size_t)g->n_pad_max;
     const double* anorm = g->d_alpha + 2 * (size_t)g->n_pad_max;
-#define ROBO_SCREEN_CALL(KIND)                                                                                            \
+    if (screen_dot_wanted(g)) {
+        const double* apack = anorm + SD_CTR + SCREEN_DOT_MAX_D;
+        const double* rows = apack + 2 * (size_t)g->n_pad_max;
+        const dim3 dgrid((unsigned)((k->m + SD_CAND - 1) / SD_CAND));
+#define ROBO_SCREEN_DOT_CALL(KIND, KS)                                                                                      \
+    hipLaunchKernelGGL((screen_bounds_dot_kernel<KIND, KS>), dgrid, dim3(256), 0, c->stream, (const double*)k->d_Xcs, rows,  \
+                       apack, anorm, g->cov, g->n, (long long)k->m, g->mean_c, g->y_mean, g->y_std, kind, par, eta,          \
+                       k->d_scr_up, k->d_scr_lo)
+#define ROBO_SCREEN_DOT_KS(KIND)                                  \
+    switch (screen_dot_ks(g)) {                                   \
+        case 1: ROBO_SCREEN_DOT_CALL(KIND, 1); break;             \
+        case 2: ROBO_SCREEN_DOT_CALL(KIND, 2); break;             \
+        case 4: ROBO_SCREEN_DOT_CALL(KIND, 4); break;             \
+        default: ROBO_SCREEN_DOT_CALL(KIND, 8); break;            \
+    }
+        if (g->kind == ROBO_KERNEL_MATERN52_ARD) ROBO_SCREEN_DOT_KS(ROBO_KERNEL_MATERN52_ARD)
+        else ROBO_SCREEN_DOT_KS(ROBO_KERNEL_RBF_ARD)
+#undef ROBO_SCREEN_DOT_KS
+#undef ROBO_SCREEN_DOT_CALL
+        ROBO_LAUNCH_CHECK();
+        k->scr_bounds_kernel = "screen_bounds_dot_kernel";
+        return ROBO_OK;
+    }
+    k->scr_bounds_kernel = "screen_bounds_kernel";
+#define ROBO_SCREEN_CALL(KIND)                                                                                           \
     do {                                                                                                                  \
         if (g->dim <= 16)                                                                                                 \
             hipLaunchKernelGGL((screen_bounds_kernel<KIND, true>), grid, dim3(256), 0, c->stream, (const double*)k->d_Xcs, \
