@@ -619,6 +619,68 @@ int32_t robo_paths_eval_cand(robo_paths* p, robo_cand* cand, double* out_values 
                              double* out_min /* S */, int64_t* out_argmin /* S */, uint32_t* out_flags);
 int32_t robo_paths_destroy(robo_paths* p);
 
+/* ---- refinement of a path's minimiser: multi-start projected gradient descent on the paths themselves, all descents of all
+ * paths in ONE launch (paths_refine.hip).  A path is a closed-form differentiable function: its value and gradient at a point
+ * need no solve and depend on nothing but that point.
+ *   Space.      Coordinates are in the GP's normalised input space, box [0, 1]^dim, as for robo_acq_refine_cand.
+ *   Value.      With x~ = x (.) ism (one rounding per coordinate, as scale_inputs_kernel), the value is the one above:
+ *               f_s(x) = (c + sum_f phi_f w_sf + sum_j k(x~, X~_j) alpha_sj) y_std + y_mean, with k formed from the squared
+ *               distance in the DIFFERENCE form sum_d (x~_d - X~_jd)^2 (cross_grad_kernel's).  These values are NOT
+ *               robo_paths_eval_cand's bits, which come off the matrix pipe in the dot form: a descent compares values of its
+ *               own kernel only, and the two agree within the bound of the path values (tests/test_paths_refine.py).
+ *   Gradient.   d f_s / d x_d = y_std ism_d [ -fscale sum_f w_sf sin(x~ . omega_f + b_f) omega_fd
+ *                                              + sum_j alpha_sj 2 k'(r_j^2) (x~_d - X~_jd) ],  fscale = sqrt(2 amp / F),
+ *               k' as in robo_gp_predict_grad: Matern-5/2 -amp (5/6)(1 + t) e^-t with t = sqrt(5 r^2), RBF -amp/2 e^(-r^2/2);
+ *               at r = 0 both are finite and the term is 0.
+ *   Order.      One wave per descent.  Lane l accumulates the terms of the training rows l, 64 + l, ... and then of the features
+ *               l, 64 + l, ... in index order (the value: one FMA per row; the gradient: one per row and coordinate); the 64
+ *               lanes' sums meet in a butterfly (xor 32, 16, .., 1).
+ *   Descent.    robo_acq_refine_cand's rule applied to -f_s.  Iteration 0 evaluates the start, which always becomes the
+ *               current point.  Then n_steps times: g_proj = g with the components that point out of the box at an active
+ *               bound set to 0 (x_d <= 0 and g_d > 0, x_d >= 1 and g_d < 0); |g_proj| = sqrt(sum_d g_proj_d^2), summed in
+ *               index order, every operation rounded once; |g_proj| = 0 or not finite: the descent is frozen;
+ *               y = clip(x - (alpha g_proj) / |g_proj|, 0, 1), each operation rounded once; accept iff f(y) < f(x) (then
+ *               x := y, alpha := min(2 alpha, 0.5)), else alpha := alpha / 2.  alpha starts at step0.  A trial whose value is
+ *               not finite is not taken and freezes the descent.  Every freeze raises ROBO_FLAG_FROZEN.
+ *   Invariance. A descent's whole trajectory depends only on its start point, the snapshot and its own path's weights: not
+ *               on P or its slot, on S or the other paths' draws, on the descents it shares a workgroup with, or on which of
+ *               the two entry points started it.
+ *   Trace.      out_trace ((n_steps + 1) x P x (2 dim + 3), nullable; P = S x n_starts path-major in the fused form): per
+ *               iteration and descent the trial point, its value, its gradient, the step length it was made with, and 1 / 0 /
+ *               2 / 3 = accepted / rejected / no trial made (frozen earlier or slot unused: the row repeats the current point,
+ *               an unused slot carries zeros and a NaN value) / value not finite (not taken; frozen from here on) -- the
+ *               layout and meaning of robo_acq_refine_cand's trace.
+ * robo_paths_descend runs P descents, descent i on path path_of[i] from x0[i]; out_x, out_value, out_grad (nullable) are the
+ * last accepted point, its value and gradient, out_code (nullable) the code of the last iteration.  n_steps = 0 evaluates
+ * value and gradient at the given points and nothing else.  A start coordinate outside [0, 1] or not finite, a path_of
+ * entry outside 0 .. S - 1, P outside 1 .. ROBO_PATHS_MAX_DESCENTS, n_steps < 0, step0 outside (0, 0.5], a NULL required
+ * pointer: ROBO_BAD_ARGUMENT.
+ * robo_paths_refine_cand runs the sweep exactly as robo_paths_eval_cand does without values, then selects the starts from
+ * what the sweep left on the device -- per path the best row of every group of 64 consecutive candidates (group = row / 64
+ * of the whole batch: a pass of the sweep covers a multiple of 128 rows, so the groups do not depend on the chunking).
+ * Path s's starts are the n_starts groups' bests with the smallest values, ties by ascending row; a group whose best is NaN
+ * (a NaN candidate loses its group) or that has no live row contributes none; fewer eligible groups than n_starts leaves
+ * unused slots (row -1 in out_starts (S x n_starts, nullable), never evolved).  Per path the descent with the smallest final
+ * value wins, first slot on ties, NaN only if nothing else is there: out_x (S x dim), out_value (S), out_start_index (S: the
+ * row of cand the winner started from; -1 and a NaN value when the path has no start).  n_steps = 0 returns the first start
+ * -- the sweep's own pick -- with its point and the sweep's value, robo_paths_eval_cand's bits on a batch without NaN.
+ * Fed the points of its own out_starts, robo_paths_descend reproduces its trajectories bit for bit.  *out_flags = the
+ * sweep's flags | ROBO_FLAG_FROZEN | ROBO_FLAG_NAN (a NaN result).  n_starts outside 1 .. ROBO_PATHS_MAX_STARTS, cand on
+ * another context, a NULL required pointer: ROBO_BAD_ARGUMENT; cand's dim is not the paths': ROBO_BAD_SHAPE.
+ * Both: dim above 64 (a descent keeps coordinate d in lane d): ROBO_BAD_SHAPE.  All refusals come before anything is
+ * launched; one synchronisation per call; the state stays with the paths object.  Event slots 30 and 31 bracket the sweep's
+ * passes as above, slots 28 and 29 the descent launch (robo_paths_descend: always; fused: under the condition of 24..27). */
+#define ROBO_PATHS_MAX_STARTS 1024      /* per path, as n_starts of robo_acq_refine_cand */
+#define ROBO_PATHS_MAX_DESCENTS 65536   /* P */
+int32_t robo_paths_descend(robo_paths* p, int32_t P, const int32_t* path_of, const double* x0 /* P x dim */,
+                           int32_t n_steps, double step0, double* out_x /* P x dim */, double* out_value /* P */,
+                           double* out_grad /* P x dim, nullable */, int32_t* out_code /* P, nullable: last code */,
+                           uint32_t* out_flags, double* out_trace /* nullable */);
+int32_t robo_paths_refine_cand(robo_paths* p, robo_cand* cand, int32_t n_starts, int32_t n_steps, double step0,
+                               double* out_x /* S x dim */, double* out_value /* S */,
+                               int64_t* out_start_index /* S: row in cand, -1 when no start */, uint32_t* out_flags,
+                               int64_t* out_starts /* S x n_starts, nullable */, double* out_trace /* nullable */);
+
 /* ---- entropy search: replaces InformationGain.innovations/_dh_fun/compute ---------------
  * (robo/acquisition_functions/information_gain.py:87-125,169-203,253-272), batched over candidates.
  * rep: the Nb <= 64 representer points as a candidate batch (same normalised space).  The EP

@@ -33,6 +33,8 @@ KG_MAX_DISC = 64                                 # robo_kg_*: cap on the discret
 EHVI_MAX_FRONT = 4096                            # robo_ehvi_*: cap on the points of the Pareto front
 PATHS_MAX = 64                                   # robo_paths_*: cap on the sample paths of one object
 PATHS_MAX_FEATURES = 4096                        # ... and on its random Fourier features
+PATHS_MAX_STARTS = 1024                          # robo_paths_refine_cand: cap on n_starts (per path)
+PATHS_MAX_DESCENTS = 65536                       # robo_paths_descend: cap on the descents of one call
 REFINE_MAX_STARTS = 1024                         # robo_acq_refine_*: cap on n_starts
 MC_MAX_NB, MC_MAX_NP, MC_MAX_NF = 64, 512, 65535   # limits of the Monte-Carlo p_min entry points (robo_pmin_mc, robo_igmc_*)
 
@@ -57,7 +59,7 @@ SYMBOLS = [
     "robo_mes_eval_cand", "robo_mes_eval_marginal_cand", "robo_mes_sample_min_moments", "robo_mes_eval_moments",
     "robo_kg_eval_cand", "robo_kg_eval_marginal_cand", "robo_kg_eval_moments",
     "robo_ehvi_eval_cand", "robo_ehvi_eval_moments",
-    "robo_paths_create", "robo_paths_eval_cand", "robo_paths_destroy",
+    "robo_paths_create", "robo_paths_eval_cand", "robo_paths_destroy", "robo_paths_descend", "robo_paths_refine_cand",
     "robo_ig_eval_cand", "robo_ig_eval_per_cost_cand", "robo_ig_eval_moments", "robo_gp_cross_cov",
     "robo_ep_joint_min", "robo_pmin_mc", "robo_igmc_eval_cand", "robo_igmc_eval_moments",
     "robo_comm_create_id", "robo_comm_init", "robo_comm_destroy", "robo_comm_info", "robo_comm_allgather",
@@ -247,6 +249,10 @@ def lib():
         "robo_paths_create": [vp, i32, i32, _dp, _dp, _dp, _dp, pp],
         "robo_paths_eval_cand": [vp, vp, _dp, _dp, C.POINTER(i64), C.POINTER(C.c_uint32)],
         "robo_paths_destroy": [vp],
+        "robo_paths_descend": [vp, i32, C.POINTER(i32), _dp, i32, dbl, _dp, _dp, _dp, C.POINTER(i32), C.POINTER(C.c_uint32),
+                               _dp],
+        "robo_paths_refine_cand": [vp, vp, i32, i32, dbl, _dp, _dp, C.POINTER(i64), C.POINTER(C.c_uint32), C.POINTER(i64),
+                                   _dp],
         "robo_ig_eval_cand": [vp, vp, vp, i32, dbl, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(i64)],
         "robo_ig_eval_per_cost_cand": [vp, vp, vp, i32, dbl, _dp, _dp, _dp, _dp, _dp, _dp, vp, vp, dbl, _dp, _dp,
                                        C.POINTER(i64)],
@@ -1084,6 +1090,27 @@ class PathsResult(object):
         self.values, self.min, self.argmin, self.flags = values, min, argmin, int(flags)
 
 
+class PathsDescentResult(object):
+    """x (P, D) the last accepted points in the GP's normalised input space, value (P,), grad (P, D) the gradient there,
+    code (P,) the code of the last iteration, flags; with diagnostics: trace (T + 1, P, 2 D + 3) = [trial point, value,
+    gradient, step length, 1 accepted / 0 rejected / 2 no trial made / 3 value not finite] per iteration and descent
+    (include/robo_hip.h)"""
+
+    def __init__(self, x, value, grad, code, flags, trace=None):
+        self.x, self.value, self.grad, self.code, self.flags, self.trace = x, value, grad, code, int(flags), trace
+
+
+class PathsRefineResult(object):
+    """per path: x (S, D) the refined minimiser in the GP's normalised input space, value (S,), start_index (S,) the row of
+    the candidate batch the winning descent started from (-1: the path had no start), flags; with diagnostics: starts
+    (S, K) rows of all starts in selection order (-1 = slot unused) and trace (T + 1, S K, 2 D + 3) as PathsDescentResult's,
+    path-major"""
+
+    def __init__(self, x, value, start_index, flags, starts=None, trace=None):
+        self.x, self.value, self.start_index, self.flags = x, value, start_index, int(flags)
+        self.starts, self.trace = starts, trace
+
+
 class PosteriorPaths(object):
     """robo_paths: S posterior sample paths of one fitted GP (Matheron's rule, include/robo_hip.h).  A snapshot: later fits
     of the GP do not change it."""
@@ -1117,6 +1144,39 @@ class PosteriorPaths(object):
         finally:
             if own:
                 cand.close()
+
+    def descend(self, path_of, x0, n_steps, step0, diagnostics=False):
+        """descent i on path path_of[i] from x0[i] ((P, D) in the GP's normalised input space, inside [0, 1]^D), all in one
+        launch (robo_paths_descend) -> PathsDescentResult; n_steps = 0: value and gradient at x0 and nothing else"""
+        x0 = _f64(x0)
+        if x0.ndim != 2 or x0.shape[1] != self.dim:
+            raise RoboBadShape("x0 must be (P, %d), got %r" % (self.dim, x0.shape))
+        P, D, T = x0.shape[0], self.dim, int(n_steps)
+        path_of = np.ascontiguousarray(path_of, dtype=np.int32)
+        if path_of.shape != (P,):
+            raise RoboBadShape("path_of must be (%d,), got %r" % (P, path_of.shape))
+        want = bool(diagnostics) and 1 <= P <= PATHS_MAX_DESCENTS and T >= 0
+        x, val, grad = np.empty((P, D)), np.empty(P), np.empty((P, D))
+        code, fl = np.empty(P, dtype=np.int32), C.c_uint32(0)
+        trace = np.empty((T + 1, P, 2 * D + 3)) if want else None
+        check(lib().robo_paths_descend(self._h, P, path_of.ctypes.data_as(C.POINTER(C.c_int32)), _arr(x0), T, float(step0),
+                                       _arr(x), _arr(val), _arr(grad), code.ctypes.data_as(C.POINTER(C.c_int32)),
+                                       C.byref(fl), _arr(trace) if want else None))
+        return PathsDescentResult(x, val, grad, code, fl.value, trace)
+
+    def refine(self, cand, n_starts, n_steps, step0, diagnostics=False):
+        """the sweep over a Candidates handle, per path the n_starts best groups' bests as starts, their descents and the
+        winners, without a host round trip (robo_paths_refine_cand) -> PathsRefineResult"""
+        S, D, K, T = self.n_paths, self.dim, int(n_starts), int(n_steps)
+        want = bool(diagnostics) and 1 <= K <= PATHS_MAX_STARTS and T >= 0
+        x, val, si, fl = np.empty((S, D)), np.empty(S), np.empty(S, dtype=np.int64), C.c_uint32(0)
+        starts = np.empty((S, K), dtype=np.int64) if want else None
+        trace = np.empty((T + 1, S * K, 2 * D + 3)) if want else None
+        check(lib().robo_paths_refine_cand(self._h, cand._h, K, T, float(step0), _arr(x), _arr(val),
+                                           si.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(fl),
+                                           starts.ctypes.data_as(C.POINTER(C.c_int64)) if want else None,
+                                           _arr(trace) if want else None))
+        return PathsRefineResult(x, val, si, fl.value, starts, trace)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:

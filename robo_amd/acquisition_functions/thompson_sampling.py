@@ -12,7 +12,10 @@ here from ``rng``; all arithmetic runs on the device (robo_amd/csrc/paths.hip; t
 * ``GaussianProcessMCMC``: every path first draws one hyper-parameter sample uniformly -- this is how Thompson sampling
   marginalises, so the class is NOT wrapped in ``MarginalizationGPMCMC``.  One paths object per distinct sample.
 
-The acquisition value is -f_0(x) (path 0), so that the maximisers' argmax is the path's minimiser.
+The acquisition value is -f_0(x) (path 0), so that the maximisers' argmax is the path's minimiser.  A path is a closed-form
+differentiable function: ``refine`` / ``select_batch(refine=True)`` continue from the best candidates by projected gradient
+descent on the paths themselves, all descents in one launch (robo_amd/csrc/paths_refine.hip), and ``value_and_gradient(X)``
+returns a path's value and gradient from one evaluation.
 """
 import numpy as np
 
@@ -124,13 +127,70 @@ class ThompsonSampling(BaseAcquisitionFunction):
             if cand is not X:
                 cand.close()
 
+    def _group_of(self, path):
+        """(PosteriorPaths, the path's number inside it) of the one group that holds ``path``"""
+        for group, members in self._groups:
+            at = np.flatnonzero(members == path)
+            if at.size:
+                return group, int(at[0])
+        raise ValueError("path %d of %d" % (path, self.n_paths))
+
     def compute(self, X, derivative=False, **kwargs):
-        """-f_0(X): the negated first path, (M,)"""
+        """-f_0(X): the negated first path, (M,).  The gradient is ``value_and_gradient``'s second half."""
         if derivative:
-            raise NotImplementedError("ThompsonSampling has no derivative")
+            raise NotImplementedError("ThompsonSampling has no derivative in compute(): value_and_gradient(X) returns the "
+                                      "value and the gradient of one consistent function")
         vals, mn, am = self._evaluate(X, True, paths=[0])
         self.last_max, self.last_argmax = -float(mn[0]), int(am[0])
         return -vals[0]
+
+    def value_and_gradient(self, X):
+        """(-f_0(X) (M,), -d f_0 / d X (M, D)) in the caller's input space (the chain rule through the input normalisation
+        applied; a device batch ``_lib.Candidates``: in the normalised space), with the shapes the other acquisitions'
+        ``derivative=True`` returns.  Both halves come from ONE evaluation of the descent kernel at X without steps
+        (robo_paths_descend, slices of ``_lib.PATHS_MAX_DESCENTS`` points), so that a line search sees one consistent
+        function.  That kernel forms the covariance entries from coordinate differences and the sweep forms them on the
+        matrix pipe: these values may differ in the last bits from ``compute(X)``.  X must lie inside the model's box."""
+        sub = self._ready()
+        if isinstance(X, _lib.CandidateShards):
+            raise NotImplementedError("ThompsonSampling runs on one device: candidate shards are not implemented")
+        if isinstance(X, _lib.Candidates):
+            if not sub.normalize_input:
+                raise TypeError("ThompsonSampling on a device candidate batch needs a model with normalize_input=True")
+            Xn, chain = X.points(), 1.0
+        else:
+            Xn = np.ascontiguousarray(sub._normalised(np.asarray(X, dtype=np.float64)), dtype=np.float64)
+            chain = 1.0
+            if sub.normalize_input:       # x_normalised = (x - lower) / (upper - lower)
+                chain = 1.0 / (np.asarray(sub.upper, dtype=np.float64) - np.asarray(sub.lower, dtype=np.float64))
+        group, at = self._group_of(0)
+        f, g = np.empty(Xn.shape[0]), np.empty(Xn.shape)
+        for c in range(0, Xn.shape[0], _lib.PATHS_MAX_DESCENTS):
+            part = Xn[c:c + _lib.PATHS_MAX_DESCENTS]
+            r = group.descend(np.full(part.shape[0], at, dtype=np.int32), part, 0, 0.05)
+            f[c:c + part.shape[0]], g[c:c + part.shape[0]] = r.value, r.grad
+        return -f, -g * chain
+
+    def refine(self, X, n_starts=256, n_steps=50, step0=0.05, diagnostics=False):
+        """Path 0's minimiser refined by gradient descent on the path itself, on the device (robo_paths_refine_cand): the
+        sweep over the candidates X ((M, D) in the caller's input space, or a device batch ``_lib.Candidates`` in the
+        normalised one), the best rows of the ``n_starts`` best groups of 64 candidates descend ``n_steps`` projected steps
+        in one launch -> the best point found, in the caller's input space.  ``last_refine`` keeps the library's result for
+        the group that holds path 0 (its paths in the group's order), ``last_max`` is the negated value."""
+        from robo_amd.acquisition_functions.base_acquisition import refine_model_check
+        sub = self._ready()
+        refine_model_check(sub, self.__class__.__name__)
+        cand = self._candidates(X, sub)
+        try:
+            group, at = self._group_of(0)
+            res = group.refine(cand, n_starts, n_steps, step0, diagnostics)
+        finally:
+            if cand is not X:
+                cand.close()
+        self.last_refine = res
+        self.last_max, self.last_argmax = -float(res.value[at]), int(res.start_index[at])
+        lower, upper = np.asarray(sub.lower, dtype=np.float64), np.asarray(sub.upper, dtype=np.float64)
+        return lower + (upper - lower) * res.x[at]
 
     def argmax(self, X):
         """Index of the first path's minimiser among X ((M, D) in the caller's input space, or a device batch
@@ -143,19 +203,37 @@ class ThompsonSampling(BaseAcquisitionFunction):
         raise NotImplementedError("ThompsonSampling has no candidate shard: multi-device and sharded forms are not "
                                   "implemented (use shard=False)")
 
-    def select_batch(self, X, q, **unused):
+    def select_batch(self, X, q, refine=False, n_starts=256, n_steps=50, step0=0.05, **unused):
         """q distinct rows of X, one per path -> (q, D) points in the caller's input space; ``last_batch`` keeps the row
         indices.  Path j takes its minimiser; when that row is taken already it takes its best row not yet taken (one
         read-back of that path's values).  With fewer than q paths, q paths are redrawn.  The fantasy arguments of the
-        greedy selections are ignored: a path needs none."""
+        greedy selections are ignored: a path needs none.
+
+        ``refine=True``: the q points are the q paths' minimisers refined on the device (``refine``'s rule, one fused call
+        per group of paths); ``last_batch`` keeps the row every path's winning descent started from.  Different paths are
+        different functions, so nothing is de-duplicated: equal points are kept."""
         q = int(q)
         sub = self._sub_models()[0]
+        if refine:
+            from robo_amd.acquisition_functions.base_acquisition import refine_model_check
+            refine_model_check(sub, self.__class__.__name__, "select_batch")
         if self._stale or not self._groups or self.n_paths < q:
             self._draw(max(q, self.n_paths) if self.n_paths < q else None)
         cand = self._candidates(X, sub)
         try:
             if q < 1 or q > cand.m:
                 raise ValueError("select_batch: q = %d outside 1 .. m = %d" % (q, cand.m))
+            if refine:
+                pts, rows, vals = np.empty((q, cand.dim)), np.empty(q, dtype=np.int64), np.empty(q)
+                for group, members in self._groups:
+                    keep = np.flatnonzero(members < q)
+                    if keep.size:
+                        r = group.refine(cand, n_starts, n_steps, step0)
+                        pts[members[keep]], rows[members[keep]], vals[members[keep]] = r.x[keep], r.start_index[keep], r.value[keep]
+                self.last_batch = rows
+                self.last_max, self.last_argmax = -float(vals[0]), int(rows[0])
+                lower, upper = np.asarray(sub.lower, dtype=np.float64), np.asarray(sub.upper, dtype=np.float64)
+                return lower + (upper - lower) * pts
             _, mn, am = self._evaluate(cand, False, paths=np.arange(q))
             picks = []
             for j in range(q):

@@ -48,6 +48,50 @@ int launch_paths_solve(robo_ctx* ctx, const double* d_L, int n_pad, const double
 int launch_paths_best(robo_ctx* ctx, const double* part_val, const long long* part_idx, long long n_part, int S, double* best_val,
                       long long* best_idx);
 
+// ---- refinement of a path's minimiser (paths_refine.hip; the rule is stated in include/robo_hip.h) ---------------------------------
+constexpr int PDG = 4;                       // descents per workgroup, one wave each (measured against 1: NOTES.md)
+constexpr int PATHS_REFINE_MAX_DIM = 64;     // a descent keeps coordinate d in lane d of its wave
+
+// one launch of the descent kernel: P descents from their starts to the last iteration
+struct PathsDescentArgs {
+    const double* Xs;            // data pass: scaled training rows, weights alpha (row path_of[i], ld_alpha doubles)
+    const double* alpha;
+    int n, ld_alpha;
+    const double* omega;         // feature pass: frequencies, phases, weights w (row path_of[i], ld_w doubles)
+    const double* phase;
+    const double* w;
+    int F, ld_w;
+    const double* ism;           // the snapshot's metric: x~ = x (.) ism
+    CovParams cp;
+    double fscale, mean_c, y_mean, y_std;
+    int P, T;
+    double step0;
+    const int* path_of;          // P
+    const long long* start;      // P rows the starts came from (-1: the slot is unused), or nullptr: every slot is used
+    const double* x0;            // P x dim starts
+    double *x, *f, *g;           // P x dim, P, P x dim: the last accepted point, its value and gradient
+    int* code;                   // P: the code of the last iteration
+    double* trace;               // (T + 1) x P x (2 dim + 3), or nullptr
+    unsigned* flags;
+};
+
+// the device state of robo_paths_descend / robo_paths_refine_cand: one block, laid out by paths_refine_ensure
+struct PathsRefineState {
+    double *x0, *x, *f, *g;      // PathsDescentArgs' arrays
+    double* sval;                // P: the sweep's value of every start (NaN: the slot is unused)
+    double* res;                 // S x (dim + 2): per path the winner's point, its value, the row its start came from
+    long long* start;
+    int *path_of, *code;
+};
+
+int launch_paths_descent(robo_ctx* ctx, const PathsDescentArgs& a);
+// per path the n_starts smallest group bests of the sweep -> start / sval / path_of / x0 of its n_starts slots
+int launch_paths_starts(robo_ctx* ctx, const double* part_val, const long long* part_idx, long long n_part, int S, int n_starts,
+                        const double* Xc, int dim, const PathsRefineState& st);
+// per path the descent with the smallest final value (sweep_only: the first start and the sweep's value of it) -> st.res
+int launch_paths_winners(robo_ctx* ctx, int S, int n_starts, int dim, const PathsRefineState& st, bool sweep_only,
+                         unsigned* flags);
+
 }  // namespace robo
 
 // a snapshot: nothing here points into the GP it was drawn from
@@ -63,4 +107,9 @@ struct robo_paths {
     double* d_best_val;
     long long* d_best_idx;
     unsigned* d_flags;
+    char* d_refine;              // the refinement's state block (grows), laid out behind `rs`; its diagnostics trace
+    size_t refine_cap;
+    double* d_trace;
+    size_t trace_cap;
+    robo::PathsRefineState rs;
 };

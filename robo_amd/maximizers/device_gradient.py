@@ -6,6 +6,10 @@ the ``n_starts`` best of them climb ``n_steps`` projected gradient steps in lock
 (robo_acq_refine_cand / robo_acq_refine_marginal_cand): the first maximiser here whose answer is not one of the
 candidates.  Not in the reference, whose gradient-based maximiser (robo/maximizers/scipy_optimizer.py) runs L-BFGS-B with
 finite differences from the host, one 1 x D acquisition call per function value.
+
+A ``ThompsonSampling`` objective is refined on its paths instead (robo_paths_refine_cand): per path the best rows of the
+best groups of candidates descend on the path itself, all in one launch; ``maximize_batch(q)`` -- which only such a
+maximiser has -- returns the q paths' refined minimisers (``ThompsonSampling.select_batch(refine=True)``).
 """
 import numpy as np
 
@@ -21,13 +25,21 @@ class DeviceGradientAscent(BaseMaximizer):
         self.n_starts = int(n_starts)
         self.n_steps = int(n_steps)
         self.step0 = float(step0)
+        from robo_amd.acquisition_functions.thompson_sampling import ThompsonSampling
+        if isinstance(objective_function, ThompsonSampling):      # (every other objective keeps the solver's refusal of batches)
+            self.maximize_batch = self._maximize_batch_paths
 
-    def maximize(self):
+    def _maximize_batch_paths(self, q, **unused):
+        """the q paths' refined minimisers from ONE candidate batch (the recipe of maximize()) -> (q, D)"""
+        return self.maximize(q=int(q))
+
+    def maximize(self, q=None):
         from robo_amd import _lib
         from robo_amd.acquisition_functions.base_acquisition import ClosedFormAcquisition
+        from robo_amd.acquisition_functions.thompson_sampling import ThompsonSampling
         acq = self.objective_func
         inner = getattr(acq, "acquisition_func", acq)
-        if not isinstance(inner, ClosedFormAcquisition):
+        if not isinstance(inner, (ClosedFormAcquisition, ThompsonSampling)):
             raise TypeError("DeviceGradientAscent needs EI, LogEI, PI or LCB (or MarginalizationGPMCMC over one of them): "
                             "%s has no gradient on the device" % type(inner).__name__)
         model = acq.model
@@ -48,6 +60,9 @@ class DeviceGradientAscent(BaseMaximizer):
         cand = _lib.Candidates(sub.gp.ctx, m=self.n_samples, seed=seed, n_uniform=int(self.n_samples * .7), loc=loc,
                                scale=scale)
         try:
+            if q is not None:
+                return acq.select_batch(cand, q, refine=True, n_starts=min(self.n_starts, self.n_samples),
+                                        n_steps=self.n_steps, step0=self.step0)
             return acq.refine(cand, n_starts=min(self.n_starts, self.n_samples), n_steps=self.n_steps, step0=self.step0)
         finally:
             cand.close()
