@@ -88,7 +88,7 @@ int32_t robo_ctx_device_name(robo_ctx* ctx, char* buf, int32_t buf_len);
  * robo_ctx_set_phase_events (off by default: four event packets cost a 1.8 ms fit ~30 us; the
  * environment variable ROBO_PHASE_EVENTS=1 switches them on at context creation), 19..23 around
  * the phases of robo_gp_fit (19 -> 21 gram kernel, 20 -> 21 gram phase, 21 -> 22 Cholesky,
- * 22 -> 23 log-likelihood).                                                                 */
+ * 22 -> 23 log-likelihood).  There are 34 slots, 0 .. 33.                                   */
 int32_t robo_ctx_event_record(robo_ctx* ctx, int32_t slot);
 int32_t robo_ctx_event_elapsed_ms(robo_ctx* ctx, int32_t slot_begin, int32_t slot_end, float* out_ms);
 int32_t robo_ctx_set_phase_events(robo_ctx* ctx, int32_t on);
@@ -572,6 +572,53 @@ int32_t robo_ehvi_eval_cand(robo_gp* gp1, robo_gp* gp2, robo_cand* cand, const d
 int32_t robo_ehvi_eval_moments(robo_ctx* ctx, int64_t m, const double* mean1, const double* var1, const double* mean2,
                                const double* var2, const double* front, int32_t P, const double* ref, double* out_ehvi,
                                double* out_max, int64_t* out_argmax, uint32_t* out_flags);
+
+/* ---- constrained expected improvement (Schonlau, Welch & Jones 1998; Gardner et al. 2014; Gelbart, Snoek & Adams 2014; not
+ * in the reference): expected improvement weighted by the probability that C black-box constraints hold, each modelled by a
+ * GP of its own.
+ *   Inputs.     The objective's posterior N(mu_0, s_0^2) and C constraints with independent posteriors N(mu_k, s_k^2),
+ *               k = 1 .. C, 0 <= C <= ROBO_CEI_MAX_CONSTRAINTS; thresholds t_k.  Constraint k holds when c_k(x) <= t_k, in the
+ *               scale robo_gp_predict_cand returns (output transform applied).
+ *   Per candidate.   z_k = (t_k - mu_k) / s_k,   L = sum_{k=1..C} norm_logcdf(z_k) summed in index order from 0,
+ *               PoF = exp(L).  norm_logcdf is the plain sweep's log Phi (erfcx form for z < -1: L stays finite where Phi has
+ *               long underflowed; log1p form otherwise).
+ *   Value.      acq_kind         has_eta   value
+ *               ROBO_ACQ_EI      1         EI(mu_0, var_0, eta, par) * PoF
+ *               ROBO_ACQ_LOG_EI  1         LogEI(mu_0, var_0, eta, par) + L
+ *               ROBO_ACQ_EI      0         PoF
+ *               ROBO_ACQ_LOG_EI  0         L
+ *               has_eta = 0 says that no feasible observation exists yet: eta and par are ignored.  The objective factor comes
+ *               from the device functions of robo_acq_eval_cand with the same guards (an EI in (-DBL_MIN, 0) is +0), so with
+ *               C = 0 and has_eta = 1 the call returns robo_acq_eval_cand's bits.  Any other acq_kind: ROBO_BAD_ARGUMENT.
+ *   Arithmetic. The difference, the quotient, every addition of the sum and the final product or addition are rounded once
+ *               and never contracted, and their order depends on nothing but C: a value's bits do not depend on the batch
+ *               position, on m, on the chunking or on which of the two entry points produced it.
+ *   Edges.      s_k == 0 (the moments form only: the fused form's variances are floored at DBL_EPSILON): the constraint's
+ *               factor is 1 (log factor 0) if mu_k <= t_k, else 0 (log factor -inf), and ROBO_FLAG_ZERO_SIGMA.  s_0 == 0 with
+ *               has_eta = 1 is handled by the objective functions' own branches and raises the same flag.  A NaN among the
+ *               2 (C + 1) moments, or a negative variance, gives NaN and ROBO_FLAG_NAN (the objective's moments count with
+ *               has_eta = 0 too).  A negative EI raises ROBO_FLAG_NEGATIVE_EI as in robo_acq_eval_cand.  argmax follows
+ *               np.argmax (first index, NaN maximal) through the sweep's own reduction.
+ * The fused form runs the C + 1 sweeps over cand, each chunked by the candidate workspace, into the rows of the handle's sample
+ * tables, then the fold kernel, the reduction and the read-back with one synchronisation.  The GPs may differ in kernel kind,
+ * hyper-parameters, N and output normalisation.  out_values (m) is nullable; out_trace, nullable, m x (2 (C + 1) + 2): per
+ * candidate mu_0, var_0, mu_1, var_1, .. mu_C, var_C as the kernel read them, then L and the objective factor (1 resp. 0 with
+ * has_eta = 0).  Later calls on the same handles return what they return on fresh ones.
+ * C out of range, a NULL required pointer, a non-finite threshold, has_eta = 1 with a non-finite eta or par, GPs or cand on
+ * different contexts: ROBO_BAD_ARGUMENT; a GP whose dim is not cand's: ROBO_BAD_SHAPE; a GP that is not fitted:
+ * ROBO_NOT_FITTED -- all before anything is launched.
+ * Event slots 32 and 33 bracket the fold kernel, under the condition of slots 24..27.                                  */
+#define ROBO_CEI_MAX_CONSTRAINTS 16
+int32_t robo_cei_eval_cand(robo_gp* objective, robo_gp* const* constraints, int32_t C, const double* thresholds,
+                           int32_t acq_kind, double par, double eta, int32_t has_eta, robo_cand* cand,
+                           double* out_values /* nullable */, double* out_max, int64_t* out_argmax, uint32_t* out_flags,
+                           double* out_trace /* nullable */);
+/* the fold kernel alone for any models' moments: mean0, var0 (m), means, vars (C x m, row-major, row k = constraint k + 1;
+ * not read when C = 0).  Equals the fused call bit for bit when fed the fused call's own trace.                          */
+int32_t robo_cei_eval_moments(robo_ctx* ctx, int64_t m, int32_t C, const double* mean0, const double* var0,
+                              const double* means, const double* vars, const double* thresholds, int32_t acq_kind,
+                              double par, double eta, int32_t has_eta, double* out_values, double* out_max,
+                              int64_t* out_argmax, uint32_t* out_flags);
 
 /* ---- pathwise posterior samples (Matheron's rule; Wilson et al. 2020, "Efficiently sampling functions from Gaussian
  * process posteriors"; not in the reference): S whole functions drawn from the posterior of one fitted GP, evaluated and

@@ -31,6 +31,7 @@ FANTASY_KINDS = {"kriging_believer": 0, "constant_liar": 1}   # robo_acq_batch_*
 MES_MAX_K = 128                                  # robo_mes_*: cap on the sampled minima per model
 KG_MAX_DISC = 64                                 # robo_kg_*: cap on the discretisation points of the knowledge gradient
 EHVI_MAX_FRONT = 4096                            # robo_ehvi_*: cap on the points of the Pareto front
+CEI_MAX_CONSTRAINTS = 16                         # robo_cei_*: cap on the constraints of constrained expected improvement
 PATHS_MAX = 64                                   # robo_paths_*: cap on the sample paths of one object
 PATHS_MAX_FEATURES = 4096                        # ... and on its random Fourier features
 PATHS_MAX_STARTS = 1024                          # robo_paths_refine_cand: cap on n_starts (per path)
@@ -59,6 +60,7 @@ SYMBOLS = [
     "robo_mes_eval_cand", "robo_mes_eval_marginal_cand", "robo_mes_sample_min_moments", "robo_mes_eval_moments",
     "robo_kg_eval_cand", "robo_kg_eval_marginal_cand", "robo_kg_eval_moments",
     "robo_ehvi_eval_cand", "robo_ehvi_eval_moments",
+    "robo_cei_eval_cand", "robo_cei_eval_moments",
     "robo_paths_create", "robo_paths_eval_cand", "robo_paths_destroy", "robo_paths_descend", "robo_paths_refine_cand",
     "robo_ig_eval_cand", "robo_ig_eval_per_cost_cand", "robo_ig_eval_moments", "robo_gp_cross_cov",
     "robo_ep_joint_min", "robo_pmin_mc", "robo_igmc_eval_cand", "robo_igmc_eval_moments",
@@ -246,6 +248,10 @@ def lib():
         "robo_ehvi_eval_cand": [vp, vp, vp, _dp, i32, _dp, _dp, _dp, C.POINTER(i64), C.POINTER(C.c_uint32), _dp],
         "robo_ehvi_eval_moments": [vp, i64, _dp, _dp, _dp, _dp, _dp, i32, _dp, _dp, _dp, C.POINTER(i64),
                                    C.POINTER(C.c_uint32)],
+        "robo_cei_eval_cand": [vp, pp, i32, _dp, i32, dbl, dbl, i32, vp, _dp, _dp, C.POINTER(i64), C.POINTER(C.c_uint32),
+                               _dp],
+        "robo_cei_eval_moments": [vp, i64, i32, _dp, _dp, _dp, _dp, _dp, i32, dbl, dbl, i32, _dp, _dp, C.POINTER(i64),
+                                  C.POINTER(C.c_uint32)],
         "robo_paths_create": [vp, i32, i32, _dp, _dp, _dp, _dp, pp],
         "robo_paths_eval_cand": [vp, vp, _dp, _dp, C.POINTER(i64), C.POINTER(C.c_uint32)],
         "robo_paths_destroy": [vp],
@@ -390,7 +396,7 @@ def mcmc_draws(random_state, n_steps, half):
 
 
 class Context(object):
-    """robo_ctx: one device, one HIP stream, 32 event slots."""
+    """robo_ctx: one device, one HIP stream, 34 event slots."""
 
     def __init__(self, device=0, stream=None):
         self._h = C.c_void_p()
@@ -933,6 +939,22 @@ class DeviceGP(object):
                                         _arr(trace) if trace is not None else None))
         return EHVIResult(out, *best.values(), trace)
 
+    def cei(self, constraint_gps, cand, thresholds, kind, par, eta, want_values=True, diagnostics=False):
+        """constrained expected improvement of ``cand`` with this GP as the objective and ``constraint_gps`` (C of them) as
+        the constraints c_k(x) <= thresholds[k]; kind "ei" or "log_ei"; eta None: no feasible incumbent yet, the probability
+        of feasibility alone (robo_cei_eval_cand) -> CEIResult"""
+        constraint_gps = list(constraint_gps)
+        Cn = len(constraint_gps)
+        thresholds = _cei_thresholds(thresholds, Cn)
+        out = np.empty(cand.m) if want_values else None
+        trace = np.empty((cand.m, 2 * (Cn + 1) + 2)) if (diagnostics and Cn <= CEI_MAX_CONSTRAINTS) else None
+        best = _Best()
+        check(lib().robo_cei_eval_cand(self._h, _handles(constraint_gps), Cn, _arr(thresholds), _cei_kind(kind), float(par),
+                                       0.0 if eta is None else float(eta), int(eta is not None), cand._h,
+                                       _arr(out) if want_values else None, *best.refs,
+                                       _arr(trace) if trace is not None else None))
+        return CEIResult(out, *best.values(), trace)
+
     def sample_paths(self, omega, phase, w, eps):
         """S posterior sample paths of the fitted GP from the caller's draws: omega (F, D) and phase (F,) in the scaled
         space (util/spectral.py draw_features), w (S, F) and eps (S, N) standard normal (robo_paths_create) -> PosteriorPaths"""
@@ -1080,6 +1102,47 @@ def ehvi_from_moments(ctx, mean1, var1, mean2, var2, front, ref):
     best = _Best()
     check(lib().robo_ehvi_eval_moments(ctx._h, mean1.shape[0], _arr(mean1), _arr(var1), _arr(mean2), _arr(var2), _arr(front),
                                        front.shape[0], _arr(ref), _arr(out), *best.refs))
+    return (out,) + best.values()
+
+
+class CEIResult(object):
+    """values (m,) or None, max, argmax, flags; with diagnostics: trace (m, 2 (C + 1) + 2) = per candidate the objective's
+    (mean, var), every constraint's (mean, var) as the kernel read them, then L = log PoF and the objective factor
+    (include/robo_hip.h)"""
+
+    def __init__(self, values, max, argmax, flags, trace=None):
+        self.values, self.max, self.argmax, self.flags, self.trace = values, float(max), int(argmax), int(flags), trace
+
+
+def _cei_kind(kind):
+    """the library's number of "ei" / "log_ei"; any other acquisition kind goes through for the library to refuse"""
+    return ACQ_KINDS[kind] if kind in ACQ_KINDS else int(kind)
+
+
+def _cei_thresholds(thresholds, C):
+    """(C,) contiguous fp64 (at least one element, so that C = 0 still has an address)"""
+    thresholds = _f64(np.asarray(thresholds, dtype=np.float64).reshape(-1))
+    if thresholds.shape[0] != C:
+        raise ValueError("%d thresholds for %d constraints" % (thresholds.shape[0], C))
+    return thresholds if C else np.zeros(1)
+
+
+def cei_from_moments(ctx, mean0, var0, means, vars, thresholds, kind, par, eta):
+    """the fold kernel of constrained expected improvement alone on the device for the moments of any models
+    (robo_cei_eval_moments): the objective's mean0, var0 (m,), the constraints' means, vars (C, m), thresholds (C,);
+    eta None: no feasible incumbent yet -> (values, max, argmax, flags)"""
+    mean0, var0 = _f64(mean0), _f64(var0)
+    assert mean0.ndim == 1 and var0.shape == mean0.shape
+    m = mean0.shape[0]
+    means, vars = _f64(means), _f64(vars)
+    assert means.ndim == 2 and means.shape[1] == m and vars.shape == means.shape
+    Cn = means.shape[0]
+    thresholds = _cei_thresholds(thresholds, Cn)
+    out = np.empty(m)
+    best = _Best()
+    check(lib().robo_cei_eval_moments(ctx._h, m, Cn, _arr(mean0), _arr(var0), _arr(means) if Cn else None,
+                                      _arr(vars) if Cn else None, _arr(thresholds), _cei_kind(kind), float(par),
+                                      0.0 if eta is None else float(eta), int(eta is not None), _arr(out), *best.refs))
     return (out,) + best.values()
 
 

@@ -93,7 +93,7 @@ static std::atomic<int> g_ctx_live{0};
 static void ctx_free(robo_ctx* c) {
     hipSetDevice(c->device);
     hipStreamSynchronize(c->stream);
-    for (int i = 0; i < 32; ++i) hipEventDestroy(c->events[i]);
+    for (int i = 0; i < ROBO_EVENT_SLOTS; ++i) hipEventDestroy(c->events[i]);
     if (c->aux_ready) {
         hipEventDestroy(c->ev_fork);
         for (int i = 0; i < ROBO_AUX_STREAMS; ++i) {
@@ -169,7 +169,7 @@ int32_t robo_ctx_create(int32_t device, void* hip_stream, robo_ctx** out) {
         ROBO_HIP_CHECK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
         c->own_stream = true;
     }
-    for (int i = 0; i < 32; ++i) ROBO_HIP_CHECK(hipEventCreate(&c->events[i]));
+    for (int i = 0; i < ROBO_EVENT_SLOTS; ++i) ROBO_HIP_CHECK(hipEventCreate(&c->events[i]));
     {   // internal phase events of robo_gp_fit (slots 19..23): off unless ROBO_PHASE_EVENTS=1 / set_phase_events
         const char* e = getenv("ROBO_PHASE_EVENTS");
         c->phase_events = e && atoi(e) != 0;
@@ -220,7 +220,7 @@ int32_t robo_ctx_device_name(robo_ctx* c, char* buf, int32_t len) {
 }
 
 int32_t robo_ctx_event_record(robo_ctx* c, int32_t slot) {
-    if (slot < 0 || slot >= 32) return ROBO_BAD_ARGUMENT;
+    if (slot < 0 || slot >= ROBO_EVENT_SLOTS) return ROBO_BAD_ARGUMENT;
     ROBO_HIP_CHECK(hipSetDevice(c->device));
     ROBO_HIP_CHECK(hipEventRecord(c->events[slot], c->stream));
     return ROBO_OK;
@@ -250,7 +250,7 @@ int32_t robo_ctx_set_tuning(robo_ctx* c, const char* key, int64_t value) {
 }
 
 int32_t robo_ctx_event_elapsed_ms(robo_ctx* c, int32_t a, int32_t b, float* out_ms) {
-    if (a < 0 || a >= 32 || b < 0 || b >= 32 || !out_ms) return ROBO_BAD_ARGUMENT;
+    if (a < 0 || a >= ROBO_EVENT_SLOTS || b < 0 || b >= ROBO_EVENT_SLOTS || !out_ms) return ROBO_BAD_ARGUMENT;
     ROBO_HIP_CHECK(hipEventSynchronize(c->events[b]));
     ROBO_HIP_CHECK(hipEventElapsedTime(out_ms, c->events[a], c->events[b]));
     return ROBO_OK;

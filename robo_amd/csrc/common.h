@@ -383,6 +383,7 @@ int launch_rep_accept(robo_ctx* ctx, const RepState& st, int acq_kind, double pa
 }  // namespace robo
 
 constexpr int ROBO_AUX_STREAMS = 3;
+constexpr int ROBO_EVENT_SLOTS = 34;    // robo_ctx_event_record's slots; the library's own phases use 19 and above
 constexpr int ROBO_CHAIN_SLOTS = 16;    // chained solves whose time-out words may be in flight between two synchronisations
 struct robo_ctx {
     int device;
@@ -398,7 +399,7 @@ struct robo_ctx {
     // (Python's cyclic GC gives no order) therefore cannot make a later robo_gp_destroy touch a dead stream.
     int users;
     bool closing;
-    hipEvent_t events[32];
+    hipEvent_t events[ROBO_EVENT_SLOTS];
     bool phase_events;   // record the internal phase events of robo_gp_fit (robo_ctx_set_phase_events, default off)
     char name[256];
     int num_cu;
@@ -517,7 +518,8 @@ struct robo_cand {
     double *d_S, *d_F, *d_Q, *d_G, *d_igc;
     size_t f_cap, q_cap, g_cap;
     double* d_kg;       // knowledge gradient (lazy, grows): [S x 64 discretisation means | S x m x (nb + 2) trace]; the expected
-                        // hypervolume improvement's [front (4096 x 2) | m x 4 trace] (api_ehvi.hip)
+                        // hypervolume improvement's [front (4096 x 2) | m x 4 trace] (api_ehvi.hip); constrained EI's trace
+                        // (m x (2 (C + 1) + 2)) or, in the moments form, the constraints' [means (C x m) | vars (C x m)]
     size_t kg_cap;
     double* h_igkey;    // host copy of the EP state whose device form d_G / d_igc hold (compared in full before an upload
     size_t igkey_len;   // is skipped: compute() is called many times per update(), information_gain.py:87-125 / :153-167)
@@ -684,6 +686,15 @@ int launch_kg(robo_ctx* ctx, const double* d_S, const double* d_var, const doubl
 int launch_ehvi(robo_ctx* ctx, const double* d_mean1, const double* d_var1, const double* d_mean2, const double* d_var2,
                 const double* d_front, int P, double r1, double r2, int64_t m, double* d_out, unsigned* d_flags,
                 double* d_trace);
+// cei.hip: EI weighted by the probability of feasibility of candidates c < m from the objective's moments and the C
+// constraints' (row k at d_means / d_vars + k * stride) into d_out; the thresholds travel as a kernel argument;
+// d_trace (m x (2 (C + 1) + 2): the moments, L, the objective factor) nullable
+struct CeiThresholds {
+    double t[ROBO_CEI_MAX_CONSTRAINTS];
+};
+int launch_cei(robo_ctx* ctx, const double* d_mean0, const double* d_var0, const double* d_means, const double* d_vars,
+               int64_t stride, int C, const CeiThresholds& th, int kind, double par, double eta, int has_eta, int64_t m,
+               double* d_out, unsigned* d_flags, double* d_trace);
 int launch_ig_dh(robo_ctx* ctx, const double* d_S, const double* d_var, double* d_F, double* d_Q, const double* d_G,
                  const double* d_consts, int64_t c0, int64_t cn, int64_t m, int nb, int npts, int kf, double sn2,
                  double H, double* d_out);

@@ -134,6 +134,8 @@ class DeviceRandomSampling(BaseMaximizer):
         sub = model.models[0] if hasattr(model, "models") and len(model.models) > 0 else model
         if hasattr(model, "objectives"):           # EHVI's pair of models: the first objective's context and box
             sub = model.objectives[0]
+        if hasattr(model, "constraints"):          # ConstrainedEI's objective and constraint models: the objective's
+            sub = model.objective
         if not getattr(sub, "normalize_input", False) or not hasattr(sub, "gp"):
             raise TypeError("DeviceRandomSampling needs a robo_amd GP model with normalize_input=True")
         lower, upper = np.asarray(sub.lower, dtype=np.float64), np.asarray(sub.upper, dtype=np.float64)
