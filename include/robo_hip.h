@@ -82,13 +82,22 @@ int32_t robo_ctx_destroy(robo_ctx* ctx);
 int32_t robo_ctx_live_count(int32_t* out_n);
 int32_t robo_ctx_synchronize(robo_ctx* ctx);
 int32_t robo_ctx_device_name(robo_ctx* ctx, char* buf, int32_t buf_len);
-/* HIP-event timing on the context's stream (what bench.py uses).  Slots 0..19 are the
- * caller's; the library itself records 24..27 around the phases of the posterior evaluation
- * (cross-gram, triangular solve, post) of the last candidate chunk and, when switched on with
- * robo_ctx_set_phase_events (off by default: four event packets cost a 1.8 ms fit ~30 us; the
- * environment variable ROBO_PHASE_EVENTS=1 switches them on at context creation), 19..23 around
- * the phases of robo_gp_fit (19 -> 21 gram kernel, 20 -> 21 gram phase, 21 -> 22 Cholesky,
- * 22 -> 23 log-likelihood).  There are 34 slots, 0 .. 33.                                   */
+/* HIP-event timing on the context's stream (what bench.py uses).  There are 34 slots, 0 .. 33.  Slots 0 .. 18 are the
+ * caller's; the library records the others itself (csrc/common.h names them; a pair is shared by calls that never run
+ * inside one another):
+ *   19 .. 23  the phases of robo_gp_fit: 19 -> 21 gram kernel, 20 -> 21 gram phase, 21 -> 22 Cholesky, 22 -> 23
+ *             log-likelihood.  Only when switched on with robo_ctx_set_phase_events (off by default: four event packets
+ *             cost a 1.8 ms fit ~30 us; the environment variable ROBO_PHASE_EVENTS=1 switches them on at context creation).
+ *   24 .. 27  the phases of the posterior evaluation of the last candidate chunk: 24 -> 25 cross-gram, 25 -> 26 triangular
+ *             solve, 26 -> 27 post.  "The condition of slots 24..27", which the pairs below share unless they say
+ *             otherwise: recorded for every batch above 16 384 rows, for smaller ones only when the phase events are
+ *             switched on.
+ *   28, 29    robo_gp_grad_loglik: everything after the factorisation (always recorded); the descent launch of
+ *             robo_paths_descend (always) and of robo_paths_refine_cand.
+ *   30, 31    what follows the sweeps: the envelope kernel of robo_kg_eval_cand and the element-wise half of
+ *             robo_mes_eval_cand (last sample each), the strip kernel of robo_ehvi_eval_cand, the passes of the path kernel
+ *             (robo_paths_eval_cand, robo_paths_refine_cand).
+ *   32, 33    the fold kernel of robo_cei_eval_cand.                                                                    */
 int32_t robo_ctx_event_record(robo_ctx* ctx, int32_t slot);
 int32_t robo_ctx_event_elapsed_ms(robo_ctx* ctx, int32_t slot_begin, int32_t slot_end, float* out_ms);
 int32_t robo_ctx_set_phase_events(robo_ctx* ctx, int32_t on);

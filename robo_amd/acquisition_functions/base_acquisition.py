@@ -9,8 +9,15 @@ arithmetic runs on the device:
   variance/mean, acquisition and argmax in one C-ABI call (robo_acq_eval);
 * any other BaseModel plugin            -> ``model.predict`` supplies (mean, var) and only the
   element-wise kernel runs (robo_acq_eval_moments).
+
+The host plumbing every acquisition on ONE device shares is stated here once: ``staged_candidates`` (a host array becomes a
+temporary device batch, a device batch is used as it is), ``host_points`` (a device batch back in the caller's input space,
+and the one condition under which that is possible), ``refuse_multi_device``, ``predicted_moments`` and
+:class:`OneDeviceAcquisition` (refusals, native / moments dispatch, ``compute`` / ``argmax``) -- what EHVI, ConstrainedEI and
+the knowledge gradient derive from and MES and Thompson sampling borrow.
 """
 import abc
+import contextlib
 import logging
 
 import numpy as np
@@ -18,6 +25,8 @@ import numpy as np
 from robo_amd import _lib
 
 logger = logging.getLogger(__name__)
+
+MOMENT_ROWS = 512           # candidates per predict() call of the moments paths
 
 
 class BaseAcquisitionFunction(object):
@@ -118,6 +127,142 @@ def refine_finish(acq, kind, model, res, cand):
     return lower + (upper - lower) * x
 
 
+@contextlib.contextmanager
+def staged_candidates(model, X):
+    """The candidates of a fused call as a device batch: a ``_lib.Candidates`` is yielded as it is and left open; an array
+    (caller's input space) goes through the model's own normalisation -- ``normalize`` where it has one (Fabolas), else the
+    [0, 1] scaling -- into a temporary batch on the model's context, closed on exit."""
+    if isinstance(X, _lib.Candidates):
+        yield X
+        return
+    norm = model.normalize if hasattr(model, "normalize") else model._normalised
+    cand = _lib.Candidates(model.gp.ctx, norm(np.asarray(X, dtype=np.float64)))
+    try:
+        yield cand
+    finally:
+        cand.close()
+
+
+def refuse_foreign_batch(model, who, needs_box=False):
+    """A device batch lives in the box [0, 1]^D of the model's normalised inputs.  It can be used as it is, or brought back
+    to the caller's input space, only by a model that normalises its inputs with that scaling alone (``needs_box``: and
+    says what the box is)."""
+    if not getattr(model, "normalize_input", False) or hasattr(model, "normalize") \
+            or (needs_box and (model.lower is None or model.upper is None)):
+        raise TypeError("%s on a device candidate batch needs a model with normalize_input=True whose input space is the "
+                        "normalised box (not a Fabolas model); pass the points as an array instead" % who)
+
+
+def host_points(model, X, who, box=None):
+    """An array as it is; a device batch in the caller's input space, under refuse_foreign_batch's condition.  ``box(model)``
+    returns (lower, upper) or raises the caller's own error for a model without a box; without ``box`` a model without one
+    is refused like the others."""
+    if not isinstance(X, _lib.Candidates):
+        return np.asarray(X, dtype=np.float64)
+    refuse_foreign_batch(model, who, needs_box=box is None)
+    lower, upper = box(model) if box is not None else (model.lower, model.upper)
+    lower, upper = np.asarray(lower, dtype=np.float64), np.asarray(upper, dtype=np.float64)
+    return lower + (upper - lower) * X.points()
+
+
+def refuse_multi_device(models, who, why):
+    """``devices=...`` models spread over several devices: NotImplementedError with the caller's reason ``why``"""
+    for m in models:
+        if getattr(m, "devices", None):
+            raise NotImplementedError("%s runs on one device: %s (devices=%r)" % (who, why, m.devices))
+
+
+def predicted_moments(models, X, rows=MOMENT_ROWS):
+    """[(mean, var)] per model, flat fp64 (M,) each, from the models' predict() on ``rows`` candidates per call"""
+    parts = [([], []) for _ in models]
+    for r0 in range(0, X.shape[0], rows):
+        for (mean, var), m in zip(parts, models):
+            a, b = m.predict(X[r0:r0 + rows])[:2]
+            mean.append(np.asarray(a, dtype=np.float64).ravel())
+            var.append(np.asarray(b, dtype=np.float64).ravel())
+    return [(np.concatenate(mean), np.concatenate(var)) for mean, var in parts]
+
+
+def same_box_natives(models):
+    """device GPs that take the same normalised candidates: one box, and one context after materialising -- what a fused
+    call over several models needs (a Fabolas model is not counted).  Raises while one of them is not trained."""
+    for m in models:
+        if not (hasattr(m, "acquisition") and hasattr(m, "gp")) or hasattr(m, "normalize"):
+            return False
+    first = models[0]
+    for m in models[1:]:
+        if bool(m.normalize_input) != bool(first.normalize_input):
+            return False
+        if first.normalize_input and not (np.array_equal(first.lower, m.lower) and np.array_equal(first.upper, m.upper)):
+            return False
+    for m in models:
+        if not m.is_trained:
+            raise Exception('Model has to be trained first!')
+        m._materialise()
+    return all(m.gp.ctx is first.gp.ctx for m in models)
+
+
+class OneDeviceAcquisition(BaseAcquisitionFunction):
+    """An acquisition over one or more fitted models that runs on ONE device: native device models take a fused call on a
+    device batch, every other model supplies its moments and the acquisition's own kernel alone runs on them.  A subclass
+    supplies ``_models()`` (the first one's normalisation and context stage the candidates), ``_is_native()`` where its rule
+    differs, ``_from_moments(Xhost, **how)`` and ``_fused(cand, want_values, **how)``, both -> (values or None, max, argmax);
+    ``why_one_device`` is its reason for refusing ``devices=...`` models."""
+
+    # no candidate shard (maximizers/random_sampling.py _check_candidate_shard)
+    candidate_shard = False
+    why_one_device = "multi-device and sharded forms are not implemented"
+
+    def __init__(self, model):
+        super(OneDeviceAcquisition, self).__init__(model)
+        self.last_max = None
+        self.last_argmax = None
+
+    def _models(self):
+        return [self.model]
+
+    def _is_native(self):
+        return hasattr(self.model, "acquisition") and hasattr(self.model, "gp")
+
+    def _evaluate(self, X, want_values, **how):
+        """-> (values or None, max, argmax); ``last_max`` / ``last_argmax`` are left to the caller"""
+        who = self.__class__.__name__
+        refuse_multi_device(self._models(), who, self.why_one_device)
+        if isinstance(X, _lib.CandidateShards):
+            raise NotImplementedError("%s runs on one device: candidate shards are not implemented" % who)
+        first = self._models()[0]
+        if not self._is_native():
+            vals, mx, am = self._from_moments(self._host_points(X), **how)
+        else:
+            if not first.is_trained:
+                raise Exception('Model has to be trained first!')
+            first._materialise()
+            if isinstance(X, _lib.Candidates):
+                refuse_foreign_batch(first, who)
+            with staged_candidates(first, X) as cand:
+                vals, mx, am = self._fused(cand, want_values, **how)
+        return vals, mx, int(am)
+
+    def _host_points(self, X):
+        return host_points(self._models()[0], X, self.__class__.__name__)
+
+    def compute(self, X, derivative=False, **kwargs):
+        if derivative:
+            raise NotImplementedError("%s has no derivative" % self.__class__.__name__)
+        vals, self.last_max, self.last_argmax = self._evaluate(X, True)
+        return vals
+
+    def argmax(self, X):
+        """Index of the best candidate of X ((M, D) in the caller's input space, or a device batch ``_lib.Candidates`` in
+        the normalised one): on the fused path only the maximiser comes back."""
+        _, self.last_max, self.last_argmax = self._evaluate(X, False)
+        return self.last_argmax
+
+    def argmax_sharded(self, comm, X_slice, global_offset):
+        raise NotImplementedError("%s has no candidate shard: multi-device and sharded forms are not implemented (use "
+                                  "shard=False)" % self.__class__.__name__)
+
+
 class ClosedFormAcquisition(BaseAcquisitionFunction):
     """EI / LogEI / PI / LCB on (mean, var, eta); subclasses set ``kind`` and the guards."""
 
@@ -177,13 +322,9 @@ class ClosedFormAcquisition(BaseAcquisitionFunction):
         model = self.model
         refine_model_check(model, self.__class__.__name__)
         model._materialise()
-        cand = X if isinstance(X, _lib.Candidates) else _lib.Candidates(model.gp.ctx, model._normalised(np.asarray(X)))
-        try:
+        with staged_candidates(model, X) as cand:       # (refine_model_check admits no model with a normalize() of its own)
             res = model.gp.refine(self.kind, self.par, self._eta(eta), cand, n_starts, n_steps, step0, diagnostics)
             return refine_finish(self, self.kind, model, res, cand)
-        finally:
-            if cand is not X:
-                cand.close()
 
     def select_batch(self, X, q, fantasy="kriging_believer", liar=None, diagnostics=False, eta=None):
         """q proposals from ONE candidate batch X ((M, D) in the caller's input space, or a device batch
@@ -196,14 +337,10 @@ class ClosedFormAcquisition(BaseAcquisitionFunction):
         model = self.model
         refine_model_check(model, self.__class__.__name__, "select_batch")
         model._materialise()
-        cand = X if isinstance(X, _lib.Candidates) else _lib.Candidates(model.gp.ctx, model._normalised(np.asarray(X)))
-        try:
+        with staged_candidates(model, X) as cand:
             res = model.gp.select_batch(self.kind, self.par, self._eta(eta), cand, q, fantasy,
                                         batch_liar(model, fantasy, liar), diagnostics)
             return batch_finish(self, self.kind, model, res, cand)
-        finally:
-            if cand is not X:
-                cand.close()
 
     def argmax_sharded(self, comm, X_slice, global_offset):
         """Candidate shard (robo_amd.sharding.sharded_argmax): this rank's slice of the candidate matrix, whose first

@@ -21,10 +21,8 @@ The incumbent is fixed per ``update()``, from the models' training targets.
 import numpy as np
 
 from robo_amd import _lib
-from robo_amd.acquisition_functions.base_acquisition import BaseAcquisitionFunction
+from robo_amd.acquisition_functions.base_acquisition import OneDeviceAcquisition, predicted_moments, same_box_natives
 from robo_amd.acquisition_functions.ehvi import _inputs, _targets
-
-_MOMENT_ROWS = 512          # candidates per predict() call of the moments path
 
 
 def _observed(C, thresholds):
@@ -104,10 +102,7 @@ class ConstrainedModels(object):
         return _inputs(self.objective)[j], self.y[j]
 
 
-class ConstrainedEI(BaseAcquisitionFunction):
-
-    # one device: no candidate shard (maximizers/random_sampling.py _check_candidate_shard)
-    candidate_shard = False
+class ConstrainedEI(OneDeviceAcquisition):
 
     def __init__(self, models, thresholds, par=0.0, log=False):
         """models: a ConstrainedModels, or a sequence (objective model, constraint model 1, .. constraint model C)"""
@@ -120,8 +115,6 @@ class ConstrainedEI(BaseAcquisitionFunction):
         self.thresholds = models.thresholds
         self.par = par
         self.log = bool(log)
-        self.last_max = None
-        self.last_argmax = None
         models.observe()
 
     kind = property(lambda self: "log_ei" if self.log else "ei")
@@ -146,98 +139,36 @@ class ConstrainedEI(BaseAcquisitionFunction):
             raise Exception('Model has to be trained first!')
         return self.model.eta
 
-    def _refuse_sharded(self):
-        for m in self.model.all_models:
-            if getattr(m, "devices", None):
-                raise NotImplementedError("ConstrainedEI runs on one device: multi-device and sharded forms are not "
-                                          "implemented (devices=%r)" % (m.devices,))
+    def _models(self):
+        return self.model.all_models
 
     def _is_native(self):
-        """device GPs that take the same normalised candidates: one context after materialising, one box"""
-        ms = self.model.all_models
-        for m in ms:
-            if not (hasattr(m, "acquisition") and hasattr(m, "gp")) or hasattr(m, "normalize"):
-                return False
-        first = ms[0]
-        for m in ms[1:]:
-            if bool(m.normalize_input) != bool(first.normalize_input):
-                return False
-            if first.normalize_input and not (np.array_equal(first.lower, m.lower) and np.array_equal(first.upper, m.upper)):
-                return False
-        for m in ms:
-            if not m.is_trained:
-                raise Exception('Model has to be trained first!')
-            m._materialise()
-        return all(m.gp.ctx is first.gp.ctx for m in ms)
-
-    def _host_points(self, X):
-        """an array as it is; a device batch (normalised box) in the caller's input space, under the condition EHVI states"""
-        if not isinstance(X, _lib.Candidates):
-            return np.asarray(X, dtype=np.float64)
-        m = self.model.objective
-        if not getattr(m, "normalize_input", False) or hasattr(m, "normalize") or m.lower is None or m.upper is None:
-            raise TypeError("ConstrainedEI on a device candidate batch needs models with normalize_input=True whose input "
-                            "space is the normalised box (not a Fabolas model); pass the points as an array instead")
-        lower, upper = np.asarray(m.lower, dtype=np.float64), np.asarray(m.upper, dtype=np.float64)
-        return lower + (upper - lower) * X.points()
+        return same_box_natives(self.model.all_models)
 
     def moments(self, X):
-        """(mean0, var0, means, vars): (M,), (M,), (C, M), (C, M) from the models' predict(), _MOMENT_ROWS candidates per call"""
-        ms = self.model.all_models
-        mu, var = [[] for _ in ms], [[] for _ in ms]
-        for r0 in range(0, X.shape[0], _MOMENT_ROWS):
-            rows = X[r0:r0 + _MOMENT_ROWS]
-            for o, m in enumerate(ms):
-                a, b = m.predict(rows)[:2]
-                mu[o].append(np.asarray(a, dtype=np.float64).ravel())
-                var[o].append(np.asarray(b, dtype=np.float64).ravel())
-        mu, var = [np.concatenate(a) for a in mu], [np.concatenate(a) for a in var]
-        M = mu[0].shape[0]
-        return mu[0], var[0], np.array(mu[1:]).reshape(len(ms) - 1, M), np.array(var[1:]).reshape(len(ms) - 1, M)
+        """(mean0, var0, means, vars): (M,), (M,), (C, M), (C, M) from the models' predict()"""
+        mv = predicted_moments(self.model.all_models, X)
+        C, M = len(mv) - 1, mv[0][0].shape[0]
+        means, vars_ = np.array([m for m, _ in mv[1:]]), np.array([v for _, v in mv[1:]])
+        return mv[0][0], mv[0][1], means.reshape(C, M), vars_.reshape(C, M)
 
-    def _evaluate(self, X, want_values, feasibility_only=False):
-        """-> (values or None, max, argmax) of the function itself, or of the probability of feasibility alone"""
-        self._refuse_sharded()
-        if isinstance(X, _lib.CandidateShards):
-            raise NotImplementedError("ConstrainedEI runs on one device: candidate shards are not implemented")
-        kind, eta = ("ei", None) if feasibility_only else (self.kind, self.eta)
-        if not self._is_native():
-            vals, mx, am, _ = _lib.cei_from_moments(_lib.default_context(), *self.moments(self._host_points(X)),
-                                                    thresholds=self.thresholds, kind=kind, par=self.par, eta=eta)
-        else:
-            obj = self.model.objective
-            cand = X
-            if isinstance(X, _lib.Candidates):
-                if not obj.normalize_input:
-                    self._host_points(X)                                         # raises the TypeError
-            else:
-                cand = _lib.Candidates(obj.gp.ctx, obj._normalised(np.asarray(X, dtype=np.float64)))
-            try:
-                res = obj.gp.cei([m.gp for m in self.model.constraints], cand, self.thresholds, kind, self.par, eta,
-                                 want_values=want_values)
-            finally:
-                if cand is not X:
-                    cand.close()
-            vals, mx, am = res.values, res.max, res.argmax
-        return vals, mx, int(am)
+    def _rule(self, feasibility_only):
+        """(kind, eta) of the function itself, or of the probability of feasibility alone"""
+        return ("ei", None) if feasibility_only else (self.kind, self.eta)
 
-    def compute(self, X, derivative=False, **kwargs):
-        if derivative:
-            raise NotImplementedError("ConstrainedEI has no derivative")
-        vals, self.last_max, self.last_argmax = self._evaluate(X, True)
-        return vals
+    def _from_moments(self, Xhost, feasibility_only=False):
+        kind, eta = self._rule(feasibility_only)
+        return _lib.cei_from_moments(_lib.default_context(), *self.moments(Xhost), thresholds=self.thresholds, kind=kind,
+                                     par=self.par, eta=eta)[:3]
 
-    def argmax(self, X):
-        """Index of the best candidate of X ((M, D) in the caller's input space, or a device batch ``_lib.Candidates`` in
-        the normalised one): on the fused path only the maximiser comes back."""
-        _, self.last_max, self.last_argmax = self._evaluate(X, False)
-        return int(self.last_argmax)
+    def _fused(self, cand, want_values, feasibility_only=False):
+        kind, eta = self._rule(feasibility_only)
+        res = self.model.objective.gp.cei([m.gp for m in self.model.constraints], cand, self.thresholds, kind, self.par, eta,
+                                          want_values=want_values)
+        return res.values, res.max, res.argmax
 
     def probability_of_feasibility(self, X):
         """prod_k P(c_k(x) <= t_k) of every candidate, by the same device rule (the value the function takes while no
         observation is feasible); ``last_max`` / ``last_argmax`` are left alone"""
         return self._evaluate(X, True, feasibility_only=True)[0]
 
-    def argmax_sharded(self, comm, X_slice, global_offset):
-        raise NotImplementedError("ConstrainedEI has no candidate shard: multi-device and sharded forms are not implemented "
-                                  "(use shard=False)")

@@ -19,10 +19,8 @@ The front is fixed per ``update()``: the non-dominated training targets of the t
 import numpy as np
 
 from robo_amd import _lib
-from robo_amd.acquisition_functions.base_acquisition import BaseAcquisitionFunction
+from robo_amd.acquisition_functions.base_acquisition import OneDeviceAcquisition, predicted_moments, same_box_natives
 from robo_amd.util.pareto import exclusive_contributions_2d, pareto_front_2d
-
-_MOMENT_ROWS = 512          # candidates per predict() call of the moments path
 
 
 def _targets(model):
@@ -91,17 +89,12 @@ class ObjectivePair(object):
         return _inputs(self.objectives[0])[j], self.Y[j]
 
 
-class EHVI(BaseAcquisitionFunction):
-
-    # one device, one front: no candidate shard (maximizers/random_sampling.py _check_candidate_shard)
-    candidate_shard = False
+class EHVI(OneDeviceAcquisition):
 
     def __init__(self, models, ref_point):
         pair = models if isinstance(models, ObjectivePair) else ObjectivePair(models, ref_point)
         super(EHVI, self).__init__(pair)
         self.ref_point = pair.ref_point
-        self.last_max = None
-        self.last_argmax = None
         pair.observe()
 
     def update(self, models):
@@ -123,87 +116,22 @@ class EHVI(BaseAcquisitionFunction):
             raise Exception('Model has to be trained first!')
         return self.model.front
 
-    def _refuse_sharded(self):
-        for m in self.model.objectives:
-            if getattr(m, "devices", None):
-                raise NotImplementedError("EHVI runs on one device: multi-device and sharded forms are not implemented "
-                                          "(devices=%r)" % (m.devices,))
+    def _models(self):
+        return self.model.objectives
 
     def _is_native(self):
-        """two device GPs that take the same normalised candidates: one context after materialising, one box"""
-        m1, m2 = self.model.objectives
-        for m in (m1, m2):
-            if not (hasattr(m, "acquisition") and hasattr(m, "gp")) or hasattr(m, "normalize"):
-                return False
-        if bool(m1.normalize_input) != bool(m2.normalize_input):
-            return False
-        if m1.normalize_input and not (np.array_equal(m1.lower, m2.lower) and np.array_equal(m1.upper, m2.upper)):
-            return False
-        for m in (m1, m2):
-            if not m.is_trained:
-                raise Exception('Model has to be trained first!')
-            m._materialise()
-        return m1.gp.ctx is m2.gp.ctx
-
-    def _host_points(self, X):
-        """an array as it is; a device batch (normalised box) in the caller's input space, under the condition the
-        knowledge gradient states"""
-        if not isinstance(X, _lib.Candidates):
-            return np.asarray(X, dtype=np.float64)
-        m = self.model.objectives[0]
-        if not getattr(m, "normalize_input", False) or hasattr(m, "normalize") or m.lower is None or m.upper is None:
-            raise TypeError("EHVI on a device candidate batch needs models with normalize_input=True whose input space is "
-                            "the normalised box (not a Fabolas model); pass the points as an array instead")
-        lower, upper = np.asarray(m.lower, dtype=np.float64), np.asarray(m.upper, dtype=np.float64)
-        return lower + (upper - lower) * X.points()
+        return same_box_natives(self.model.objectives)
 
     def moments(self, X):
-        """(mean1, var1, mean2, var2), (M,) each, from the two models' predict(), _MOMENT_ROWS candidates per call"""
-        out = [[], [], [], []]
-        for r0 in range(0, X.shape[0], _MOMENT_ROWS):
-            rows = X[r0:r0 + _MOMENT_ROWS]
-            for o, m in enumerate(self.model.objectives):
-                mu, var = m.predict(rows)[:2]
-                out[2 * o].append(np.asarray(mu, dtype=np.float64).ravel())
-                out[2 * o + 1].append(np.asarray(var, dtype=np.float64).ravel())
-        return tuple(np.concatenate(a) for a in out)
+        """(mean1, var1, mean2, var2), (M,) each, from the two models' predict()"""
+        (mean1, var1), (mean2, var2) = predicted_moments(self.model.objectives, X)
+        return mean1, var1, mean2, var2
 
-    def _evaluate(self, X, want_values):
-        self._refuse_sharded()
-        if isinstance(X, _lib.CandidateShards):
-            raise NotImplementedError("EHVI runs on one device: candidate shards are not implemented")
+    def _from_moments(self, Xhost):
         front = self.front
-        if not self._is_native():
-            vals, mx, am, _ = _lib.ehvi_from_moments(_lib.default_context(), *self.moments(self._host_points(X)), front=front,
-                                                     ref=self.ref_point)
-        else:
-            m1, m2 = self.model.objectives
-            cand = X
-            if isinstance(X, _lib.Candidates):
-                if not m1.normalize_input:
-                    self._host_points(X)                                         # raises the TypeError
-            else:
-                cand = _lib.Candidates(m1.gp.ctx, m1._normalised(np.asarray(X, dtype=np.float64)))
-            try:
-                res = m1.gp.ehvi(m2.gp, cand, front, self.ref_point, want_values=want_values)
-            finally:
-                if cand is not X:
-                    cand.close()
-            vals, mx, am = res.values, res.max, res.argmax
-        self.last_max, self.last_argmax = mx, int(am)
-        return vals
+        return _lib.ehvi_from_moments(_lib.default_context(), *self.moments(Xhost), front=front, ref=self.ref_point)[:3]
 
-    def compute(self, X, derivative=False, **kwargs):
-        if derivative:
-            raise NotImplementedError("EHVI has no derivative")
-        return self._evaluate(X, True)
-
-    def argmax(self, X):
-        """Index of the best candidate of X ((M, D) in the caller's input space, or a device batch ``_lib.Candidates`` in
-        the normalised one): on the fused path only the maximiser comes back."""
-        self._evaluate(X, False)
-        return int(self.last_argmax)
-
-    def argmax_sharded(self, comm, X_slice, global_offset):
-        raise NotImplementedError("EHVI has no candidate shard: multi-device and sharded forms are not implemented (use "
-                                  "shard=False)")
+    def _fused(self, cand, want_values):
+        m1, m2 = self.model.objectives
+        res = m1.gp.ehvi(m2.gp, cand, self.front, self.ref_point, want_values=want_values)
+        return res.values, res.max, res.argmax

@@ -24,16 +24,12 @@ from copy import deepcopy
 import numpy as np
 
 from robo_amd import _lib
-from robo_amd.acquisition_functions.base_acquisition import BaseAcquisitionFunction
+from robo_amd.acquisition_functions.base_acquisition import (MOMENT_ROWS, OneDeviceAcquisition, host_points,
+                                                             refuse_multi_device)
 from robo_amd.acquisition_functions.max_value_entropy_search import mes_box, mes_grid
 
-_MOMENT_ROWS = 512          # candidates per predict(full_cov=True) call of the moments path
-
-
-def kg_refuse_sharded(model, who):
-    if getattr(model, "devices", None):
-        raise NotImplementedError("%s runs on one device: multi-device and sharded forms of the knowledge gradient are "
-                                  "not implemented (devices=%r)" % (who, model.devices))
+# why a ``devices=...`` model is refused (refuse_multi_device)
+KG_ONE_DEVICE = "multi-device and sharded forms of the knowledge gradient are not implemented"
 
 
 def kg_discretisation(model, rng, n_disc, n_grid, given=None):
@@ -50,11 +46,10 @@ def kg_discretisation(model, rng, n_disc, n_grid, given=None):
     return G[np.argsort(mean, kind="stable")[:n_disc]]
 
 
-class KnowledgeGradient(BaseAcquisitionFunction):
+class KnowledgeGradient(OneDeviceAcquisition):
 
-    # the discretisation is chosen over the whole box: no candidate shard (maximizers/random_sampling.py
-    # _check_candidate_shard)
-    candidate_shard = False
+    # (the discretisation is chosen over the whole box: no candidate shard)
+    why_one_device = KG_ONE_DEVICE
 
     def __init__(self, model, n_disc=50, n_grid=10000, discretisation=None, include_self=True, rng=None):
         super(KnowledgeGradient, self).__init__(model)
@@ -67,8 +62,6 @@ class KnowledgeGradient(BaseAcquisitionFunction):
         self.rng = np.random.RandomState(np.random.randint(0, 10000)) if rng is None else rng
         self._disc = None            # this update's discretisation (caller's input space)
         self._rep = None             # ... as a device handle (native models): its solve is kept between calls
-        self.last_max = None
-        self.last_argmax = None
 
     def __deepcopy__(self, memo):
         new = self.__class__.__new__(self.__class__)
@@ -87,16 +80,13 @@ class KnowledgeGradient(BaseAcquisitionFunction):
         self._disc = None
         self._drop_rep()
 
-    def _is_native(self):
-        return hasattr(self.model, "acquisition") and hasattr(self.model, "gp")
-
     def _norm(self):
         return self.model.normalize if hasattr(self.model, "normalize") else self.model._normalised
 
     def discretisation_points(self):
         """this update's discretisation (nb, D) in the caller's input space (chosen on first use)"""
         if self._disc is None:
-            kg_refuse_sharded(self.model, "KnowledgeGradient")
+            refuse_multi_device([self.model], "KnowledgeGradient", KG_ONE_DEVICE)
             self._disc = kg_discretisation(self.model, self.rng, self.n_disc, self.n_grid, self.discretisation)
             self._drop_rep()
         return self._disc
@@ -112,23 +102,17 @@ class KnowledgeGradient(BaseAcquisitionFunction):
         return float(get()) if get is not None else 0.0
 
     def _host_points(self, X):
-        """an array as it is; a device batch (normalised box) in the caller's input space, under MES's condition"""
-        if not isinstance(X, _lib.Candidates):
-            return np.asarray(X, dtype=np.float64)
-        if not getattr(self.model, "normalize_input", False) or hasattr(self.model, "normalize"):
-            raise TypeError("KnowledgeGradient on a device candidate batch needs a model with normalize_input=True whose "
-                            "input space is the normalised box (not a Fabolas model); pass the points as an array instead")
-        lower, upper = mes_box(self.model)
-        return lower + (upper - lower) * X.points()
+        """(a model without a box: mes_box's ValueError)"""
+        return host_points(self.model, X, "KnowledgeGradient", box=mes_box)
 
     def moments(self, X):
         """(s (M, nb) signed-as-given covariances with the discretisation, v (M,), mean (M,), disc_mean (nb,)) from the
-        model's predict(full_cov=True), _MOMENT_ROWS candidates per call"""
+        model's predict(full_cov=True), MOMENT_ROWS candidates per call"""
         Z = self.discretisation_points()
         nb = Z.shape[0]
         s, v, mean, disc = [], [], [], None
-        for r0 in range(0, X.shape[0], _MOMENT_ROWS):
-            rows = X[r0:r0 + _MOMENT_ROWS]
+        for r0 in range(0, X.shape[0], MOMENT_ROWS):
+            rows = X[r0:r0 + MOMENT_ROWS]
             mu, cov = self.model.predict(np.concatenate((rows, Z), axis=0), full_cov=True)
             mu, cov = np.asarray(mu, dtype=np.float64).ravel(), np.asarray(cov, dtype=np.float64)
             k = rows.shape[0]
@@ -138,45 +122,10 @@ class KnowledgeGradient(BaseAcquisitionFunction):
             disc = mu[k:k + nb] if disc is None else disc
         return np.concatenate(s), np.concatenate(v), np.concatenate(mean), disc
 
-    def _evaluate(self, X, want_values):
-        kg_refuse_sharded(self.model, "KnowledgeGradient")
-        if isinstance(X, _lib.CandidateShards):
-            raise NotImplementedError("KnowledgeGradient runs on one device: candidate shards are not implemented")
-        if not self._is_native():
-            vals, mx, am, _ = _lib.kg_from_moments(_lib.default_context(), *self.moments(self._host_points(X)), sn2=self._sn2(),
-                                                   include_self=self.include_self)
-        else:
-            model = self.model
-            if not model.is_trained:
-                raise Exception('Model has to be trained first!')
-            model._materialise()
-            cand = X
-            if isinstance(X, _lib.Candidates):
-                # a device batch lives in the normalised box: used as it is, under the condition MES states
-                if not getattr(model, "normalize_input", False) or hasattr(model, "normalize"):
-                    self._host_points(X)                                         # raises the TypeError
-            else:
-                cand = _lib.Candidates(model.gp.ctx, self._norm()(np.asarray(X, dtype=np.float64)))
-            try:
-                res = model.gp.kg(cand, self._rep_handle(), self._sn2(), self.include_self, want_values=want_values)
-            finally:
-                if cand is not X:
-                    cand.close()
-            vals, mx, am = res.values, res.max, res.argmax
-        self.last_max, self.last_argmax = mx, int(am)
-        return vals
+    def _from_moments(self, Xhost):
+        return _lib.kg_from_moments(_lib.default_context(), *self.moments(Xhost), sn2=self._sn2(),
+                                    include_self=self.include_self)[:3]
 
-    def compute(self, X, derivative=False, **kwargs):
-        if derivative:
-            raise NotImplementedError("KnowledgeGradient has no derivative")
-        return self._evaluate(X, True)
-
-    def argmax(self, X):
-        """Index of the best candidate of X ((M, D) in the caller's input space, or a device batch ``_lib.Candidates`` in
-        the normalised one): the fused call with only the maximiser coming back."""
-        self._evaluate(X, False)
-        return int(self.last_argmax)
-
-    def argmax_sharded(self, comm, X_slice, global_offset):
-        raise NotImplementedError("KnowledgeGradient has no candidate shard: multi-device and sharded forms are not "
-                                  "implemented (use shard=False)")
+    def _fused(self, cand, want_values):
+        res = self.model.gp.kg(cand, self._rep_handle(), self._sn2(), self.include_self, want_values=want_values)
+        return res.values, res.max, res.argmax

@@ -17,7 +17,8 @@ from copy import deepcopy
 import numpy as np
 
 from robo_amd import _lib
-from robo_amd.acquisition_functions.base_acquisition import BaseAcquisitionFunction, ClosedFormAcquisition
+from robo_amd.acquisition_functions.base_acquisition import (BaseAcquisitionFunction, ClosedFormAcquisition,
+                                                             refuse_multi_device, staged_candidates)
 
 logger = logging.getLogger(__name__)
 
@@ -295,13 +296,8 @@ class MarginalizationGPMCMC(BaseAcquisitionFunction):
         # FabolasGP sub-models map their inputs through normalize() ([0,1] scaling of the configuration
         # columns + basis function on the fidelity column, fabolas_gp.py:122-126); plain GPs through the
         # [0,1] normalisation
-        norm = models[0].normalize if hasattr(models[0], "normalize") else models[0]._normalised
-        cand = X_test if isinstance(X_test, _lib.Candidates) else _lib.Candidates(gps[0].ctx, norm(X_test))
-        try:
+        with staged_candidates(models[0], X_test) as cand:
             vals, mx, am, flags = _lib.acq_marginal(gps, est[0].kind, est[0].par, eta, cand, want_values)
-        finally:
-            if cand is not X_test:
-                cand.close()
         self.last_max, self.last_argmax = mx, am
         return vals, flags
 
@@ -312,15 +308,15 @@ class MarginalizationGPMCMC(BaseAcquisitionFunction):
 
     def _mes_native(self):
         """all sub-models are trained device GPs on one context -> the marginal entry points (robo_mes_eval_marginal_cand)"""
-        from robo_amd.acquisition_functions.max_value_entropy_search import mes_refuse_sharded
-        mes_refuse_sharded(self.model, "MarginalizationGPMCMC(MES)")
+        from robo_amd.acquisition_functions.max_value_entropy_search import MES_ONE_DEVICE
+        refuse_multi_device([self.model], "MarginalizationGPMCMC(MES)", MES_ONE_DEVICE)
         if self.sample_shard:
             raise NotImplementedError("MarginalizationGPMCMC(MES) has no sample shard: y* is sampled per hyper-parameter "
                                       "sample on one device")
         if not self.estimators:
             return False
         for e in self.estimators:
-            mes_refuse_sharded(e.model, "MarginalizationGPMCMC(MES)")
+            refuse_multi_device([e.model], "MarginalizationGPMCMC(MES)", MES_ONE_DEVICE)
             if not (hasattr(e.model, "acquisition") and hasattr(e.model, "gp")) or hasattr(e.model, "normalize") \
                     or not getattr(e.model, "is_trained", False):
                 return False
@@ -335,13 +331,9 @@ class MarginalizationGPMCMC(BaseAcquisitionFunction):
         f, est = self.acquisition_func, self.estimators
         gps = [e.model.gp for e in est]
         etas = np.array([e._eta() for e in est])
-        cand = X if isinstance(X, _lib.Candidates) else _lib.Candidates(gps[0].ctx, est[0].model._normalised(np.asarray(X)))
-        try:
+        with staged_candidates(est[0].model, X) as cand:      # (_mes_native admits no model with a normalize() of its own)
             u = mes_uniforms(f.rng, (len(est), f.n_samples))
             return _lib.mes_marginal(gps, etas, cand, u, f.clamp, want_values, diagnostics)
-        finally:
-            if cand is not X:
-                cand.close()
 
     def _mes_compute(self, X_test):
         """the paper's form: per model update one set of y*_s per sample, drawn over ONE discretisation by the fused
@@ -375,15 +367,15 @@ class MarginalizationGPMCMC(BaseAcquisitionFunction):
 
     def _kg_native(self):
         """all sub-models are trained device GPs on one context -> the marginal entry point (robo_kg_eval_marginal_cand)"""
-        from robo_amd.acquisition_functions.knowledge_gradient import kg_refuse_sharded
-        kg_refuse_sharded(self.model, "MarginalizationGPMCMC(KnowledgeGradient)")
+        from robo_amd.acquisition_functions.knowledge_gradient import KG_ONE_DEVICE
+        refuse_multi_device([self.model], "MarginalizationGPMCMC(KnowledgeGradient)", KG_ONE_DEVICE)
         if self.sample_shard:
             raise NotImplementedError("MarginalizationGPMCMC(KnowledgeGradient) has no sample shard: multi-device and "
                                       "sharded forms of the knowledge gradient are not implemented")
         if not self.estimators:
             return False
         for e in self.estimators:
-            kg_refuse_sharded(e.model, "MarginalizationGPMCMC(KnowledgeGradient)")
+            refuse_multi_device([e.model], "MarginalizationGPMCMC(KnowledgeGradient)", KG_ONE_DEVICE)
             if not (hasattr(e.model, "acquisition") and hasattr(e.model, "gp")) or hasattr(e.model, "normalize") \
                     or not getattr(e.model, "is_trained", False):
                 return False
@@ -406,12 +398,8 @@ class MarginalizationGPMCMC(BaseAcquisitionFunction):
                 e._drop_rep()
             self._kg_rep = _lib.Candidates(gps[0].ctx, est[0].model._normalised(Z))
         sn2s = np.array([e._sn2() for e in est])
-        cand = X if isinstance(X, _lib.Candidates) else _lib.Candidates(gps[0].ctx, est[0].model._normalised(np.asarray(X)))
-        try:
+        with staged_candidates(est[0].model, X) as cand:      # (_kg_native admits no model with a normalize() of its own)
             res = _lib.kg_marginal(gps, cand, self._kg_rep, sn2s, f.include_self, want_values, diagnostics)
-        finally:
-            if cand is not X:
-                cand.close()
         self.last_max, self.last_argmax = res.max, res.argmax
         return res
 
@@ -499,14 +487,9 @@ class MarginalizationGPMCMC(BaseAcquisitionFunction):
             raise NotImplementedError("MarginalizationGPMCMC.refine: the sub-models live on several contexts")
         eta = np.array([e._eta(None) for e in est])
         m0 = est[0].model
-        cand = X_test if isinstance(X_test, _lib.Candidates) else _lib.Candidates(gps[0].ctx,
-                                                                                  m0._normalised(np.asarray(X_test)))
-        try:
+        with staged_candidates(m0, X_test) as cand:
             res = _lib.acq_refine(gps, est[0].kind, est[0].par, eta, cand, n_starts, n_steps, step0, diagnostics)
             return refine_finish(self, est[0].kind, m0, res, cand)
-        finally:
-            if cand is not X_test:
-                cand.close()
 
     def select_batch(self, X_test, q, fantasy="kriging_believer", liar=None, diagnostics=False):
         """Greedy batch of q proposals under the marginalised acquisition (robo_acq_batch_marginal_cand): as
@@ -528,15 +511,10 @@ class MarginalizationGPMCMC(BaseAcquisitionFunction):
             raise NotImplementedError("MarginalizationGPMCMC.select_batch: the sub-models live on several contexts")
         eta = np.array([e._eta(None) for e in est])
         m0 = est[0].model
-        cand = X_test if isinstance(X_test, _lib.Candidates) else _lib.Candidates(gps[0].ctx,
-                                                                                  m0._normalised(np.asarray(X_test)))
-        try:
+        with staged_candidates(m0, X_test) as cand:
             res = _lib.acq_batch(gps, est[0].kind, est[0].par, eta, cand, q, fantasy, batch_liar(m0, fantasy, liar),
                                  diagnostics)
             return batch_finish(self, est[0].kind, m0, res, cand)
-        finally:
-            if cand is not X_test:
-                cand.close()
 
     def argmax(self, X_test):
         if self._is_kg() and self._kg_native():

@@ -20,7 +20,8 @@ Random numbers come from ``rng`` in a stated order: first the ``n_grid x D`` gri
 import numpy as np
 
 from robo_amd import _lib
-from robo_amd.acquisition_functions.base_acquisition import BaseAcquisitionFunction
+from robo_amd.acquisition_functions.base_acquisition import (BaseAcquisitionFunction, host_points, refuse_multi_device,
+                                                             staged_candidates)
 
 
 def mes_uniforms(rng, shape):
@@ -50,10 +51,8 @@ def mes_grid(model, rng, n_grid):
     return G
 
 
-def mes_refuse_sharded(model, who):
-    if getattr(model, "devices", None):
-        raise NotImplementedError("%s runs on one device: a shard-consistent y* needs a cross-device reduction of F, which "
-                                  "is not implemented (devices=%r)" % (who, model.devices))
+# why a ``devices=...`` model is refused (refuse_multi_device)
+MES_ONE_DEVICE = "a shard-consistent y* needs a cross-device reduction of F, which is not implemented"
 
 
 class MES(BaseAcquisitionFunction):
@@ -98,7 +97,7 @@ class MES(BaseAcquisitionFunction):
     def sampled_minima(self):
         """the K values y* this update's compute() calls use (drawn on first use)"""
         if self._ystar is None:
-            mes_refuse_sharded(self.model, "MES")
+            refuse_multi_device([self.model], "MES", MES_ONE_DEVICE)
             G = mes_grid(self.model, self.rng, self.n_grid)
             u = mes_uniforms(self.rng, self.n_samples)
             m, v = self._moments(G)
@@ -108,16 +107,10 @@ class MES(BaseAcquisitionFunction):
     def compute(self, X, derivative=False, **kwargs):
         if derivative:
             raise NotImplementedError("MES has no derivative")
-        mes_refuse_sharded(self.model, "MES")
-        if isinstance(X, _lib.Candidates):
-            # a device batch lives in the box [0, 1]^D of the model's normalised inputs
-            if not getattr(self.model, "normalize_input", False) or hasattr(self.model, "normalize"):
-                raise TypeError("MES.compute on a device candidate batch needs a model with normalize_input=True whose input "
-                                "space is the normalised box (not a Fabolas model); pass the points as an array instead")
-            lower, upper = mes_box(self.model)
-            X = lower + (upper - lower) * X.points()
+        refuse_multi_device([self.model], "MES", MES_ONE_DEVICE)
+        X = host_points(self.model, X, "MES.compute", box=mes_box)
         ystar = self.sampled_minima()
-        m, v = self._moments(np.asarray(X, dtype=np.float64))
+        m, v = self._moments(X)
         vals, mx, am, _ = _lib.mes_from_moments(self._ctx(), m, v, ystar)
         self.last_max, self.last_argmax, self.last_ystar = mx, am, ystar
         return vals
@@ -127,7 +120,7 @@ class MES(BaseAcquisitionFunction):
         the normalised one), X itself being the discretisation y* is sampled over; fresh draws from ``rng`` per call."""
         if isinstance(X, _lib.CandidateShards):
             raise NotImplementedError("MES.argmax runs on one device: candidate shards are not implemented")
-        mes_refuse_sharded(self.model, "MES")
+        refuse_multi_device([self.model], "MES", MES_ONE_DEVICE)
         if not self._is_native():
             m, v = self._moments(np.asarray(X, dtype=np.float64))
             u = mes_uniforms(self.rng, self.n_samples)
@@ -138,14 +131,9 @@ class MES(BaseAcquisitionFunction):
             if not model.is_trained:
                 raise Exception('Model has to be trained first!')
             model._materialise()
-            norm = model.normalize if hasattr(model, "normalize") else model._normalised
-            cand = X if isinstance(X, _lib.Candidates) else _lib.Candidates(model.gp.ctx, norm(np.asarray(X)))
-            try:
+            with staged_candidates(model, X) as cand:
                 u = mes_uniforms(self.rng, self.n_samples)
                 res = model.gp.mes(self._eta(), cand, u, self.clamp, want_values=False)
-            finally:
-                if cand is not X:
-                    cand.close()
             mx, am, ystar = res.max, res.argmax, res.ystar
         self.last_max, self.last_argmax, self.last_ystar = mx, am, ystar
         return int(am)

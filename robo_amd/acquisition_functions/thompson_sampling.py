@@ -20,7 +20,8 @@ returns a path's value and gradient from one evaluation.
 import numpy as np
 
 from robo_amd import _lib
-from robo_amd.acquisition_functions.base_acquisition import BaseAcquisitionFunction
+from robo_amd.acquisition_functions.base_acquisition import (BaseAcquisitionFunction, refine_model_check,
+                                                             refuse_foreign_batch, refuse_multi_device, staged_candidates)
 from robo_amd.util.spectral import draw_features
 
 
@@ -48,9 +49,7 @@ class ThompsonSampling(BaseAcquisitionFunction):
     def _sub_models(self):
         model = self.model
         subs = list(model.models) if hasattr(model, "models") else [model]
-        if getattr(model, "devices", None) or any(getattr(m, "devices", None) for m in subs):
-            raise NotImplementedError("ThompsonSampling runs on one device: multi-device models are not implemented "
-                                      "(devices=%r)" % (getattr(model, "devices", None),))
+        refuse_multi_device([model] + subs, "ThompsonSampling", "multi-device models are not implemented")
         for m in subs:
             if not (hasattr(m, "acquisition") and hasattr(m, "gp") and hasattr(m, "_normalised")) or hasattr(m, "normalize"):
                 raise TypeError("ThompsonSampling needs a robo_amd GaussianProcess or GaussianProcessMCMC model (got %s)"
@@ -99,19 +98,17 @@ class ThompsonSampling(BaseAcquisitionFunction):
 
     # ---- evaluation ---------------------------------------------------------------------------------------------------------
     def _candidates(self, X, sub):
+        """X as a device batch (staged_candidates; _sub_models admits no model with a normalize() of its own)"""
         if isinstance(X, _lib.CandidateShards):
             raise NotImplementedError("ThompsonSampling runs on one device: candidate shards are not implemented")
         if isinstance(X, _lib.Candidates):
-            if not sub.normalize_input:
-                raise TypeError("ThompsonSampling on a device candidate batch needs a model with normalize_input=True")
-            return X
-        return _lib.Candidates(sub.gp.ctx, sub._normalised(np.asarray(X, dtype=np.float64)))
+            refuse_foreign_batch(sub, "ThompsonSampling")
+        return staged_candidates(sub, X)
 
     def _evaluate(self, X, want_values, paths=None):
         """-> (values (S, m) or None, min (S,), argmin (S,)) in path order; ``paths``: only the groups that hold one of them"""
         sub = self._ready()
-        cand = self._candidates(X, sub)
-        try:
+        with self._candidates(X, sub) as cand:
             S = self.n_paths
             vals = np.empty((S, cand.m)) if want_values else None
             mn, am = np.full(S, np.nan), np.full(S, -1, dtype=np.int64)
@@ -123,9 +120,6 @@ class ThompsonSampling(BaseAcquisitionFunction):
                 if want_values:
                     vals[members] = r.values
             return vals, mn, am
-        finally:
-            if cand is not X:
-                cand.close()
 
     def _group_of(self, path):
         """(PosteriorPaths, the path's number inside it) of the one group that holds ``path``"""
@@ -155,8 +149,7 @@ class ThompsonSampling(BaseAcquisitionFunction):
         if isinstance(X, _lib.CandidateShards):
             raise NotImplementedError("ThompsonSampling runs on one device: candidate shards are not implemented")
         if isinstance(X, _lib.Candidates):
-            if not sub.normalize_input:
-                raise TypeError("ThompsonSampling on a device candidate batch needs a model with normalize_input=True")
+            refuse_foreign_batch(sub, "ThompsonSampling")
             Xn, chain = X.points(), 1.0
         else:
             Xn = np.ascontiguousarray(sub._normalised(np.asarray(X, dtype=np.float64)), dtype=np.float64)
@@ -177,16 +170,11 @@ class ThompsonSampling(BaseAcquisitionFunction):
         normalised one), the best rows of the ``n_starts`` best groups of 64 candidates descend ``n_steps`` projected steps
         in one launch -> the best point found, in the caller's input space.  ``last_refine`` keeps the library's result for
         the group that holds path 0 (its paths in the group's order), ``last_max`` is the negated value."""
-        from robo_amd.acquisition_functions.base_acquisition import refine_model_check
         sub = self._ready()
         refine_model_check(sub, self.__class__.__name__)
-        cand = self._candidates(X, sub)
-        try:
+        with self._candidates(X, sub) as cand:
             group, at = self._group_of(0)
             res = group.refine(cand, n_starts, n_steps, step0, diagnostics)
-        finally:
-            if cand is not X:
-                cand.close()
         self.last_refine = res
         self.last_max, self.last_argmax = -float(res.value[at]), int(res.start_index[at])
         lower, upper = np.asarray(sub.lower, dtype=np.float64), np.asarray(sub.upper, dtype=np.float64)
@@ -215,12 +203,10 @@ class ThompsonSampling(BaseAcquisitionFunction):
         q = int(q)
         sub = self._sub_models()[0]
         if refine:
-            from robo_amd.acquisition_functions.base_acquisition import refine_model_check
             refine_model_check(sub, self.__class__.__name__, "select_batch")
         if self._stale or not self._groups or self.n_paths < q:
             self._draw(max(q, self.n_paths) if self.n_paths < q else None)
-        cand = self._candidates(X, sub)
-        try:
+        with self._candidates(X, sub) as cand:
             if q < 1 or q > cand.m:
                 raise ValueError("select_batch: q = %d outside 1 .. m = %d" % (q, cand.m))
             if refine:
@@ -247,9 +233,6 @@ class ThompsonSampling(BaseAcquisitionFunction):
             self.last_batch = np.array(picks, dtype=np.int64)
             self.last_max, self.last_argmax = -float(mn[0]), int(am[0])
             pts = np.array([cand.point(i) for i in picks]).reshape(q, cand.dim)
-        finally:
-            if cand is not X:
-                cand.close()
         if not sub.normalize_input:
             return pts
         lower, upper = np.asarray(sub.lower, dtype=np.float64), np.asarray(sub.upper, dtype=np.float64)

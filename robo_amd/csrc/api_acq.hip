@@ -125,6 +125,66 @@ int moments_handle(robo_ctx* ctx, const double* mean, const double* var, int64_t
     return ROBO_OK;
 }
 
+int upload_rows(robo_ctx* ctx, const char* what, std::initializer_list<UploadRows> rows, bool sync) {
+    hipError_t e = hipSuccess;
+    for (const UploadRows& r : rows)
+        if (e == hipSuccess && r.count > 0)
+            e = hipMemcpyAsync(r.dst, r.src, r.count * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess && sync) e = hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess) return ROBO_OK;
+    set_error("%s failed: %s", what, hipGetErrorString(e));
+    return ROBO_RUNTIME_ERROR;
+}
+
+int moments_finish(robo_cand* k, int status, bool reduce, double* out_vec, double* out_max, int64_t* out_argmax,
+                   uint32_t* out_flags) {
+    if (status == ROBO_OK && reduce) status = launch_argmax(k, k->d_acq_sum, 1.0);
+    if (status == ROBO_OK) status = acq_read_back(k, k->d_acq, out_vec, out_max, out_argmax, out_flags);
+    else hipStreamSynchronize(k->ctx->stream);
+    robo_cand_destroy(k);
+    return status;
+}
+
+int models_check(const char* label, const char* the_models, robo_gp* const* gps, int32_t S, const robo_cand* k,
+                 const std::function<void(int)>& shape_error) {
+    if (!gps || S < 1 || !k) return ROBO_BAD_ARGUMENT;
+    for (int s = 0; s < S; ++s)
+        if (!gps[s]) return ROBO_BAD_ARGUMENT;
+    for (int s = 0; s < S; ++s)
+        if (gps[s]->ctx != k->ctx) {
+            set_error("%s: %s and the candidates must live on one context", label, the_models);
+            return ROBO_BAD_ARGUMENT;
+        }
+    for (int s = 0; s < S; ++s)
+        if (gps[s]->dim != k->dim) {
+            shape_error(s);
+            return ROBO_BAD_SHAPE;
+        }
+    for (int s = 0; s < S; ++s)
+        if (!gps[s]->fitted) {
+            set_error("Model has to be trained first!");
+            return ROBO_NOT_FITTED;
+        }
+    ROBO_HIP_CHECK(hipSetDevice(k->ctx->device));
+    return ROBO_OK;
+}
+
+int models_fold(const char* label, robo_gp* const* gps, int32_t S, robo_cand* k, int slot_begin,
+                const std::function<int()>& fold, ReadBack trace, double* out_vec, double* out_max, int64_t* out_argmax,
+                uint32_t* out_flags) {
+    robo_ctx* c = k->ctx;
+    // the S sweeps, each chunked by the workspace
+    ROBO_TRY(clear_flags_on_error(k, predict_samples(gps, S, k, S)));
+    const bool ev = phase_events_on(c, k);
+    if (ev) ROBO_TRY(record_phase(c, slot_begin));
+    ROBO_TRY(clear_flags_on_error(k, fold()));
+    if (ev) ROBO_TRY(record_phase(c, slot_begin + 1));
+    ROBO_TRY(clear_flags_on_error(k, launch_argmax(k, k->d_acq_sum, 1.0)));
+    ROBO_TRY(finish_call(k, label, ROBO_OK, {trace}, false));
+    // (max, argmax, flags) [+ the values] and the one synchronisation of the call
+    return clear_flags_on_error(k, acq_read_back(k, k->d_acq, out_vec, out_max, out_argmax, out_flags));
+}
+
 // ---------------------------------------------------------------------------------------
 // entropy search: information gain of a candidate batch
 // ---------------------------------------------------------------------------------------
@@ -337,10 +397,8 @@ int32_t robo_acq_eval_moments(robo_ctx* ctx, int32_t acq_kind, double par, doubl
     ROBO_TRY(check_acq_kind(acq_kind));
     robo_cand* k = nullptr;
     ROBO_TRY(moments_handle(ctx, mean, var, m, "robo_acq_eval_moments upload", &k));
-    int st = launch_acq(ctx, k, acq_kind, par, eta, false, false);
-    if (st == ROBO_OK) st = acq_read_back(k, k->d_acq, out_acq, out_max, out_argmax, out_flags);
-    robo_cand_destroy(k);
-    return st;
+    return moments_finish(k, launch_acq(ctx, k, acq_kind, par, eta, false, false), false, out_acq, out_max, out_argmax,
+                          out_flags);
 }
 
 int32_t robo_gp_cross_cov(robo_gp* g, robo_cand* k, robo_cand* rep, double* out_cov) {

@@ -55,36 +55,18 @@ int32_t robo_ehvi_eval_cand(robo_gp* gp1, robo_gp* gp2, robo_cand* k, const doub
                             double* out_ehvi, double* out_max, int64_t* out_argmax, uint32_t* out_flags, double* out_trace) {
     if (!gp1 || !gp2 || !k) return ROBO_BAD_ARGUMENT;
     ROBO_TRY(ehvi_check(front, P, ref));
-    if (gp1->ctx != gp2->ctx || k->ctx != gp1->ctx) {
-        set_error("%s: the two GPs and the candidates must live on one context", EHVI_LABEL);
-        return ROBO_BAD_ARGUMENT;
-    }
-    if (gp1->dim != k->dim || gp2->dim != k->dim) {
+    robo_gp* gps[2] = {gp1, gp2};
+    ROBO_TRY(models_check(EHVI_LABEL, "the two GPs", gps, 2, k, [&](int) {
         set_error("%s: the GPs (dim %d, %d) do not match the candidates (dim %d)", EHVI_LABEL, gp1->dim, gp2->dim, k->dim);
-        return ROBO_BAD_SHAPE;
-    }
-    if (!gp1->fitted || !gp2->fitted) {
-        set_error("Model has to be trained first!");
-        return ROBO_NOT_FITTED;
-    }
-    robo_ctx* c = k->ctx;
-    ROBO_HIP_CHECK(hipSetDevice(c->device));
+    }));
     const size_t trace_len = out_trace ? (size_t)k->m * 4 : 0;
     ROBO_TRY(ehvi_stage_front(k, front, P, trace_len));
-    // the two sweeps, each chunked by the workspace: rows 0 and 1 of the handle's sample tables
-    robo_gp* gps[2] = {gp1, gp2};
-    ROBO_TRY(clear_flags_on_error(k, predict_samples(gps, 2, k, 2)));
     double* d_trace = out_trace ? k->d_kg + (size_t)2 * ROBO_EHVI_MAX_FRONT : nullptr;
-    // event slots 30 -> 31 bracket the strip kernel, under the condition of slots 24..27
-    const bool ev = c->phase_events || k->m_pad > 16384;
-    if (ev) ROBO_HIP_CHECK(hipEventRecord(c->events[30], c->stream));
-    ROBO_TRY(clear_flags_on_error(k, launch_ehvi(c, k->d_mu_all, k->d_var_all, k->d_mu_all + k->m_pad, k->d_var_all + k->m_pad,
-                                                 k->d_kg, P, ref[0], ref[1], k->m, k->d_acq_sum, k->d_flags, d_trace)));
-    if (ev) ROBO_HIP_CHECK(hipEventRecord(c->events[31], c->stream));
-    ROBO_TRY(clear_flags_on_error(k, launch_argmax(k, k->d_acq_sum, 1.0)));
-    ROBO_TRY(finish_call(k, EHVI_LABEL, ROBO_OK, {{out_trace, d_trace, trace_len * sizeof(double)}}, false));
-    // (max, argmax, flags) [+ the values] and the one synchronisation of the call
-    return clear_flags_on_error(k, acq_read_back(k, k->d_acq, out_ehvi, out_max, out_argmax, out_flags));
+    // the two objectives' posteriors are rows 0 and 1 of the handle's sample tables; slots 30 -> 31 bracket the strip kernel
+    return models_fold(EHVI_LABEL, gps, 2, k, EV_FOLD_BEGIN, [&] {
+        return launch_ehvi(k->ctx, k->d_mu_all, k->d_var_all, k->d_mu_all + k->m_pad, k->d_var_all + k->m_pad, k->d_kg, P,
+                           ref[0], ref[1], k->m, k->d_acq_sum, k->d_flags, d_trace);
+    }, {out_trace, d_trace, trace_len * sizeof(double)}, out_ehvi, out_max, out_argmax, out_flags);
 }
 
 int32_t robo_ehvi_eval_moments(robo_ctx* ctx, int64_t m, const double* mean1, const double* var1, const double* mean2,
@@ -96,22 +78,13 @@ int32_t robo_ehvi_eval_moments(robo_ctx* ctx, int64_t m, const double* mean1, co
     ROBO_TRY(moments_handle(ctx, mean1, var1, m, "expected hypervolume improvement: upload of the moments", &k));
     // the second objective's moments ride in the handle's d_mu / d_q (m_pad doubles each, otherwise unused here)
     int st = ehvi_stage_front(k, front, P, 0);
-    if (st == ROBO_OK) {
-        hipError_t e = hipMemcpyAsync(k->d_mu, mean2, (size_t)m * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(k->d_q, var2, (size_t)m * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) {
-            set_error("%s: upload of the moments failed: %s", EHVI_LABEL, hipGetErrorString(e));
-            st = ROBO_RUNTIME_ERROR;
-        }
-    }
+    if (st == ROBO_OK)
+        st = upload_rows(ctx, "expected hypervolume improvement: upload of the moments",
+                         {{k->d_mu, mean2, (size_t)m}, {k->d_q, var2, (size_t)m}});
     if (st == ROBO_OK)
         st = launch_ehvi(ctx, k->d_mean, k->d_var, k->d_mu, k->d_q, k->d_kg, P, ref[0], ref[1], m, k->d_acq_sum, k->d_flags,
                          nullptr);
-    if (st == ROBO_OK) st = launch_argmax(k, k->d_acq_sum, 1.0);
-    if (st == ROBO_OK) st = acq_read_back(k, k->d_acq, out_ehvi, out_max, out_argmax, out_flags);
-    else hipStreamSynchronize(ctx->stream);
-    robo_cand_destroy(k);
-    return st;
+    return moments_finish(k, st, true, out_ehvi, out_max, out_argmax, out_flags);
 }
 
 }  // extern "C"

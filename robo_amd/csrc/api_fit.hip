@@ -216,7 +216,7 @@ static int gp_build_gram(robo_gp* g, const double* theta, double mean_c) {
     g->mean_c = mean_c;
     // theta travels as kernel arguments; block 0 of the scaling kernel leaves d_theta (metrics) and d_sp behind
     ROBO_TRY(launch_scale_inputs_theta(c, g->d_X, g->d_Xs, ta, g->n, g->n_pad, D, g->d_theta, g->d_sp));
-    if (c->phase_events) ROBO_HIP_CHECK(hipEventRecord(c->events[19], c->stream));   // slot 19 -> 21: the gram kernel alone (K1)
+    if (phase_events_on(c, nullptr)) ROBO_TRY(record_phase(c, EV_GRAM_KERNEL));   // 19 -> 21: the gram kernel alone (K1)
     FitBuffers fb = own_buffers(g);
     fb.gram_mixed = ta.sp.direct != 0;
     ROBO_TRY(launch_gram(g, fb));
@@ -232,12 +232,13 @@ int32_t robo_gp_fit(robo_gp* g, const double* theta, double mean_c, double* out_
     robo_ctx* c = g->ctx;
     g->fitted = false;
     // event slots 20..23: 20 -> 21 gram build, 21 -> 22 Cholesky, 22 -> 23 log-likelihood reduce
-    if (c->phase_events) ROBO_HIP_CHECK(hipEventRecord(c->events[20], c->stream));
+    const bool ev = phase_events_on(c, nullptr);
+    if (ev) ROBO_TRY(record_phase(c, EV_FIT_BEGIN));
     ROBO_TRY(gp_build_gram(g, theta, mean_c));
-    if (c->phase_events) ROBO_HIP_CHECK(hipEventRecord(c->events[21], c->stream));
+    if (ev) ROBO_TRY(record_phase(c, EV_FIT_GRAM_END));
     ROBO_TRY(launch_potrf(g, own_buffers(g)));
-    if (c->phase_events) ROBO_HIP_CHECK(hipEventRecord(c->events[22], c->stream));
-    if (c->phase_events) ROBO_HIP_CHECK(hipEventRecord(c->events[23], c->stream));
+    if (ev) ROBO_TRY(record_phase(c, EV_FIT_POTRF_END));
+    if (ev) ROBO_TRY(record_phase(c, EV_FIT_END));
     // the tail kernel of the factorisation wrote (z.z, log det, failure flag) straight into the pinned buffer
     double* hp = c->h_pinned;
     ROBO_HIP_CHECK(hipStreamSynchronize(c->stream));
@@ -281,10 +282,10 @@ int32_t robo_gp_grad_loglik(robo_gp* g, const double* theta, double mean_c, doub
         ROBO_TRY(dev_alloc(&g->d_gout, (size_t)P));
     }
     // event slots 28 -> 29: everything after the factorisation (W^T, A, the reductions)
-    ROBO_HIP_CHECK(hipEventRecord(c->events[28], c->stream));
+    ROBO_TRY(record_phase(c, EV_GRAD_BEGIN));
     double* hg = c->h_pinned + 8;          // P <= MAX_DIM + 3 doubles behind the fit's three result slots
     ROBO_TRY(launch_grad_loglik(g, g->d_gV, g->d_gA, g->d_galpha, g->d_gpart, g->d_gout, hg));
-    ROBO_HIP_CHECK(hipEventRecord(c->events[29], c->stream));
+    ROBO_TRY(record_phase(c, EV_GRAD_END));
     ROBO_HIP_CHECK(hipStreamSynchronize(c->stream));
     memcpy(out_grad, hg, (size_t)P * sizeof(double));
     return ROBO_OK;

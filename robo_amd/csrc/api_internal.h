@@ -1,8 +1,10 @@
 // Host helpers shared by the files that hold C ABI entry points (api_*.hip, refine.hip, batch.hip, mes.hip, hyperopt.hip,
 // comm.hip, multi.hip): each is declared here once and defined in the file named above its group.  An ensemble driver reads as
-// "ensemble_check, acq_sweep, its own kernels, finish_call".  A driver that keeps device state between its launches lays its
-// arrays out in one allocation with BlockLayout (block_layout.h); its diagnostics trace and every other buffer that only grows
-// go through dev_grow.
+// "ensemble_check, acq_sweep, its own kernels, finish_call"; a driver over several models' posteriors as "models_check, its
+// staging, models_fold"; a moments entry point as "moments_handle, upload_rows, its kernel, moments_finish".  The library's
+// own event slots have names (common.h RoboEventSlot) and are recorded with record_phase under phase_events_on.  A driver
+// that keeps device state between its launches lays its arrays out in one allocation with BlockLayout (block_layout.h); its
+// diagnostics trace and every other buffer that only grows go through dev_grow.
 #pragma once
 #include <functional>
 #include <initializer_list>
@@ -92,8 +94,33 @@ struct ReadBack {
     size_t bytes;
 };
 int finish_call(robo_cand* k, const char* label, int status, std::initializer_list<ReadBack> copies, bool sync = true);
+// A fused call that folds the posteriors of SEVERAL MODELS at one candidate batch into one value per candidate (EHVI: two
+// objectives; constrained EI: the objective and its constraints) is models_check, the caller's own staging, models_fold.
+// models_check: every model non-null and on the candidates' context (ROBO_BAD_ARGUMENT, "<label>: <the_models> and the
+// candidates must live on one context"), of their dimension (ROBO_BAD_SHAPE; shape_error(i) words the message for the
+// first model i that is not), fitted (ROBO_NOT_FITTED) -- in this order over all models -- then hipSetDevice.
+int models_check(const char* label, const char* the_models, robo_gp* const* gps, int32_t S, const robo_cand* k,
+                 const std::function<void(int)>& shape_error);
+// models_fold: the S sweeps into rows 0 .. S - 1 of k's sample tables, fold() -- the caller's kernel, values into
+// k->d_acq_sum -- between the event slots slot_begin and slot_begin + 1, the argmax, the trace's copy, then (max, argmax,
+// flags) [+ the values] and the one synchronisation of the call.
+int models_fold(const char* label, robo_gp* const* gps, int32_t S, robo_cand* k, int slot_begin,
+                const std::function<int()>& fold, ReadBack trace, double* out_vec, double* out_max, int64_t* out_argmax,
+                uint32_t* out_flags);
 // a one-dimensional candidate handle holding (mean, var) of any model; failure reads "<what> failed: <hip error>"
 int moments_handle(robo_ctx* ctx, const double* mean, const double* var, int64_t m, const char* what, robo_cand** out);
+// further host rows of a moments call onto the device (asynchronous unless sync; count == 0: skipped); failure as above
+struct UploadRows {
+    double* dst;
+    const double* src;
+    size_t count;
+};
+int upload_rows(robo_ctx* ctx, const char* what, std::initializer_list<UploadRows> rows, bool sync = false);
+// The end of a moments call on moments_handle's temporary handle, which it destroys either way -> status.  status ==
+// ROBO_OK: the argmax over k->d_acq_sum (reduce; false: the kernel left its own partials, launch_acq's single form) and
+// acq_read_back with its one synchronisation.  Otherwise: wait for the stream.
+int moments_finish(robo_cand* k, int status, bool reduce, double* out_vec, double* out_max, int64_t* out_argmax,
+                   uint32_t* out_flags);
 // dH / (exp(log-cost mean) + overhead) of every candidate into k->d_acq and the argmax partials (asynchronous)
 int ig_per_cost_core(robo_gp* g, robo_cand* k, robo_cand* rep, int32_t npts, double sn2, const double* logP,
                      const double* lmb, const double* W, const double* dlogPdMu, const double* dlogPdSigma,

@@ -36,8 +36,8 @@ static int kg_accumulate(robo_gp* const* gps, int32_t S, robo_cand* k, robo_cand
     const int nb = (int)rep->m;
     robo_ctx* c = k->ctx;
     double* d_trace = k->d_kg + (size_t)S * KG_MAX_DISC;
-    // event slots 30 -> 31 bracket the KG kernel of the LAST sample, under the condition of slots 24..27
-    const bool ev = c->phase_events || k->m_pad > 16384;
+    // event slots 30 -> 31 bracket the KG kernel of the LAST sample
+    const bool ev = phase_events_on(c, k);
     for (int s = 0; s < S; ++s) {
         robo_gp* g = gps[s];
         // the discretisation's solve is kept across calls while the factor and the points stay the same, as in ig_core
@@ -51,11 +51,11 @@ static int kg_accumulate(robo_gp* const* gps, int32_t S, robo_cand* k, robo_cand
         ROBO_TRY(clear_flags_on_error(k, predict_core(g, k, false, [&](int64_t c0, int64_t cn) {
             return launch_cross_cov(g, k, rep, c0, cn, k->d_S, false);
         })));
-        if (ev) ROBO_HIP_CHECK(hipEventRecord(c->events[30], c->stream));
+        if (ev) ROBO_TRY(record_phase(c, EV_FOLD_BEGIN));
         ROBO_TRY(clear_flags_on_error(k, launch_kg(c, k->d_S, k->d_var, k->d_mean, d_disc, k->m, nb, sn2s[s], include_self, s == 0,
                                                    k->d_acq_sum, k->d_flags,
                                                    want_trace ? d_trace + (size_t)s * k->m * (nb + 2) : nullptr)));
-        if (ev) ROBO_HIP_CHECK(hipEventRecord(c->events[31], c->stream));
+        if (ev) ROBO_TRY(record_phase(c, EV_FOLD_END));
     }
     return ROBO_OK;
 }
@@ -119,23 +119,14 @@ int32_t robo_kg_eval_moments(robo_ctx* ctx, int64_t m, int32_t nb, double sn2, i
         std::vector<double> hs((size_t)k->m_pad * NB, 0.0);
         for (int64_t c = 0; c < m; ++c)
             for (int b = 0; b < nb; ++b) hs[(size_t)c * NB + b] = s[c * nb + b];
-        hipError_t e = hipMemcpyAsync(k->d_S, hs.data(), hs.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(k->d_kg, disc_mean, (size_t)nb * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);     // the staging vector dies with this scope
-        if (e != hipSuccess) {
-            set_error("knowledge gradient: upload of the covariances failed: %s", hipGetErrorString(e));
-            st = ROBO_RUNTIME_ERROR;
-        }
+        // (synchronised: the staging vector dies with this scope)
+        st = upload_rows(ctx, "knowledge gradient: upload of the covariances",
+                         {{k->d_S, hs.data(), hs.size()}, {k->d_kg, disc_mean, (size_t)nb}}, true);
     }
     if (st == ROBO_OK)
         st = launch_kg(ctx, k->d_S, k->d_var, k->d_mean, k->d_kg, m, nb, sn2, include_self, true, k->d_acq_sum, k->d_flags,
                        nullptr);
-    if (st == ROBO_OK) st = launch_argmax(k, k->d_acq_sum, 1.0);
-    if (st == ROBO_OK) st = acq_read_back(k, k->d_acq, out_kg, out_max, out_argmax, out_flags);
-    else hipStreamSynchronize(ctx->stream);
-    robo_cand_destroy(k);
-    return st;
+    return moments_finish(k, st, true, out_kg, out_max, out_argmax, out_flags);
 }
 
 }  // extern "C"

@@ -130,8 +130,8 @@ static int paths_sweep(robo_paths* p, robo_cand* k, double* out_values, size_t* 
     a.part_idx = p->d_part_idx;
     a.n_part = (long long)n_part;
     // event slots 30 -> 31 bracket the passes of the path kernel, under the condition of slots 24..27
-    const bool ev = c->phase_events || k->m_pad > 16384;
-    if (ev && st == ROBO_OK && hipEventRecord(c->events[30], c->stream) != hipSuccess) st = ROBO_RUNTIME_ERROR;
+    const bool ev = phase_events_on(c, k);
+    if (ev && st == ROBO_OK) st = record_phase(c, EV_FOLD_BEGIN);
     for (int64_t c0 = 0; st == ROBO_OK && c0 < k->m_pad; c0 += chunk) {
         const int64_t cn = k->m_pad - c0 < chunk ? k->m_pad - c0 : chunk;
         a.c0 = c0;
@@ -144,7 +144,7 @@ static int paths_sweep(robo_paths* p, robo_cand* k, double* out_values, size_t* 
                 st = ROBO_RUNTIME_ERROR;
             }
     }
-    if (ev && st == ROBO_OK && hipEventRecord(c->events[31], c->stream) != hipSuccess) st = ROBO_RUNTIME_ERROR;
+    if (ev && st == ROBO_OK) st = record_phase(c, EV_FOLD_END);
     return st;
 }
 
@@ -214,9 +214,9 @@ static int paths_descent(robo_paths* p, int P, int T, double step0, const long l
     a.code = rs.code;
     a.trace = trace ? p->d_trace : nullptr;
     a.flags = p->d_flags;
-    if (ev && hipEventRecord(c->events[28], c->stream) != hipSuccess) return ROBO_RUNTIME_ERROR;
+    if (ev) ROBO_TRY(record_phase(c, EV_GRAD_BEGIN));
     ROBO_TRY(launch_paths_descent(c, a));
-    if (ev && hipEventRecord(c->events[29], c->stream) != hipSuccess) return ROBO_RUNTIME_ERROR;
+    if (ev) ROBO_TRY(record_phase(c, EV_GRAD_END));
     return ROBO_OK;
 }
 
@@ -458,8 +458,8 @@ int32_t robo_paths_refine_cand(robo_paths* p, robo_cand* k, int32_t n_starts, in
     size_t n_part = 0;
     int st = paths_sweep(p, k, nullptr, &n_part);
     if (st == ROBO_OK) st = launch_paths_starts(c, p->d_part_val, p->d_part_idx, (long long)n_part, S, K, k->d_Xc, D, rs);
-    const bool ev = c->phase_events || k->m_pad > 16384;
-    if (st == ROBO_OK && (T > 0 || out_trace)) st = paths_descent(p, P, T, step0, rs.start, out_trace != nullptr, ev);
+    if (st == ROBO_OK && (T > 0 || out_trace))
+        st = paths_descent(p, P, T, step0, rs.start, out_trace != nullptr, phase_events_on(c, k));
     if (st == ROBO_OK) st = launch_paths_winners(c, S, K, D, rs, T == 0, p->d_flags);
     unsigned flags = 0;
     std::vector<double> res((size_t)S * (D + 2));

@@ -125,33 +125,31 @@ int predict_scaled(robo_gp* g, robo_cand* k, bool winv, const std::function<int(
     k->solved_gen = 0;
     // event slots 24..27 bracket the phases of the LAST chunk (bench.py reads them after a sync):
     //   24 -> 25 cross-gram, 25 -> 26 triangular solve (the MFMA kernel), 26 -> 27 post
-    // (small batches are latency-bound and four event packets cost several microseconds: recorded for them only when
-    // the phase events are switched on, robo_ctx_set_phase_events)
-    hipStream_t st = g->ctx->stream;
-    const bool ev = g->ctx->phase_events || events || k->m_pad > 16384;
+    // (for small batches only when the phase events are switched on: phase_events_on)
+    const bool ev = events || phase_events_on(g->ctx, k);
     for (int64_t c0 = 0; c0 < k->m_pad; c0 += k->chunk) {
         const int64_t cn = k->m_pad - c0 < k->chunk ? k->m_pad - c0 : k->chunk;
-        if (ev) ROBO_HIP_CHECK(hipEventRecord(g->ctx->events[24], st));
+        if (ev) ROBO_TRY(record_phase(g->ctx, EV_PREDICT_BEGIN));
         if (winv) {
-            if (ev) ROBO_HIP_CHECK(hipEventRecord(g->ctx->events[25], st));
+            if (ev) ROBO_TRY(record_phase(g->ctx, EV_PREDICT_GRAM_END));
             ROBO_TRY(launch_predict_winv(g, k, c0, cn, need_v || (bool)after_chunk));
         } else if (g->fp32_gram || g->ctx->tune.predict_stepwise) {
             // mixed precision (fp32 covariance entries) keeps the two-pass form
             ROBO_TRY(launch_cross_gram(g, k, c0, cn));
-            if (ev) ROBO_HIP_CHECK(hipEventRecord(g->ctx->events[25], st));
+            if (ev) ROBO_TRY(record_phase(g->ctx, EV_PREDICT_GRAM_END));
             ROBO_TRY(launch_trsm(g, k, c0, cn));
         } else {
-            if (ev) ROBO_HIP_CHECK(hipEventRecord(g->ctx->events[25], st));
+            if (ev) ROBO_TRY(record_phase(g->ctx, EV_PREDICT_GRAM_END));
             // small batches on two or more block rows: one launch chained by hand-offs, where the caller looks at its
             // time-out word at the synchronisation it ends in (allow_chain)
             if (allow_chain && chain_wanted(g, cn)) ROBO_TRY(launch_predict_chain(g, k, c0, cn));
             else ROBO_TRY(launch_predict_fused(g, k, c0, cn));
         }
-        if (ev) ROBO_HIP_CHECK(hipEventRecord(g->ctx->events[26], st));
+        if (ev) ROBO_TRY(record_phase(g->ctx, EV_PREDICT_SOLVE_END));
         if (after_chunk) ROBO_TRY(after_chunk(c0, cn));
     }
     ROBO_TRY(launch_post(g, k, 0, k->m_pad));
-    if (ev) ROBO_HIP_CHECK(hipEventRecord(g->ctx->events[27], st));
+    if (ev) ROBO_TRY(record_phase(g->ctx, EV_PREDICT_END));
     return ROBO_OK;
 }
 

@@ -383,7 +383,28 @@ int launch_rep_accept(robo_ctx* ctx, const RepState& st, int acq_kind, double pa
 }  // namespace robo
 
 constexpr int ROBO_AUX_STREAMS = 3;
-constexpr int ROBO_EVENT_SLOTS = 34;    // robo_ctx_event_record's slots; the library's own phases use 19 and above
+// robo_ctx_event_record's slots.  Those below EV_GRAM_KERNEL are the caller's; the library records the named ones itself
+// (include/robo_hip.h states the same pairs; bench.py and the tools read them by number).  A pair is shared by calls that
+// never run inside one another.
+enum RoboEventSlot {
+    EV_GRAM_KERNEL = 19,      // robo_gp_fit, phase events switched on: 19 -> 21 the gram kernel alone,
+    EV_FIT_BEGIN = 20,        //   20 -> 21 the gram phase,
+    EV_FIT_GRAM_END = 21,     //   21 -> 22 Cholesky,
+    EV_FIT_POTRF_END = 22,    //   22 -> 23 log-likelihood
+    EV_FIT_END = 23,
+    EV_PREDICT_BEGIN = 24,    // the posterior's last chunk (predict_scaled): 24 -> 25 cross-gram,
+    EV_PREDICT_GRAM_END = 25,   // 25 -> 26 triangular solve,
+    EV_PREDICT_SOLVE_END = 26,  // 26 -> 27 post
+    EV_PREDICT_END = 27,
+    EV_GRAD_BEGIN = 28,       // robo_gp_grad_loglik (always): everything after the factorisation; the descent launch of
+    EV_GRAD_END = 29,         //   robo_paths_descend (always) and robo_paths_refine_cand
+    EV_FOLD_BEGIN = 30,       // what follows the sweeps: KG's envelope kernel and MES's element-wise half (last sample),
+    EV_FOLD_END = 31,         //   EHVI's strip kernel, the passes of the path kernel
+    EV_CEI_BEGIN = 32,        // constrained EI's fold kernel
+    EV_CEI_END = 33,
+    EV_LAST = EV_CEI_END
+};
+constexpr int ROBO_EVENT_SLOTS = EV_LAST + 1;
 constexpr int ROBO_CHAIN_SLOTS = 16;    // chained solves whose time-out words may be in flight between two synchronisations
 struct robo_ctx {
     int device;
@@ -550,6 +571,17 @@ struct robo_cand {
     char* d_chain;
     size_t chain_bytes;
 };
+
+namespace robo {
+// The library's own event slots (24 and above) are recorded for every batch above 16 384 rows.  Small batches are
+// latency-bound and an event packet costs microseconds: for them, and for the fit (k = nullptr), only when the phase
+// events are switched on (robo_ctx_set_phase_events).
+inline bool phase_events_on(const robo_ctx* c, const robo_cand* k) { return c->phase_events || (k && k->m_pad > 16384); }
+inline int record_phase(robo_ctx* c, int slot) {
+    ROBO_HIP_CHECK(hipEventRecord(c->events[slot], c->stream));
+    return ROBO_OK;
+}
+}  // namespace robo
 
 // ---- launchers implemented in the .hip files (all asynchronous on ctx->stream) ------------
 namespace robo {

@@ -393,14 +393,14 @@ static int mes_core(robo_gp* const* gps, int32_t S, const double* etas, robo_can
     const MesState& st = w->st;
     ROBO_TRY(mes_upload_draws(c, w, u));
     // event slots 27 -> 30 -> 31 bracket the tail of the LAST sample: minimum sampling, element-wise half
-    const bool ev = c->phase_events || k->m_pad > 16384;
+    const bool ev = phase_events_on(c, k);
     for (int s = 0; s < S; ++s) {
         ROBO_TRY(clear_flags_on_error(k, predict_core(gps[s], k)));
         ROBO_TRY(clear_flags_on_error(k, launch_mes_sample(c, st, s, k->d_mean, k->d_var,
                                                       out_trace ? w->d_trace + (size_t)s * k->m * 2 : nullptr, clamp, etas[s])));
-        if (ev) ROBO_HIP_CHECK(hipEventRecord(c->events[30], c->stream));
+        if (ev) ROBO_TRY(record_phase(c, EV_FOLD_BEGIN));
         ROBO_TRY(clear_flags_on_error(k, launch_mes_value(k, st.ystar + (size_t)s * K, K, s == 0)));
-        if (ev) ROBO_HIP_CHECK(hipEventRecord(c->events[31], c->stream));
+        if (ev) ROBO_TRY(record_phase(c, EV_FOLD_END));
     }
     ROBO_TRY(clear_flags_on_error(k, launch_argmax(k, k->d_acq_sum, (double)S)));
     ROBO_TRY(finish_call(k, MES_LABEL, ROBO_OK, {{w->h_stage, w->d_block, w->rep_doubles * sizeof(double)},
@@ -457,17 +457,9 @@ int32_t robo_mes_eval_moments(robo_ctx* ctx, const double* mean, const double* v
     ROBO_TRY(moments_handle(ctx, mean, var, m, "max-value entropy search: upload of the moments", &k));
     // y* (K <= 128 <= m_pad doubles) rides in the handle's d_q, which the moments form never fills: no state block, no
     // pinned allocation -- this entry point runs once per point under the single-point maximisers
-    int st = ROBO_OK;
-    if (hipMemcpyAsync(k->d_q, ystar, (size_t)K * sizeof(double), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
-        set_error("max-value entropy search: upload of y* failed");
-        st = ROBO_RUNTIME_ERROR;
-    }
+    int st = upload_rows(ctx, "max-value entropy search: upload of y*", {{k->d_q, ystar, (size_t)K}});
     if (st == ROBO_OK) st = launch_mes_value(k, k->d_q, K, true);
-    if (st == ROBO_OK) st = launch_argmax(k, k->d_acq_sum, 1.0);
-    if (st == ROBO_OK) st = acq_read_back(k, k->d_acq, out_acq, out_max, out_argmax, out_flags);
-    else hipStreamSynchronize(ctx->stream);
-    robo_cand_destroy(k);
-    return st;
+    return moments_finish(k, st, true, out_acq, out_max, out_argmax, out_flags);
 }
 
 }  // extern "C"

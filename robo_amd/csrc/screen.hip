@@ -827,7 +827,7 @@ int acq_sweep_best(robo_gp* g, int32_t kind, double par, double eta, robo_cand* 
     ROBO_LAUNCH_CHECK();
     // the path the unscreened call runs for the whole batch; its event pair 25 -> 26 is the batch's (bench.py reads it)
     ROBO_TRY(cand_ensure_workspace(s, g->n_pad, false));
-    ROBO_TRY(predict_scaled(g, s, false, nullptr, false, k->m_pad > 16384, allow_chain));
+    ROBO_TRY(predict_scaled(g, s, false, nullptr, false, phase_events_on(g->ctx, k), allow_chain));
     int status = launch_acq(c, s, kind, par, eta, false, false);
     if (status == ROBO_OK) {
         hipLaunchKernelGGL(screen_map_best_kernel, dim3(1), dim3(64), 0, st, (const double*)(s->d_part_val + s->n_part),

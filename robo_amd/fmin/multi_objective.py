@@ -12,34 +12,12 @@ One model per objective, each built as ``bayesian_optimization`` builds its mode
 The loop is this module's own (solver.BayesianOptimization assumes a scalar y): ``n_init`` Latin-hypercube points, then per
 iteration both models are refitted, the front is updated and EHVI is maximised.
 """
-import logging
-import time
-
 import numpy as np
 
 from robo_amd.acquisition_functions import EHVI
-from robo_amd.initial_design import init_latin_hypercube_sampling
-from robo_amd.kernels import Matern52Kernel
+from robo_amd.fmin import _multi_output
 from robo_amd.maximizers import DeviceRandomSampling, RandomSampling
-from robo_amd.models import GaussianProcess, GaussianProcessMCMC
-from robo_amd.priors import DefaultPrior
 from robo_amd.util.pareto import hypervolume_2d, pareto_front_2d
-
-logger = logging.getLogger(__name__)
-
-
-def _objective_model(model_type, lower, upper, rng, hyper_optimizer, n_restarts, chain_length, burnin_steps):
-    n_dims = lower.shape[0]
-    kernel = 2 * Matern52Kernel(np.ones([n_dims]), ndim=n_dims)
-    prior = DefaultPrior(len(kernel) + 1)
-    if model_type == "gp":
-        return GaussianProcess(kernel, prior=prior, rng=rng, normalize_output=False, normalize_input=True, lower=lower,
-                               upper=upper, optimizer=hyper_optimizer, n_restarts=n_restarts)
-    n_hypers = 3 * len(kernel)
-    if n_hypers % 2 == 1:
-        n_hypers += 1
-    return GaussianProcessMCMC(kernel, prior=prior, n_hypers=n_hypers, chain_length=chain_length, burnin_steps=burnin_steps,
-                               normalize_input=True, normalize_output=False, rng=rng, lower=lower, upper=upper)
 
 
 def multi_objective_optimization(objective_function, lower, upper, ref_point, num_iterations=30, n_init=3, maximizer="random",
@@ -50,56 +28,20 @@ def multi_objective_optimization(objective_function, lower, upper, ref_point, nu
     evaluation), runtime and overhead (per evaluation).  ``num_iterations`` counts the ``n_init`` initial points."""
     lower, upper = np.asarray(lower, dtype=np.float64), np.asarray(upper, dtype=np.float64)
     ref_point = np.array(ref_point, dtype=np.float64).reshape(2)
-    assert upper.shape[0] == lower.shape[0], "Dimension miss match"
-    assert np.all(lower < upper), "Lower bound >= upper bound"
-    assert n_init <= num_iterations, "Number of initial design point has to be <= than the number of iterations"
-    if model_type not in ("gp", "gp_mcmc"):
-        raise ValueError("'{}' is not a valid model (robo_amd provides 'gp' and 'gp_mcmc')".format(model_type))
-    if maximizer not in ("random", "device_random"):
-        raise ValueError("'{}' is not a valid function to maximize EHVI ('random' or 'device_random')".format(maximizer))
-    if maximizer == "device_random" and model_type != "gp":
-        raise ValueError("maximizer='device_random' scores its candidates with the fused call of two 'gp' models; "
-                         "'gp_mcmc' goes through its mixture moments (use 'random')")
-    if hyper_optimizer != "host" and model_type == "gp_mcmc":
-        raise ValueError("hyper_optimizer='{}' applies to model_type='gp'; 'gp_mcmc' samples its hyper-parameters"
-                         .format(hyper_optimizer))
-    if rng is None:
-        rng = np.random.RandomState(np.random.randint(0, 10000))
-
-    models = [_objective_model(model_type, lower, upper, rng, hyper_optimizer, n_restarts, chain_length, burnin_steps)
-              for _ in range(2)]
+    rng, models = _multi_output.output_models(2, lower, upper, num_iterations, n_init, maximizer, model_type, rng,
+                                              hyper_optimizer, n_restarts, chain_length, burnin_steps, acq_name="EHVI",
+                                              fused_over="two 'gp' models")
     acq = EHVI(models, ref_point)
     cls = RandomSampling if maximizer == "random" else DeviceRandomSampling
     max_func = cls(acq, lower, upper, n_samples=n_candidates, rng=rng)
+    hv = []
 
-    t_begin = time.time()
-    X, Y, hv, runtime, overhead = [], [], [], [], []
-
-    def evaluate(x, spent):
-        y = np.asarray(objective_function(x), dtype=np.float64).reshape(-1)
-        if y.shape != (2,):
-            raise ValueError("objective_function must return two values, got shape %r" % (y.shape,))
-        X.append(np.array(x, dtype=np.float64))
-        Y.append(y)
+    def record(X, Y):
         hv.append(hypervolume_2d(pareto_front_2d(np.array(Y), ref_point)[0], ref_point))
-        overhead.append(spent)
-        runtime.append(time.time() - t_begin)
-        logger.info("Evaluation %d: %s -> %s, hypervolume %f", len(X), x, y, hv[-1])
+        return "hypervolume %f" % hv[-1]
 
-    t0 = time.time()
-    init = init_latin_hypercube_sampling(lower, upper, n_init, rng=rng)
-    spent = (time.time() - t0) / max(n_init, 1)
-    for x in init:
-        evaluate(x, spent)
-    for _ in range(n_init, num_iterations):
-        t0 = time.time()
-        Xa, Ya = np.array(X), np.array(Y)
-        for o, model in enumerate(models):
-            model.train(Xa, Ya[:, o].copy(), do_optimize=True)
-        acq.update(models)
-        x = np.asarray(max_func.maximize(), dtype=np.float64)
-        evaluate(x, time.time() - t0)
-
+    X, Y, runtime, overhead = _multi_output.run(objective_function, lower, upper, models, acq, max_func, num_iterations,
+                                                n_init, rng, "two values", record)
     Xa, Ya = np.array(X), np.array(Y)
     front, idx = pareto_front_2d(Ya, ref_point)
     return {"X": [x.tolist() for x in X], "Y": [y.tolist() for y in Y], "pareto_X": Xa[idx], "pareto_Y": front,

@@ -1738,3 +1738,90 @@ def check_factor_schedules(ctx, sizes=(100, 127, 255, 256, 257, 383, 384, 511, 5
     finally:
         for key in SCHEDULE_KEYS:
             ctx.set_tuning(key, None)
+
+
+def check_event_slot_numbers(ctx):
+    """The numbers behind the library's named event slots (csrc/common.h RoboEventSlot; include/robo_hip.h documents
+    them): with the phase events switched on, one small call each (n = 16, m = 8) of predict, KG, EHVI, constrained EI and
+    MES records the slots documented for it INSIDE the call, in order -- between a caller slot recorded in front of the
+    call and one recorded behind it every interval is finite and non-negative."""
+    rs = np.random.RandomState(17)
+    N, D, M = 16, 2, 8
+    X = rs.rand(N, D)
+    theta = np.concatenate([[0.0], np.full(D, np.log(0.5)), [np.log(1e-2)]])
+    gps = []
+    for j in range(2):
+        g = _lib.DeviceGP(ctx, "matern52", N, D)
+        y = np.sin(3 * X.sum(axis=1) + j)
+        g.set_data(X, y)
+        g.fit(theta, float(y.mean()))
+        gps.append(g)
+    cand, rep = _lib.Candidates(ctx, rs.rand(M, D)), _lib.Candidates(ctx, rs.rand(4, D))
+    u = np.array([0.25, 0.5, 0.75])
+    calls = (("predict", (24, 25, 26, 27), lambda: gps[0].predict(cand)),
+             ("kg", (24, 27, 30, 31), lambda: gps[0].kg(cand, rep, 1e-2)),
+             ("ehvi", (24, 27, 30, 31), lambda: gps[0].ehvi(gps[1], cand, np.array([[-0.5, 0.5]]), [2.0, 2.0])),
+             ("cei", (24, 27, 32, 33), lambda: gps[0].cei([gps[1]], cand, [0.0], "ei", 0.0, 0.0)),
+             ("mes", (24, 27, 30, 31), lambda: gps[0].mes(0.0, cand, u)))
+    ctx.set_phase_events(True)
+    try:
+        for name, slots, call in calls:
+            ctx.record(0)
+            call()
+            ctx.record(1)
+            ctx.synchronize()
+            chain = (0,) + slots + (1,)
+            for a, b in zip(chain[:-1], chain[1:]):
+                ms = ctx.elapsed_ms(a, b)
+                assert np.isfinite(ms) and ms >= 0.0, (name, a, b, ms)
+    finally:
+        ctx.set_phase_events(False)
+        cand.close()
+        rep.close()
+        for g in gps:
+            g.close()
+
+
+def check_staged_candidates(ctx):
+    """base_acquisition.staged_candidates: an array becomes a temporary batch on the model's context, built with the
+    model's own normalisation (``normalize`` before ``_normalised``) and closed after the block, also when the body raises;
+    a device batch is yielded as it is and left open."""
+    from robo_amd.acquisition_functions.base_acquisition import staged_candidates
+
+    class Plain(object):
+        def __init__(self):
+            self.gp = type("G", (), {"ctx": ctx})()
+
+        def _normalised(self, X):
+            return 0.5 * X
+
+    class Own(Plain):
+        def normalize(self, X):
+            return 0.25 * X
+
+    X = np.random.RandomState(5).rand(5, 3)
+    for model, scale in ((Plain(), 0.5), (Own(), 0.25)):
+        with staged_candidates(model, X) as cand:
+            assert isinstance(cand, _lib.Candidates) and cand.ctx is ctx and (cand.m, cand.dim) == (5, 3) and cand._h
+            np.testing.assert_array_equal(cand.points(), scale * X)
+        assert cand._h is None                                   # closed
+    try:
+        with staged_candidates(Plain(), X.tolist()) as cand:     # (anything np.asarray takes)
+            assert cand._h
+            raise KeyError("body")
+    except KeyError:
+        pass
+    assert cand._h is None
+    mine = _lib.Candidates(ctx, X)
+    try:
+        for raises in (False, True):
+            try:
+                with staged_candidates(Plain(), mine) as cand:
+                    assert cand is mine
+                    if raises:
+                        raise KeyError("body")
+            except KeyError:
+                assert raises
+            assert mine._h and np.array_equal(mine.points(), X)  # left open
+    finally:
+        mine.close()

@@ -763,6 +763,24 @@ def test_front_end_emu(emu_ctx):
     _check_front_end_mcmc(emu_ctx)
 
 
+@pytest.mark.parametrize("model_type", ["gp", "gp_mcmc"])
+def test_front_end_trajectory_emu(emu_ctx, model_type):
+    """a seeded run on the interpreter repeats, bit for bit, the trajectory recorded before the front ends' shared loop was
+    stated once (tests/golden/fmin_trajectories.json; NOTES.md names the commit): the points ``rng`` is consumed at, and
+    every number behind the proposals, are where they were"""
+    import json
+    from robo_amd.fmin import constrained_optimization
+    with open(os.path.join(HERE, "golden", "fmin_trajectories.json")) as f:
+        want = json.load(f)["constrained/" + model_type]
+    kw = dict(chain_length=4, burnin_steps=2) if model_type == "gp_mcmc" else {}
+    np.random.seed(12)
+    res = constrained_optimization(_toy1, _BOX[0], _BOX[1], [0.0], num_iterations=5, n_init=3, n_candidates=32,
+                                   model_type=model_type, rng=np.random.RandomState(12), **kw)
+    assert np.array(res["X"]).shape == (5, 2)
+    for key in ("X", "y", "C", "incumbents"):
+        assert _bits(res[key], want[key]), (key, res[key], want[key])
+
+
 @pytest.mark.gpu
 def test_moments_gpu(gpu_ctx):
     _check_moments(gpu_ctx, "MI355X")

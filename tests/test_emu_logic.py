@@ -256,6 +256,14 @@ def test_phase_events(emu_ctx):
     P.check_phase_events(emu_ctx)
 
 
+def test_event_slot_numbers(emu_ctx):
+    P.check_event_slot_numbers(emu_ctx)
+
+
+def test_staged_candidates(emu_ctx):
+    P.check_staged_candidates(emu_ctx)
+
+
 def test_small_and_large_candidate_tiles_agree(emu_ctx, monkeypatch):
     P.check_small_and_large_tiles_agree(emu_ctx, monkeypatch)
 

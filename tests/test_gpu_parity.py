@@ -517,6 +517,10 @@ def test_phase_events(ctx):
     P.check_phase_events(ctx)
 
 
+def test_event_slot_numbers(ctx):
+    P.check_event_slot_numbers(ctx)
+
+
 def test_small_and_large_candidate_tiles_agree(ctx, monkeypatch):
     P.check_small_and_large_tiles_agree(ctx, monkeypatch)
 
