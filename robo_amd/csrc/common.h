@@ -65,6 +65,47 @@ __device__ __forceinline__ unsigned ld_agent_u32(const unsigned* p) {
 __device__ __forceinline__ void add_agent_u32(unsigned* p, unsigned v) {
     __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
+// The same in 16-byte pieces (the chained solve's tile v_i, trsm_chain.hip): global_store_dwordx4 ... sc1 and
+// global_load_dwordx4 ... sc1 at a 16-byte aligned address.  There is no 16-byte atomic to lower to them, so the device forms
+// are written out, and the compiler does not count them in vmcnt.  A store has left the CU behind drain_vmem like any other.
+// A load's registers are defined only behind a wait the compiler cannot see either, so the loads and their wait are ONE
+// statement (early-clobber results: as separate statements the compiler moved a result register between a load and the
+// wait): ld_agent2x4 reads four consecutive pieces, in flight together, and returns when every vector-memory operation of
+// the wave has completed.  Off the device (the interpreter under tests/hipemu) all of them are plain C++.
+__device__ __forceinline__ void st_agent2(double* p, double2 v) {
+#ifdef __AMDGCN__
+    typedef double v2d __attribute__((ext_vector_type(2)));
+    const v2d x = {v.x, v.y};
+    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(x) : "memory");
+#else
+    p[0] = v.x;
+    p[1] = v.y;
+#endif
+}
+__device__ __forceinline__ void ld_agent2x4(const double* p, double2& a, double2& b, double2& c, double2& d) {
+#ifdef __AMDGCN__
+    typedef double v2d __attribute__((ext_vector_type(2)));
+    v2d x0, x1, x2, x3;
+    asm volatile(
+        "global_load_dwordx4 %0, %4, off sc1\n\t"
+        "global_load_dwordx4 %1, %4, off offset:16 sc1\n\t"
+        "global_load_dwordx4 %2, %4, off offset:32 sc1\n\t"
+        "global_load_dwordx4 %3, %4, off offset:48 sc1\n\t"
+        "s_waitcnt vmcnt(0)"
+        : "=&v"(x0), "=&v"(x1), "=&v"(x2), "=&v"(x3)
+        : "v"(p)
+        : "memory");
+    a = make_double2(x0.x, x0.y);
+    b = make_double2(x1.x, x1.y);
+    c = make_double2(x2.x, x2.y);
+    d = make_double2(x3.x, x3.y);
+#else
+    a = make_double2(p[0], p[1]);
+    b = make_double2(p[2], p[3]);
+    c = make_double2(p[4], p[5]);
+    d = make_double2(p[6], p[7]);
+#endif
+}
 // every vector-memory operation of this wave has completed (vmcnt(0); expcnt / lgkmcnt fields left at their maxima)
 __device__ __forceinline__ void drain_vmem() { __builtin_amdgcn_s_waitcnt(0x0F70); }
 constexpr long long FOLLOW_SENTINEL = 0x7FF8DEAD00C0FFEELL;   // a NaN no arithmetic produces: "W_77 of this panel is not published yet"
