@@ -622,6 +622,46 @@ int32_t robo_cei_eval_cand(robo_gp* objective, robo_gp* const* constraints, int3
                            int32_t acq_kind, double par, double eta, int32_t has_eta, robo_cand* cand,
                            double* out_values /* nullable */, double* out_max, int64_t* out_argmax, uint32_t* out_flags,
                            double* out_trace /* nullable */);
+/* ---- gradient refinement of the constrained value: robo_acq_refine_cand's multi-start projected ascent on the value of
+ * robo_cei_eval_cand.  The constrained optimum usually lies on a constraint boundary, which random candidates only straddle.
+ *   Sweep.      Exactly robo_cei_eval_cand's without values read back: the same arguments, the same checks, the same values
+ *               left in the handle.
+ *   Starts, ascent, result, trace.   Exactly robo_acq_refine_cand's: the n_starts (K <= 1024) best candidates in descending
+ *               value, ties by ascending index, NaN never; projected unit-length steps in [0, 1]^dim; accept iff f(y) > f(x);
+ *               alpha doubles up to 0.5 or halves; a start freezes (ROBO_FLAG_FROZEN) when a trial's variance sits on the
+ *               floor, its value is not finite or no direction is left; out_trace ((n_steps + 1) x n_starts x (2 dim + 3)) has
+ *               the same columns and codes 0 / 1 / 2 / 3; n_steps = 0 returns the sweep's own argmax, point and value; one
+ *               synchronisation per call.
+ *   Value at a trial point.   The fold's rule on the moments the (dim + 1)-row solve gives for that point: per GP m, v, dm, dv
+ *               as robo_acq_refine_cand forms them, the variance floored at DBL_EPSILON -- the floor in ANY of the GPs solved
+ *               marks the trial (code 3).  z_k = (t_k - m_k) / s_k and the sum L of norm_logcdf(z_k) in index order from 0,
+ *               each operation rounded once; value = f0 (C = 0), f0 + L (LogEI), f0 * exp(L) (EI), rounded once, with f0 the
+ *               objective factor of robo_acq_refine_cand (EI's guard included); has_eta = 0: L resp. exp(L).
+ *   Gradient.   dz_k = (-dm_k - z_k ds_k) / s_k, ds = dv / (2 s); dl_k = r(z_k) dz_k, r = phi / Phi as the plain quotient for
+ *               z >= -1 and 1 / (sqrt(pi / 2) erfcx(-z / sqrt 2)) below, which is finite wherever L is; dL summed in index
+ *               order.  With g0 the objective's gradient (robo_acq_refine_cand's formulas): g0 + dL (LogEI),
+ *               exp(L) (g0 + f0 dL) (EI); has_eta = 0: dL resp. exp(L) dL.  The gradient carries no bit contract; the value's
+ *               last operation, the accept test, the step-length update, the trial point and its clip are single rounded
+ *               operations on stored doubles.
+ *   Order.      Per trial the GPs are solved one after the other, constraints 1 .. C first, the objective last; its epilogue
+ *               combines, decides and writes the next trial.  With has_eta = 0 the iterations leave the objective's GP out
+ *               entirely (only the sweep reads it) and the last constraint's epilogue decides; with C = 0 as well the value is
+ *               constant and every start freezes after its evaluation.
+ *   Consequences.   With C = 0 and has_eta = 1 the call returns robo_acq_refine_cand's result and trace bit for bit.  A start's
+ *               trajectory does not depend on n_starts or on its slot.  In the product form (EI) a start whose value has
+ *               underflowed to 0 has a zero gradient, hence no direction, and freezes: the log form (LogEI) is the one that
+ *               climbs out of infeasible regions.
+ * The GPs may differ in kernel kind (Matern-5/2, RBF), hyper-parameters, N and output normalisation; each is solved through
+ * the explicit inverse or by block rows by the library's rule for its own factor.  A Fabolas kernel: ROBO_BAD_ARGUMENT (its
+ * fidelity column is not a box coordinate).  n_starts, n_steps, step0 out of range: ROBO_BAD_ARGUMENT; n_starts (dim + 1)
+ * rows of the LARGEST n_pad among the GPs the iterations solve exceeding the solve workspace: ROBO_BAD_SHAPE; otherwise
+ * robo_cei_eval_cand's refusals -- all before anything is launched.  State and workspace stay with `objective` (shared with
+ * robo_acq_refine_cand on it).  No event slot of its own: the sweep records 32 and 33 as robo_cei_eval_cand does.        */
+int32_t robo_cei_refine_cand(robo_gp* objective, robo_gp* const* constraints, int32_t C, const double* thresholds,
+                             int32_t acq_kind, double par, double eta, int32_t has_eta, robo_cand* cand,
+                             int32_t n_starts, int32_t n_steps, double step0,
+                             double* out_x, double* out_value, int64_t* out_start_index, uint32_t* out_flags,
+                             int64_t* out_starts /* nullable */, double* out_trace /* nullable */);
 /* the fold kernel alone for any models' moments: mean0, var0 (m), means, vars (C x m, row-major, row k = constraint k + 1;
  * not read when C = 0).  Equals the fused call bit for bit when fed the fused call's own trace.                          */
 int32_t robo_cei_eval_moments(robo_ctx* ctx, int64_t m, int32_t C, const double* mean0, const double* var0,

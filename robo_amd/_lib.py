@@ -60,7 +60,7 @@ SYMBOLS = [
     "robo_mes_eval_cand", "robo_mes_eval_marginal_cand", "robo_mes_sample_min_moments", "robo_mes_eval_moments",
     "robo_kg_eval_cand", "robo_kg_eval_marginal_cand", "robo_kg_eval_moments",
     "robo_ehvi_eval_cand", "robo_ehvi_eval_moments",
-    "robo_cei_eval_cand", "robo_cei_eval_moments",
+    "robo_cei_eval_cand", "robo_cei_eval_moments", "robo_cei_refine_cand",
     "robo_paths_create", "robo_paths_eval_cand", "robo_paths_destroy", "robo_paths_descend", "robo_paths_refine_cand",
     "robo_ig_eval_cand", "robo_ig_eval_per_cost_cand", "robo_ig_eval_moments", "robo_gp_cross_cov",
     "robo_ep_joint_min", "robo_pmin_mc", "robo_igmc_eval_cand", "robo_igmc_eval_moments",
@@ -252,6 +252,8 @@ def lib():
                                _dp],
         "robo_cei_eval_moments": [vp, i64, i32, _dp, _dp, _dp, _dp, _dp, i32, dbl, dbl, i32, _dp, _dp, C.POINTER(i64),
                                   C.POINTER(C.c_uint32)],
+        "robo_cei_refine_cand": [vp, pp, i32, _dp, i32, dbl, dbl, i32, vp, i32, i32, dbl, _dp, _dp, C.POINTER(i64),
+                                 C.POINTER(C.c_uint32), C.POINTER(i64), _dp],
         "robo_paths_create": [vp, i32, i32, _dp, _dp, _dp, _dp, pp],
         "robo_paths_eval_cand": [vp, vp, _dp, _dp, C.POINTER(i64), C.POINTER(C.c_uint32)],
         "robo_paths_destroy": [vp],
@@ -943,17 +945,31 @@ class DeviceGP(object):
         """constrained expected improvement of ``cand`` with this GP as the objective and ``constraint_gps`` (C of them) as
         the constraints c_k(x) <= thresholds[k]; kind "ei" or "log_ei"; eta None: no feasible incumbent yet, the probability
         of feasibility alone (robo_cei_eval_cand) -> CEIResult"""
-        constraint_gps = list(constraint_gps)
-        Cn = len(constraint_gps)
-        thresholds = _cei_thresholds(thresholds, Cn)
+        head = self._cei_head(constraint_gps, thresholds, kind, par, eta)
+        Cn = head[2]
         out = np.empty(cand.m) if want_values else None
         trace = np.empty((cand.m, 2 * (Cn + 1) + 2)) if (diagnostics and Cn <= CEI_MAX_CONSTRAINTS) else None
         best = _Best()
-        check(lib().robo_cei_eval_cand(self._h, _handles(constraint_gps), Cn, _arr(thresholds), _cei_kind(kind), float(par),
-                                       0.0 if eta is None else float(eta), int(eta is not None), cand._h,
-                                       _arr(out) if want_values else None, *best.refs,
+        check(lib().robo_cei_eval_cand(*head, cand._h, _arr(out) if want_values else None, *best.refs,
                                        _arr(trace) if trace is not None else None))
         return CEIResult(out, *best.values(), trace)
+
+    def _cei_head(self, constraint_gps, thresholds, kind, par, eta):
+        """the leading arguments of the fused constrained-EI entry points: (objective, constraints, C, thresholds, kind, par,
+        eta, has_eta); the pointer of the thresholds keeps its array alive"""
+        constraint_gps = list(constraint_gps)
+        Cn = len(constraint_gps)
+        return (self._h, _handles(constraint_gps), Cn, _arr(_cei_thresholds(thresholds, Cn)), _cei_kind(kind), float(par),
+                0.0 if eta is None else float(eta), int(eta is not None))
+
+    def cei_refine(self, constraint_gps, cand, thresholds, kind, par, eta, n_starts=256, n_steps=50, step0=0.05,
+                   diagnostics=False):
+        """constrained expected improvement's sweep over ``cand`` (as :meth:`cei`) + multi-start projected gradient ascent on
+        the constrained value on the device (robo_cei_refine_cand) -> RefineResult.  The log form ("log_ei") climbs out of
+        infeasible regions; in the product form ("ei") a start whose value has underflowed to 0 has no direction and
+        freezes.  eta None: the probability of feasibility alone is refined and the objective's GP is only swept."""
+        return _refine_call(lib().robo_cei_refine_cand, self._cei_head(constraint_gps, thresholds, kind, par, eta), cand,
+                            n_starts, n_steps, step0, diagnostics)
 
     def sample_paths(self, omega, phase, w, eps):
         """S posterior sample paths of the fitted GP from the caller's draws: omega (F, D) and phase (F,) in the scaled
@@ -1300,6 +1316,14 @@ class RefineResult(object):
 def acq_refine(gps, kind, par, eta, cand, n_starts=256, n_steps=50, step0=0.05, diagnostics=False, marginal=True):
     """the gradient-refined maximiser of a closed-form acquisition over device GPs (one: robo_acq_refine_cand; the mean
     over several hyper-parameter samples: robo_acq_refine_marginal_cand).  eta: one incumbent value, or one per sample."""
+    fn = lib().robo_acq_refine_marginal_cand if marginal else lib().robo_acq_refine_cand
+    return _refine_call(fn, _ensemble_head(gps, eta, marginal, ACQ_KINDS[kind], float(par)), cand, n_starts, n_steps, step0,
+                        diagnostics)
+
+
+def _refine_call(fn, head, cand, n_starts, n_steps, step0, diagnostics):
+    """what the refinement entry points share behind their own leading arguments ``head``: (cand, n_starts, n_steps, step0,
+    out_x, out_value, out_start_index, out_flags, out_starts, out_trace) -> RefineResult"""
     K, T, D = int(n_starts), int(n_steps), cand.dim
     x = np.empty(D)
     best = _Best()                           # (value, start index, flags)
@@ -1308,8 +1332,6 @@ def acq_refine(gps, kind, par, eta, cand, n_starts=256, n_steps=50, step0=0.05, 
     trace = np.empty((T + 1, K, 2 * D + 3)) if want else None
     p_starts = starts.ctypes.data_as(C.POINTER(C.c_int64)) if want else None
     p_trace = _arr(trace) if want else None
-    fn = lib().robo_acq_refine_marginal_cand if marginal else lib().robo_acq_refine_cand
-    head = _ensemble_head(gps, eta, marginal, ACQ_KINDS[kind], float(par))
     check(fn(*head, cand._h, K, T, float(step0), _arr(x), *best.refs, p_starts, p_trace))
     return RefineResult(x, *best.values(), starts, trace)
 

@@ -18,10 +18,13 @@ All arithmetic runs on the device (robo_amd/csrc/cei.hip; the rule is stated in 
 
 The incumbent is fixed per ``update()``, from the models' training targets.
 """
+import contextlib
+
 import numpy as np
 
 from robo_amd import _lib
-from robo_amd.acquisition_functions.base_acquisition import OneDeviceAcquisition, predicted_moments, same_box_natives
+from robo_amd.acquisition_functions.base_acquisition import (OneDeviceAcquisition, predicted_moments, refine_finish,
+                                                             refuse_multi_device, same_box_natives, staged_candidates)
 from robo_amd.acquisition_functions.ehvi import _inputs, _targets
 
 
@@ -166,6 +169,53 @@ class ConstrainedEI(OneDeviceAcquisition):
         res = self.model.objective.gp.cei([m.gp for m in self.model.constraints], cand, self.thresholds, kind, self.par, eta,
                                           want_values=want_values)
         return res.values, res.max, res.argmax
+
+    @contextlib.contextmanager
+    def _refined(self, X, n_starts, n_steps, step0, diagnostics, what):
+        """the checks of the device refinement, then robo_cei_refine_cand on the staged candidates: yields (objective model,
+        candidates, result) while the candidates are open.  n_starts None: every candidate is a start."""
+        who = self.__class__.__name__
+        models = self.model.all_models
+        refuse_multi_device(models, who, self.why_one_device)
+        from robo_amd.models.fabolas_gp import FabolasGP
+        if any(isinstance(m, FabolasGP) for m in models):
+            raise TypeError("%s.%s: the fidelity column of a Fabolas model is not a box coordinate to refine" % (who, what))
+        if not same_box_natives(models) or not getattr(self.model.objective, "normalize_input", False):
+            raise TypeError("%s.%s needs robo_amd GaussianProcess models on one context with normalize_input=True and one "
+                            "input box: the ascent runs in the box [0, 1]^D of their normalised inputs" % (who, what))
+        obj = self.model.objective
+        with staged_candidates(obj, X) as cand:
+            res = obj.gp.cei_refine([m.gp for m in self.model.constraints], cand, self.thresholds, self.kind, self.par,
+                                    self.eta, cand.m if n_starts is None else n_starts, n_steps, step0, diagnostics)
+            yield obj, cand, res
+
+    def refine(self, X, n_starts=256, n_steps=50, step0=0.05, diagnostics=False):
+        """The constrained maximiser refined by gradient ascent on the device (robo_cei_refine_cand): sweep over the
+        candidates X ((M, D) in the caller's input space, or a device batch in the normalised one), the ``n_starts`` best of
+        them climb ``n_steps`` projected steps in lock step -> the best point found, in the caller's input space;
+        ``last_refine`` keeps the library's result.  While no observation is feasible the probability of feasibility alone is
+        refined (the objective's model is only swept).  ``log=True`` is the form that climbs out of infeasible regions: in
+        the product form a start whose value has underflowed to 0 has no direction and stays where it is.  Native models
+        with one input box only (TypeError otherwise; ``devices=`` models: NotImplementedError)."""
+        with self._refined(X, n_starts, n_steps, step0, diagnostics, "refine") as (obj, cand, res):
+            return refine_finish(self, self.kind, obj, res, cand)
+
+    def value_and_gradient(self, X):
+        """values (M,) and gradients (M, D) of the function at X ((M, D), M <= 1024, caller's input space) by the device's
+        refinement epilogue: one call with the points as candidates, every one a start, no step.  The gradient is with
+        respect to the caller's inputs (the normalised one / (upper - lower))."""
+        X = np.atleast_2d(np.asarray(X, dtype=np.float64))
+        if X.shape[0] > _lib.REFINE_MAX_STARTS:
+            raise ValueError("%s.value_and_gradient takes at most %d points, got %d"
+                             % (self.__class__.__name__, _lib.REFINE_MAX_STARTS, X.shape[0]))
+        with self._refined(X, None, 0, 0.05, True, "value_and_gradient") as (obj, _, res):
+            pass
+        M, D = X.shape
+        vals, grads = np.full(M, np.nan), np.full((M, D), np.nan)
+        used = res.starts >= 0                      # (a NaN point is no start: its value stays NaN)
+        vals[res.starts[used]] = res.trace[0, used, D]
+        grads[res.starts[used]] = res.trace[0, used, D + 1:2 * D + 1]
+        return vals, grads / (np.asarray(obj.upper, dtype=np.float64) - np.asarray(obj.lower, dtype=np.float64))
 
     def probability_of_feasibility(self, X):
         """prod_k P(c_k(x) <= t_k) of every candidate, by the same device rule (the value the function takes while no

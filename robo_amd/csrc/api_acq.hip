@@ -169,9 +169,7 @@ int models_check(const char* label, const char* the_models, robo_gp* const* gps,
     return ROBO_OK;
 }
 
-int models_fold(const char* label, robo_gp* const* gps, int32_t S, robo_cand* k, int slot_begin,
-                const std::function<int()>& fold, ReadBack trace, double* out_vec, double* out_max, int64_t* out_argmax,
-                uint32_t* out_flags) {
+int models_fold_launch(robo_gp* const* gps, int32_t S, robo_cand* k, int slot_begin, const std::function<int()>& fold) {
     robo_ctx* c = k->ctx;
     // the S sweeps, each chunked by the workspace
     ROBO_TRY(clear_flags_on_error(k, predict_samples(gps, S, k, S)));
@@ -179,7 +177,13 @@ int models_fold(const char* label, robo_gp* const* gps, int32_t S, robo_cand* k,
     if (ev) ROBO_TRY(record_phase(c, slot_begin));
     ROBO_TRY(clear_flags_on_error(k, fold()));
     if (ev) ROBO_TRY(record_phase(c, slot_begin + 1));
-    ROBO_TRY(clear_flags_on_error(k, launch_argmax(k, k->d_acq_sum, 1.0)));
+    return clear_flags_on_error(k, launch_argmax(k, k->d_acq_sum, 1.0));
+}
+
+int models_fold(const char* label, robo_gp* const* gps, int32_t S, robo_cand* k, int slot_begin,
+                const std::function<int()>& fold, ReadBack trace, double* out_vec, double* out_max, int64_t* out_argmax,
+                uint32_t* out_flags) {
+    ROBO_TRY(models_fold_launch(gps, S, k, slot_begin, fold));
     ROBO_TRY(finish_call(k, label, ROBO_OK, {trace}, false));
     // (max, argmax, flags) [+ the values] and the one synchronisation of the call
     return clear_flags_on_error(k, acq_read_back(k, k->d_acq, out_vec, out_max, out_argmax, out_flags));

@@ -104,6 +104,9 @@ int models_check(const char* label, const char* the_models, robo_gp* const* gps,
 // models_fold: the S sweeps into rows 0 .. S - 1 of k's sample tables, fold() -- the caller's kernel, values into
 // k->d_acq_sum -- between the event slots slot_begin and slot_begin + 1, the argmax, the trace's copy, then (max, argmax,
 // flags) [+ the values] and the one synchronisation of the call.
+// models_fold_launch: everything of it before the read-back (launches only: the values stay in k->d_acq, the winner in
+// k's argmax slots), for a driver that goes on from the fold on the device.
+int models_fold_launch(robo_gp* const* gps, int32_t S, robo_cand* k, int slot_begin, const std::function<int()>& fold);
 int models_fold(const char* label, robo_gp* const* gps, int32_t S, robo_cand* k, int slot_begin,
                 const std::function<int()>& fold, ReadBack trace, double* out_vec, double* out_max, int64_t* out_argmax,
                 uint32_t* out_flags);
@@ -125,6 +128,17 @@ int moments_finish(robo_cand* k, int status, bool reduce, double* out_vec, doubl
 int ig_per_cost_core(robo_gp* g, robo_cand* k, robo_cand* rep, int32_t npts, double sn2, const double* logP,
                      const double* lmb, const double* W, const double* dlogPdMu, const double* dlogPdSigma,
                      const double* dlogPdMudMu, robo_gp* cost_gp, robo_cand* cost_k, double overhead);
+
+// ---- refine.hip: what the refinement drivers share (robo_acq_refine_*, robo_cei_refine_cand) -----------------------------------------
+inline size_t refine_trace_len(int K, int T, int D) { return (size_t)(T + 1) * K * (2 * D + 3); }
+int refine_check_steps(int32_t n_starts, int32_t n_steps, double step0);      // out of range: ROBO_BAD_ARGUMENT
+// K (D + 1) rows of n_pad columns must fit the solve workspace (ROBO_BAD_SHAPE) -> the state block and pseudo-row workspace
+// kept with `holder`, sized, the trace buffer grown and bound when asked for
+int refine_prepare(robo_gp* holder, int n_pad, int K, int T, bool want_trace, RefineWork** out);
+int launch_refine_solve(robo_gp* g, RefineWork* w, int K, double* d_rhs);
+// the winner's kernel, the copies (point, value, start, flags [+ starts, trace]) and the one synchronisation of the call
+int refine_read_back(robo_cand* k, RefineWork* w, int status, int T, double* out_x, double* out_value,
+                     int64_t* out_start_index, uint32_t* out_flags, int64_t* out_starts, double* out_trace);
 
 // ---- comm.hip: the exchange kernels multi.hip reduces with, too ------------------------------------------------------------------
 int launch_comm_pack_sum(hipStream_t st, const double* d_part, long long m, int have, const unsigned* d_flags, int status,

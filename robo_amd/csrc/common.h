@@ -734,6 +734,18 @@ int launch_refine_select(robo_ctx* ctx, const RefineState& st, const double* d_v
 int launch_refine_eval(robo_gp* gp, const RefineState& st, const robo_cand* ws, int acq_kind, double par, double eta, int s,
                        int S, int t, int T);
 int launch_refine_result(robo_ctx* ctx, const RefineState& st, unsigned* d_cand_flags, bool sweep_only);
+// state + pseudo-row workspace for K starts in D dimensions, kept with g between calls of one (K, D)
+int refine_ensure(robo_gp* g, int K, int D, RefineWork** out);
+// cei_refine.hip: the epilogue of one GP of the constrained refinement at the K trial points.  A constraint (threshold thr)
+// adds log Phi(z) and its gradient to the running L / dL in st.fy / st.gy (first: starts them); the objective (objective =
+// true, always the last launch of a trial) forms its own factor unless has_eta = 0.  last: combine, decide, next trial.
+struct CeiRefineStep {
+    bool objective, first, last;
+    double thr;
+    int C, kind, has_eta;
+    double par, eta;
+};
+int launch_cei_refine_eval(robo_gp* gp, const RefineState& st, const robo_cand* ws, const CeiRefineStep& step, int t, int T);
 // batch.hip: outputs to "no pick"; a sample's latent moments after its posterior; the reduction's winner -> pick j; one
 // conditioning step (k_*(x_j), beta, the pass over the candidates) of sample s for pick j >= 1
 int launch_batch_reset(robo_ctx* ctx, const BatchState& st);

@@ -14,6 +14,7 @@
 
 #include "api_internal.h"
 #include "kern_math.h"
+#include "refine_eval.h"
 
 namespace robo {
 
@@ -159,46 +160,10 @@ __global__ __launch_bounds__(64) void refine_gather_kernel(RefineState st, const
     }
 }
 
-// ---- Phi(z) / h(z), h = z Phi + phi: the factor of dz in d log EI ----------------------------------------------------------
-// z >= -1: the plain quotient (h has no cancellation there).  z < -1, t = -z: with the Mills ratio
-// M(t) = Phi(-t) / phi(t) = sqrt(pi / 2) erfcx(t / sqrt 2) the quotient is M / (1 - t M), free of underflow; 1 - t M
-// ~ 1 / t^2 cancels and amplifies erfcx's rounding by t^2 (relative error ~ t^2 eps: 5.7e-14 at t = 16).  From t = 16 on
-// the asymptotic series in u = 1 / t^2
-//     t M = 1 - u + 3 u^2 - 15 u^3 + ...,      1 - t M = u (1 - 3 u + 15 u^2 - 105 u^3 + ...)
-// is used with 12 terms: the first omitted term is 23!! u^12 = 4e-18 at t = 16 (below one ulp) and falls from there.
-constexpr double REFINE_TAIL_T = 16.0;
-__device__ __forceinline__ double cdf_over_h(double z) {
-    if (z >= -1.0) {
-        const double P = norm_cdf(z);
-        return P / (z * P + norm_pdf(z));
-    }
-    const double t = -z;
-    if (t < REFINE_TAIL_T) {
-        const double M = 1.25331413731550025121 * erfcx(t * SQRT1_2);
-        return M / (1.0 - t * M);
-    }
-    const double u = 1.0 / (t * t);
-    double num = 0.0, den = 0.0;       // Horner from the highest term: coefficients (-1)^n (2n - 1)!! and (-1)^n (2n + 1)!!
-    double c = 316234143225.0;         // 23!!
-    for (int n = 12; n >= 1; --n) {    // c = (2n - 1)!! on entry
-        const double sgn = (n & 1) ? -1.0 : 1.0;
-        num = (num + sgn * c) * u;
-        den = (den + sgn * c * (double)(2 * n + 1)) * u;
-        c /= (double)(2 * n - 1);
-    }
-    // t M = 1 + num,  (1 - t M) / u = 1 + den  ->  M / (1 - t M) = t (1 + num) / (1 + den)
-    return t * (1.0 + num) / (1.0 + den);
-}
-
 // ---- value + gradient + step: one workgroup per start ----------------------------------------------------------------------
-// Rows (k E .. k E + D) of the solved workspace are v = L^-1 k_*(y_k) and w_d = L^-1 dk_*/dxs_d; q / mu are the solve's
-// reductions |row|^2 and row . z.  The D dot products v . w_d over the N columns are the memory-bound part: wave w takes
-// the rows d = w, w + 4, ..., every lane two adjacent columns per load (16 B), so each w_d row is requested once and v (one
-// row, reused D times by the four waves) is expected to come from the cache -- by construction, not measured; with one
-// workgroup per start and two FMA chains per lane the kernel is more likely bound by load latency than by bandwidth
-// (its measured share of an iteration is in NOTES.md "Gradient refinement on the device").  Then m, v, dm, dv as predgrad_post_kernel forms
-// them, the acquisition value and gradient, the sum over hyper-parameter samples (s = 0 .. S - 1 in order, then / S:
-// NumPy's axis-0 mean), and after the last sample the accept test and the next trial point.
+// The parts are refine_eval.h's: what the launch overwrites is read first, the D dot products and m, v, dm, dv, then the
+// acquisition value and gradient; here the sum over hyper-parameter samples (s = 0 .. S - 1 in order, then / S: NumPy's
+// axis-0 mean), and after the last sample the accept test and the next trial point.
 __global__ __launch_bounds__(256) void refine_eval_kernel(RefineState st, const double* __restrict__ V, int ldv, int ncols,
                                                           const double* __restrict__ q, const double* __restrict__ mu,
                                                           const double* __restrict__ ism, CovParams cp, double mean_c,
@@ -206,149 +171,23 @@ __global__ __launch_bounds__(256) void refine_eval_kernel(RefineState st, const 
                                                           int s, int S, int t, int T) {
     __shared__ double sdot[MAX_DIM];
     __shared__ double sgp[MAX_DIM];
-    const int k = blockIdx.x, D = cp.dim, E = D + 1, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const double ninf = -__builtin_huge_val();
-    // everything this launch overwrites is read first
-    const long long start = st.start[k];
-    const int was_frozen = st.frozen[k];
-    const double fx = st.f[k], alpha0 = st.alpha[k], aused = st.aused[k];
-    const double facc0 = s > 0 ? st.fy[k] : 0.0;
-    const int bad0 = s > 0 ? st.bad[k] : 0;
-    const bool mine = tid < D;
-    const size_t kd = (size_t)k * D + (mine ? tid : 0);
-    const double xd0 = st.x[kd], gd0 = st.g[kd], yd = st.y[kd];
-    const double gacc0 = s > 0 ? st.gy[kd] : 0.0;
-
-    const double* v0 = V + (size_t)k * E * ldv;
-    for (int d = wave; d < D; d += 4) {
-        const double* vd = v0 + (size_t)(1 + d) * ldv;
-        double a0 = 0.0, a1 = 0.0;
-        for (int j = 2 * lane; j < ncols; j += 128) {
-            const double2 a = *reinterpret_cast<const double2*>(v0 + j);
-            const double2 b = *reinterpret_cast<const double2*>(vd + j);
-            a0 = fma(a.x, b.x, a0);
-            a1 = fma(a.y, b.y, a1);
-        }
-        double acc = a0 + a1;
-        for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-        if (lane == 0) sdot[d] = acc;
-    }
-    __syncthreads();
-
-    // posterior moments at the trial (every thread: a few dozen flops) and this thread's gradient components
-    const double u = st.ys[(size_t)k * D + D - 1];
-    const double m = (mu[(size_t)k * E] + mean_c) * y_std + y_mean;
-    const double vraw = (cov_self(cp, u) - q[(size_t)k * E]) * (y_std * y_std);
-    const double eps = 2.220446049250313e-16;
-    const bool floored = !(vraw >= eps);
-    const double v = floored ? eps : vraw;
-    const double sd = sqrt(v);
-    double dm = 0.0, dv = 0.0;
-    if (mine) {
-        const double dself = (cp.kind == ROBO_KERNEL_FABOLAS && tid == D - 1) ? 2.0 * cp.amp * cp.blr_b * u : 0.0;
-        dm = mu[(size_t)k * E + 1 + tid] * ism[tid] * y_std;
-        dv = (dself - 2.0 * sdot[tid]) * ism[tid] * (y_std * y_std);
-    }
-    const double ds = dv / (2.0 * sd);
+    const int k = blockIdx.x, D = cp.dim, tid = threadIdx.x;
+    const RefineCarried c = refine_carried(st, k, D, tid, s > 0);
+    const RefineMoments p = refine_moments(st, k, tid, c.mine, V, ldv, ncols, q, mu, ism, cp, mean_c, y_mean, y_std, sdot);
     double f, df;
-    if (kind == ROBO_ACQ_LCB) {
-        f = acq_lcb(m, v, par);
-        df = -(dm - par * ds);
-    } else {
-        const double z = (eta - m - par) / sd;
-        if (kind == ROBO_ACQ_EI) {
-            f = acq_ei(m, v, eta, par);
-            if (f < 0.0 && f > -2.2250738585072014e-308) f = 0.0;    // as acq_kernel
-            df = -dm * norm_cdf(z) + ds * norm_pdf(z);
-        } else if (kind == ROBO_ACQ_PI) {
-            f = acq_pi(m, v, eta, par);
-            df = -(norm_pdf(z) / sd) * (dm + ds * z);
-        } else {
-            f = acq_log_ei(m, v, eta, par);
-            const double dz = (-dm - z * ds) / sd;
-            df = ds / sd + cdf_over_h(z) * dz;
-        }
-    }
-    const double facc = s > 0 ? facc0 + f : f;
-    const double gacc = s > 0 ? gacc0 + df : df;
-    const int bad = bad0 | (floored ? 1 : 0);
+    refine_acq(kind, par, eta, p, &f, &df);
+    const double facc = s > 0 ? c.facc0 + f : f;
+    const double gacc = s > 0 ? c.gacc0 + df : df;
+    const int bad = c.bad0 | (p.floored ? 1 : 0);
     if (s + 1 < S) {               // more samples to come: leave the partial sums behind
-        if (mine) st.gy[kd] = gacc;
+        if (c.mine) st.gy[c.kd] = gacc;
         if (tid == 0) {
             st.fy[k] = facc;
             st.bad[k] = bad;
         }
         return;
     }
-    const double fy = rn_div(facc, (double)S);
-    const double gyd = rn_div(gacc, (double)S);
-
-    // the decision (identical in every thread)
-    const bool trial_bad = bad != 0 || !isfinite(fy);
-    int frozen = was_frozen, code;
-    bool accept = false;
-    double alpha = alpha0;
-    if (start < 0) {
-        code = 2;
-    } else if (t == 0) {             // the start itself: always the current point
-        accept = true;
-        code = trial_bad ? 3 : 1;
-        if (trial_bad) frozen = 1;
-    } else if (was_frozen) {
-        code = 2;
-    } else if (trial_bad) {          // variance on its floor or value not finite: not taken, and the start stops here
-        code = 3;
-        frozen = 1;
-    } else {
-        accept = fy > fx;
-        code = accept ? 1 : 0;
-        alpha = accept ? fmin(rn_mul(2.0, alpha0), 0.5) : rn_mul(alpha0, 0.5);
-    }
-    const double xd = accept ? yd : xd0, gd = accept ? gyd : gd0;
-
-    if (st.trace) {
-        double* row = st.trace + ((size_t)t * st.K + k) * (2 * D + 3);
-        if (mine) {
-            row[tid] = yd;
-            row[D + 1 + tid] = gyd;
-        }
-        if (tid == 0) {
-            row[D] = fy;
-            row[2 * D + 1] = aused;
-            row[2 * D + 2] = (double)code;
-        }
-    }
-
-    // next trial: projected direction of unit length, clipped to the box
-    double gp = 0.0;
-    if (mine) gp = ((xd <= 0.0 && gd < 0.0) || (xd >= 1.0 && gd > 0.0)) ? 0.0 : gd;
-    if (mine) sgp[tid] = gp;
-    __syncthreads();
-    double n2 = 0.0;
-    for (int d = 0; d < D; ++d) n2 += sgp[d] * sgp[d];
-    const double nrm = sqrt(n2);
-    const bool more = t < T;
-    if (more && !frozen && !(nrm > 0.0 && isfinite(nrm))) frozen = 1;    // no ascent direction left inside the box
-    if (mine) {
-        double yn = xd;
-        if (more && !frozen) {
-            yn = rn_add(xd, rn_div(rn_mul(alpha, gp), nrm));
-            yn = yn < 0.0 ? 0.0 : (yn > 1.0 ? 1.0 : yn);
-        }
-        st.y[kd] = yn;
-        if (accept) {
-            st.x[kd] = xd;
-            st.g[kd] = gd;
-        }
-    }
-    if (tid == 0) {
-        if (accept) st.f[k] = fy;
-        else if (start < 0) st.f[k] = ninf;
-        st.alpha[k] = alpha;
-        st.aused[k] = alpha;
-        st.frozen[k] = frozen;
-        if (frozen && !was_frozen) atomicOr(st.flags, ROBO_FLAG_FROZEN);
-    }
+    refine_step(st, k, tid, D, c, rn_div(facc, (double)S), rn_div(gacc, (double)S), bad, t, T, sgp);
 }
 
 // the start with the largest final value, first index on ties (NaN only if nothing else is there) -> st.out; the flag
@@ -460,6 +299,16 @@ int launch_refine_eval(robo_gp* gp, const RefineState& st, const robo_cand* ws, 
     return ROBO_OK;
 }
 
+// the pending trial points of all K starts against g: scaled with its metrics, value and gradient rows of the cross-covariance,
+// the solve -- through W = L^-1 when d_rhs (winv_rows_buffer's) is given, else by block rows -- into w->ws
+int launch_refine_solve(robo_gp* g, RefineWork* w, int K, double* d_rhs) {
+    const RefineState& st = w->st;
+    const int64_t rows_pad = round_up64((int64_t)K * (st.D + 1), NB);
+    ROBO_TRY(launch_scale_inputs(g->ctx, st.y, st.ys, g->d_theta, K, K, st.D));
+    ROBO_TRY(launch_cross_grad(g, st.ys, d_rhs ? d_rhs : w->ws->d_V, 0, K, rows_pad));
+    return d_rhs ? launch_winv_rows(g, w->ws, rows_pad) : launch_trsm(g, w->ws, 0, rows_pad);
+}
+
 int launch_refine_result(robo_ctx* ctx, const RefineState& st, unsigned* d_cand_flags, bool sweep_only) {
     hipLaunchKernelGGL(refine_result_kernel, dim3(1), dim3(64), 0, ctx->stream, st, d_cand_flags, sweep_only ? 1 : 0);
     ROBO_LAUNCH_CHECK();
@@ -468,7 +317,7 @@ int launch_refine_result(robo_ctx* ctx, const RefineState& st, unsigned* d_cand_
 
 // ---- the driver ---------------------------------------------------------------------------------------------------------------
 // state + pseudo-row workspace for K starts in D dimensions, kept with the GP like the host-array candidate handle
-static int refine_ensure(robo_gp* g, int K, int D, RefineWork** out) {
+int refine_ensure(robo_gp* g, int K, int D, RefineWork** out) {
     if (g->refine && (g->refine->K != K || g->refine->D != D)) {
         ROBO_HIP_CHECK(hipStreamSynchronize(g->ctx->stream));
         robo_cand_destroy(g->refine->ws);
@@ -489,31 +338,67 @@ static int refine_ensure(robo_gp* g, int K, int D, RefineWork** out) {
     return ROBO_OK;
 }
 
+int refine_check_steps(int32_t n_starts, int32_t n_steps, double step0) {
+    if (n_starts < 1 || n_starts > 1024 || n_steps < 0 || !(step0 > 0.0) || !(step0 <= 0.5)) {
+        set_error("refine: n_starts %d (1 .. 1024), n_steps %d (>= 0), step0 %g (0 < step0 <= 0.5)", n_starts, n_steps, step0);
+        return ROBO_BAD_ARGUMENT;
+    }
+    return ROBO_OK;
+}
+
+int refine_prepare(robo_gp* holder, int n_pad, int K, int T, bool want_trace, RefineWork** out) {
+    robo_ctx* c = holder->ctx;
+    const int D = holder->dim, E = D + 1;
+    const int64_t rows_pad = round_up64((int64_t)K * E, NB);
+    if ((size_t)rows_pad * n_pad * sizeof(double) > workspace_bytes(c)) {
+        set_error("refine: %d starts x %d rows of %d columns exceed the solve workspace (ws_bytes)", K, E, n_pad);
+        return ROBO_BAD_SHAPE;
+    }
+    RefineWork* w = nullptr;
+    ROBO_TRY(refine_ensure(holder, K, D, &w));
+    ROBO_TRY(cand_ensure_workspace(w->ws, n_pad, true));
+    if (want_trace) ROBO_TRY(dev_grow(c->stream, &w->d_trace, &w->trace_cap, refine_trace_len(K, T, D)));
+    w->st.trace = want_trace ? w->d_trace : nullptr;
+    *out = w;
+    return ROBO_OK;
+}
+
+int refine_read_back(robo_cand* k, RefineWork* w, int status, int T, double* out_x, double* out_value,
+                     int64_t* out_start_index, uint32_t* out_flags, int64_t* out_starts, double* out_trace) {
+    const RefineState& st = w->st;
+    const int K = st.K, D = st.D;
+    if (status == ROBO_OK) status = launch_refine_result(k->ctx, st, k->d_flags, T == 0);
+    // read-back: the one synchronisation of the call
+    std::vector<double> h((size_t)D + 4);
+    std::vector<long long> hs(out_starts ? (size_t)K : 0);
+    ROBO_TRY(finish_call(k, "refine", status, {{h.data(), st.out, h.size() * sizeof(double)},
+                                               {hs.data(), st.start, hs.size() * sizeof(long long)},
+                                               {out_trace, w->d_trace, refine_trace_len(K, T, D) * sizeof(double)}}));
+    memcpy(out_x, h.data(), (size_t)D * sizeof(double));
+    if (out_value) *out_value = h[D];
+    long long v;
+    memcpy(&v, &h[D + 1], sizeof(v));
+    if (out_start_index) *out_start_index = (int64_t)v;
+    memcpy(&v, &h[D + 2], sizeof(v));
+    if (out_flags) *out_flags = (uint32_t)v;
+    for (size_t i = 0; i < hs.size(); ++i) out_starts[i] = (int64_t)hs[i];
+    return ROBO_OK;
+}
+
 // marginal: the sweep is robo_acq_eval_marginal_cand's (accumulate, divide); otherwise robo_acq_eval_cand's
 static int refine_core(robo_gp* const* gps, int32_t S, bool marginal, int32_t acq_kind, double par, const double* etas,
                        robo_cand* k, int32_t n_starts, int32_t n_steps, double step0, double* out_x, double* out_value,
                        int64_t* out_start_index, uint32_t* out_flags, int64_t* out_starts, double* out_trace) {
     if (!gps || S < 1 || !etas || !k || !out_x) return ROBO_BAD_ARGUMENT;
     ROBO_TRY(check_acq_kind(acq_kind));
-    if (n_starts < 1 || n_starts > 1024 || n_steps < 0 || !(step0 > 0.0) || !(step0 <= 0.5)) {
-        set_error("refine: n_starts %d (1 .. 1024), n_steps %d (>= 0), step0 %g (0 < step0 <= 0.5)", n_starts, n_steps, step0);
-        return ROBO_BAD_ARGUMENT;
-    }
+    ROBO_TRY(refine_check_steps(n_starts, n_steps, step0));
     ROBO_TRY(ensemble_check("refine", 0, gps, S, k));
     robo_gp* g0 = gps[0];
     robo_ctx* c = g0->ctx;
-    const int K = n_starts, T = n_steps, D = g0->dim, E = D + 1;
-    const int64_t rows_pad = round_up64((int64_t)K * E, NB);
-    if ((size_t)rows_pad * g0->n_pad * sizeof(double) > workspace_bytes(c)) {
-        set_error("refine: %d starts x %d rows of %d columns exceed the solve workspace (ws_bytes)", K, E, g0->n_pad);
-        return ROBO_BAD_SHAPE;
-    }
+    const int K = n_starts, T = n_steps, D = g0->dim;
+    const int64_t rows_pad = round_up64((int64_t)K * (D + 1), NB);
     RefineWork* w = nullptr;
-    ROBO_TRY(refine_ensure(g0, K, D, &w));
-    ROBO_TRY(cand_ensure_workspace(w->ws, g0->n_pad, true));
-    const size_t trace_len = (size_t)(T + 1) * K * (2 * D + 3);
-    if (out_trace) ROBO_TRY(dev_grow(c->stream, &w->d_trace, &w->trace_cap, trace_len));
-    w->st.trace = out_trace ? w->d_trace : nullptr;
+    ROBO_TRY(refine_prepare(g0, g0->n_pad, K, T, out_trace != nullptr, &w));
     const RefineState& st = w->st;
 
     ROBO_TRY(acq_sweep(gps, S, marginal, acq_kind, par, etas, k));
@@ -534,28 +419,11 @@ static int refine_core(robo_gp* const* gps, int32_t S, bool marginal, int32_t ac
     for (int t = 0; status == ROBO_OK && iterate && t <= T; ++t) {
         for (int s = 0; status == ROBO_OK && s < S; ++s) {
             robo_gp* g = gps[s];
-            status = launch_scale_inputs(c, st.y, st.ys, g->d_theta, K, K, D);
-            if (status == ROBO_OK) status = launch_cross_grad(g, st.ys, use_w[s] ? d_rhs : w->ws->d_V, 0, K, rows_pad);
-            if (status == ROBO_OK) status = use_w[s] ? launch_winv_rows(g, w->ws, rows_pad) : launch_trsm(g, w->ws, 0, rows_pad);
+            status = launch_refine_solve(g, w, K, use_w[s] ? d_rhs : nullptr);
             if (status == ROBO_OK) status = launch_refine_eval(g, st, w->ws, acq_kind, par, etas[s], s, S, t, T);
         }
     }
-    if (status == ROBO_OK) status = launch_refine_result(c, st, k->d_flags, T == 0);
-    // read-back: the one synchronisation of the call
-    std::vector<double> h((size_t)D + 4);
-    std::vector<long long> hs(out_starts ? (size_t)K : 0);
-    ROBO_TRY(finish_call(k, "refine", status, {{h.data(), st.out, h.size() * sizeof(double)},
-                                               {hs.data(), st.start, hs.size() * sizeof(long long)},
-                                               {out_trace, w->d_trace, trace_len * sizeof(double)}}));
-    memcpy(out_x, h.data(), (size_t)D * sizeof(double));
-    if (out_value) *out_value = h[D];
-    long long v;
-    memcpy(&v, &h[D + 1], sizeof(v));
-    if (out_start_index) *out_start_index = (int64_t)v;
-    memcpy(&v, &h[D + 2], sizeof(v));
-    if (out_flags) *out_flags = (uint32_t)v;
-    for (size_t i = 0; i < hs.size(); ++i) out_starts[i] = (int64_t)hs[i];
-    return ROBO_OK;
+    return refine_read_back(k, w, status, T, out_x, out_value, out_start_index, out_flags, out_starts, out_trace);
 }
 
 }  // namespace robo

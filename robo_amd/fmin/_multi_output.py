@@ -34,20 +34,20 @@ def _objective_model(model_type, lower, upper, rng, hyper_optimizer, n_restarts,
 
 
 def output_models(n_out, lower, upper, num_iterations, n_init, maximizer, model_type, rng, hyper_optimizer, n_restarts,
-                  chain_length, burnin_steps, acq_name, fused_over):
+                  chain_length, burnin_steps, acq_name, fused_over, maximizers=("random", "device_random")):
     """The shared argument checks, then -> (rng, the n_out models).  ``acq_name`` and ``fused_over`` word the messages: what
-    the maximiser maximises, and whose fused call ``device_random`` needs."""
+    the maximiser maximises, and whose fused call the device maximisers need.  ``maximizers``: the ones the caller allows."""
     assert upper.shape[0] == lower.shape[0], "Dimension miss match"
     assert np.all(lower < upper), "Lower bound >= upper bound"
     assert n_init <= num_iterations, "Number of initial design point has to be <= than the number of iterations"
     if model_type not in ("gp", "gp_mcmc"):
         raise ValueError("'{}' is not a valid model (robo_amd provides 'gp' and 'gp_mcmc')".format(model_type))
-    if maximizer not in ("random", "device_random"):
-        raise ValueError("'{}' is not a valid function to maximize {} ('random' or 'device_random')"
-                         .format(maximizer, acq_name))
-    if maximizer == "device_random" and model_type != "gp":
-        raise ValueError("maximizer='device_random' scores its candidates with the fused call of {}; "
-                         "'gp_mcmc' goes through its mixture moments (use 'random')".format(fused_over))
+    if maximizer not in maximizers:
+        raise ValueError("'{}' is not a valid function to maximize {} ({})"
+                         .format(maximizer, acq_name, " or ".join("'%s'" % m for m in maximizers)))
+    if maximizer != "random" and model_type != "gp":
+        raise ValueError("maximizer='{}' scores its candidates with the fused call of {}; "
+                         "'gp_mcmc' goes through its mixture moments (use 'random')".format(maximizer, fused_over))
     if hyper_optimizer != "host" and model_type == "gp_mcmc":
         raise ValueError("hyper_optimizer='{}' applies to model_type='gp'; 'gp_mcmc' samples its hyper-parameters"
                          .format(hyper_optimizer))

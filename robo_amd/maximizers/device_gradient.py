@@ -7,7 +7,8 @@ the ``n_starts`` best of them climb ``n_steps`` projected gradient steps in lock
 candidates.  Not in the reference, whose gradient-based maximiser (robo/maximizers/scipy_optimizer.py) runs L-BFGS-B with
 finite differences from the host, one 1 x D acquisition call per function value.
 
-A ``ThompsonSampling`` objective is refined on its paths instead (robo_paths_refine_cand): per path the best rows of the
+A ``ConstrainedEI`` climbs on the constrained value (robo_cei_refine_cand), its candidates drawn around the feasible
+incumbent.  A ``ThompsonSampling`` objective is refined on its paths instead (robo_paths_refine_cand): per path the best rows of the
 best groups of candidates descend on the path itself, all in one launch; ``maximize_batch(q)`` -- which only such a
 maximiser has -- returns the q paths' refined minimisers (``ThompsonSampling.select_batch(refine=True)``).
 """
@@ -36,14 +37,17 @@ class DeviceGradientAscent(BaseMaximizer):
     def maximize(self, q=None):
         from robo_amd import _lib
         from robo_amd.acquisition_functions.base_acquisition import ClosedFormAcquisition
+        from robo_amd.acquisition_functions.constrained_ei import ConstrainedEI
         from robo_amd.acquisition_functions.thompson_sampling import ThompsonSampling
         acq = self.objective_func
         inner = getattr(acq, "acquisition_func", acq)
-        if not isinstance(inner, (ClosedFormAcquisition, ThompsonSampling)):
-            raise TypeError("DeviceGradientAscent needs EI, LogEI, PI or LCB (or MarginalizationGPMCMC over one of them): "
-                            "%s has no gradient on the device" % type(inner).__name__)
+        if not isinstance(inner, (ClosedFormAcquisition, ThompsonSampling, ConstrainedEI)):
+            raise TypeError("DeviceGradientAscent needs EI, LogEI, PI or LCB (or MarginalizationGPMCMC over one of them), "
+                            "ConstrainedEI or ThompsonSampling: %s has no gradient on the device" % type(inner).__name__)
         model = acq.model
         sub = model.models[0] if hasattr(model, "models") and len(model.models) > 0 else model
+        if isinstance(inner, ConstrainedEI):       # the objective's context and box, the feasible incumbent (as
+            sub = model.objective                  # DeviceRandomSampling draws for it); refine() checks the constraints' models
         from robo_amd.models.fabolas_gp import FabolasGP      # (its fidelity column is not a box coordinate)
         if not getattr(sub, "normalize_input", False) or not hasattr(sub, "gp") or isinstance(sub, FabolasGP):
             raise TypeError("DeviceGradientAscent needs a robo_amd GaussianProcess model with normalize_input=True")
