@@ -139,6 +139,62 @@ class Posterior(object):
             solve_lower(self.Lf, kernel(self.kind, self.amp, Xb_s, self.Xs, blr=self.blr, dtype=self.dtype).T)
         return kernel(self.kind, self.amp, Xa_s, Xb_s, blr=self.blr, dtype=self.dtype) - Va.T @ Vb
 
+    def grad_loglik(self):
+        """(g, S): the gradient of the log marginal likelihood in the log-space hyper-parameters
+        [ln amp, ln m_d ..., (ln a, ln b,) NOISE], and the magnitude each sum is conditioned by, in the instance's precision:
+            W = L^-1,  alpha = W^T z,  A = alpha alpha^T - W^T W,
+            g_p = 1/2 sum_ij A_ij dK_ij / d theta_p,      S_p = 1/2 sum_ij |A_ij dK_ij / d theta_p|
+        with dK / d theta_p by the formulas of oracle.gp_oracle.kernel_gradient, on the SCALED rows (d r2 / d ln m_d =
+        -(xs_d - xs'_d)^2).  The last entry is 1/2 tr A: the derivative in sigma^2, not in ln sigma^2 (the reference's grad_nll,
+        DESIGN.md "Mirrored quirks").  One dK / d theta_p exists at a time (D = 256 would otherwise hold 256 N x N matrices)."""
+        T = np.dtype(self.dtype).type
+        n = self.K.shape[0]
+        W = solve_lower(self.Lf, np.eye(n, dtype=self.dtype))
+        alpha = W.T @ self.z
+        KI = np.zeros((n, n), dtype=self.dtype)
+        for r0 in range(0, n, 64):                                          # W is lower triangular: rows r0.. reach columns < r0 + 64
+            r1 = min(r0 + 64, n)
+            KI[:r1, :r1] += W[r0:r1, :r1].T @ W[r0:r1, :r1]
+        A = np.outer(alpha, alpha) - KI
+        X = np.asarray(self.Xs).astype(self.dtype)
+        Kc = kernel(self.kind, self.amp, X, blr=self.blr, dtype=self.dtype)  # without the noise on the diagonal
+        g, S = [], []
+
+        def add(dK):
+            t = A * dK
+            g.append(T(0.5) * np.sum(t))
+            S.append(T(0.5) * np.sum(np.abs(t)))
+        add(Kc)                                                             # d / d ln amp
+        fab = self.kind == "fabolas"
+        d_in = X.shape[1] - 1 if fab else X.shape[1]
+        if fab:
+            for d in range(d_in):
+                diff = X[:, d][:, None] - X[:, d][None, :]
+                s = diff * diff
+                t = np.sqrt(T(5) * s)
+                add(Kc * (T(5) / T(6)) * (T(1) + t) * s / (T(1) + t + T(5) * s / T(3)))
+            uu = X[:, -1][:, None] * X[:, -1][None, :]
+            B = T(self.blr[0]) + T(self.blr[1]) * uu
+            add(Kc * T(self.blr[0]) / B)
+            add(Kc * T(self.blr[1]) * uu / B)
+        else:
+            if self.kind == "matern52":
+                r2 = np.zeros((n, n), dtype=self.dtype)
+                for d in range(d_in):
+                    diff = X[:, d][:, None] - X[:, d][None, :]
+                    r2 += diff * diff
+                t = np.sqrt(T(5) * r2)
+                dk = -T(self.amp) * (T(5) / T(6)) * (T(1) + t) * np.exp(-t)   # amp f'(r2)
+            elif self.kind == "rbf":
+                dk = T(-0.5) * Kc
+            else:
+                raise ValueError(self.kind)
+            for d in range(d_in):
+                diff = X[:, d][:, None] - X[:, d][None, :]
+                add(dk * (-(diff * diff)))
+        add(np.eye(n, dtype=self.dtype))                                    # the mirrored quirk: d / d sigma^2
+        return np.array(g, dtype=self.dtype), np.array(S, dtype=self.dtype)
+
     def gradients(self, Xcs, inv_sqrt_metric):
         """(d mean / d x, d variance / d x), each (M, D), at scaled candidate rows, in the UNSCALED input space:
         inv_sqrt_metric (D,) = d xs_d / d x_d (1 for the Fabolas fidelity column).  With v = L^-1 k_*, w_d = L^-1 d k_* / d xs_d:

@@ -756,8 +756,8 @@ def check_fit_batch(ctx, sizes=((60, 3), (300, 4)), kind="matern52"):
 def check_grad_loglik(ctx, cases=(("matern52", 70, 3), ("rbf", 200, 5), ("fabolas", 150, 4), ("matern52", 300, 20),
                                   ("matern52", 650, 2))):
     """robo_gp_grad_loglik == the oracle's restatement of GaussianProcess.grad_nll
-    (robo/models/gaussian_process.py:168-191) for every kernel kind, several block counts (N below,
-    across and well above one 128 block) and D above one 16-dimension staging pass; the GP is left
+    (robo/models/gaussian_process.py:168-191) for every kernel kind, at N = 70, 150, 200, 300 and 650 (none at a block
+    edge: tests/grad_checks.py holds those) and D above one 16-dimension staging pass; the GP is left
     fitted at theta; the call is deterministic (bitwise repeatable)."""
     rs = np.random.RandomState(23)
     for kind, N, D in cases:
