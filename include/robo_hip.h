@@ -120,7 +120,12 @@ int32_t robo_ctx_set_phase_events(robo_ctx* ctx, int32_t on);
  * forms the screen's bounds: -1 = default: the dot-form kernel, whose squared distances come from the fp64 matrix
  * instruction on centred coordinates, for Matern-5/2 and RBF up to D = 32 where the fitted theta's worst-case distance
  * error stays within 1e-12, the direct-difference kernel otherwise; 0 never the dot form; 1 wherever the kind and D permit,
- * whatever the error: tests.  Both give rigorous bounds, so results do not depend on it),
+ * whatever the error: tests.  Both give rigorous bounds, so results do not depend on it), acq_screen_lean (how the dot-form
+ * kernel finishes a pair: -1 = default: the lean finish, which evaluates the covariance to a proven 8e-13 amp and adds 1e4
+ * times that error to the margin, where that term stays within 1e-2 of the prior standard deviation, the finish to the
+ * last bit otherwise; 0 never the lean finish; 1 wherever the dot-form kernel runs: tests.  Rigorous bounds either way),
+ * acq_screen_fused_tail (1 = default: when the screen's survivors fit one block of 256, their output transform, acquisition
+ * values, argmax, index map and report run as one single-workgroup launch; 0: the five launches.  Same bits either way),
  * trsm_chain (small batches on two or more block rows, solved by ONE launch whose block rows hand their tiles to each
  * other instead of one launch per block row, trsm_chain.hip: -1 = default: automatic (from three block rows on, while the
  * launch stays within trsm_chain_max_wg), 0 never, 1 wherever legal (from two block rows on); taken by
@@ -344,6 +349,13 @@ int32_t robo_acq_eval(robo_gp* gp, int32_t acq_kind, double par, double eta, con
 #define ROBO_SCREEN_PROBE_USED 2   /* ... after the incumbent was taken from the exact values of the 128 candidates with the largest upper bounds */
 #define ROBO_SCREEN_FELL_BACK 3    /* too many survivors (or none below the bound): the plain sweep ran on the whole batch */
 int32_t robo_cand_last_screen(robo_cand* cand, int64_t* out_n_screened, int64_t* out_n_survivors, int32_t* out_outcome);
+/* How the last bounds pass on this handle finished its covariances (tuning key acq_screen_lean).  *out_finish: */
+#define ROBO_SCREEN_FINISH_NONE 0  /* no bounds pass yet, or the direct-difference kernel (it has one finish)        */
+#define ROBO_SCREEN_FINISH_FULL 1  /* the dot-form kernel, square root and exponential to the last bit               */
+#define ROBO_SCREEN_FINISH_LEAN 2  /* the dot-form kernel, covariance to 8e-13 amp, that error in the margin           */
+/* *out_fused_tail (may be NULL): 1 when the last argmax-only acquisition call on this handle ran its survivors' output
+ * transform, acquisition, argmax, index map and report as the one single-workgroup launch (acq_screen_fused_tail), else 0. */
+int32_t robo_cand_last_screen_finish(robo_cand* cand, int32_t* out_finish, int32_t* out_fused_tail);
 /* The screen's bounds themselves (soundness tests, A/B tools): out_upper / out_lower (m,) with
  * lower <= the value robo_acq_eval_cand returns for the candidate <= upper; NaN coordinates give NaN bounds.  Needs a
  * (kind, par) the screen handles (LCB: kappa >= 0) and fp64 covariance entries; batch size, tuning keys and the

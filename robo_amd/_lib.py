@@ -27,6 +27,7 @@ KERNEL_KINDS = {"matern52": 0, "rbf": 1, "fabolas": 2}
 ACQ_KINDS = {"ei": 0, "log_ei": 1, "pi": 2, "lcb": 3}
 FLAG_ZERO_SIGMA, FLAG_NEGATIVE_EI, FLAG_NAN, FLAG_NOT_FACTORED, FLAG_FROZEN = 1, 2, 4, 8, 16
 SCREEN_NOT_ELIGIBLE, SCREEN_SCREENED, SCREEN_PROBE_USED, SCREEN_FELL_BACK = 0, 1, 2, 3     # robo_cand_last_screen's outcome
+SCREEN_FINISH_NONE, SCREEN_FINISH_FULL, SCREEN_FINISH_LEAN = 0, 1, 2                          # robo_cand_last_screen_finish
 FANTASY_KINDS = {"kriging_believer": 0, "constant_liar": 1}   # robo_acq_batch_*: how a pick's fantasy target is chosen
 MES_MAX_K = 128                                  # robo_mes_*: cap on the sampled minima per model
 KG_MAX_DISC = 64                                 # robo_kg_*: cap on the discretisation points of the knowledge gradient
@@ -53,7 +54,7 @@ SYMBOLS = [
     "robo_cand_create_random", "robo_cand_create_sobol", "robo_cand_get_point", "robo_cand_workspace_chunk", "robo_cand_last_solve_kernel",
     "robo_gp_predict_cand", "robo_gp_predict", "robo_gp_predict_cov", "robo_gp_predict_grad", "robo_gp_predict_mixture_cand",
     "robo_acq_eval_cand", "robo_acq_eval", "robo_acq_eval_moments", "robo_acq_eval_marginal_cand", "robo_acq_eval_sum_cand",
-    "robo_cand_last_screen", "robo_acq_screen_bounds",
+    "robo_cand_last_screen", "robo_cand_last_screen_finish", "robo_acq_screen_bounds",
     "robo_acq_refine_cand", "robo_acq_refine_marginal_cand",
     "robo_rep_sample", "robo_rep_sample_batch",
     "robo_acq_batch_cand", "robo_acq_batch_marginal_cand",
@@ -219,6 +220,7 @@ def lib():
         "robo_acq_eval_cand": [vp, i32, dbl, dbl, vp, _dp, _dp, C.POINTER(i64), C.POINTER(C.c_uint32)],
         "robo_acq_eval": [vp, i32, dbl, dbl, _dp, i64, _dp, _dp, C.POINTER(i64), C.POINTER(C.c_uint32)],
         "robo_cand_last_screen": [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i32)],
+        "robo_cand_last_screen_finish": [vp, C.POINTER(i32), C.POINTER(i32)],
         "robo_acq_screen_bounds": [vp, i32, dbl, dbl, vp, _dp, _dp],
         "robo_acq_eval_moments": [vp, i32, dbl, dbl, _dp, _dp, i64, _dp, _dp, C.POINTER(i64), C.POINTER(C.c_uint32)],
         "robo_acq_eval_marginal_cand": [pp, i32, i32, dbl, _dp, vp, _dp, _dp, C.POINTER(i64),
@@ -644,6 +646,18 @@ class Candidates(object):
         buf = C.create_string_buffer(128)
         check(lib().robo_cand_last_solve_kernel(self._h, buf, 128))
         return buf.raw.split(b"\0")[1].decode()
+
+    def screen_finish(self):
+        """how the last bounds pass of the acquisition screen on this handle finished its covariances: a SCREEN_FINISH_* value"""
+        f = C.c_int32(0)
+        check(lib().robo_cand_last_screen_finish(self._h, C.byref(f), None))
+        return int(f.value)
+
+    def screen_tail_fused(self):
+        """whether the last argmax-only acquisition call on this handle ran its survivors' tail as the one fused launch"""
+        f, t = C.c_int32(0), C.c_int32(0)
+        check(lib().robo_cand_last_screen_finish(self._h, C.byref(f), C.byref(t)))
+        return bool(t.value)
 
     def last_screen(self):
         """what the last argmax-only acquisition call on this handle did -> (candidates screened, survivors, SCREEN_* outcome)"""

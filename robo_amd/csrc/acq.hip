@@ -12,6 +12,7 @@
 // the launch geometry.
 #include "common.h"
 #include "kern_math.h"
+#include "post_dev.h"
 
 namespace robo {
 
@@ -45,6 +46,28 @@ __device__ __forceinline__ Best block_best(Best x, Best* sh) {
     return r;
 }
 
+// one candidate's acquisition value and the flags it raises
+__device__ __forceinline__ double acq_value(int kind, double mu, double v, double eta, double par, unsigned& f) {
+    double a;
+    if (kind == ROBO_ACQ_EI) {
+        a = acq_ei(mu, v, eta, par);
+        // z*Phi(z) + phi(z) cancels to O(phi/z^2); below DBL_MIN (z < -37.5) the sign of the
+        // rounded sum is libm noise.  Such values are returned as +0 instead of tripping the
+        // reference's `EI < 0 -> ValueError` guard (ei.py:86-88); see DESIGN.md "Conscious fixes".
+        if (a < 0.0 && a > -2.2250738585072014e-308) a = 0.0;
+        if (a < 0.0) f |= ROBO_FLAG_NEGATIVE_EI;
+    } else if (kind == ROBO_ACQ_LOG_EI) {
+        a = acq_log_ei(mu, v, eta, par);
+    } else if (kind == ROBO_ACQ_PI) {
+        a = acq_pi(mu, v, eta, par);
+    } else {
+        a = acq_lcb(mu, v, par);
+    }
+    if (sqrt(v) == 0.0) f |= ROBO_FLAG_ZERO_SIGMA;
+    if (isnan(a)) f |= ROBO_FLAG_NAN;
+    return a;
+}
+
 // mode 0: acq[i] = a         (plain)
 // mode 1: sum[i]  = a        (first hyper-parameter sample)
 // mode 2: sum[i] += a        (next samples; fixed sample order = NumPy's axis-0 accumulation)
@@ -60,24 +83,7 @@ __global__ __launch_bounds__(256) void acq_kernel(const double* __restrict__ mea
     b.i = -1;
     unsigned f = 0;
     if (i < m) {
-        const double mu = mean[i], v = var[i];
-        double a;
-        if (kind == ROBO_ACQ_EI) {
-            a = acq_ei(mu, v, eta, par);
-            // z*Phi(z) + phi(z) cancels to O(phi/z^2); below DBL_MIN (z < -37.5) the sign of the
-            // rounded sum is libm noise.  Such values are returned as +0 instead of tripping the
-            // reference's `EI < 0 -> ValueError` guard (ei.py:86-88); see DESIGN.md "Conscious fixes".
-            if (a < 0.0 && a > -2.2250738585072014e-308) a = 0.0;
-            if (a < 0.0) f |= ROBO_FLAG_NEGATIVE_EI;
-        } else if (kind == ROBO_ACQ_LOG_EI) {
-            a = acq_log_ei(mu, v, eta, par);
-        } else if (kind == ROBO_ACQ_PI) {
-            a = acq_pi(mu, v, eta, par);
-        } else {
-            a = acq_lcb(mu, v, par);
-        }
-        if (sqrt(v) == 0.0) f |= ROBO_FLAG_ZERO_SIGMA;
-        if (isnan(a)) f |= ROBO_FLAG_NAN;
+        const double a = acq_value(kind, mean[i], var[i], eta, par, f);
         if (mode == 0) acq[i] = a;
         else if (mode == 1) acq_sum[i] = a;
         else acq_sum[i] += a;
@@ -145,6 +151,86 @@ __global__ void report_best_kernel(const double* __restrict__ best_val, const lo
     reinterpret_cast<long long*>(host)[1] = *best_idx;
     reinterpret_cast<unsigned*>(host + 2)[0] = *flags;
     *flags = 0u;
+}
+
+// The acquisition screen's tail for survivors that fit one partial block (m_pad <= 256), ONE workgroup: post_kernel, acq_kernel,
+// best_final_kernel, screen_map_best_kernel and, where host != nullptr, report_best_kernel, statement for statement through the
+// same device functions -- the same bits as the five launches.
+__global__ __launch_bounds__(256) void acq_tail_kernel(const double* __restrict__ q, const double* __restrict__ mu,
+                                                       const double* __restrict__ Xcs, double* __restrict__ mean,
+                                                       double* __restrict__ var, double* __restrict__ acq, long long m,
+                                                       long long m_pad, CovParams cp, double mean_c, double y_mean, double y_std,
+                                                       int kind, double par, double eta, double* __restrict__ part_val,
+                                                       long long* __restrict__ part_idx, unsigned* __restrict__ sub_flags,
+                                                       const long long* __restrict__ map, double* __restrict__ best_val,
+                                                       long long* __restrict__ best_idx, unsigned* __restrict__ flags,
+                                                       double* __restrict__ host) {
+    __shared__ Best sh[4];
+    __shared__ unsigned sf;
+    const long long i = threadIdx.x;
+    if (threadIdx.x == 0) sf = 0u;
+    __syncthreads();
+    Best b;
+    b.v = 0.0;
+    b.i = -1;
+    unsigned f = 0;
+    if (i < m_pad) {
+        double pm, pv;
+        post_point(q[i], mu[i], Xcs[i * cp.dim + cp.dim - 1], cp, mean_c, y_mean, y_std, pm, pv);
+        mean[i] = pm;
+        var[i] = pv;
+        if (i < m) {
+            const double a = acq_value(kind, pm, pv, eta, par, f);
+            acq[i] = a;
+            b.v = a;
+            b.i = i;
+        }
+    }
+    if (f != 0) atomicOr(&sf, f);
+    const Best r = block_best(b, sh);
+    if (threadIdx.x == 0) {
+        part_val[0] = r.v;
+        part_idx[0] = r.i;
+    }
+    __syncthreads();
+    // best_final_kernel over the one partial
+    Best b2;
+    b2.v = 0.0;
+    b2.i = -1;
+    if (threadIdx.x == 0) {
+        Best c;
+        c.v = r.v;
+        c.i = r.i;
+        if (better(c, b2)) b2 = c;
+    }
+    const Best r2 = block_best(b2, sh);
+    if (threadIdx.x != 0) return;
+    part_val[1] = r2.v;
+    part_idx[1] = r2.i;
+    // screen_map_best_kernel, report_best_kernel
+    const long long bi = r2.i < 0 ? r2.i : map[r2.i];
+    const unsigned fl = *flags | *sub_flags | sf;
+    *best_val = r2.v;
+    *best_idx = bi;
+    *sub_flags = 0u;
+    if (host) {
+        host[0] = r2.v;
+        reinterpret_cast<long long*>(host)[1] = bi;
+        reinterpret_cast<unsigned*>(host + 2)[0] = fl;
+        *flags = 0u;
+    } else {
+        *flags = fl;
+    }
+}
+
+int launch_acq_tail(robo_gp* gp, robo_cand* s, int acq_kind, double par, double eta, const long long* d_map, robo_cand* k,
+                    double* h_report) {
+    hipLaunchKernelGGL(acq_tail_kernel, dim3(1), dim3(256), 0, gp->ctx->stream, (const double*)s->d_q, (const double*)s->d_mu,
+                       (const double*)s->d_Xcs, s->d_mean, s->d_var, s->d_acq, (long long)s->m, (long long)s->m_pad, gp->cov,
+                       gp->mean_c, gp->y_mean, gp->y_std, acq_kind, par, eta, s->d_part_val, s->d_part_idx, s->d_flags, d_map,
+                       k->d_part_val + k->n_part, k->d_part_idx + k->n_part, k->d_flags, h_report);
+    ROBO_LAUNCH_CHECK();
+    return ROBO_OK;
 }
 
 int launch_report_best(robo_cand* cand, double* h_pinned) {

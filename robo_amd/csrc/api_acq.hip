@@ -30,7 +30,9 @@ int acq_read_back(robo_cand* k, const double* d_vec, double* out_vec, double* ou
                          uint32_t* out_flags) {
     robo_ctx* c = k->ctx;
     double* hp = c->h_pinned;
-    ROBO_TRY(launch_report_best(k, hp));   // (max, argmax, flags) -> pinned memory; clears the flag word
+    // (max, argmax, flags) -> pinned memory; clears the flag word (the screen's fused tail has done both already)
+    if (!k->best_reported) ROBO_TRY(launch_report_best(k, hp));
+    k->best_reported = false;
     if (out_vec)
         ROBO_HIP_CHECK(hipMemcpyAsync(out_vec, d_vec, (size_t)k->m * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     ROBO_HIP_CHECK(hipStreamSynchronize(c->stream));
@@ -352,7 +354,7 @@ int32_t robo_acq_eval_cand(robo_gp* g, int32_t acq_kind, double par, double eta,
     // the chained solve's time-out word is looked at behind the read-back's synchronisation: a launch that gave up (it never
     // should) turns the chain off for the context, and the second pass runs the launches
     for (int pass = 0;; ++pass) {
-        int st = acq_sweep_best(g, acq_kind, par, eta, k, out_acq != nullptr, true);
+        int st = acq_sweep_best(g, acq_kind, par, eta, k, out_acq != nullptr, true, k->ctx->h_pinned);
         if (st == ROBO_CHAIN_RETRY && pass == 0) continue;
         ROBO_TRY(st);
         st = acq_read_back(k, k->d_acq, out_acq, out_max, out_argmax, out_flags);

@@ -65,6 +65,8 @@ static const TuneKey TUNE_KEYS[] = {
     {"acq_screen_min", &Tuning::acq_screen_min, nullptr, -1},
     {"acq_screen_keep_max", nullptr, &Tuning::acq_screen_keep_max, 25},
     {"acq_screen_dot", nullptr, &Tuning::acq_screen_dot, -1},
+    {"acq_screen_lean", nullptr, &Tuning::acq_screen_lean, -1},
+    {"acq_screen_fused_tail", nullptr, &Tuning::acq_screen_fused_tail, 1},
     {"trsm_chain", nullptr, &Tuning::trsm_chain, -1},
     {"trsm_chain_max_wg", nullptr, &Tuning::trsm_chain_max_wg, 4},
     {"trsm_chain_spin_limit", &Tuning::trsm_chain_spin_limit, nullptr, -1},

@@ -80,8 +80,10 @@ int acq_sweep(robo_gp* const* gps, int32_t S, bool marginal, int32_t acq_kind, d
 // allow_chain (see predict_core): also for the survivors and the probe.  ROBO_CHAIN_RETRY: the probe's solve gave up at the
 // synchronisation behind it -- the caller repeats the call.
 constexpr int ROBO_CHAIN_RETRY = 0x7C01;     // internal: never leaves the library
+// h_report != nullptr: the caller's next step is acq_read_back(k, ...) into that pinned block; a screened call whose tail is
+// fused writes the report there itself and sets k->best_reported
 int acq_sweep_best(robo_gp* g, int32_t acq_kind, double par, double eta, robo_cand* k, bool want_values,
-                   bool allow_chain = false);
+                   bool allow_chain = false, double* h_report = nullptr);
 // the samples of an ensemble call against the candidates, then hipSetDevice.  `label` opens the messages.
 constexpr unsigned ENSEMBLE_MES_VERDICTS = 1;      // an unfitted sample is ROBO_BAD_ARGUMENT naming the sample; no shape checks
 constexpr unsigned ENSEMBLE_ONE_KIND_FP64 = 2;     // every sample has the first one's kernel kind and fp64 covariance entries

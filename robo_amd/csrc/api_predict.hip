@@ -148,7 +148,7 @@ int predict_scaled(robo_gp* g, robo_cand* k, bool winv, const std::function<int(
         if (ev) ROBO_TRY(record_phase(g->ctx, EV_PREDICT_SOLVE_END));
         if (after_chunk) ROBO_TRY(after_chunk(c0, cn));
     }
-    ROBO_TRY(launch_post(g, k, 0, k->m_pad));
+    if (!k->defer_post) ROBO_TRY(launch_post(g, k, 0, k->m_pad));
     if (ev) ROBO_TRY(record_phase(g->ctx, EV_PREDICT_END));
     return ROBO_OK;
 }

@@ -237,6 +237,11 @@ struct Tuning {
     int acq_screen_dot;          // ... with the bounds pass's squared distances from the matrix pipe (screen_bounds_dot_kernel): -1
                                  // (default) where the fitted theta's worst-case r2 error stays within SCREEN_DOT_BOUND, 0 never,
                                  // 1 wherever the kind and D permit, whatever the bound (tests)
+    int acq_screen_lean;         // ... and that kernel's pairs finished to SD_LEAN_EPS amp instead of to the last bit: -1 (default)
+                                 // where the term this adds to delta stays within SCREEN_LEAN_MAX of the prior standard
+                                 // deviation, 0 never, 1 wherever the dot kernel runs (tests)
+    int acq_screen_fused_tail;   // ... survivors that fit one partial block: output transform, acquisition, argmax, index map and
+                                 // report in ONE single-workgroup launch (1, default); 0: the five launches (tests, A/B)
     int trsm_chain;              // small batches on >= 2 block rows: all block rows in ONE launch chained by hand-offs (trsm_chain.hip)
                                  // from the entry points that look at its time-out word: -1 auto (>= 3 block rows, within
                                  // trsm_chain_max_wg), 0 never, 1 wherever legal
@@ -550,6 +555,7 @@ struct robo_gp {
     // then, for the kinds and D the dot-form bounds kernel takes, its per-fit inputs (screen.hip "The dot form")]
     double* d_alpha;
     double dot_extent;              // sum_d max_j (x_jd - centre_d)^2 of the scaled training rows alpha was computed for
+    double dot_alpha_sum;           // sum_j |alpha_j| of the same fit (the lean finish's rule)
     unsigned long long alpha_gen;   // fit_gen alpha was computed for (0: none)
     unsigned long long screen_gen;  // fit_gen the back-off below belongs to
     int screen_skip, screen_backoff;   // eligible calls still to pass unscreened after a failed screen; length of the next pause
@@ -607,10 +613,16 @@ struct robo_cand {
     int64_t scr_n, scr_kept;        // robo_cand_last_screen: candidates screened, survivors
     int scr_outcome;
     const char* scr_bounds_kernel;  // name of the kernel that ran the last bounds pass on this handle (diagnostics: tests)
+    int scr_finish;                 // ... and its finish: ROBO_SCREEN_FINISH_* (robo_cand_last_screen_finish)
+    bool scr_tail_fused;            // the last argmax-only call ran its survivors' tail as acq_tail_kernel (same accessor)
     // the chained solve (trsm_chain.hip), lazy, grows: [ticket | time-out | progress words] zeroed per launch, then the
     // per-(tile, block row) partial sums
     char* d_chain;
     size_t chain_bytes;
+    bool defer_post;                // predict_scaled leaves the output transform to the caller's next launch (the screen's fused tail)
+    bool best_reported;             // (max, argmax, flags) are in the context's pinned block already: acq_read_back launches no report
+    size_t chain_cleared;           // bytes at d_chain's head that a kernel queued on the stream has zeroed for the NEXT chained
+                                    // launch (the screen's gather); 0: none, launch_predict_chain runs its memset
 };
 
 namespace robo {
@@ -628,7 +640,7 @@ inline int record_phase(robo_ctx* c, int slot) {
 namespace robo {
 int launch_scale_inputs(robo_ctx* ctx, const double* d_in, double* d_out, const double* d_inv_sqrt_metric,
                         int64_t rows_real, int64_t rows_pad, int dim, int S = 1, size_t out_stride = 0,
-                        size_t ism_stride = 0);
+                        size_t ism_stride = 0, unsigned long long* d_word = nullptr, unsigned long long word_value = 0);
 // the fit pipeline on S matrices at once (S = 1: the GP's own buffers)
 struct FitBuffers {
     double* K; size_t k_stride;          // (n_pad x n_pad) per sample
@@ -701,6 +713,7 @@ int launch_predict_fused(robo_gp* gp, robo_cand* cand, int64_t c0, int64_t cn);
 // words after a synchronisation of the stream (true: a launch gave up -- the caller repeats its call, which runs the launches)
 bool chain_wanted(const robo_gp* gp, int64_t cn);
 int launch_predict_chain(robo_gp* gp, robo_cand* cand, int64_t c0, int64_t cn);
+int chain_state_ensure(const robo_gp* gp, robo_cand* cand, int64_t cn, size_t* state_bytes_out);
 bool chain_timed_out(robo_ctx* ctx);
 int launch_pack_linv(robo_gp* gp);
 int launch_grad_loglik(robo_gp* gp, double* d_V, double* d_A, double* d_alpha, double* d_part, double* d_out,
@@ -756,6 +769,8 @@ int launch_batch_condition(robo_gp* gp, const BatchState& st, const robo_cand* c
 int launch_acq(robo_ctx* ctx, robo_cand* cand, int acq_kind, double par, double eta, bool accumulate, bool first);
 int launch_argmax(robo_cand* cand, const double* d_vals, double scale);
 int launch_report_best(robo_cand* cand, double* h_pinned);
+int launch_acq_tail(robo_gp* gp, robo_cand* s, int acq_kind, double par, double eta, const long long* d_map, robo_cand* k,
+                    double* h_report);
 // batch.hip: beta = L^-T v for ONE right-hand side by backward block rows with the fit's inverted diagonal blocks (v is consumed)
 int launch_bwd_rows(robo_gp* gp, double* d_v, double* d_beta, const int* d_stop = nullptr);   // *d_stop != 0: no-op
 int launch_cov(robo_gp* gp, robo_cand* cand, double* d_cov);

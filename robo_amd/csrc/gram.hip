@@ -20,7 +20,10 @@ namespace robo {
 __global__ __launch_bounds__(256) void scale_inputs_kernel(const double* __restrict__ in, double* __restrict__ out,
                                                            const double* __restrict__ inv_sqrt_m, long long rows_real,
                                                            long long rows_pad, int dim, size_t out_stride,
-                                                           size_t ism_stride) {
+                                                           size_t ism_stride, unsigned long long* __restrict__ word,
+                                                           unsigned long long word_value) {
+    // a word the kernels behind this one start from (the acquisition screen's running maximum): no launch of its own
+    if (word && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *word = word_value;
     out += (size_t)blockIdx.y * out_stride;          // batch coordinate: one scaling per theta
     inv_sqrt_m += (size_t)blockIdx.y * ism_stride;
     const long long total = rows_pad * dim;
@@ -251,13 +254,15 @@ __global__ __launch_bounds__(256) void cross_gram_kernel(const double* __restric
 }
 
 int launch_scale_inputs(robo_ctx* ctx, const double* d_in, double* d_out, const double* d_inv_sqrt_metric,
-                        int64_t rows_real, int64_t rows_pad, int dim, int S, size_t out_stride, size_t ism_stride) {
+                        int64_t rows_real, int64_t rows_pad, int dim, int S, size_t out_stride, size_t ism_stride,
+                        unsigned long long* d_word, unsigned long long word_value) {
     const long long total = (long long)rows_pad * dim;
     int blocks = (int)((total + 255) / 256);
     if (blocks > 4096) blocks = 4096;
     if (blocks < 1) blocks = 1;
     hipLaunchKernelGGL(scale_inputs_kernel, dim3(blocks, S), dim3(256), 0, ctx->stream, d_in, d_out,
-                       d_inv_sqrt_metric, (long long)rows_real, (long long)rows_pad, dim, out_stride, ism_stride);
+                       d_inv_sqrt_metric, (long long)rows_real, (long long)rows_pad, dim, out_stride, ism_stride, d_word,
+                       word_value);
     ROBO_LAUNCH_CHECK();
     return ROBO_OK;
 }

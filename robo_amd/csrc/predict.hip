@@ -17,6 +17,7 @@
 // MFMA flops per candidate: n_pad^2 - n_pad*128 + 72 n_pad.
 #include "common.h"
 #include "gemm_f64.h"
+#include "post_dev.h"
 #include "kern_math.h"
 #include "trsm_small.h"
 
@@ -649,12 +650,8 @@ __global__ __launch_bounds__(256) void post_kernel(const double* __restrict__ q,
                                                    double mean_c, double y_mean, double y_std) {
     const long long i = c0 + (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= c0 + cn) return;
-    double m = mu[i] + mean_c;
-    double v = cov_self(cp, Xcs[i * cp.dim + cp.dim - 1]) - q[i];
-    m = m * y_std + y_mean;
-    v = v * (y_std * y_std);
-    const double eps = 2.220446049250313e-16;
-    v = v < eps ? eps : v;   // np.clip(var, eps, inf); NaN propagates like np.clip
+    double m, v;
+    post_point(q[i], mu[i], Xcs[i * cp.dim + cp.dim - 1], cp, mean_c, y_mean, y_std, m, v);
     mean[i] = m;
     var[i] = v;
 }

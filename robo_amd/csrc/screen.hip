@@ -75,6 +75,47 @@
 //   is at most SCREEN_DOT_BOUND = GRAM_DIRECT_BOUND = 1e-12.  Measured (tests/test_acq_screen_dot.py): at that bound the
 //   largest |mu~ - mu_sweep| stays below 1e-4 of the delta the kernel applies; the headline theta gives 8.4e-15.  The direct
 //   kernel keeps Fabolas, D above the limit and every theta beyond the bound (ln m = -10 at the prior's edge).
+//
+// The lean finish (screen_dot_finish_lean; Matern-5/2 and RBF, the dot kernel only).  The finish above evaluates sqrt and exp
+// to the last bit (35 fp64 VALU instructions per pair, 26 of them sqrt + exp) for a mean whose margin is 1e-11 sum |alpha|.
+// The lean finish evaluates k~ with  |k~ - k| <= SD_LEAN_EPS amp,  SD_LEAN_EPS = 8e-13  (27 instructions), and candidate c's
+// delta gains   SCREEN_LEAN_SAFETY SD_LEAN_EPS |y_std| sum_j |amp alpha_j|,   SCREEN_LEAN_SAFETY = 1e4: with a true bound
+// the mean moves by at most 1e-4 of the delta applied, the ratio tests/test_acq_screen_dot.py asserts.
+//   Error of that k~, in units of amp, u = 2^-53.  Matern-5/2: k = q e^-s, q = 1 + s + t / 3, s = sqrt(t), t = 5 r2; RBF: q = 1,
+//   x = -r2 / 2.  The error of r2 itself is the dot form's term above; here t (x) is taken as given.
+//     seed       y0 = rsq(t) = (1 + d) / sqrt(t).  e = 1 - t y0^2 = -2 d - d^2, and  y0 (1 + e / 2 + 3 e^2 / 8)  is 1 / sqrt(t)
+//                up to (5 / 16) |e|^3 (1 + |e|): the 0.375 e term is KEPT, only the residual step  s += (t - s^2) y / 2  is
+//                dropped.  The proof needs |d| <= 2^-18 of the seed.  No figure of the ISA manual is cited for that: the form is
+//                chosen so as not to depend on one (kern_math.h takes v_rsq_f64 as ~2^-23, 32 times better, and the MI355X
+//                twin of the finish test reproduces the interpreter's error to four digits): then |e| <= 7.7e-6 and the truncation is 1.5e-16.  Roundings: t y0, e (absolute u: it enters
+//                times y0 / 2), y0 e, the inner and the outer FMA, s = t y:  s~ = s (1 + rho), |rho| <= 4 u + 1.5e-16 < 6e-16.
+//     its effect q is formed from the same s~, so  k~(s~) = (1 + s~ + t / 3) e^-s~  and  |d k~ / d ln s| = s^2 (1 + s / 3) e^-s
+//                <= 0.942 (at s = sqrt 6):  0.942 rho < 5.7e-16.
+//     q          1 + s~ and the FMA: 2 u q; the constant 1/3: u t / 3 <= u q.  With k <= 1:  3 u = 3.4e-16.
+//     reduction  n = rint(x log2 e); r = fma(n, -L, x) with ONE constant
+//                L = 0x1.62e42fefa39efp-1, |L - ln 2| = 2.32e-17, so r is off by |n| 2.32e-17 + u |r|: relative in e^x.
+//                |n| <= |x| / ln 2 + 1/2 and  k |x| <= max_s s q e^-s = 1.18:  < 1.18 / ln 2 x 2.32e-17 + u < 2e-16 in k.
+//                |r| <= ln 2 / 2 (1 + 2^-40): the rounding of x log2 e moves the tie by |x| u <= 8e-14.
+//     polynomial degree 8, Remez for the relative error of e^r on |r| <= (ln 2 / 2)(1 + 1e-3), coefficients rounded to
+//                double, evaluated with fp64 FMA Horner steps on 2e6 points against long double: 7.8153e-13 (the fit's
+//                levelled error 7.8142e-13; tools/exp_lean_coeffs.py prints both, and 1.4e-14 for degree 9, 5.4e-11 for 7).
+//                That figure is SAMPLED, not a maximum over the interval: neighbouring points lie h = 3.5e-7 apart, and the
+//                error's derivative is (p' - p) e^-r with |p' - p| <= 6e-9 (the degree-8 truncation term r^8 / 8!, 5.2e-9 at
+//                the edge, plus the fit's 1e-12), so between two points it moves by at most 2.1e-15: <= 7.84e-13.
+//                Relative in e^x, and q e^x <= 1.
+//     2^n        v_ldexp_f64, as in the full finish: exact down to the subnormals (there off by <= 2^-1075) and 0 below them by
+//                itself, so a far candidate gives k~ = 0 or a subnormal times q, never a large number; no clamp of x is needed
+//                (with |x| > 745 both k and k~ are below 1e-300 whatever r is).  The lower clamp of t (x) is the full finish's.
+//                (t = inf or NaN: k~ is NaN, and so is the candidate's norm term of delta: a survivor, as above.)
+//     product    q times p 2^n: u.
+//   Sum: 7.84e-13 + 5.7e-16 + 3.4e-16 + 2e-16 + 1.2e-16 < 7.86e-13 < SD_LEAN_EPS.  Measured (tests/test_acq_screen_lean.py,
+//   N = 1 so that the mean is one product): 7.81e-13 (Matern-5/2), 7.28e-13 (RBF), interpreter and MI355X alike.
+//   The rule (screen_lean_wanted).  acq_screen_lean: -1 the rule, 0 never, 1 wherever the dot kernel runs.  Under the rule the
+//   lean finish runs where its term is at most SCREEN_LEAN_MAX = 1e-2 of the prior standard deviation |y_std| sqrt(amp),
+//       SCREEN_LEAN_SAFETY SD_LEAN_EPS sqrt(amp) sum_j |alpha_j| <= 1e-2        (sum_j |alpha_j| <= 1.25e6 at amp = 1)
+//   -- U_c falls by at most delta while the prior variance it is taken at is loose by orders more.  The headline's fit gives
+//   2.7e-3, config 2's 1.4e-3; a nearly singular K (tiny noise, long length scales) takes the full finish, whose kernel and
+//   delta are the previous ones bit for bit.  sum_j |alpha_j| reaches the host in alpha_ensure's one copy per fit_gen.
 #include <cmath>
 
 #include "api_internal.h"
@@ -144,6 +185,30 @@ __device__ __forceinline__ void screen_bounds(int kind, double par, double eta, 
     }
 }
 
+// ---- b = max_c L_c, formed inside both bounds kernels (NaN ignored; -inf when there is none) -----------------------------------
+// One maximum per workgroup, one atomicMax per workgroup on an order-preserving 64-bit key of the double; the slot is set to the
+// key of -inf by the scale_inputs launch that precedes the pass.  A maximum does not depend on order: b keeps its bits.
+__device__ __forceinline__ unsigned long long screen_key(double x) {
+    const unsigned long long u = (unsigned long long)__double_as_longlong(x);
+    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double screen_unkey(unsigned long long k) {
+    return __longlong_as_double((long long)((k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k));
+}
+constexpr unsigned long long SCREEN_KEY_NONE = 0x000FFFFFFFFFFFFFull;      // screen_key(-inf)
+
+__device__ __forceinline__ double screen_block_max(double x, double* sh) {
+    for (int o = 32; o > 0; o >>= 1) {
+        const double y = __shfl_xor(x, o);
+        x = y > x ? y : x;
+    }
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = x;
+    __syncthreads();
+    double r = sh[0];
+    for (int w = 1; w < 4; ++w) r = sh[w] > r ? sh[w] : r;
+    return r;
+}
+
 // ---- the bounds pass -------------------------------------------------------------------------------------------------------
 // SIBLING of batch_cond_kernel (batch.hip): the same staging, SMALLD split and pair loop -- change the two together.  A
 // workgroup owns 64 candidates, one per lane; its four waves split every
@@ -156,7 +221,7 @@ __global__ __launch_bounds__(256) void screen_bounds_kernel(const double* __rest
                                                             const double* __restrict__ alpha_norm, CovParams cp, int n,
                                                             long long m, double mean_c, double y_mean, double y_std,
                                                             int acq_kind, double par, double eta, double* __restrict__ up,
-                                                            double* __restrict__ lo) {
+                                                            double* __restrict__ lo, unsigned long long* __restrict__ bkey) {
     __shared__ double sX[16 * SC_LD];
     __shared__ double sA[NB];
     __shared__ double sP[4][SC_CAND];
@@ -214,17 +279,27 @@ __global__ __launch_bounds__(256) void screen_bounds_kernel(const double* __rest
     }
     sP[wave][lane] = dot;
     __syncthreads();
-    if (wave != 0 || !live) return;
-    const double mu = (sP[0][lane] + sP[1][lane]) + (sP[2][lane] + sP[3][lane]);
-    const double kself = cov_self(cp, Xcs[i * D + D - 1]);
-    double mt = mu + mean_c;
-    mt = mt * y_std + y_mean;
-    const double v_prior = kself * (y_std * y_std);
-    const double delta = SCREEN_DELTA_REL * (fabs(y_mean) + fabs(y_std) * (fabs(mean_c) + sqrt(fabs(kself)) * alpha_norm[0]));
-    double u, l;
-    screen_bounds(acq_kind, par, eta, mt, delta, v_prior, u, l);
-    up[i] = u;
-    lo[i] = l;
+    if (wave != 0) return;
+    double lmax = -__builtin_huge_val();
+    if (live) {
+        const double mu = (sP[0][lane] + sP[1][lane]) + (sP[2][lane] + sP[3][lane]);
+        const double kself = cov_self(cp, Xcs[i * D + D - 1]);
+        double mt = mu + mean_c;
+        mt = mt * y_std + y_mean;
+        const double v_prior = kself * (y_std * y_std);
+        const double delta = SCREEN_DELTA_REL * (fabs(y_mean) + fabs(y_std) * (fabs(mean_c) + sqrt(fabs(kself)) * alpha_norm[0]));
+        double u, l;
+        screen_bounds(acq_kind, par, eta, mt, delta, v_prior, u, l);
+        up[i] = u;
+        lo[i] = l;
+        if (!isnan(l)) lmax = l;
+    }
+    // the workgroup's 64 candidates live in wave 0
+    for (int o = 32; o > 0; o >>= 1) {
+        const double y = __shfl_xor(lmax, o);
+        lmax = y > lmax ? y : lmax;
+    }
+    if (lane == 0) atomicMax(bkey, screen_key(lmax));
 }
 
 // ---- the bounds pass, dot form ------------------------------------------------------------------------------------------------
@@ -374,6 +449,57 @@ __device__ __forceinline__ void screen_dot_finish(const v4d acc, double nc, cons
     }
 }
 
+// The lean finish (header: "The lean finish"): the same covariance to SD_LEAN_EPS amp, not to the last bit.  One third-order
+// correction of the rsq seed and no residual step, one ln 2 constant, degree 8 (tools/exp_lean_coeffs.py printed the literals).
+// rint / cvt / ldexp stay: the add-and-subtract constant for n with an integer add into the exponent word for 2^n (and the
+// clamp of x that form needs) was built and measured no faster (NOTES.md "The screen's lean finish and folded launches").
+constexpr double SD_LEAN_EPS = 8e-13;
+constexpr double SCREEN_LEAN_SAFETY = 1e4;
+constexpr double SCREEN_LEAN_MAX = 1e-2;      // of the prior standard deviation: the most the lean term may add to delta
+template <int KIND>
+__device__ __forceinline__ void screen_dot_finish_lean(const v4d acc, double nc, const double* __restrict__ al, double (&dot)[4]) {
+    double x[4], q[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        if (KIND == ROBO_KERNEL_MATERN52_ARD) {
+            const double t = fmax(fma(5.0, acc[r], nc), 5.0 * SD_R2_MIN);
+            double y = __builtin_amdgcn_rsq(t);
+            const double e = fma(-t * y, y, 1.0);
+            y = fma(y * e, fma(e, 0.375, 0.5), y);
+            const double s = t * y;
+            x[r] = -s;
+            q[r] = fma(t, 1.0 / 3.0, 1.0 + s);
+        } else {
+            x[r] = fmin(fma(-0.5, acc[r], nc), -0.5 * SD_R2_MIN);
+            q[r] = 1.0;
+        }
+    }
+    double nn[4], rr[4], p[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        nn[r] = rint(x[r] * 1.4426950408889634074);
+        rr[r] = fma(nn[r], -6.93147180559945286e-01, x[r]);
+        p[r] = 2.47270673012491639e-05;
+    }
+#define ROBO_SD_HORNER(C)                                     \
+    _Pragma("unroll") for (int r = 0; r < 4; ++r) p[r] = fma(p[r], rr[r], C)
+    ROBO_SD_HORNER(1.99155698002864343e-04);
+    ROBO_SD_HORNER(1.38891798039418699e-03);
+    ROBO_SD_HORNER(8.33326676781509339e-03);
+    ROBO_SD_HORNER(4.16666642053601585e-02);
+    ROBO_SD_HORNER(1.66666668867537560e-01);
+    ROBO_SD_HORNER(5.00000000062317818e-01);
+    ROBO_SD_HORNER(9.99999999980468957e-01);
+    ROBO_SD_HORNER(9.99999999999759970e-01);
+#undef ROBO_SD_HORNER
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        double kv = ldexp(p[r], (int)nn[r]);
+        if (KIND == ROBO_KERNEL_MATERN52_ARD) kv *= q[r];
+        dot[r] = fma(kv, al[r], dot[r]);
+    }
+}
+
 constexpr int SD_CAND = 64;          // candidates per workgroup: one MFMA column tile of 16 per wave
 constexpr int SD_STAGE = NB;         // training rows per LDS stage: 8 row tiles, swept by every wave
 
@@ -381,13 +507,14 @@ constexpr int SD_STAGE = NB;         // training rows per LDS stage: 8 row tiles
 // and norms, alpha_norm = the block [sum_j |alpha_j| sqrt(k_jj), sum_j |alpha_j|, max_j |b_j|^2, -, centre].  A wave holds its 16
 // candidates' centred coordinates as the B operand for the whole sweep; a lane owns 4 training rows x 1 candidate of every
 // 16 x 16 pair tile and finishes the tile while the matrix pipe forms the next one.
-template <int KIND, int KS>
+template <int KIND, int KS, bool LEAN>
 __global__ __launch_bounds__(256) void screen_bounds_dot_kernel(const double* __restrict__ Xcs, const double* __restrict__ Xs,
                                                                 const double* __restrict__ alpha,
                                                                 const double* __restrict__ alpha_norm, CovParams cp, int n,
                                                                 long long m, double mean_c, double y_mean, double y_std,
                                                                 int acq_kind, double par, double eta, double* __restrict__ up,
-                                                                double* __restrict__ lo) {
+                                                                double* __restrict__ lo, unsigned long long* __restrict__ bkey) {
+    __shared__ double sMx[4];
     constexpr int TILES = SD_STAGE / 16, STAGE_DOUBLES = TILES * KS * 64, PER = STAGE_DOUBLES / 256;
     __shared__ double sA[STAGE_DOUBLES];
     __shared__ __attribute__((aligned(32))) double sAN[2 * SD_STAGE];      // amp alpha | norms of the stage's rows
@@ -438,7 +565,8 @@ __global__ __launch_bounds__(256) void screen_bounds_dot_kernel(const double* __
 #pragma unroll
                 for (int kk = 0; kk < KS; ++kk) nxt = mfma_f64(sA[((t + 1) * KS + kk) * 64 + lane], b[kk], nxt);
             }
-            screen_dot_finish<KIND>(acc, ncf, sAl + t * 16 + g * 4, dot);
+            if (LEAN) screen_dot_finish_lean<KIND>(acc, ncf, sAl + t * 16 + g * 4, dot);
+            else screen_dot_finish<KIND>(acc, ncf, sAl + t * 16 + g * 4, dot);
             acc = nxt;
         }
     }
@@ -446,49 +574,25 @@ __global__ __launch_bounds__(256) void screen_bounds_dot_kernel(const double* __
     double mu = (dot[0] + dot[1]) + (dot[2] + dot[3]);
     mu += __shfl_xor(mu, 16);
     mu += __shfl_xor(mu, 32);
-    if (g != 0 || !live) return;
-    const double kself = cp.amp;
-    double mt = mu + mean_c;
-    mt = mt * y_std + y_mean;
-    const double v_prior = kself * (y_std * y_std);
-    const double ck = KIND == ROBO_KERNEL_MATERN52_ARD ? 5.0 / 6.0 : 0.5;
-    const double r2_err = (double)(4 * KS + 6) * 4.44089209850062616e-16 * (nc + alpha_norm[2]);
-    const double delta = SCREEN_DELTA_REL * (fabs(y_mean) + fabs(y_std) * (fabs(mean_c) + sqrt(fabs(kself)) * alpha_norm[0])) +
-                         SCREEN_DOT_SAFETY * fabs(y_std) * fabs(cp.amp) * ck * r2_err * alpha_norm[1];
-    double u, l;
-    screen_bounds(acq_kind, par, eta, mt, delta, v_prior, u, l);
-    up[i] = u;
-    lo[i] = l;
-}
-
-// ---- b = max_c L_c (NaN ignored; -inf when there is none) ---------------------------------------------------------------------
-__device__ __forceinline__ double screen_block_max(double x, double* sh) {
-    for (int o = 32; o > 0; o >>= 1) {
-        const double y = __shfl_xor(x, o);
-        x = y > x ? y : x;
+    double lmax = -__builtin_huge_val();
+    if (g == 0 && live) {
+        const double kself = cp.amp;
+        double mt = mu + mean_c;
+        mt = mt * y_std + y_mean;
+        const double v_prior = kself * (y_std * y_std);
+        const double ck = KIND == ROBO_KERNEL_MATERN52_ARD ? 5.0 / 6.0 : 0.5;
+        const double r2_err = (double)(4 * KS + 6) * 4.44089209850062616e-16 * (nc + alpha_norm[2]);
+        double delta = SCREEN_DELTA_REL * (fabs(y_mean) + fabs(y_std) * (fabs(mean_c) + sqrt(fabs(kself)) * alpha_norm[0])) +
+                       SCREEN_DOT_SAFETY * fabs(y_std) * fabs(cp.amp) * ck * r2_err * alpha_norm[1];
+        if (LEAN) delta += SCREEN_LEAN_SAFETY * SD_LEAN_EPS * fabs(y_std) * fabs(cp.amp) * alpha_norm[1];
+        double u, l;
+        screen_bounds(acq_kind, par, eta, mt, delta, v_prior, u, l);
+        up[i] = u;
+        lo[i] = l;
+        if (!isnan(l)) lmax = l;
     }
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = x;
-    __syncthreads();
-    double r = sh[0];
-    for (int w = 1; w < 4; ++w) r = sh[w] > r ? sh[w] : r;
-    return r;
-}
-
-__global__ __launch_bounds__(256) void screen_maxlo_kernel(const double* __restrict__ lo, long long m, double* __restrict__ part) {
-    __shared__ double sh[4];
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    double x = -__builtin_huge_val();
-    if (i < m && !isnan(lo[i])) x = lo[i];
-    const double r = screen_block_max(x, sh);
-    if (threadIdx.x == 0) part[blockIdx.x] = r;
-}
-
-__global__ __launch_bounds__(256) void screen_maxlo_final_kernel(double* __restrict__ part, int n_part) {
-    __shared__ double sh[4];
-    double x = -__builtin_huge_val();
-    for (int p = threadIdx.x; p < n_part; p += 256) x = part[p] > x ? part[p] : x;
-    const double r = screen_block_max(x, sh);
-    if (threadIdx.x == 0) part[n_part] = r;
+    lmax = screen_block_max(lmax, sMx);
+    if (tid == 0) atomicMax(bkey, screen_key(lmax));
 }
 
 // ---- survivors: count per 256 candidates, offsets, ordered gather ---------------------------------------------------------------
@@ -497,19 +601,8 @@ __device__ __forceinline__ bool screen_survives(const double* __restrict__ up, l
     return c < m && !(up[c] < b);
 }
 
-__global__ __launch_bounds__(256) void screen_count_kernel(const double* __restrict__ up, long long m,
-                                                           const double* __restrict__ b, int* __restrict__ cnt) {
-    __shared__ int sw[4];
-    const long long c = (long long)blockIdx.x * 256 + threadIdx.x;
-    const unsigned long long mask = __ballot(screen_survives(up, c, m, *b) ? 1 : 0);
-    if ((threadIdx.x & 63) == 0) sw[threadIdx.x >> 6] = __builtin_popcountll(mask);
-    __syncthreads();
-    if (threadIdx.x == 0) cnt[blockIdx.x] = (sw[0] + sw[1]) + (sw[2] + sw[3]);
-}
-
 // one workgroup: cnt[0 .. n_part) -> exclusive offsets, cnt[n_part] = the total; (total, b) -> pinned host memory
-__global__ __launch_bounds__(256) void screen_scan_kernel(int* __restrict__ cnt, int n_part, const double* __restrict__ b,
-                                                          double* __restrict__ host) {
+__device__ __forceinline__ void screen_scan(int* cnt, int n_part, double b, double* __restrict__ host) {
     __shared__ int s[256];
     __shared__ int carry;
     const int t = threadIdx.x;
@@ -534,36 +627,71 @@ __global__ __launch_bounds__(256) void screen_scan_kernel(int* __restrict__ cnt,
     if (t == 0) {
         cnt[n_part] = carry;
         host[0] = (double)carry;
-        host[1] = *b;
+        host[1] = b;
     }
 }
 
-// the survivors' scaled rows in ascending original index -> sub_Xcs, their indices -> map
-__global__ __launch_bounds__(256) void screen_gather_kernel(const double* __restrict__ up, long long m,
-                                                            const double* __restrict__ b, const int* __restrict__ cnt,
-                                                            const double* __restrict__ Xcs, int dim, long long cap,
-                                                            double* __restrict__ sub_Xcs, long long* __restrict__ map) {
+// Count and scan in one launch: every workgroup writes its count and draws a ticket (cnt[n_part + 1], zero between launches);
+// the one that draws the last ticket finds every count written (fence before the ticket, fence behind it), runs the scan and
+// puts the ticket back to zero.  No workgroup waits for another.
+__global__ __launch_bounds__(256) void screen_count_scan_kernel(const double* __restrict__ up, long long m,
+                                                                const unsigned long long* __restrict__ bkey, int* cnt,
+                                                                int n_part, double* __restrict__ host) {
     __shared__ int sw[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __shared__ int last;
+    const double b = screen_unkey(*bkey);
     const long long c = (long long)blockIdx.x * 256 + threadIdx.x;
-    const bool keep = screen_survives(up, c, m, *b);
-    const unsigned long long mask = __ballot(keep ? 1 : 0);
-    if (lane == 0) sw[wave] = __builtin_popcountll(mask);
+    const unsigned long long mask = __ballot(screen_survives(up, c, m, b) ? 1 : 0);
+    if ((threadIdx.x & 63) == 0) sw[threadIdx.x >> 6] = __builtin_popcountll(mask);
     __syncthreads();
-    if (!keep) return;
-    int before = __builtin_popcountll(mask & ((1ull << lane) - 1ull));
-    for (int w = 0; w < wave; ++w) before += sw[w];
-    const long long dst = (long long)cnt[blockIdx.x] + before;
-    if (dst >= cap) return;
-    map[dst] = c;
-    for (int d = 0; d < dim; ++d) sub_Xcs[dst * dim + d] = Xcs[c * dim + d];
+    if (threadIdx.x == 0) {
+        cnt[blockIdx.x] = (sw[0] + sw[1]) + (sw[2] + sw[3]);
+        __threadfence();
+        last = atomicAdd(cnt + n_part + 1, 1) == n_part - 1;
+    }
+    __syncthreads();
+    if (!last) return;
+    __threadfence();
+    screen_scan(cnt, n_part, b, host);
+    if (threadIdx.x == 0) cnt[n_part + 1] = 0;
 }
 
-// pad rows replicate row 0, as in every candidate handle
-__global__ __launch_bounds__(256) void screen_pad_kernel(double* __restrict__ sub_Xcs, int dim, long long rows, long long rows_pad) {
-    const long long total = (rows_pad - rows) * dim;
-    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256)
-        sub_Xcs[rows * dim + e] = sub_Xcs[e % dim];
+// the survivors' scaled rows in ascending original index -> sub_Xcs, their indices -> map
+// The workgroup that writes row 0 also writes the pad rows rows .. cap - 1 with the same values (pad rows replicate row 0, as
+// in every candidate handle; one thread doing it alone took 110 us at config 2), and the launch zeroes `clear_words` words at `clear`: the state block of the chained solve that
+// follows on the stream (0: none).
+__global__ __launch_bounds__(256) void screen_gather_kernel(const double* __restrict__ up, long long m,
+                                                            const unsigned long long* __restrict__ bkey,
+                                                            const int* __restrict__ cnt, const double* __restrict__ Xcs, int dim,
+                                                            long long rows, long long cap, double* __restrict__ sub_Xcs,
+                                                            long long* __restrict__ map, unsigned* __restrict__ clear,
+                                                            long long clear_words) {
+    __shared__ int sw[4];
+    __shared__ long long first;                 // the candidate that becomes row 0, in the workgroup that holds it (-1: elsewhere)
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < clear_words; e += (long long)gridDim.x * 256) clear[e] = 0u;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long c = (long long)blockIdx.x * 256 + threadIdx.x;
+    const bool keep = screen_survives(up, c, m, screen_unkey(*bkey));
+    const unsigned long long mask = __ballot(keep ? 1 : 0);
+    if (lane == 0) sw[wave] = __builtin_popcountll(mask);
+    if (threadIdx.x == 0) first = -1;
+    __syncthreads();
+    if (keep) {
+        int before = __builtin_popcountll(mask & ((1ull << lane) - 1ull));
+        for (int w = 0; w < wave; ++w) before += sw[w];
+        const long long dst = (long long)cnt[blockIdx.x] + before;
+        if (dst < cap) {
+            map[dst] = c;
+            for (int d = 0; d < dim; ++d) sub_Xcs[dst * dim + d] = Xcs[c * dim + d];
+            if (dst == 0) first = c;
+        }
+    }
+    __syncthreads();
+    // the pad rows, by the workgroup that wrote row 0, from the same source values
+    const long long c0 = first;
+    if (c0 < 0) return;
+    const long long total = (cap - rows) * dim;
+    for (long long e = threadIdx.x; e < total; e += 256) sub_Xcs[rows * dim + e] = Xcs[c0 * dim + e % dim];
 }
 
 // the survivors' winner under its original index into the batch's own argmax slots; their flags into the batch's word.
@@ -581,14 +709,14 @@ __global__ void screen_map_best_kernel(const double* __restrict__ sub_val, const
 
 // b := max(b, best exact value of the probed candidates less rho); the probe's flags are dropped
 __global__ void screen_probe_bound_kernel(const double* __restrict__ vals, const RefineSel* __restrict__ sel, int kind,
-                                          double* __restrict__ b, unsigned* __restrict__ probe_flags) {
+                                          unsigned long long* __restrict__ bkey, unsigned* __restrict__ probe_flags) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     double best = -__builtin_huge_val();
     const int keff = (int)sel->keff;             // slots beyond the candidates with a bound hold no candidate
     for (int i = 0; i < keff; ++i)
         if (vals[i] > best) best = vals[i];
     if (kind != ROBO_ACQ_LCB) best = screen_widen(best, -1.0, kind == ROBO_ACQ_LOG_EI ? 1.0 : 0.0);
-    if (best > *b) *b = best;
+    if (best > screen_unkey(*bkey)) *bkey = screen_key(best);
     *probe_flags = 0u;
 }
 
@@ -622,7 +750,7 @@ static int alpha_ensure(robo_gp* g) {
     double* stats = g->d_alpha + 2 * np;
     hipLaunchKernelGGL(screen_alpha_norm_kernel, dim3(1), dim3(256), 0, st, (const double*)a, (const double*)g->d_Xs, g->cov,
                        g->n, stats);
-    g->dot_extent = 0.0;
+    g->dot_extent = g->dot_alpha_sum = 0.0;
     if (ks) {
         double* apack = stats + SD_CTR + SCREEN_DOT_MAX_D;
         const int nst = (g->n + SD_STAGE - 1) / SD_STAGE;
@@ -631,11 +759,13 @@ static int alpha_ensure(robo_gp* g) {
         hipLaunchKernelGGL(screen_dot_pack_kernel, dim3((unsigned)(nst * SD_STAGE / 64)), dim3(256), 0, st, (const double*)a,
                            (const double*)g->d_Xs, (const double*)stats, g->cov.amp, g->dim, ks, g->n, apack + 2 * np, apack);
         ROBO_LAUNCH_CHECK();
-        // the centred extent decides between the two kernels on the host: one small copy per fit_gen
+        // the centred extent decides between the two kernels on the host, sum_j |alpha_j| between the two finishes: one
+        // small copy per fit_gen
         double* hp = c->h_pinned + MAX_DIM + 16;
-        ROBO_HIP_CHECK(hipMemcpyAsync(hp, stats + 3, sizeof(double), hipMemcpyDeviceToHost, st));
+        ROBO_HIP_CHECK(hipMemcpyAsync(hp, stats + 1, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
         ROBO_HIP_CHECK(hipStreamSynchronize(st));
-        g->dot_extent = hp[0];
+        g->dot_alpha_sum = hp[0];
+        g->dot_extent = hp[2];
     }
     ROBO_LAUNCH_CHECK();
     g->alpha_gen = g->fit_gen;
@@ -651,11 +781,25 @@ static bool screen_dot_wanted(const robo_gp* g) {
     return worst <= SCREEN_DOT_BOUND;            // (a NaN extent takes the direct kernel)
 }
 
+// whether the dot kernel finishes its pairs with the lean finish (header: "The lean finish"); alpha_ensure has run
+static bool screen_lean_wanted(const robo_gp* g) {
+    const int t = g->ctx->tune.acq_screen_lean;
+    if (t == 0) return false;
+    if (t > 0) return true;
+    // the term the finish adds to delta, in units of the prior standard deviation |y_std| sqrt(amp)
+    const double term = SCREEN_LEAN_SAFETY * SD_LEAN_EPS * std::sqrt(std::fabs(g->cov.amp)) * g->dot_alpha_sum;
+    return term <= SCREEN_LEAN_MAX;              // (a NaN sum takes the full finish)
+}
+
 static int screen_buffers(robo_cand* k) {
     const size_t mp = (size_t)k->m_pad;
     if (!k->d_scr_up) ROBO_TRY(dev_alloc(&k->d_scr_up, mp));
-    if (!k->d_scr_lo) ROBO_TRY(dev_alloc(&k->d_scr_lo, mp + (size_t)k->n_part + 2));    // bounds | partial maxima | b
-    if (!k->d_scr_cnt) ROBO_TRY(dev_alloc(&k->d_scr_cnt, (size_t)k->n_part + 2));
+    if (!k->d_scr_lo) ROBO_TRY(dev_alloc(&k->d_scr_lo, mp + 2));    // bounds | b (as its order-preserving key)
+    if (!k->d_scr_cnt) {
+        // counts -> offsets | total | the ticket of screen_count_scan_kernel, zero between launches
+        ROBO_TRY(dev_alloc(&k->d_scr_cnt, (size_t)k->n_part + 2));
+        ROBO_HIP_CHECK(hipMemsetAsync(k->d_scr_cnt, 0, ((size_t)k->n_part + 2) * sizeof(int), k->ctx->stream));
+    }
     return ROBO_OK;
 }
 
@@ -664,7 +808,8 @@ static int launch_screen_bounds(robo_gp* g, robo_cand* k, int kind, double par, 
     robo_ctx* c = g->ctx;
     ROBO_TRY(alpha_ensure(g));
     ROBO_TRY(screen_buffers(k));
-    ROBO_TRY(launch_scale_inputs(c, k->d_Xc, k->d_Xcs, g->d_theta, k->m, k->m_pad, g->dim));
+    unsigned long long* bkey = reinterpret_cast<unsigned long long*>(k->d_scr_lo + k->m_pad);
+    ROBO_TRY(launch_scale_inputs(c, k->d_Xc, k->d_Xcs, g->d_theta, k->m, k->m_pad, g->dim, 1, 0, 0, bkey, SCREEN_KEY_NONE));
     const dim3 grid((unsigned)((k->m + SC_CAND - 1) / SC_CAND));
     const double* alpha = g->d_alpha + (size_t)g->n_pad_max;
     const double* anorm = g->d_alpha + 2 * (size_t)g->n_pad_max;
@@ -672,36 +817,44 @@ static int launch_screen_bounds(robo_gp* g, robo_cand* k, int kind, double par, 
         const double* apack = anorm + SD_CTR + SCREEN_DOT_MAX_D;
         const double* rows = apack + 2 * (size_t)g->n_pad_max;
         const dim3 dgrid((unsigned)((k->m + SD_CAND - 1) / SD_CAND));
-#define ROBO_SCREEN_DOT_CALL(KIND, KS)                                                                                      \
-    hipLaunchKernelGGL((screen_bounds_dot_kernel<KIND, KS>), dgrid, dim3(256), 0, c->stream, (const double*)k->d_Xcs, rows,  \
+#define ROBO_SCREEN_DOT_CALL(KIND, KS, LEAN)                                                                                  \
+    hipLaunchKernelGGL((screen_bounds_dot_kernel<KIND, KS, LEAN>), dgrid, dim3(256), 0, c->stream, (const double*)k->d_Xcs, rows,  \
                        apack, anorm, g->cov, g->n, (long long)k->m, g->mean_c, g->y_mean, g->y_std, kind, par, eta,          \
-                       k->d_scr_up, k->d_scr_lo)
-#define ROBO_SCREEN_DOT_KS(KIND)                                  \
+                       k->d_scr_up, k->d_scr_lo, bkey)
+#define ROBO_SCREEN_DOT_KS(KIND, LEAN)                            \
     switch (screen_dot_ks(g)) {                                   \
-        case 1: ROBO_SCREEN_DOT_CALL(KIND, 1); break;             \
-        case 2: ROBO_SCREEN_DOT_CALL(KIND, 2); break;             \
-        case 4: ROBO_SCREEN_DOT_CALL(KIND, 4); break;             \
-        default: ROBO_SCREEN_DOT_CALL(KIND, 8); break;            \
+        case 1: ROBO_SCREEN_DOT_CALL(KIND, 1, LEAN); break;       \
+        case 2: ROBO_SCREEN_DOT_CALL(KIND, 2, LEAN); break;       \
+        case 4: ROBO_SCREEN_DOT_CALL(KIND, 4, LEAN); break;       \
+        default: ROBO_SCREEN_DOT_CALL(KIND, 8, LEAN); break;      \
     }
-        if (g->kind == ROBO_KERNEL_MATERN52_ARD) ROBO_SCREEN_DOT_KS(ROBO_KERNEL_MATERN52_ARD)
-        else ROBO_SCREEN_DOT_KS(ROBO_KERNEL_RBF_ARD)
+        const bool lean = screen_lean_wanted(g);
+        if (g->kind == ROBO_KERNEL_MATERN52_ARD) {
+            if (lean) ROBO_SCREEN_DOT_KS(ROBO_KERNEL_MATERN52_ARD, true)
+            else ROBO_SCREEN_DOT_KS(ROBO_KERNEL_MATERN52_ARD, false)
+        } else {
+            if (lean) ROBO_SCREEN_DOT_KS(ROBO_KERNEL_RBF_ARD, true)
+            else ROBO_SCREEN_DOT_KS(ROBO_KERNEL_RBF_ARD, false)
+        }
 #undef ROBO_SCREEN_DOT_KS
 #undef ROBO_SCREEN_DOT_CALL
         ROBO_LAUNCH_CHECK();
         k->scr_bounds_kernel = "screen_bounds_dot_kernel";
+        k->scr_finish = lean ? ROBO_SCREEN_FINISH_LEAN : ROBO_SCREEN_FINISH_FULL;
         return ROBO_OK;
     }
     k->scr_bounds_kernel = "screen_bounds_kernel";
+    k->scr_finish = ROBO_SCREEN_FINISH_NONE;
 #define ROBO_SCREEN_CALL(KIND)                                                                                           \
     do {                                                                                                                  \
         if (g->dim <= 16)                                                                                                 \
             hipLaunchKernelGGL((screen_bounds_kernel<KIND, true>), grid, dim3(256), 0, c->stream, (const double*)k->d_Xcs, \
                                (const double*)g->d_Xs, alpha, anorm, g->cov, g->n, (long long)k->m, g->mean_c, g->y_mean, \
-                               g->y_std, kind, par, eta, k->d_scr_up, k->d_scr_lo);                                       \
+                               g->y_std, kind, par, eta, k->d_scr_up, k->d_scr_lo, bkey);                                     \
         else                                                                                                              \
             hipLaunchKernelGGL((screen_bounds_kernel<KIND, false>), grid, dim3(256), 0, c->stream, (const double*)k->d_Xcs, \
                                (const double*)g->d_Xs, alpha, anorm, g->cov, g->n, (long long)k->m, g->mean_c, g->y_mean, \
-                               g->y_std, kind, par, eta, k->d_scr_up, k->d_scr_lo);                                       \
+                               g->y_std, kind, par, eta, k->d_scr_up, k->d_scr_lo, bkey);                                     \
     } while (0)
     if (g->kind == ROBO_KERNEL_MATERN52_ARD) ROBO_SCREEN_CALL(ROBO_KERNEL_MATERN52_ARD);
     else if (g->kind == ROBO_KERNEL_RBF_ARD) ROBO_SCREEN_CALL(ROBO_KERNEL_RBF_ARD);
@@ -737,10 +890,13 @@ static int screen_sub(robo_cand* k, int64_t cap) {
     return ROBO_OK;
 }
 
-int acq_sweep_best(robo_gp* g, int32_t kind, double par, double eta, robo_cand* k, bool want_values, bool allow_chain) {
+int acq_sweep_best(robo_gp* g, int32_t kind, double par, double eta, robo_cand* k, bool want_values, bool allow_chain,
+                   double* h_report) {
     if (k) {
+        k->best_reported = false;
         k->scr_outcome = ROBO_SCREEN_NOT_ELIGIBLE;
         k->scr_n = k->scr_kept = 0;
+        k->scr_tail_fused = false;
     }
     if (want_values || !screen_eligible(g, k, kind, par, eta)) return acq_sweep(&g, 1, false, kind, par, &eta, k, allow_chain);
     if (g->screen_gen != g->fit_gen) {
@@ -757,18 +913,14 @@ int acq_sweep_best(robo_gp* g, int32_t kind, double par, double eta, robo_cand* 
     ROBO_HIP_CHECK(hipSetDevice(c->device));
     k->solved_gen = 0;
     ROBO_TRY(launch_screen_bounds(g, k, kind, par, eta));
-    double* part = k->d_scr_lo + k->m_pad;
-    double* b = part + k->n_part;
+    unsigned long long* b = reinterpret_cast<unsigned long long*>(k->d_scr_lo + k->m_pad);     // max_c L_c: the bounds kernel's
     double* hp = c->h_pinned + 8;
     const dim3 blocks((unsigned)k->n_part);
-    hipLaunchKernelGGL(screen_maxlo_kernel, blocks, dim3(256), 0, st, (const double*)k->d_scr_lo, (long long)k->m, part);
-    hipLaunchKernelGGL(screen_maxlo_final_kernel, dim3(1), dim3(256), 0, st, part, k->n_part);
     // survivors of the current b: counts, offsets, the total into pinned memory (one synchronisation)
     int64_t kept = 0;
     auto count_survivors = [&]() -> int {
-        hipLaunchKernelGGL(screen_count_kernel, blocks, dim3(256), 0, st, (const double*)k->d_scr_up, (long long)k->m,
-                           (const double*)b, k->d_scr_cnt);
-        hipLaunchKernelGGL(screen_scan_kernel, dim3(1), dim3(256), 0, st, k->d_scr_cnt, k->n_part, (const double*)b, hp);
+        hipLaunchKernelGGL(screen_count_scan_kernel, blocks, dim3(256), 0, st, (const double*)k->d_scr_up, (long long)k->m,
+                           (const unsigned long long*)b, k->d_scr_cnt, k->n_part, hp);
         ROBO_LAUNCH_CHECK();
         ROBO_HIP_CHECK(hipStreamSynchronize(st));
         kept = (int64_t)hp[0];
@@ -796,7 +948,7 @@ int acq_sweep_best(robo_gp* g, int32_t kind, double par, double eta, robo_cand* 
         ROBO_TRY(predict_scaled(g, s, false, nullptr, false, false, allow_chain));
         ROBO_TRY(clear_flags_on_error(s, launch_acq(c, s, kind, par, eta, false, false)));
         hipLaunchKernelGGL(screen_probe_bound_kernel, dim3(1), dim3(64), 0, st, (const double*)s->d_acq,
-                           (const RefineSel*)ps.sel, kind, part + k->n_part, s->d_flags);
+                           (const RefineSel*)ps.sel, kind, b, s->d_flags);
         ROBO_LAUNCH_CHECK();
         ROBO_TRY(count_survivors());
         // (a probe whose chained solve gave up has produced no incumbent: the caller starts over, on launches)
@@ -819,17 +971,34 @@ int acq_sweep_best(robo_gp* g, int32_t kind, double par, double eta, robo_cand* 
     s->m_pad = round_up64(kept, NB);
     s->n_part = (int)((kept + 255) / 256);
     s->solved_gen = 0;
-    hipLaunchKernelGGL(screen_gather_kernel, blocks, dim3(256), 0, st, (const double*)k->d_scr_up, (long long)k->m, b,
-                       (const int*)k->d_scr_cnt, (const double*)k->d_Xcs, k->dim, (long long)s->m_pad, s->d_Xcs, k->d_scr_map);
-    if (s->m_pad > kept)
-        hipLaunchKernelGGL(screen_pad_kernel, dim3((unsigned)(((s->m_pad - kept) * k->dim + 255) / 256)), dim3(256), 0, st,
-                           s->d_Xcs, k->dim, (long long)kept, (long long)s->m_pad);
-    ROBO_LAUNCH_CHECK();
-    // the path the unscreened call runs for the whole batch; its event pair 25 -> 26 is the batch's (bench.py reads it)
+    // where the survivors' solve will be ONE chained launch, the gather zeroes its state block too (launch_predict_chain
+    // then skips its memset; any other outcome keeps it)
     ROBO_TRY(cand_ensure_workspace(s, g->n_pad, false));
-    ROBO_TRY(predict_scaled(g, s, false, nullptr, false, phase_events_on(g->ctx, k), allow_chain));
-    int status = launch_acq(c, s, kind, par, eta, false, false);
-    if (status == ROBO_OK) {
+    unsigned* clear = nullptr;
+    size_t clear_bytes = 0;
+    s->chain_cleared = 0;
+    if (allow_chain && s->chunk >= s->m_pad && !g->fp32_gram && !c->tune.predict_stepwise && chain_wanted(g, s->m_pad)) {
+        ROBO_TRY(chain_state_ensure(g, s, s->m_pad, &clear_bytes));
+        clear = reinterpret_cast<unsigned*>(s->d_chain);
+    }
+    hipLaunchKernelGGL(screen_gather_kernel, blocks, dim3(256), 0, st, (const double*)k->d_scr_up, (long long)k->m,
+                       (const unsigned long long*)b, (const int*)k->d_scr_cnt, (const double*)k->d_Xcs, k->dim, (long long)kept,
+                       (long long)s->m_pad, s->d_Xcs, k->d_scr_map, clear, (long long)(clear_bytes / sizeof(unsigned)));
+    ROBO_LAUNCH_CHECK();
+    s->chain_cleared = clear_bytes;
+    // the path the unscreened call runs for the whole batch; its event pair 25 -> 26 is the batch's (bench.py reads it)
+    // survivors within one partial block: the tail is one single-workgroup launch (acq.hip acq_tail_kernel)
+    const bool fused = c->tune.acq_screen_fused_tail != 0 && s->n_part == 1 && s->m_pad <= 256;
+    s->defer_post = fused;
+    const int solved = predict_scaled(g, s, false, nullptr, false, phase_events_on(g->ctx, k), allow_chain);
+    s->chain_cleared = 0;
+    s->defer_post = false;
+    ROBO_TRY(solved);
+    int status = fused ? launch_acq_tail(g, s, kind, par, eta, k->d_scr_map, k, h_report) : launch_acq(c, s, kind, par, eta, false, false);
+    if (fused) {
+        k->scr_tail_fused = true;
+        if (status == ROBO_OK) k->best_reported = h_report != nullptr;
+    } else if (status == ROBO_OK) {
         hipLaunchKernelGGL(screen_map_best_kernel, dim3(1), dim3(64), 0, st, (const double*)(s->d_part_val + s->n_part),
                            (const long long*)(s->d_part_idx + s->n_part), s->d_flags, (const long long*)k->d_scr_map,
                            k->d_part_val + k->n_part, k->d_part_idx + k->n_part, k->d_flags);
@@ -851,6 +1020,13 @@ int32_t robo_cand_last_screen(robo_cand* k, int64_t* out_n_screened, int64_t* ou
     if (out_n_screened) *out_n_screened = k->scr_n;
     if (out_n_survivors) *out_n_survivors = k->scr_kept;
     if (out_outcome) *out_outcome = k->scr_outcome;
+    return ROBO_OK;
+}
+
+int32_t robo_cand_last_screen_finish(robo_cand* k, int32_t* out_finish, int32_t* out_fused_tail) {
+    if (!k || !out_finish) return ROBO_BAD_ARGUMENT;
+    *out_finish = k->scr_finish;
+    if (out_fused_tail) *out_fused_tail = k->scr_tail_fused ? 1 : 0;
     return ROBO_OK;
 }
 

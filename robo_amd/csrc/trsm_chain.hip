@@ -351,12 +351,11 @@ bool chain_wanted(const robo_gp* gp, int64_t cn) {
     return cn / 16 * nbk <= (int64_t)t.trsm_chain_max_wg * c->num_cu;
 }
 
-int launch_predict_chain(robo_gp* gp, robo_cand* cand, int64_t c0, int64_t cn) {
-    robo_ctx* c = gp->ctx;
+// the state block of a chained solve of cn candidates on this handle, grown if need be: [ticket | time-out | pad | pad | per
+// tile: progress words, slot counter], padded to 16 bytes and zeroed before every launch; the slots behind it
+int chain_state_ensure(const robo_gp* gp, robo_cand* cand, int64_t cn, size_t* state_bytes_out) {
     const int nbk = (gp->n + NB - 1) / NB;
     const int64_t tiles = cn / 16, wgs = tiles * nbk;
-    // [ticket | time-out | pad | pad | per tile: progress words, slot counter], padded to 16 bytes and zeroed before every
-    // launch; the slots behind it
     const size_t state_bytes = (size_t)round_up64((CHAIN_HDR + tiles * chain_tile_words(nbk)) * (int64_t)sizeof(unsigned), 16);
     const size_t slot_off = (size_t)round_up64((int64_t)state_bytes, 256);
     const size_t need = slot_off + (size_t)wgs * CHAIN_SLOT * sizeof(double);
@@ -364,16 +363,30 @@ int launch_predict_chain(robo_gp* gp, robo_cand* cand, int64_t c0, int64_t cn) {
         if (cand->d_chain) ROBO_HIP_CHECK(hipFree(cand->d_chain));
         cand->d_chain = nullptr;
         cand->chain_bytes = 0;
+        cand->chain_cleared = 0;
         ROBO_HIP_CHECK(hipMalloc((void**)&cand->d_chain, need));
         cand->chain_bytes = need;
     }
+    *state_bytes_out = state_bytes;
+    return ROBO_OK;
+}
+
+int launch_predict_chain(robo_gp* gp, robo_cand* cand, int64_t c0, int64_t cn) {
+    robo_ctx* c = gp->ctx;
+    const int nbk = (gp->n + NB - 1) / NB;
+    const int64_t tiles = cn / 16, wgs = tiles * nbk;
+    size_t state_bytes = 0;
+    ROBO_TRY(chain_state_ensure(gp, cand, cn, &state_bytes));
+    const size_t slot_off = (size_t)round_up64((int64_t)state_bytes, 256);
     if (!c->h_chain) ROBO_HIP_CHECK(hipHostMalloc((void**)&c->h_chain, ROBO_CHAIN_SLOTS * sizeof(unsigned), 0));
     unsigned* state = reinterpret_cast<unsigned*>(cand->d_chain);
     double* slots = reinterpret_cast<double*>(cand->d_chain + slot_off);
     const Tuning& tune = c->tune;
     const unsigned spin_limit = tune.trsm_chain_spin_limit >= 0 ? (unsigned)tune.trsm_chain_spin_limit : PROG_SPIN_LIMIT;
     const bool deep = tune.trsm_small_deep >= 0 ? tune.trsm_small_deep != 0 : wgs <= c->num_cu;
-    ROBO_HIP_CHECK(hipMemsetAsync(state, 0, state_bytes, c->stream));
+    // the acquisition screen's gather has zeroed exactly this block already (screen.hip): every other call keeps the memset
+    if (cand->chain_cleared != state_bytes) ROBO_HIP_CHECK(hipMemsetAsync(state, 0, state_bytes, c->stream));
+    cand->chain_cleared = 0;
     cand->solve_kernel = "trsm_chain_kernel";
 #define ROBO_CHAIN_LAUNCH(KIND, DK)                                                                              \
     hipLaunchKernelGGL((trsm_chain_kernel<KIND, DK>), dim3((unsigned)wgs), dim3(256), 0, c->stream,              \
