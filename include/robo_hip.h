@@ -96,7 +96,7 @@ int32_t robo_ctx_device_name(robo_ctx* ctx, char* buf, int32_t buf_len);
  *             robo_paths_descend (always) and of robo_paths_refine_cand.
  *   30, 31    what follows the sweeps: the envelope kernel of robo_kg_eval_cand and the element-wise half of
  *             robo_mes_eval_cand (last sample each), the strip kernel of robo_ehvi_eval_cand, the passes of the path kernel
- *             (robo_paths_eval_cand, robo_paths_refine_cand).
+ *             (robo_paths_eval_cand, robo_paths_refine_cand), the fold kernel of robo_qei_batch_cand's last pick.
  *   32, 33    the fold kernel of robo_cei_eval_cand.                                                                    */
 int32_t robo_ctx_event_record(robo_ctx* ctx, int32_t slot);
 int32_t robo_ctx_event_elapsed_ms(robo_ctx* ctx, int32_t slot_begin, int32_t slot_end, float* out_ms);
@@ -463,6 +463,56 @@ int32_t robo_acq_batch_marginal_cand(robo_gp* const* gps, int32_t S, int32_t acq
                                      robo_cand* cand, int32_t q, int32_t fantasy_kind, double liar, int64_t* out_idx,
                                      double* out_values, double* out_fantasy, uint32_t* out_flags, int32_t* out_n_made,
                                      double* out_trace);
+
+/* ---- joint Monte-Carlo batch EI (q-EI) with greedy picks (no counterpart in the reference).  What the fantasies above stand
+ * in for:  qEI(x_0 .. x_{q-1}) = E[(eta - par - min_t f(x_t))^+]  under the joint posterior of the q points, estimated over
+ * K scenarios and maximised greedily over ONE candidate batch.  Greedy selection is exact for the estimate: with
+ * b^k = min(eta - par, f^k(picks so far)) in scenario k,  qEI(picks, x) = qEI(picks) + E[(b - f(x))^+], so pick j maximises
+ * the increment and the increments (out_gain) sum to the batch's q-EI estimate.  The innermost normal is integrated in
+ * closed form, so a term is plain EI with a per-scenario shifted mean and incumbent.  EI only: LogEI, PI and LCB have no
+ * joint form here (the mean of logs over hyper-parameter samples is not the log of the mean).
+ * Everything is per hyper-parameter sample s, in the latent scale, at FIXED theta, constant mean and output transform.
+ * z: K x q row-major finite doubles, standard-normal base samples shared by all hyper-parameter samples; z[k][t] drives
+ * pick t in scenario k.  eps = DBL_EPSILON.
+ * Pick 0 is robo_acq_eval_cand's (robo_acq_eval_marginal_cand's) EI sweep and argmax, launch for launch; after it
+ * b^k := eta_s - par (one rounded subtraction) for all k.
+ * After pick t at candidate p_t -- no noise term and no jitter, a pick is not an observation --
+ *   c_t(x) = k(x, p_t) - k_*(x)^T beta_t - sum_{u<t} c_u(x) c_u(p_t) / d_u,   beta_t = K^-1 k_*(p_t) (the two triangular
+ *            solves, never the explicit inverse W),
+ *   d_t = max(var_lat(p_t), eps / y_std^2)   (var_lat(p_t): the residual variance before this step; NaN propagates),
+ *   l_t(x) = c_t(x) / sqrt(d_t),   var_lat(x) -= l_t(x)^2;   mu_lat is never touched,
+ *   f^k(p_t) = mean_t(p_t) + y_std (sum_{u<t} l_u(p_t) z[k][u] + sqrt(d_t) z[k][t]),   b^k := min(b^k, f^k(p_t))
+ *            (u ascending, products fused into the sum, the outer product-sum one fma; a NaN f^k makes b^k NaN).
+ * Value of candidate x at pick j >= 1:
+ *   g_s(x) = (1/K) sum_k EI(mean_t(x) + y_std sum_{u<j} l_u(x) z[k][u], max(var_lat(x) y_std^2, eps), b^k, 0)
+ * with robo_acq_eval's EI, its +0 for a term in (-DBL_MIN, 0) and its flags.  The K terms are summed in FOUR groups of
+ * ceil(K / 4) consecutive scenarios (group w starts at k = w ceil(K / 4)), each with k ascending from +0, combined as
+ * ((G0 + G1) + (G2 + G3)) / K: the grouping depends on K alone -- not on m, the candidate's position or the grid -- so a
+ * candidate's value has the same bits at any batch position.  The marginal form averages g_s over the samples in sample
+ * order.  The winner follows np.argmax (first index, NaN maximal).  A NaN winner is recorded and ends the selection as in
+ * robo_acq_batch_cand: the remaining out_idx are -1, out_gain NaN.  Nothing is masked.
+ * out_idx / out_gain / out_flags [q]: the pick, its value (the running sum of gains is the batch's q-EI estimate), the
+ * ROBO_FLAG_* of the values it was made from; *out_n_made = picks recorded.  Diagnostics, all nullable; rows of picks that
+ * were not made are NaN:
+ *   out_acq   q x m            every candidate's value at every pick
+ *   out_trace q x S x m x 2    the transformed mean and the transformed, floored residual variance every pick was made from
+ *   out_coef  (q-1) x S x m    c_t(x)
+ *   out_d     q x S            d_t (NaN for the last pick made: nothing is conditioned on it)
+ *   out_best  q x S x K        the b^k every pick was made from
+ * ROBO_BAD_ARGUMENT with a message: q outside 1 .. min(m, ROBO_QEI_MAX_Q), K outside 1 .. ROBO_QEI_MAX_K, z NULL or not
+ * finite (also for q = 1, which does not use it), an unfitted GP, a GP with fp32 covariance entries, samples that do not
+ * match the candidates or each other (what robo_acq_batch_marginal_cand refuses).  q = 1 is robo_acq_eval_cand(EI) bit
+ * for bit.  One synchronisation per call; the state stays with gp (gps[0]) between calls of one (m, S, q, K).  Event slots
+ * 30 and 31 bracket the fold kernel of the last pick (last sample), under the condition of slots 24..27.            */
+#define ROBO_QEI_MAX_Q 64
+#define ROBO_QEI_MAX_K 1024
+int32_t robo_qei_batch_cand(robo_gp* gp, double par, double eta, robo_cand* cand, int32_t q, const double* z, int32_t K,
+                            int64_t* out_idx, double* out_gain, uint32_t* out_flags, int32_t* out_n_made, double* out_acq,
+                            double* out_trace, double* out_coef, double* out_d, double* out_best);
+int32_t robo_qei_batch_marginal_cand(robo_gp* const* gps, int32_t S, double par, const double* etas, robo_cand* cand,
+                                     int32_t q, const double* z, int32_t K, int64_t* out_idx, double* out_gain,
+                                     uint32_t* out_flags, int32_t* out_n_made, double* out_acq, double* out_trace,
+                                     double* out_coef, double* out_d, double* out_best);
 
 /* ---- max-value entropy search (Wang & Jegelka, ICML 2017; no counterpart in the reference), for minimisation.
  * Inputs are the sweep's transformed, floored moments (mu_i, v_i) of the m candidates (what robo_gp_predict_cand returns),

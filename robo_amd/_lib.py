@@ -57,7 +57,7 @@ SYMBOLS = [
     "robo_cand_last_screen", "robo_cand_last_screen_finish", "robo_acq_screen_bounds",
     "robo_acq_refine_cand", "robo_acq_refine_marginal_cand",
     "robo_rep_sample", "robo_rep_sample_batch",
-    "robo_acq_batch_cand", "robo_acq_batch_marginal_cand",
+    "robo_acq_batch_cand", "robo_acq_batch_marginal_cand", "robo_qei_batch_cand", "robo_qei_batch_marginal_cand",
     "robo_mes_eval_cand", "robo_mes_eval_marginal_cand", "robo_mes_sample_min_moments", "robo_mes_eval_moments",
     "robo_kg_eval_cand", "robo_kg_eval_marginal_cand", "robo_kg_eval_moments",
     "robo_ehvi_eval_cand", "robo_ehvi_eval_moments",
@@ -238,6 +238,10 @@ def lib():
                                 C.POINTER(i32), _dp],
         "robo_acq_batch_marginal_cand": [pp, i32, i32, dbl, _dp, vp, i32, i32, dbl, C.POINTER(i64), _dp, _dp,
                                          C.POINTER(C.c_uint32), C.POINTER(i32), _dp],
+        "robo_qei_batch_cand": [vp, dbl, dbl, vp, i32, _dp, i32, C.POINTER(i64), _dp, C.POINTER(C.c_uint32), C.POINTER(i32),
+                                _dp, _dp, _dp, _dp, _dp],
+        "robo_qei_batch_marginal_cand": [pp, i32, dbl, _dp, vp, i32, _dp, i32, C.POINTER(i64), _dp, C.POINTER(C.c_uint32),
+                                         C.POINTER(i32), _dp, _dp, _dp, _dp, _dp],
         "robo_mes_eval_cand": [vp, dbl, vp, _dp, i32, i32, _dp, _dp, C.POINTER(i64), C.POINTER(C.c_uint32), _dp, _dp, _dp],
         "robo_mes_eval_marginal_cand": [pp, i32, _dp, vp, _dp, i32, i32, _dp, _dp, C.POINTER(i64), C.POINTER(C.c_uint32),
                                         _dp, _dp, _dp],
@@ -929,6 +933,11 @@ class DeviceGP(object):
         see :func:`acq_batch`"""
         return acq_batch([self], kind, par, eta, cand, q, fantasy, liar, diagnostics, marginal=False)
 
+    def select_batch_joint(self, par, eta, cand, q, z, diagnostics=False):
+        """q greedy picks from ``cand`` by joint Monte-Carlo batch EI over the base samples z (K, q) (robo_qei_batch_cand)
+        -> QEIResult; see :func:`qei_batch`"""
+        return qei_batch([self], par, eta, cand, q, z, diagnostics, marginal=False)
+
 
     def mes(self, eta, cand, u, clamp=True, want_values=True, diagnostics=False):
         """max-value entropy search over ``cand`` with the caller's uniforms u (K,) (robo_mes_eval_cand) -> MESResult;
@@ -1314,6 +1323,45 @@ def acq_batch(gps, kind, par, eta, cand, q, fantasy="kriging_believer", liar=0.0
     check(fn(*head, cand._h, q, FANTASY_KINDS[fantasy], float(liar), p_idx, _arr(val), _arr(fant), p_fl, C.byref(made),
              p_trace))
     return BatchResult(idx, val, fant, fl, made.value, trace)
+
+
+class QEIResult(object):
+    """indices (q,) rows of the candidate batch in pick order (-1: not made, a NaN winner ended the selection), gains (q,)
+    the winning increments, qei (q,) their running sum (the q-EI estimate of the first j + 1 picks), flags (q,), n_made;
+    with diagnostics: acq (q, m), trace (q, S, m, 2), coef (q - 1, S, m), d (q, S), best (q, S, K) (include/robo_hip.h)"""
+
+    def __init__(self, indices, gains, flags, n_made, acq=None, trace=None, coef=None, d=None, best=None):
+        self.indices, self.gains, self.flags, self.n_made = indices, gains, flags, int(n_made)
+        self.values = gains                         # (what a pick won with: BatchResult's name, for the shared tails)
+        self.qei = np.cumsum(gains)
+        self.acq, self.trace, self.coef, self.d, self.best = acq, trace, coef, d, best
+
+
+def qei_batch(gps, par, eta, cand, q, z, diagnostics=False, marginal=True):
+    """joint Monte-Carlo batch EI with greedy picks over device GPs (one: robo_qei_batch_cand; the mean over several
+    hyper-parameter samples: robo_qei_batch_marginal_cand).  eta: one incumbent value, or one per sample.  z (K, q):
+    standard-normal base samples, shared by the samples."""
+    S, q = len(gps), int(q)
+    z = None if z is None else np.ascontiguousarray(z, dtype=np.float64)
+    if z is not None and (z.ndim != 2 or z.shape[1] != max(q, 1)):
+        raise ValueError("z must have shape (K, q = %d), got %r" % (q, z.shape))
+    K = 0 if z is None else z.shape[0]
+    ok = 1 <= q <= cand.m and K >= 1
+    n = max(q, 1)
+    idx = np.full(n, -1, dtype=np.int64)
+    gain = np.full(n, np.nan)
+    fl = np.zeros(n, dtype=np.uint32)
+    made = C.c_int32(0)
+    diag = [None] * 5
+    if diagnostics and ok:
+        diag = [np.empty((q, cand.m)), np.empty((q, S, cand.m, 2)), np.empty((q - 1, S, cand.m)), np.empty((q, S)),
+                np.empty((q, S, K))]
+    p_idx, p_fl = idx.ctypes.data_as(C.POINTER(C.c_int64)), fl.ctypes.data_as(C.POINTER(C.c_uint32))
+    fn = lib().robo_qei_batch_marginal_cand if marginal else lib().robo_qei_batch_cand
+    head = _ensemble_head(gps, eta, marginal, float(par))
+    check(fn(*head, cand._h, q, _arr(z) if z is not None else None, K, p_idx, _arr(gain), p_fl, C.byref(made),
+             *[_arr(a) if a is not None else None for a in diag]))
+    return QEIResult(idx, gain, fl, made.value, *diag)
 
 
 class RefineResult(object):

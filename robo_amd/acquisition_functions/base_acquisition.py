@@ -78,6 +78,20 @@ def batch_liar(model, fantasy, liar):
     return float(liar)
 
 
+def joint_base_samples(acq, q, n_mc, z, rng):
+    """the base samples of ``fantasy="joint"``: z (n_mc, q) as given, or drawn from ``rng``; TypeError for any acquisition
+    other than EI (LogEI, PI and LCB have no joint form)"""
+    from robo_amd.acquisition_functions.ei import EI
+    if not isinstance(acq, EI):
+        raise TypeError("fantasy='joint' (joint Monte-Carlo batch EI) is available for EI only (got %s)"
+                        % type(acq).__name__)
+    if z is not None:
+        return np.ascontiguousarray(z, dtype=np.float64)
+    if rng is None:
+        rng = np.random.RandomState(np.random.randint(0, 2 ** 31 - 1))
+    return rng.standard_normal((int(n_mc), max(int(q), 1)))
+
+
 def batch_finish(acq, kind, model, res, cand):
     """shared tail of the select_batch() methods: the reference's EI guards act on pick 0's flags only (a floored variance
     at an already-picked point is expected, not a degenerate batch); the picked rows in the caller's input space"""
@@ -326,18 +340,27 @@ class ClosedFormAcquisition(BaseAcquisitionFunction):
             res = model.gp.refine(self.kind, self.par, self._eta(eta), cand, n_starts, n_steps, step0, diagnostics)
             return refine_finish(self, self.kind, model, res, cand)
 
-    def select_batch(self, X, q, fantasy="kriging_believer", liar=None, diagnostics=False, eta=None):
+    def select_batch(self, X, q, fantasy="kriging_believer", liar=None, diagnostics=False, eta=None, *, n_mc=128, z=None,
+                     rng=None):
         """q proposals from ONE candidate batch X ((M, D) in the caller's input space, or a device batch
         ``_lib.Candidates`` in the normalised one) by greedy selection with fantasised picks (robo_acq_batch_cand): pick 0
         is the sweep's argmax; after every pick the posterior of all candidates is conditioned on a fantasy observation
         there -- the posterior mean (``kriging_believer``) or the constant ``liar`` ("min" | "mean" | "max" of the observed
         targets, or a float) -- with the hyper-parameters, the constant mean and the output normalisation frozen.
         -> (q', D) points in the caller's input space, q' < q only when a NaN winner ended the selection.  ``last_batch``
-        keeps the library's result (indices, values, fantasies, flags, diagnostics)."""
+        keeps the library's result (indices, values, fantasies, flags, diagnostics).
+        ``fantasy="joint"`` (EI only) picks by joint Monte-Carlo batch EI instead (robo_qei_batch_cand): no fantasies; the
+        increments of q-EI over ``n_mc`` scenarios whose base samples are ``z`` (n_mc, q), or drawn from ``rng``;
+        ``last_batch`` is then a ``_lib.QEIResult`` (gains, qei)."""
         model = self.model
+        if fantasy == "joint":
+            z = joint_base_samples(self, q, n_mc, z, rng)
         refine_model_check(model, self.__class__.__name__, "select_batch")
         model._materialise()
         with staged_candidates(model, X) as cand:
+            if fantasy == "joint":
+                res = model.gp.select_batch_joint(self.par, self._eta(eta), cand, q, z, diagnostics)
+                return batch_finish(self, self.kind, model, res, cand)
             res = model.gp.select_batch(self.kind, self.par, self._eta(eta), cand, q, fantasy,
                                         batch_liar(model, fantasy, liar), diagnostics)
             return batch_finish(self, self.kind, model, res, cand)

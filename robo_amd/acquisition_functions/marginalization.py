@@ -491,11 +491,17 @@ class MarginalizationGPMCMC(BaseAcquisitionFunction):
             res = _lib.acq_refine(gps, est[0].kind, est[0].par, eta, cand, n_starts, n_steps, step0, diagnostics)
             return refine_finish(self, est[0].kind, m0, res, cand)
 
-    def select_batch(self, X_test, q, fantasy="kriging_believer", liar=None, diagnostics=False):
+    def select_batch(self, X_test, q, fantasy="kriging_believer", liar=None, diagnostics=False, *, n_mc=128, z=None,
+                     rng=None):
         """Greedy batch of q proposals under the marginalised acquisition (robo_acq_batch_marginal_cand): as
         ClosedFormAcquisition.select_batch; every hyper-parameter sample is conditioned on its own fantasy (its own posterior
-        mean for the kriging believer) and keeps its own incumbent, the values are averaged in sample order."""
-        from robo_amd.acquisition_functions.base_acquisition import batch_finish, batch_liar, refine_model_check
+        mean for the kriging believer) and keeps its own incumbent, the values are averaged in sample order.
+        ``fantasy="joint"`` (EI only): joint Monte-Carlo batch EI (robo_qei_batch_marginal_cand), the base samples shared
+        by the hyper-parameter samples."""
+        from robo_amd.acquisition_functions.base_acquisition import (batch_finish, batch_liar, joint_base_samples,
+                                                                     refine_model_check)
+        if fantasy == "joint":
+            z = joint_base_samples(self.acquisition_func, q, n_mc, z, rng)
         if not isinstance(self.acquisition_func, ClosedFormAcquisition) or not self.estimators:
             raise TypeError("MarginalizationGPMCMC.select_batch is available for EI, LogEI, PI and LCB only (got %s)"
                             % type(self.acquisition_func).__name__)
@@ -512,6 +518,9 @@ class MarginalizationGPMCMC(BaseAcquisitionFunction):
         eta = np.array([e._eta(None) for e in est])
         m0 = est[0].model
         with staged_candidates(m0, X_test) as cand:
+            if fantasy == "joint":
+                res = _lib.qei_batch(gps, est[0].par, eta, cand, q, z, diagnostics)
+                return batch_finish(self, est[0].kind, m0, res, cand)
             res = _lib.acq_batch(gps, est[0].kind, est[0].par, eta, cand, q, fantasy, batch_liar(m0, fantasy, liar),
                                  diagnostics)
             return batch_finish(self, est[0].kind, m0, res, cand)

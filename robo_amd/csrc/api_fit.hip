@@ -61,6 +61,7 @@ int32_t robo_gp_destroy(robo_gp* g) {
         refine_free(g->refine);
     }
     batch_free(g->batch);
+    qei_free(g->qei);
     mes_free(g->mes);
     rep_free(g->rep);
     hyper_free(g->hyper);

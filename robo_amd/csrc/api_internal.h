@@ -131,6 +131,9 @@ int ig_per_cost_core(robo_gp* g, robo_cand* k, robo_cand* rep, int32_t npts, dou
                      const double* lmb, const double* W, const double* dlogPdMu, const double* dlogPdSigma,
                      const double* dlogPdMudMu, robo_gp* cost_gp, robo_cand* cost_k, double overhead);
 
+// ---- qei.hip: joint Monte-Carlo batch EI -------------------------------------------------------------------------------------
+void qei_free(QeiWork* w);      // the state robo_qei_batch_* keeps with a GP (its BatchWork, the scenarios' block, the diagnostics)
+
 // ---- refine.hip: what the refinement drivers share (robo_acq_refine_*, robo_cei_refine_cand) -----------------------------------------
 inline size_t refine_trace_len(int K, int T, int D) { return (size_t)(T + 1) * K * (2 * D + 3); }
 int refine_check_steps(int32_t n_starts, int32_t n_steps, double step0);      // out of range: ROBO_BAD_ARGUMENT

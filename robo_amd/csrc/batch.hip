@@ -23,13 +23,9 @@
 // Ordering is the stream's alone: the winner's index stays in device memory (BatchState::idx) and the next pick's
 // kernels read x_j from the candidate buffer through it.  Every sum has a fixed order that does not depend on the grid.
 #include "api_internal.h"
-#include "kern_math.h"
+#include "batch_cond.h"
 
 namespace robo {
-
-constexpr int BC_CAND = 64;          // candidates per workgroup of the conditioning pass (one per lane; the 4 waves split the rows)
-constexpr int BC_ROWS = 32;          // training rows per wave and tile
-constexpr int BC_LD = NB + 2;
 
 __device__ __forceinline__ double batch_nan() { return __longlong_as_double(0x7FF8000000000000LL); }
 
@@ -194,11 +190,7 @@ __global__ __launch_bounds__(256) void batch_bwd_kernel(const double* __restrict
 }
 
 // ---- the fused conditioning pass ----------------------------------------------------------------------------------------
-// A workgroup owns 64 candidates, one per lane; its four waves split every tile of 128 training points (32 rows each,
-// staged as [dimension][row]: all lanes of a wave read the same word, a broadcast).  A lane keeps its candidate's scaled
-// coordinates in registers while dim <= 16 (SMALLD) and re-reads them per chunk of 16 dimensions otherwise.  Per pair the
-// covariance is accumulated dimension by dimension with direct differences, as the cross-gram generators of predict.hip
-// do, and multiplied into the lane's running k_*(x)^T beta.  The four partial sums are added in wave order.
+// k_*(x)^T beta of a workgroup's 64 candidates by the shared tile loop (batch_cond.h).
 // Then lane by lane: c, the update of (mu_lat, var_lat) in memory, transform + floor, the acquisition as acq_kernel
 // forms it, accumulated over the samples in sample order.  The reduction over the candidates is the sweep's own
 // (launch_argmax, acq.hip).
@@ -219,66 +211,13 @@ __global__ __launch_bounds__(256) void batch_cond_kernel(BatchState st, int s, i
     const long long ii = live ? i : 0;
     const long long pj = st.idx[j - 1];
     for (int d = tid; d < D; d += 256) sJ[d] = Xc[pj * D + d] * ism[d];
-    double xc[16];
-    if (SMALLD) {
-#pragma unroll
-        for (int d = 0; d < 16; ++d) xc[d] = d < D ? Xc[ii * D + d] * ism[d] : 0.0;
-    }
-    const double* beta = st.beta + (size_t)s * n_pad;
-    const int nbk = (n + NB - 1) / NB;
-    double dot = 0.0;
-    for (int tile = 0; tile < nbk; ++tile) {
-        double acc[BC_ROWS], uu[BC_ROWS];
-#pragma unroll
-        for (int r = 0; r < BC_ROWS; ++r) cov_init<double, KIND>(cp, acc[r], uu[r]);
-        for (int d0 = 0; d0 < D; d0 += 16) {
-            __syncthreads();
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const int idx = tid + e * 256, row = idx >> 4, d = idx & 15;
-                const int rg = tile * NB + row;
-                sX[d * BC_LD + row] = (d0 + d < D && rg < n) ? Xs[(size_t)rg * D + d0 + d] : 0.0;
-            }
-            if (d0 == 0 && tid < NB) sB[tid] = tile * NB + tid < n ? beta[tile * NB + tid] : 0.0;
-            __syncthreads();
-            const int dn = D - d0 < 16 ? D - d0 : 16;
-            const double* sx = sX + wave * BC_ROWS;
-            if (SMALLD) {
-#pragma unroll
-                for (int d = 0; d < 16; ++d) {
-                    if (d < dn) {
-#pragma unroll
-                        for (int r = 0; r < BC_ROWS; ++r)
-                            cov_step<double, KIND>(cp, d, xc[d], sx[d * BC_LD + r], acc[r], uu[r]);
-                    }
-                }
-            } else {
-                for (int d = 0; d < dn; ++d) {
-                    const double xi = Xc[ii * D + d0 + d] * ism[d0 + d];
-#pragma unroll
-                    for (int r = 0; r < BC_ROWS; ++r)
-                        cov_step<double, KIND>(cp, d0 + d, xi, sx[d * BC_LD + r], acc[r], uu[r]);
-                }
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < BC_ROWS; ++r)
-            dot = fma(cov_finish<double, KIND>(cp, acc[r], uu[r]), sB[wave * BC_ROWS + r], dot);
-    }
+    const double dot = cond_kstar_dot<KIND, SMALLD>(Xc, Xs, ism, cp, n, st.beta + (size_t)s * n_pad, ii, sX, sB);
     sP[wave][lane] = dot;
     __syncthreads();
     if (wave != 0 || !live) return;
     const double ktb = (sP[0][lane] + sP[1][lane]) + (sP[2][lane] + sP[3][lane]);
-    double a0, u0;
-    cov_init<double, KIND>(cp, a0, u0);
-    for (int d = 0; d < D; ++d) cov_step<double, KIND>(cp, d, Xc[i * D + d] * ism[d], sJ[d], a0, u0);
-    // covariance of x and x_j under the real data, then under the earlier fantasies as well: c_t(x) of every earlier
-    // conditioning step t is kept, and  cov_t+1(x, x') = cov_t(x, x') - c_t(x) c_t(x') / d_t
-    double c = cov_finish<double, KIND>(cp, a0, u0) - ktb;
-    for (int t = 0; t < j - 1; ++t) {
-        const double* ct = st.chist + ((size_t)s * st.qcap + t) * st.m_pad;
-        c -= ct[i] * (ct[pj] / st.dhist[(size_t)s * st.qcap + t]);
-    }
+    const double c = cond_cov<KIND>(Xc, ism, cp, sJ, ktb, i, pj, j - 1, st.chist + (size_t)s * st.qcap * st.m_pad,
+                                    st.dhist + (size_t)s * st.qcap, st.m_pad);
     st.chist[((size_t)s * st.qcap + (j - 1)) * st.m_pad + i] = c;
 
     const size_t at = (size_t)s * st.m_pad + i;
@@ -404,6 +343,15 @@ int launch_batch_record(robo_ctx* ctx, const BatchState& st, const robo_cand* ca
     return ROBO_OK;
 }
 
+int launch_fwd_rows(robo_gp* gp, double* d_w, double* d_v, const int* d_stop) {
+    const int n = gp->n, n_pad = gp->n_pad, nbk = (n + NB - 1) / NB;
+    for (int i = 0; i < nbk; ++i)
+        hipLaunchKernelGGL(batch_fwd_kernel, dim3((unsigned)(nbk - 1 - i > 1 ? nbk - 1 - i : 1)), dim3(256), 0,
+                           gp->ctx->stream, (const double*)gp->d_K, n_pad, (const double*)gp->d_Linv, d_w, d_v, i, n, d_stop);
+    ROBO_LAUNCH_CHECK();
+    return ROBO_OK;
+}
+
 int launch_bwd_rows(robo_gp* gp, double* d_v, double* d_beta, const int* d_stop) {
     const int n = gp->n, n_pad = gp->n_pad, nbk = (n + NB - 1) / NB;
     for (int i = nbk - 1; i >= 0; --i)
@@ -417,7 +365,7 @@ int launch_bwd_rows(robo_gp* gp, double* d_v, double* d_beta, const int* d_stop)
 int launch_batch_condition(robo_gp* gp, const BatchState& st, const robo_cand* cand, int s, int j, int acq_kind, double par,
                            int fantasy_kind, double liar) {
     hipStream_t stream = gp->ctx->stream;
-    const int n = gp->n, n_pad = gp->n_pad, nbk = (n + NB - 1) / NB;
+    const int n = gp->n, n_pad = gp->n_pad;
     const double* Xc = cand->d_Xc;
     const double* Xs = gp->d_Xs;
     const double* ism = gp->d_theta;
@@ -426,9 +374,7 @@ int launch_batch_condition(robo_gp* gp, const BatchState& st, const robo_cand* c
     double* beta = st.beta + (size_t)s * n_pad;
     hipLaunchKernelGGL(batch_kstar_kernel, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, stream, st, s, j, Xc, Xs, ism,
                        gp->cov, n, n_pad, gp->noise, gp->y_mean, gp->y_std, fantasy_kind, liar);
-    for (int i = 0; i < nbk; ++i)
-        hipLaunchKernelGGL(batch_fwd_kernel, dim3((unsigned)(nbk - 1 - i > 1 ? nbk - 1 - i : 1)), dim3(256), 0, stream,
-                           (const double*)gp->d_K, n_pad, (const double*)gp->d_Linv, w, v, i, n, (const int*)st.stop);
+    ROBO_TRY(launch_fwd_rows(gp, w, v, st.stop));
     ROBO_TRY(launch_bwd_rows(gp, v, beta, st.stop));
     const dim3 grid((unsigned)((st.m + BC_CAND - 1) / BC_CAND));
 #define ROBO_COND_CALL(KIND)                                                                                              \

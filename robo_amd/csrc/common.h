@@ -335,6 +335,28 @@ struct BatchWork {
 int batch_alloc(robo_ctx* ctx, int64_t m, int64_t m_pad, int S, int n_pad, int q, BatchWork** out);
 void batch_free(BatchWork* w);
 
+// ---- joint Monte-Carlo batch EI (qei.hip) -------------------------------------------------------------------------------------
+// what a joint selection keeps on top of a BatchState of its own (whose chist / dhist hold c_t(x) / d_t, whose `fant` slots
+// report d_t and whose mean state is never touched); all arrays device memory of one block
+constexpr int QEI_MAX_Q = 64, QEI_MAX_K = 1024;
+struct QeiState {
+    int K;                          // scenarios
+    double* z;                      // [K][q] the caller's base samples
+    double* b;                      // [S][K] b^k = min(eta_s - par, f^k(picks so far))
+    double* acq;                    // q x m every candidate's value at every pick, or nullptr
+    double* coef;                   // (q - 1) x S x m c_t(x), or nullptr
+    double* best;                   // q x S x K the b^k every pick was made from, or nullptr
+};
+struct QeiWork {
+    int64_t m;
+    int S, n_pad, q, K;
+    BatchWork* base;                // the picks, the latent moments and the conditioning history (batch.hip's own block)
+    char* d_block;                  // z and b, laid out by qei_alloc's BlockLayout (block_layout.h)
+    double* d_diag;                 // [acq | coef | best] of a call that asks for them (grows)
+    size_t diag_cap;                // doubles
+    QeiState qs;
+};
+
 // ---- max-value entropy search (mes.hip) ------------------------------------------------------------------------------------
 // the state of one call; all arrays device memory of one block, per-sample arrays [S][K] / [S][7]
 struct MesState {
@@ -445,7 +467,7 @@ enum RoboEventSlot {
     EV_GRAD_BEGIN = 28,       // robo_gp_grad_loglik (always): everything after the factorisation; the descent launch of
     EV_GRAD_END = 29,         //   robo_paths_descend (always) and robo_paths_refine_cand
     EV_FOLD_BEGIN = 30,       // what follows the sweeps: KG's envelope kernel and MES's element-wise half (last sample),
-    EV_FOLD_END = 31,         //   EHVI's strip kernel, the passes of the path kernel
+    EV_FOLD_END = 31,         //   EHVI's strip kernel, the passes of the path kernel, q-EI's fold kernel of the last pick
     EV_CEI_BEGIN = 32,        // constrained EI's fold kernel
     EV_CEI_END = 33,
     EV_LAST = EV_CEI_END
@@ -548,6 +570,7 @@ struct robo_gp {
     unsigned long long winv_launched;   // fit_gen whose W build has been LAUNCHED (robo_gp_prefetch_inverse) but not yet read
     robo::RefineWork* refine;       // state + solve workspace of robo_acq_refine_* (refine.hip), kept between calls of one (K, D)
     robo::BatchWork* batch;         // state of robo_acq_batch_* (batch.hip), kept between calls of one (m, S)
+    robo::QeiWork* qei;             // state of robo_qei_batch_* (qei.hip), kept between calls of one (m, S, q, K)
     robo::MesWork* mes;             // state of robo_mes_eval_* (mes.hip), kept between calls of one (m, S, K)
     robo::RepWork* rep;             // state of robo_rep_sample* (represent.hip), kept with gps[0] between calls
     robo::HyperWork* hyper;         // workspace of robo_gp_grad_loglik_batch / robo_gp_optimize_hypers (hyperopt.hip)
@@ -771,7 +794,9 @@ int launch_argmax(robo_cand* cand, const double* d_vals, double scale);
 int launch_report_best(robo_cand* cand, double* h_pinned);
 int launch_acq_tail(robo_gp* gp, robo_cand* s, int acq_kind, double par, double eta, const long long* d_map, robo_cand* k,
                     double* h_report);
-// batch.hip: beta = L^-T v for ONE right-hand side by backward block rows with the fit's inverted diagonal blocks (v is consumed)
+// batch.hip: v = L^-1 w (w is consumed), then beta = L^-T v for ONE right-hand side by forward / backward block rows with
+// the fit's inverted diagonal blocks (v is consumed)
+int launch_fwd_rows(robo_gp* gp, double* d_w, double* d_v, const int* d_stop);                // *d_stop != 0: no-op
 int launch_bwd_rows(robo_gp* gp, double* d_v, double* d_beta, const int* d_stop = nullptr);   // *d_stop != 0: no-op
 int launch_cov(robo_gp* gp, robo_cand* cand, double* d_cov);
 int launch_mixture(robo_cand* cand, int S);

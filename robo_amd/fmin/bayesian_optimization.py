@@ -37,7 +37,7 @@ def bayesian_optimization(objective_function, lower, upper, num_iterations=30, X
                           maximizer="random", acquisition_func="log_ei", model_type="gp_mcmc", n_init=3, rng=None,
                           output_path=None, n_candidates=500, chain_length=200, burnin_steps=100, n_gpus=None,
                           devices=None, batch_size=1, fantasy="kriging_believer", liar="min", evaluate_batch=None,
-                          hyper_optimizer="host", n_restarts=8, n_features=1024):
+                          hyper_optimizer="host", n_restarts=8, n_features=1024, n_mc=128):
     """Minimise ``objective_function`` over the box [lower, upper] -> dict with x_opt, f_opt,
     incumbents, incumbent_values, runtime, overhead, X, y (same keys as the reference).
 
@@ -55,7 +55,15 @@ def bayesian_optimization(objective_function, lower, upper, num_iterations=30, X
     minimiser of one posterior sample path over the candidates, so ``batch_size=q`` proposes one point per path from one
     call: ``fantasy`` and ``liar`` are ignored (a path needs no fantasies).  With ``model_type="gp_mcmc"`` every path
     draws its own hyper-parameter sample.  One device only.
+
+    ``fantasy="joint"`` (``acquisition_func="ei"`` only): the proposals of a round are picked by joint Monte-Carlo batch
+    EI over ``n_mc`` scenarios drawn from this call's rng (``EI.select_batch``); ``liar`` is ignored.  Any other
+    acquisition with ``fantasy="joint"`` is a ValueError before anything is evaluated -- also with ``batch_size=1``, where
+    ``fantasy`` is otherwise unused.
     """
+    if fantasy == "joint" and acquisition_func != "ei":
+        raise ValueError("fantasy='joint' (joint Monte-Carlo batch EI) needs acquisition_func='ei', got '{}'"
+                         .format(acquisition_func))
     assert upper.shape[0] == lower.shape[0], "Dimension miss match"
     assert np.all(lower < upper), "Lower bound >= upper bound"
     assert n_init <= num_iterations, "Number of initial design point has to be <= than the number of iterations"
@@ -114,7 +122,8 @@ def bayesian_optimization(objective_function, lower, upper, num_iterations=30, X
 
     # batch_size > 1: rounds of batch_size proposals from one model fit (greedy selection with fantasised picks on the
     # device), evaluated one by one or by evaluate_batch(Xq) -> yq; batch_size = 1 is the reference's loop, untouched
-    batch = {} if batch_size == 1 else dict(batch_size=batch_size, fantasy=fantasy, liar=liar, evaluate_batch=evaluate_batch)
+    batch = {} if batch_size == 1 else dict(batch_size=batch_size, fantasy=fantasy, liar=liar, evaluate_batch=evaluate_batch,
+                                            **({"n_mc": n_mc} if fantasy == "joint" else {}))
     bo = BayesianOptimization(objective_function, lower, upper, acq, model, max_func, initial_points=n_init, rng=rng,
                               initial_design=init_latin_hypercube_sampling, output_path=output_path, **batch)
     x_best, f_min = bo.run(num_iterations, X=X_init, y=Y_init)

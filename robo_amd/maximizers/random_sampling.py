@@ -79,19 +79,22 @@ class RandomSampling(BaseMaximizer):
         return X[y.argmax()]
 
 
-    def maximize_batch(self, q, fantasy="kriging_believer", liar=None):
+    def maximize_batch(self, q, fantasy="kriging_believer", liar=None, n_mc=128):
         """q proposals from ONE candidate draw (the same recipe and random streams as maximize()) by the acquisition's
         greedy batch selection with fantasised picks (``select_batch``) -> (q', D).  q = 1 is maximize()."""
         if int(q) == 1:
             return np.asarray(self.maximize())[None, :]
         if self.shard:
             raise NotImplementedError("RandomSampling.maximize_batch: the candidate shard is not implemented for batches")
-        return _select_batch(self.objective_func, self.candidates(), q, fantasy, liar)
+        return _select_batch(self.objective_func, self.candidates(), q, fantasy, liar, n_mc, self.rng)
 
 
-def _select_batch(acq, X, q, fantasy, liar):
+def _select_batch(acq, X, q, fantasy, liar, n_mc=128, rng=None):
+    """fantasy="joint": joint Monte-Carlo batch EI over n_mc scenarios drawn from the maximiser's rng"""
     if not hasattr(acq, "select_batch"):
         raise TypeError("%s has no select_batch" % type(acq).__name__)
+    if fantasy == "joint":
+        return acq.select_batch(X, q, fantasy=fantasy, n_mc=n_mc, rng=rng)
     return acq.select_batch(X, q, fantasy=fantasy, liar=liar)
 
 
@@ -185,7 +188,7 @@ class DeviceRandomSampling(BaseMaximizer):
             cand.close()
 
 
-    def maximize_batch(self, q, fantasy="kriging_believer", liar=None):
+    def maximize_batch(self, q, fantasy="kriging_believer", liar=None, n_mc=128):
         """q proposals from ONE device-generated candidate batch (the recipe, the rng draw and the Philox seed of
         maximize()) by greedy selection with fantasised picks -> (q', D).  q = 1 is maximize()."""
         if int(q) == 1:
@@ -198,7 +201,7 @@ class DeviceRandomSampling(BaseMaximizer):
         cand = _lib.Candidates(sub.gp.ctx, m=max(self.n_samples, 1), seed=seed, n_uniform=int(self.n_samples * .7),
                                loc=(inc - lower) / (upper - lower), scale=0.1 / (upper - lower))
         try:
-            return _select_batch(self.objective_func, cand, q, fantasy, liar)
+            return _select_batch(self.objective_func, cand, q, fantasy, liar, n_mc, self.rng)
         finally:
             cand.close()
 
@@ -259,7 +262,7 @@ class DeviceSobolSampling(BaseMaximizer):
         finally:
             cand.close()
 
-    def maximize_batch(self, q, fantasy="kriging_believer", liar=None):
+    def maximize_batch(self, q, fantasy="kriging_believer", liar=None, n_mc=128):
         """q proposals from the same Sobol' points as maximize() by greedy selection with fantasised picks -> (q', D).
         q = 1 is maximize()."""
         if int(q) == 1:
@@ -270,6 +273,6 @@ class DeviceSobolSampling(BaseMaximizer):
         eng = qmc.Sobol(d=np.asarray(sub.lower).shape[0], scramble=True, seed=self.seed)
         cand = _lib.Candidates(sub.gp.ctx, m=max(self.n_samples, 1), sobol=eng, first=0)
         try:
-            return _select_batch(self.objective_func, cand, q, fantasy, liar)
+            return _select_batch(self.objective_func, cand, q, fantasy, liar, n_mc, self.rng)
         finally:
             cand.close()

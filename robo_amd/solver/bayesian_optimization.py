@@ -72,13 +72,21 @@ class BayesianOptimization(BaseSolver):
 
     def __init__(self, objective_func, lower, upper, acquisition_func, model, maximize_func,
                  initial_design=init_random_uniform, initial_points=3, output_path=None, train_interval=1,
-                 n_restarts=1, rng=None, batch_size=1, fantasy="kriging_believer", liar="min", evaluate_batch=None):
+                 n_restarts=1, rng=None, batch_size=1, fantasy="kriging_believer", liar="min", evaluate_batch=None,
+                 n_mc=128):
         self.rng = np.random.RandomState(np.random.randint(100000)) if rng is None else rng
         # batch_size > 1: a round trains once, takes batch_size proposals from maximize_func.maximize_batch (greedy
         # selection with fantasised picks) and evaluates them one by one -- or all at once with evaluate_batch(Xq) -> yq
         self.batch_size, self.fantasy, self.liar, self.evaluate_batch = int(batch_size), fantasy, liar, evaluate_batch
+        self.n_mc = int(n_mc)                  # fantasy="joint": scenarios of the joint Monte-Carlo batch EI
         if self.batch_size < 1:
             raise ValueError("batch_size must be >= 1")
+        if fantasy == "joint":                 # before anything is evaluated; also with batch_size = 1, where no fantasy is used
+            from robo_amd.acquisition_functions.ei import EI
+            inner = getattr(acquisition_func, "acquisition_func", acquisition_func)
+            if not isinstance(inner, EI):
+                raise ValueError("fantasy='joint' (joint Monte-Carlo batch EI) is available for EI only (got %s)"
+                                 % type(inner).__name__)
         if self.batch_size > 1 and not hasattr(maximize_func, "maximize_batch"):      # before anything is evaluated
             raise TypeError("%s has no maximize_batch: batch_size > 1 needs RandomSampling, DeviceRandomSampling or "
                             "DeviceSobolSampling" % type(maximize_func).__name__)
@@ -242,6 +250,8 @@ class BayesianOptimization(BaseSolver):
             return self.initial_design(self.lower, self.upper, n, rng=self.rng)
         self.model.train(X, y, do_optimize=do_optimize)
         self.acquisition_func.update(self.model)
+        if self.fantasy == "joint":
+            return self.maximize_func.maximize_batch(n, fantasy=self.fantasy, n_mc=self.n_mc)
         return self.maximize_func.maximize_batch(n, fantasy=self.fantasy, liar=self.liar)
 
     def choose_next(self, X=None, y=None, do_optimize=True):
