@@ -124,6 +124,12 @@ int32_t robo_ctx_set_phase_events(robo_ctx* ctx, int32_t on);
  * kernel finishes a pair: -1 = default: the lean finish, which evaluates the covariance to a proven 8e-13 amp and adds 1e4
  * times that error to the margin, where that term stays within 1e-2 of the prior standard deviation, the finish to the
  * last bit otherwise; 0 never the lean finish; 1 wherever the dot-form kernel runs: tests.  Rigorous bounds either way),
+ * acq_screen_single (a single-precision first stage in front of that pass: -1 = default: where the lean finish is selected
+ * and the first stage's own margin, 1.5 times a proven 6.3e-7 amp per covariance, stays within half the prior standard
+ * deviation, an argmax-only call first forms its bounds with a single-precision finish and solves that stage's survivors
+ * when they fit one tile of 128 and the cap; otherwise the fp64 pass runs as before and the factor's first stage pauses for
+ * 1, 2, 4, ... calls; 0 never; 1 wherever the lean finish runs; 2 as 1, and robo_acq_screen_bounds returns the first
+ * stage's bounds: tests.  Rigorous bounds either way, same results),
  * acq_screen_fused_tail (1 = default: when the screen's survivors fit one block of 256, their output transform, acquisition
  * values, argmax, index map and report run as one single-workgroup launch; 0: the five launches.  Same bits either way),
  * trsm_chain (small batches on two or more block rows, solved by ONE launch whose block rows hand their tiles to each
@@ -349,17 +355,25 @@ int32_t robo_acq_eval(robo_gp* gp, int32_t acq_kind, double par, double eta, con
 #define ROBO_SCREEN_PROBE_USED 2   /* ... after the incumbent was taken from the exact values of the 128 candidates with the largest upper bounds */
 #define ROBO_SCREEN_FELL_BACK 3    /* too many survivors (or none below the bound): the plain sweep ran on the whole batch */
 int32_t robo_cand_last_screen(robo_cand* cand, int64_t* out_n_screened, int64_t* out_n_survivors, int32_t* out_outcome);
-/* How the last bounds pass on this handle finished its covariances (tuning key acq_screen_lean).  *out_finish: */
+/* How the last bounds pass on this handle finished its covariances (tuning key acq_screen_lean): the fp64 finish selected
+ * for the call, lean or full -- also when the single-precision first stage decided the call alone or supplied the bounds
+ * (robo_cand_last_screen_first tells).  *out_finish: */
 #define ROBO_SCREEN_FINISH_NONE 0  /* no bounds pass yet, or the direct-difference kernel (it has one finish)        */
 #define ROBO_SCREEN_FINISH_FULL 1  /* the dot-form kernel, square root and exponential to the last bit               */
 #define ROBO_SCREEN_FINISH_LEAN 2  /* the dot-form kernel, covariance to 8e-13 amp, that error in the margin           */
 /* *out_fused_tail (may be NULL): 1 when the last argmax-only acquisition call on this handle ran its survivors' output
  * transform, acquisition, argmax, index map and report as the one single-workgroup launch (acq_screen_fused_tail), else 0. */
 int32_t robo_cand_last_screen_finish(robo_cand* cand, int32_t* out_finish, int32_t* out_fused_tail);
+/* The single-precision first stage of the last argmax-only acquisition call on this handle (tuning key acq_screen_single).
+ * *out_stage: 0 it did not run (not an eligible call, the rule, its pause), 1 it decided the call: its survivors are the
+ * ones robo_cand_last_screen counts as solved, 2 it ran and the fp64 pass followed on the whole batch.  *out_kept: the
+ * first stage's survivor count (0 with stage 0).  Either pointer may be NULL.                                          */
+int32_t robo_cand_last_screen_first(robo_cand* cand, int32_t* out_stage, int64_t* out_kept);
 /* The screen's bounds themselves (soundness tests, A/B tools): out_upper / out_lower (m,) with
  * lower <= the value robo_acq_eval_cand returns for the candidate <= upper; NaN coordinates give NaN bounds.  Needs a
  * (kind, par) the screen handles (LCB: kappa >= 0) and fp64 covariance entries; batch size, tuning keys and the
- * conditioning guard are not consulted.                                                                            */
+ * conditioning guard are not consulted.  The bounds are the fp64 pass's; with acq_screen_single = 2 (tests) they are the
+ * single-precision first stage's wherever that stage may run.                                                        */
 int32_t robo_acq_screen_bounds(robo_gp* gp, int32_t acq_kind, double par, double eta, robo_cand* cand, double* out_upper,
                                double* out_lower);
 /* the element-wise half alone, for (mean, var) produced by any other BaseModel plugin

@@ -54,7 +54,7 @@ SYMBOLS = [
     "robo_cand_create_random", "robo_cand_create_sobol", "robo_cand_get_point", "robo_cand_workspace_chunk", "robo_cand_last_solve_kernel",
     "robo_gp_predict_cand", "robo_gp_predict", "robo_gp_predict_cov", "robo_gp_predict_grad", "robo_gp_predict_mixture_cand",
     "robo_acq_eval_cand", "robo_acq_eval", "robo_acq_eval_moments", "robo_acq_eval_marginal_cand", "robo_acq_eval_sum_cand",
-    "robo_cand_last_screen", "robo_cand_last_screen_finish", "robo_acq_screen_bounds",
+    "robo_cand_last_screen", "robo_cand_last_screen_finish", "robo_cand_last_screen_first", "robo_acq_screen_bounds",
     "robo_acq_refine_cand", "robo_acq_refine_marginal_cand",
     "robo_rep_sample", "robo_rep_sample_batch",
     "robo_acq_batch_cand", "robo_acq_batch_marginal_cand", "robo_qei_batch_cand", "robo_qei_batch_marginal_cand",
@@ -221,6 +221,7 @@ def lib():
         "robo_acq_eval": [vp, i32, dbl, dbl, _dp, i64, _dp, _dp, C.POINTER(i64), C.POINTER(C.c_uint32)],
         "robo_cand_last_screen": [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i32)],
         "robo_cand_last_screen_finish": [vp, C.POINTER(i32), C.POINTER(i32)],
+        "robo_cand_last_screen_first": [vp, C.POINTER(i32), C.POINTER(i64)],
         "robo_acq_screen_bounds": [vp, i32, dbl, dbl, vp, _dp, _dp],
         "robo_acq_eval_moments": [vp, i32, dbl, dbl, _dp, _dp, i64, _dp, _dp, C.POINTER(i64), C.POINTER(C.c_uint32)],
         "robo_acq_eval_marginal_cand": [pp, i32, i32, dbl, _dp, vp, _dp, _dp, C.POINTER(i64),
@@ -307,6 +308,13 @@ def lib():
         "robo_gp_predict_mixture_cand_multi": [vp, pp, C.POINTER(i32), pp, _dp, _dp],
     }
     for name, args in sig.items():
+        if path != DEFAULT_LIBRARY and not hasattr(L, name):
+            # a build given through use_library (bench.py --lib: an A/B build of another commit) may lack an entry point of
+            # this binding: it loads, and the call says so.  The product library must export every one (build() checks it)
+            def missing(*_, _name=name, _path=path):
+                raise RoboHipUnavailable("%s does not export %s" % (_path, _name))
+            setattr(L, name, missing)
+            continue
         fn = getattr(L, name)
         fn.argtypes = args
         fn.restype = i32
@@ -662,6 +670,13 @@ class Candidates(object):
         f, t = C.c_int32(0), C.c_int32(0)
         check(lib().robo_cand_last_screen_finish(self._h, C.byref(f), C.byref(t)))
         return bool(t.value)
+
+    def screen_first(self):
+        """the single-precision first stage of the last argmax-only acquisition call on this handle -> (stage, survivors):
+        stage 0 it did not run, 1 it decided the call, 2 it ran and the fp64 pass followed"""
+        stage, kept = C.c_int32(0), C.c_int64(0)
+        check(lib().robo_cand_last_screen_first(self._h, C.byref(stage), C.byref(kept)))
+        return int(stage.value), int(kept.value)
 
     def last_screen(self):
         """what the last argmax-only acquisition call on this handle did -> (candidates screened, survivors, SCREEN_* outcome)"""

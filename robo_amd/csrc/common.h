@@ -240,6 +240,10 @@ struct Tuning {
     int acq_screen_lean;         // ... and that kernel's pairs finished to SD_LEAN_EPS amp instead of to the last bit: -1 (default)
                                  // where the term this adds to delta stays within SCREEN_LEAN_MAX of the prior standard
                                  // deviation, 0 never, 1 wherever the dot kernel runs (tests)
+    int acq_screen_single;       // ... and, in front of that pass, the same kernel with a single-precision finish (SD_SINGLE_EPS amp) whose
+                                 // survivors are solved when they fit one tile: -1 (default) where the lean finish is selected and the
+                                 // term this adds to delta stays within SCREEN_SINGLE_MAX of the prior standard deviation, 0 never, 1
+                                 // wherever the lean finish runs, 2 as 1 and robo_acq_screen_bounds returns that stage's bounds (tests)
     int acq_screen_fused_tail;   // ... survivors that fit one partial block: output transform, acquisition, argmax, index map and
                                  // report in ONE single-workgroup launch (1, default); 0: the five launches (tests, A/B)
     int trsm_chain;              // small batches on >= 2 block rows: all block rows in ONE launch chained by hand-offs (trsm_chain.hip)
@@ -582,6 +586,7 @@ struct robo_gp {
     unsigned long long alpha_gen;   // fit_gen alpha was computed for (0: none)
     unsigned long long screen_gen;  // fit_gen the back-off below belongs to
     int screen_skip, screen_backoff;   // eligible calls still to pass unscreened after a failed screen; length of the next pause
+    int single_skip, single_backoff;   // the same pair for the screen's single-precision first stage alone (same screen_gen)
 };
 
 struct robo_cand {
@@ -637,6 +642,8 @@ struct robo_cand {
     int scr_outcome;
     const char* scr_bounds_kernel;  // name of the kernel that ran the last bounds pass on this handle (diagnostics: tests)
     int scr_finish;                 // ... and its finish: ROBO_SCREEN_FINISH_* (robo_cand_last_screen_finish)
+    int scr_first_stage;            // robo_cand_last_screen_first: 0 no first stage, 1 it decided the call, 2 the fp64 pass followed
+    int64_t scr_first_kept;         // ... and its survivor count
     bool scr_tail_fused;            // the last argmax-only call ran its survivors' tail as acq_tail_kernel (same accessor)
     // the chained solve (trsm_chain.hip), lazy, grows: [ticket | time-out | progress words] zeroed per launch, then the
     // per-(tile, block row) partial sums

@@ -60,6 +60,24 @@ __device__ __forceinline__ double exp_nonpos(double x) {   // x <= 0
     return x < -745.2 ? 0.0 : ldexp(p, (int)n);
 }
 
+// The single-precision hardware functions, bare: ONE instruction each on the device (v_sqrt_f32, v_exp_f32: no
+// denormal scaling, no special-value fix-up, 1 ulp each by the ISA manual), the C++ library's float functions off it (the
+// interpreter under tests/hipemu, which rounds correctly: the MI355X twins of the tests are the binding ones).
+__device__ __forceinline__ float hw_sqrt_f32(float x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_sqrtf(x);
+#else
+    return std::sqrt(x);
+#endif
+}
+__device__ __forceinline__ float hw_exp2_f32(float x) {     // 2^x; a result below 2^-126 is 0 on the device
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_exp2f(x);
+#else
+    return std::exp2(x);
+#endif
+}
+
 // exp of a non-positive argument: the trimmed fp64 form above, the library's for fp32
 template <class T>
 __device__ __forceinline__ T exp_np(T x) {

@@ -116,6 +116,51 @@
 //   -- U_c falls by at most delta while the prior variance it is taken at is loose by orders more.  The headline's fit gives
 //   2.7e-3, config 2's 1.4e-3; a nearly singular K (tiny noise, long length scales) takes the full finish, whose kernel and
 //   delta are the previous ones bit for bit.  sum_j |alpha_j| reaches the host in alpha_ensure's one copy per fit_gen.
+//
+// The single-precision first stage (screen_dot_finish_single; acq_sweep_best's cascade).  The chained solve costs the same for
+// 1 and for 128 survivors, and the survivor count stays below a dozen while delta is a few tenths of the prior standard
+// deviation (NOTES.md "A single-precision first stage"), so an argmax-only call first forms its bounds from a covariance
+// good to  |k~ - k| <= SD_SINGLE_EPS amp,  SD_SINGLE_EPS = 6.3e-7:  the fp64 MFMA distance, the centred norms, alpha, the four
+// fp64 accumulators and the reduction as in the other finishes, but t (x) rounded to float and k~ from v_sqrt_f32, v_exp_f32
+// and five more fp32 instructions.  Candidate c's delta gains
+//     SCREEN_SINGLE_SAFETY SD_SINGLE_EPS |y_std| sum_j |amp alpha_j|,     SCREEN_SINGLE_SAFETY = 1.5   (together 9.45e-7).
+//   Error of that k~, in units of amp, v = 2^-24 (the unit roundoff of float).  k = q e^-s, q = 1 + s + t / 3, s = sqrt(t) as
+//   above; t (x) in fp64 is taken as given, and the fp64 steps in front of the conversion are the lean finish's.
+//   Hardware figures ASSUMED: v_sqrt_f32 and v_exp_f32 return their result within 1 ulp (relative 2 v) of the exact function of
+//   the float they are given (the CDNA ISA manual's accuracy table); the conversions and v_add / v_mul / v_fma_f32 round to
+//   nearest.  tests/test_acq_screen_single.py measures the whole finish on every float of the binade [4, 8) of t.
+//     rounding t  t~ = t (1 + d), |d| <= v:  s moves by v / 2 relative, and |dk / d ln s| = s^2 (1 + s) e^-s / 3 <= 0.60 (at
+//                s = 1 + sqrt 3; q is formed from t~ and s~ = sqrt(t~) consistently); taken at the lean finish's 0.942:  0.47 v.
+//     root        s~ = sqrt(t~) (1 + 2 v'):  0.942 x 2 v = 1.88 v.
+//     q           1 + s~ one rounding (<= v q), the FMA one (v q), the constant 1/3 as a float is off by 2.98e-8 = 0.5 v
+//                relative (v t / 6 <= 0.5 v q):  2.5 v q, and q e^-s <= 1:  2.5 v.
+//     exponent    the argument of 2^x is ONE product  s~ x (-log2 e as a float):  the constant is off by 1.33e-8 = 0.224 v
+//                relative, the product rounds once (v):  1.224 v |x| in x, i.e. 1.224 v s relative in e^-s, and
+//                k s <= max_s s q e^-s = 1.18:  1.45 v.  (A residual-corrected argument -- a second FMA with the constant's
+//                low part -- would take 0.26 v of that; the budget does not need it.)
+//     2^x         1 ulp: 2 v relative, k <= 1:  2 v.  Below 2^-126 the instruction returns 0 (no denormals): off by < 1.2e-38.
+//     product     q~ e~ one rounding:  v.  The conversion to double is exact, the FMA with alpha is the other finishes'.
+//   Sum: (0.47 + 1.88 + 2.5 + 1.45 + 2 + 1) v = 9.3 v; second-order terms (products of two of the above) < 0.1 v; the lean
+//   fp64 steps in front 1e-15.  9.4 v = 5.6e-7 < SD_SINGLE_EPS = 10.5 v = 6.3e-7.  RBF (q = 1, x = -r2 / 2): rounding x (v),
+//   the product with log2 e (1.224 v), each times |x| e^x <= 1 / e, and 2 v of 2^x:  2.9 v.
+//   No select.  The lower clamp of t (x) stays, in fp64; t below the floats' range becomes 0 and gives s = 0, k~ = 1 (true k
+//   within 1e-38 of it).  A far candidate: s and q stay finite floats up to t = 3.4e38, 2^x is 0 from x = -150 on, so k~ is 0,
+//   never a large number.  t beyond the floats' range (r2 > 6.8e37) or a NaN / infinite coordinate gives k~ = NaN (inf x 0):
+//   the mean and both bounds are NaN, `U_c < b` is false, a survivor -- and the NaN / infinite coordinate makes the norm term
+//   of delta NaN whatever k~ is, as above.
+//   The rule (screen_single_wanted).  acq_screen_single: -1 the rule, 0 never, 1 wherever the lean finish runs, 2 as 1 and
+//   robo_acq_screen_bounds returns the FIRST STAGE's bounds instead of the fp64 ones (tests; under every other value it
+//   returns the fp64 bounds, bit for bit what it returned before).  Under the rule the first stage runs where the lean finish
+//   is selected, its term is at most SCREEN_SINGLE_MAX = 0.5 of the prior standard deviation,
+//       SCREEN_SINGLE_SAFETY SD_SINGLE_EPS sqrt(amp) sum_j |alpha_j| <= 0.5            (sum_j |alpha_j| <= 5.3e5 at amp = 1)
+//   (the headline's fit: 0.32, config 2's: 0.16), and the factor is not in the first stage's own pause.
+//   The cascade (acq_sweep_best).  First stage admitted: scale_inputs, the bounds kernel with the single finish, the count, the
+//   one synchronisation.  With 1 <= kept <= min(NB, cap) the call goes on from the gather exactly as after the fp64 pass -- the
+//   same launches, no further synchronisation; every survivor of the fp64 bounds is among the first stage's (its U_c is
+//   larger, its b smaller), so (max, argmax, flags) are the same bits.  Otherwise the fp64 path runs on the whole batch from
+//   launch_screen_bounds, unchanged (count, probe, cap, fall-back, screen_skip), and the factor's first stage pauses for
+//   1, 2, 4, ... eligible calls (reset by a new fit, back to 1 after a success): a regime the first stage cannot decide pays
+//   its kernel a vanishing number of times.
 #include <cmath>
 
 #include "api_internal.h"
@@ -500,6 +545,33 @@ __device__ __forceinline__ void screen_dot_finish_lean(const v4d acc, double nc,
     }
 }
 
+// The single-precision finish (header: "The single-precision first stage"): t (x) rounded to float behind the fp64 clamp, k~ from
+// the bare hardware root and 2^x (kern_math.h hw_sqrt_f32 / hw_exp2_f32), back to double for the FMA with alpha.  Per pair: two
+// fp64 instructions in front, two conversions, sqrt, add, fma, mul, exp, mul, and the fp64 FMA -- 11 against the lean
+// finish's 27, no select.
+constexpr double SD_SINGLE_EPS = 6.3e-7;
+constexpr double SCREEN_SINGLE_SAFETY = 1.5;
+constexpr double SCREEN_SINGLE_MAX = 0.5;     // of the prior standard deviation: the most the first stage's term may add to delta
+template <int KIND>
+__device__ __forceinline__ void screen_dot_finish_single(const v4d acc, double nc, const double* __restrict__ al, double (&dot)[4]) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        float kv;
+        if (KIND == ROBO_KERNEL_MATERN52_ARD) {
+            const float t = (float)fmax(fma(5.0, acc[r], nc), 5.0 * SD_R2_MIN);
+            const float s = hw_sqrt_f32(t);
+            const float q = fmaf(t, 0.333333333f, 1.0f + s);
+            kv = q * hw_exp2_f32(s * -1.44269504f);
+        } else {
+            const float x = (float)fmin(fma(-0.5, acc[r], nc), -0.5 * SD_R2_MIN);
+            kv = hw_exp2_f32(x * 1.44269504f);
+        }
+        dot[r] = fma((double)kv, al[r], dot[r]);
+    }
+}
+
+enum ScreenFinish { SD_FULL = 0, SD_LEAN = 1, SD_SINGLE = 2 };     // the template argument of screen_bounds_dot_kernel
+
 constexpr int SD_CAND = 64;          // candidates per workgroup: one MFMA column tile of 16 per wave
 constexpr int SD_STAGE = NB;         // training rows per LDS stage: 8 row tiles, swept by every wave
 
@@ -507,7 +579,7 @@ constexpr int SD_STAGE = NB;         // training rows per LDS stage: 8 row tiles
 // and norms, alpha_norm = the block [sum_j |alpha_j| sqrt(k_jj), sum_j |alpha_j|, max_j |b_j|^2, -, centre].  A wave holds its 16
 // candidates' centred coordinates as the B operand for the whole sweep; a lane owns 4 training rows x 1 candidate of every
 // 16 x 16 pair tile and finishes the tile while the matrix pipe forms the next one.
-template <int KIND, int KS, bool LEAN>
+template <int KIND, int KS, ScreenFinish FINISH>
 __global__ __launch_bounds__(256) void screen_bounds_dot_kernel(const double* __restrict__ Xcs, const double* __restrict__ Xs,
                                                                 const double* __restrict__ alpha,
                                                                 const double* __restrict__ alpha_norm, CovParams cp, int n,
@@ -565,7 +637,8 @@ __global__ __launch_bounds__(256) void screen_bounds_dot_kernel(const double* __
 #pragma unroll
                 for (int kk = 0; kk < KS; ++kk) nxt = mfma_f64(sA[((t + 1) * KS + kk) * 64 + lane], b[kk], nxt);
             }
-            if (LEAN) screen_dot_finish_lean<KIND>(acc, ncf, sAl + t * 16 + g * 4, dot);
+            if (FINISH == SD_SINGLE) screen_dot_finish_single<KIND>(acc, ncf, sAl + t * 16 + g * 4, dot);
+            else if (FINISH == SD_LEAN) screen_dot_finish_lean<KIND>(acc, ncf, sAl + t * 16 + g * 4, dot);
             else screen_dot_finish<KIND>(acc, ncf, sAl + t * 16 + g * 4, dot);
             acc = nxt;
         }
@@ -584,7 +657,8 @@ __global__ __launch_bounds__(256) void screen_bounds_dot_kernel(const double* __
         const double r2_err = (double)(4 * KS + 6) * 4.44089209850062616e-16 * (nc + alpha_norm[2]);
         double delta = SCREEN_DELTA_REL * (fabs(y_mean) + fabs(y_std) * (fabs(mean_c) + sqrt(fabs(kself)) * alpha_norm[0])) +
                        SCREEN_DOT_SAFETY * fabs(y_std) * fabs(cp.amp) * ck * r2_err * alpha_norm[1];
-        if (LEAN) delta += SCREEN_LEAN_SAFETY * SD_LEAN_EPS * fabs(y_std) * fabs(cp.amp) * alpha_norm[1];
+        if (FINISH != SD_FULL) delta += SCREEN_LEAN_SAFETY * SD_LEAN_EPS * fabs(y_std) * fabs(cp.amp) * alpha_norm[1];
+        if (FINISH == SD_SINGLE) delta += SCREEN_SINGLE_SAFETY * SD_SINGLE_EPS * fabs(y_std) * fabs(cp.amp) * alpha_norm[1];
         double u, l;
         screen_bounds(acq_kind, par, eta, mt, delta, v_prior, u, l);
         up[i] = u;
@@ -791,6 +865,16 @@ static bool screen_lean_wanted(const robo_gp* g) {
     return term <= SCREEN_LEAN_MAX;              // (a NaN sum takes the full finish)
 }
 
+// whether this factor's argmax-only calls may form their bounds with the single-precision finish first (header: "The
+// single-precision first stage"; the pause is acq_sweep_best's); alpha_ensure has run
+static bool screen_single_wanted(const robo_gp* g) {
+    const int t = g->ctx->tune.acq_screen_single;
+    if (t == 0 || !screen_dot_wanted(g) || !screen_lean_wanted(g)) return false;
+    if (t > 0) return true;
+    const double term = SCREEN_SINGLE_SAFETY * SD_SINGLE_EPS * std::sqrt(std::fabs(g->cov.amp)) * g->dot_alpha_sum;
+    return term <= SCREEN_SINGLE_MAX;            // (a NaN sum: no first stage)
+}
+
 static int screen_buffers(robo_cand* k) {
     const size_t mp = (size_t)k->m_pad;
     if (!k->d_scr_up) ROBO_TRY(dev_alloc(&k->d_scr_up, mp));
@@ -803,8 +887,10 @@ static int screen_buffers(robo_cand* k) {
     return ROBO_OK;
 }
 
-// scaled rows of k and the bounds of every candidate into k->d_scr_up / d_scr_lo (asynchronous)
-static int launch_screen_bounds(robo_gp* g, robo_cand* k, int kind, double par, double eta) {
+// scaled rows of k and the bounds of every candidate into k->d_scr_up / d_scr_lo (asynchronous); `single`: with the
+// single-precision finish (the caller has asked screen_single_wanted).  scr_finish reports the fp64 finish selected for the
+// factor either way
+static int launch_screen_bounds(robo_gp* g, robo_cand* k, int kind, double par, double eta, bool single = false) {
     robo_ctx* c = g->ctx;
     ROBO_TRY(alpha_ensure(g));
     ROBO_TRY(screen_buffers(k));
@@ -830,11 +916,13 @@ static int launch_screen_bounds(robo_gp* g, robo_cand* k, int kind, double par, 
     }
         const bool lean = screen_lean_wanted(g);
         if (g->kind == ROBO_KERNEL_MATERN52_ARD) {
-            if (lean) ROBO_SCREEN_DOT_KS(ROBO_KERNEL_MATERN52_ARD, true)
-            else ROBO_SCREEN_DOT_KS(ROBO_KERNEL_MATERN52_ARD, false)
+            if (single) ROBO_SCREEN_DOT_KS(ROBO_KERNEL_MATERN52_ARD, SD_SINGLE)
+            else if (lean) ROBO_SCREEN_DOT_KS(ROBO_KERNEL_MATERN52_ARD, SD_LEAN)
+            else ROBO_SCREEN_DOT_KS(ROBO_KERNEL_MATERN52_ARD, SD_FULL)
         } else {
-            if (lean) ROBO_SCREEN_DOT_KS(ROBO_KERNEL_RBF_ARD, true)
-            else ROBO_SCREEN_DOT_KS(ROBO_KERNEL_RBF_ARD, false)
+            if (single) ROBO_SCREEN_DOT_KS(ROBO_KERNEL_RBF_ARD, SD_SINGLE)
+            else if (lean) ROBO_SCREEN_DOT_KS(ROBO_KERNEL_RBF_ARD, SD_LEAN)
+            else ROBO_SCREEN_DOT_KS(ROBO_KERNEL_RBF_ARD, SD_FULL)
         }
 #undef ROBO_SCREEN_DOT_KS
 #undef ROBO_SCREEN_DOT_CALL
@@ -897,12 +985,16 @@ int acq_sweep_best(robo_gp* g, int32_t kind, double par, double eta, robo_cand* 
         k->scr_outcome = ROBO_SCREEN_NOT_ELIGIBLE;
         k->scr_n = k->scr_kept = 0;
         k->scr_tail_fused = false;
+        k->scr_first_stage = 0;
+        k->scr_first_kept = 0;
     }
     if (want_values || !screen_eligible(g, k, kind, par, eta)) return acq_sweep(&g, 1, false, kind, par, &eta, k, allow_chain);
     if (g->screen_gen != g->fit_gen) {
         g->screen_gen = g->fit_gen;
         g->screen_skip = 0;
         g->screen_backoff = 1;
+        g->single_skip = 0;
+        g->single_backoff = 1;
     }
     if (g->screen_skip > 0) {
         --g->screen_skip;
@@ -912,7 +1004,15 @@ int acq_sweep_best(robo_gp* g, int32_t kind, double par, double eta, robo_cand* 
     hipStream_t st = c->stream;
     ROBO_HIP_CHECK(hipSetDevice(c->device));
     k->solved_gen = 0;
-    ROBO_TRY(launch_screen_bounds(g, k, kind, par, eta));
+    // the first stage (header: "The cascade"): the same launches with the single-precision finish, unless the factor's rule or
+    // its pause says no
+    ROBO_TRY(alpha_ensure(g));
+    bool first = screen_single_wanted(g);
+    if (first && g->single_skip > 0) {
+        --g->single_skip;
+        first = false;
+    }
+    ROBO_TRY(launch_screen_bounds(g, k, kind, par, eta, first));
     unsigned long long* b = reinterpret_cast<unsigned long long*>(k->d_scr_lo + k->m_pad);     // max_c L_c: the bounds kernel's
     double* hp = c->h_pinned + 8;
     const dim3 blocks((unsigned)k->n_part);
@@ -930,6 +1030,21 @@ int acq_sweep_best(robo_gp* g, int32_t kind, double par, double eta, robo_cand* 
     int64_t cap = k->m / 100 * c->tune.acq_screen_keep_max + k->m % 100 * c->tune.acq_screen_keep_max / 100;
     if (cap > k->m) cap = k->m;
     if (cap < 1) cap = 1;
+    if (first) {
+        k->scr_first_kept = kept;
+        if (kept >= 1 && kept <= (cap < NB ? cap : (int64_t)NB)) {
+            // decided: on from the gather with these survivors (a superset of the fp64 pass's)
+            k->scr_first_stage = 1;
+            g->single_backoff = 1;
+        } else {
+            // the fp64 path on the whole batch, as without a first stage; the first stage pauses
+            k->scr_first_stage = 2;
+            g->single_skip = g->single_backoff;
+            if (g->single_backoff < (1 << 20)) g->single_backoff *= 2;
+            ROBO_TRY(launch_screen_bounds(g, k, kind, par, eta));
+            ROBO_TRY(count_survivors());
+        }
+    }
     k->scr_n = k->m;
     k->scr_kept = kept;
     bool probed = false;
@@ -1030,6 +1145,13 @@ int32_t robo_cand_last_screen_finish(robo_cand* k, int32_t* out_finish, int32_t*
     return ROBO_OK;
 }
 
+int32_t robo_cand_last_screen_first(robo_cand* k, int32_t* out_stage, int64_t* out_kept) {
+    if (!k) return ROBO_BAD_ARGUMENT;
+    if (out_stage) *out_stage = k->scr_first_stage;
+    if (out_kept) *out_kept = k->scr_first_kept;
+    return ROBO_OK;
+}
+
 int32_t robo_acq_screen_bounds(robo_gp* g, int32_t acq_kind, double par, double eta, robo_cand* k, double* out_upper,
                                double* out_lower) {
     if (!g || !k) return ROBO_BAD_ARGUMENT;
@@ -1050,7 +1172,9 @@ int32_t robo_acq_screen_bounds(robo_gp* g, int32_t acq_kind, double par, double 
     hipStream_t st = g->ctx->stream;
     ROBO_HIP_CHECK(hipSetDevice(g->ctx->device));
     k->solved_gen = 0;
-    ROBO_TRY(launch_screen_bounds(g, k, acq_kind, par, eta));
+    // acq_screen_single = 2 (tests): the first stage's bounds where it would run, its pause aside
+    ROBO_TRY(alpha_ensure(g));
+    ROBO_TRY(launch_screen_bounds(g, k, acq_kind, par, eta, g->ctx->tune.acq_screen_single == 2 && screen_single_wanted(g)));
     if (out_upper)
         ROBO_HIP_CHECK(hipMemcpyAsync(out_upper, k->d_scr_up, (size_t)k->m * sizeof(double), hipMemcpyDeviceToHost, st));
     if (out_lower)
