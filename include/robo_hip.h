@@ -130,6 +130,11 @@ int32_t robo_ctx_set_phase_events(robo_ctx* ctx, int32_t on);
  * when they fit one tile of 128 and the cap; otherwise the fp64 pass runs as before and the factor's first stage pauses for
  * 1, 2, 4, ... calls; 0 never; 1 wherever the lean finish runs; 2 as 1, and robo_acq_screen_bounds returns the first
  * stage's bounds: tests.  Rigorous bounds either way, same results),
+ * acq_screen_int (how that first stage forms its squared distances: -1 = default: for 8 < D <= 16, from exact int8 matrix
+ * products of the centred coordinates on a 24-bit grid spanning twice the training rows' extent, where the rows have an
+ * extent and the stage's margin with the grid's proven error added still stays within half the prior standard deviation,
+ * from the fp64 matrix instruction otherwise; 0 never the integer form; 1 wherever the first stage runs and D <= 16: tests.
+ * Rigorous bounds either way, same results),
  * acq_screen_fused_tail (1 = default: when the screen's survivors fit one block of 256, their output transform, acquisition
  * values, argmax, index map and report run as one single-workgroup launch; 0: the five launches.  Same bits either way),
  * trsm_chain (small batches on two or more block rows, solved by ONE launch whose block rows hand their tiles to each
@@ -369,6 +374,12 @@ int32_t robo_cand_last_screen_finish(robo_cand* cand, int32_t* out_finish, int32
  * ones robo_cand_last_screen counts as solved, 2 it ran and the fp64 pass followed on the whole batch.  *out_kept: the
  * first stage's survivor count (0 with stage 0).  Either pointer may be NULL.                                          */
 int32_t robo_cand_last_screen_first(robo_cand* cand, int32_t* out_stage, int64_t* out_kept);
+/* How that first stage -- of the last argmax-only acquisition call on this handle, or of the last robo_acq_screen_bounds
+ * under acq_screen_single = 2 -- formed its squared distances (tuning key acq_screen_int).  *out_form:                   */
+#define ROBO_SCREEN_FORM_FP64 0    /* no first stage, or |a|^2 + |b|^2 - 2 a.b from the fp64 matrix instruction           */
+#define ROBO_SCREEN_FORM_INT8 1    /* exact int8 matrix products of the centred coordinates on a 24-bit grid              */
+/* *out_step: the grid step in scaled coordinates (0 with ROBO_SCREEN_FORM_FP64).  Either pointer may be NULL.            */
+int32_t robo_cand_last_screen_form(robo_cand* cand, int32_t* out_form, double* out_step);
 /* The screen's bounds themselves (soundness tests, A/B tools): out_upper / out_lower (m,) with
  * lower <= the value robo_acq_eval_cand returns for the candidate <= upper; NaN coordinates give NaN bounds.  Needs a
  * (kind, par) the screen handles (LCB: kappa >= 0) and fp64 covariance entries; batch size, tuning keys and the

@@ -11,7 +11,8 @@ extern "C" {
 #endif
 
 /* ---- self tests / micro benchmarks (used by tests and bench.py, not by the product) --- */
-/* runs one v_mfma_f64_16x16x4_f64 with asymmetric operands, returns max |D - A*B|          */
+/* runs one v_mfma_f64_16x16x4_f64 and one v_mfma_i32_16x16x64_i8 with asymmetric operands,
+ * returns max |D - (A*B + C)| over both                                                    */
 int32_t robo_selftest_mfma_layout(robo_ctx* ctx, double* out_max_err);
 /* issues `iters` dependent-free MFMA f64 per wave on every CU; returns TFLOP/s               */
 int32_t robo_microbench_mfma_f64(robo_ctx* ctx, int32_t iters, double* out_tflops);

@@ -54,7 +54,8 @@ SYMBOLS = [
     "robo_cand_create_random", "robo_cand_create_sobol", "robo_cand_get_point", "robo_cand_workspace_chunk", "robo_cand_last_solve_kernel",
     "robo_gp_predict_cand", "robo_gp_predict", "robo_gp_predict_cov", "robo_gp_predict_grad", "robo_gp_predict_mixture_cand",
     "robo_acq_eval_cand", "robo_acq_eval", "robo_acq_eval_moments", "robo_acq_eval_marginal_cand", "robo_acq_eval_sum_cand",
-    "robo_cand_last_screen", "robo_cand_last_screen_finish", "robo_cand_last_screen_first", "robo_acq_screen_bounds",
+    "robo_cand_last_screen", "robo_cand_last_screen_finish", "robo_cand_last_screen_first", "robo_cand_last_screen_form",
+    "robo_acq_screen_bounds",
     "robo_acq_refine_cand", "robo_acq_refine_marginal_cand",
     "robo_rep_sample", "robo_rep_sample_batch",
     "robo_acq_batch_cand", "robo_acq_batch_marginal_cand", "robo_qei_batch_cand", "robo_qei_batch_marginal_cand",
@@ -222,6 +223,7 @@ def lib():
         "robo_cand_last_screen": [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i32)],
         "robo_cand_last_screen_finish": [vp, C.POINTER(i32), C.POINTER(i32)],
         "robo_cand_last_screen_first": [vp, C.POINTER(i32), C.POINTER(i64)],
+        "robo_cand_last_screen_form": [vp, C.POINTER(i32), C.POINTER(C.c_double)],
         "robo_acq_screen_bounds": [vp, i32, dbl, dbl, vp, _dp, _dp],
         "robo_acq_eval_moments": [vp, i32, dbl, dbl, _dp, _dp, i64, _dp, _dp, C.POINTER(i64), C.POINTER(C.c_uint32)],
         "robo_acq_eval_marginal_cand": [pp, i32, i32, dbl, _dp, vp, _dp, _dp, C.POINTER(i64),
@@ -677,6 +679,13 @@ class Candidates(object):
         stage, kept = C.c_int32(0), C.c_int64(0)
         check(lib().robo_cand_last_screen_first(self._h, C.byref(stage), C.byref(kept)))
         return int(stage.value), int(kept.value)
+
+    def screen_form(self):
+        """how that first stage formed its squared distances -> (SCREEN_FORM_* value, grid step in scaled coordinates; 0.0
+        with SCREEN_FORM_FP64)"""
+        form, step = C.c_int32(0), C.c_double(0.0)
+        check(lib().robo_cand_last_screen_form(self._h, C.byref(form), C.byref(step)))
+        return int(form.value), float(step.value)
 
     def last_screen(self):
         """what the last argmax-only acquisition call on this handle did -> (candidates screened, survivors, SCREEN_* outcome)"""

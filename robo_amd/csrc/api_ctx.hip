@@ -67,6 +67,7 @@ static const TuneKey TUNE_KEYS[] = {
     {"acq_screen_dot", nullptr, &Tuning::acq_screen_dot, -1},
     {"acq_screen_lean", nullptr, &Tuning::acq_screen_lean, -1},
     {"acq_screen_single", nullptr, &Tuning::acq_screen_single, -1},
+    {"acq_screen_int", nullptr, &Tuning::acq_screen_int, -1},
     {"acq_screen_fused_tail", nullptr, &Tuning::acq_screen_fused_tail, 1},
     {"trsm_chain", nullptr, &Tuning::trsm_chain, -1},
     {"trsm_chain_max_wg", nullptr, &Tuning::trsm_chain_max_wg, 4},

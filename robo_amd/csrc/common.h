@@ -26,6 +26,41 @@ __device__ __forceinline__ v4d mfma_f64(double a, double b, v4d c) {
     return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
 }
 
+// v_mfma_i32_16x16x64_i8: 16 int8 per lane of A and of B, 4 int32 per lane of C / D, no rounding anywhere.  Lane l holds
+// A[row l & 15][k = 16 (l >> 4) + j] and B[k = 16 (l >> 4) + j][column l & 15] in byte j of its four words (little endian), and
+// D[row 4 (l >> 4) + r][column l & 15] in register r -- the bf16 map of the 16x16 shape carried over, pinned with asymmetric
+// integer data by robo_selftest_mfma_layout (diag/selftest.hip).  Off the device (the interpreter under tests/hipemu) the
+// same sum in plain C++ from the wave's shuffles.
+typedef int v4i __attribute__((vector_size(16)));
+
+__device__ __forceinline__ int dot_i8x8(long long x, long long y) {
+    int s = 0;
+    for (int j = 0; j < 8; ++j) s += (int)(signed char)(x >> (8 * j)) * (int)(signed char)(y >> (8 * j));
+    return s;
+}
+
+__device__ __forceinline__ v4i mfma_i8(v4i a, v4i b, v4i c) {
+#ifdef __AMDGCN__
+    return __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b, c, 0, 0, 0);
+#else
+    const int l = threadIdx.x & 63;
+    const long long a0 = (long long)(((unsigned long long)(unsigned)a[1] << 32) | (unsigned)a[0]);
+    const long long a1 = (long long)(((unsigned long long)(unsigned)a[3] << 32) | (unsigned)a[2]);
+    const long long b0 = (long long)(((unsigned long long)(unsigned)b[1] << 32) | (unsigned)b[0]);
+    const long long b1 = (long long)(((unsigned long long)(unsigned)b[3] << 32) | (unsigned)b[2]);
+    v4i d = c;
+    for (int gk = 0; gk < 4; ++gk) {
+        const long long y0 = __shfl(b0, (l & 15) + 16 * gk), y1 = __shfl(b1, (l & 15) + 16 * gk);
+        for (int r = 0; r < 4; ++r) {
+            const int src = 4 * (l >> 4) + r + 16 * gk;
+            const long long x0 = __shfl(a0, src), x1 = __shfl(a1, src);
+            d[r] += dot_i8x8(x0, y0) + dot_i8x8(x1, y1);
+        }
+    }
+    return d;
+#endif
+}
+
 // Single correctly rounded fp64 operations that are NEVER contracted into a fused multiply-add, for the places whose
 // results must equal NumPy's bit for bit (the stretch-move proposal of the hyper-parameter chain, mcmc_dev.h).
 // ROCm's __dmul_rn / __dadd_rn / __dsub_rn are the plain operators (__clang_hip_math.h) and hipcc's default
@@ -244,6 +279,10 @@ struct Tuning {
                                  // survivors are solved when they fit one tile: -1 (default) where the lean finish is selected and the
                                  // term this adds to delta stays within SCREEN_SINGLE_MAX of the prior standard deviation, 0 never, 1
                                  // wherever the lean finish runs, 2 as 1 and robo_acq_screen_bounds returns that stage's bounds (tests)
+    int acq_screen_int;          // ... that first stage's squared distances from exact int8 matrix products on a 24-bit grid
+                                 // (screen_bounds_dot_int_kernel): -1 (default) where the first stage runs, 8 < D <= 16, the training
+                                 // rows have an extent and the stage's whole term, the grid's included, stays within
+                                 // SCREEN_SINGLE_MAX; 0 never; 1 wherever the first stage runs and D <= 16
     int acq_screen_fused_tail;   // ... survivors that fit one partial block: output transform, acquisition, argmax, index map and
                                  // report in ONE single-workgroup launch (1, default); 0: the five launches (tests, A/B)
     int trsm_chain;              // small batches on >= 2 block rows: all block rows in ONE launch chained by hand-offs (trsm_chain.hip)
@@ -583,6 +622,7 @@ struct robo_gp {
     double* d_alpha;
     double dot_extent;              // sum_d max_j (x_jd - centre_d)^2 of the scaled training rows alpha was computed for
     double dot_alpha_sum;           // sum_j |alpha_j| of the same fit (the lean finish's rule)
+    double int_step, int_eps;       // the integer form's grid step h and its covariance error in units of amp (0: no extent, no grid)
     unsigned long long alpha_gen;   // fit_gen alpha was computed for (0: none)
     unsigned long long screen_gen;  // fit_gen the back-off below belongs to
     int screen_skip, screen_backoff;   // eligible calls still to pass unscreened after a failed screen; length of the next pause
@@ -644,6 +684,8 @@ struct robo_cand {
     int scr_finish;                 // ... and its finish: ROBO_SCREEN_FINISH_* (robo_cand_last_screen_finish)
     int scr_first_stage;            // robo_cand_last_screen_first: 0 no first stage, 1 it decided the call, 2 the fp64 pass followed
     int64_t scr_first_kept;         // ... and its survivor count
+    int scr_int;                    // robo_cand_last_screen_form: 1 the last bounds pass took its squared distances from the int8 products
+    double scr_int_step;            // ... on this grid step (0 otherwise)
     bool scr_tail_fused;            // the last argmax-only call ran its survivors' tail as acq_tail_kernel (same accessor)
     // the chained solve (trsm_chain.hip), lazy, grows: [ticket | time-out | progress words] zeroed per launch, then the
     // per-(tile, block row) partial sums

@@ -20,6 +20,24 @@ __global__ __launch_bounds__(64) void mfma_layout_kernel(const double* __restric
     for (int r = 0; r < 4; ++r) C[((l >> 4) + 4 * r) * 16 + (l & 15)] = acc[r];
 }
 
+// v_mfma_i32_16x16x64_i8 through common.h's mfma_i8, by the map stated there
+__global__ __launch_bounds__(64) void mfma_i8_layout_kernel(const signed char* __restrict__ A, const signed char* __restrict__ B,
+                                                            int* __restrict__ C) {
+    // A: 16x64 row-major, B: 64x16 row-major, C: 16x16 row-major, holds the C operand on entry
+    const int l = threadIdx.x;
+    v4i a = {0, 0, 0, 0}, b = {0, 0, 0, 0}, c;
+    for (int j = 0; j < 16; ++j) {
+        const int k = 16 * (l >> 4) + j;
+        a[j >> 2] |= ((int)A[(l & 15) * 64 + k] & 255) << (8 * (j & 3));
+        b[j >> 2] |= ((int)B[k * 16 + (l & 15)] & 255) << (8 * (j & 3));
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) c[r] = C[(4 * (l >> 4) + r) * 16 + (l & 15)];
+    c = mfma_i8(a, b, c);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) C[(4 * (l >> 4) + r) * 16 + (l & 15)] = c[r];
+}
+
 __global__ __launch_bounds__(256) void mfma_bench_kernel(double* __restrict__ sink, int iters, double seed,
                                                          long long* __restrict__ clocks) {
     const int l = threadIdx.x & 63;
@@ -161,6 +179,31 @@ int launch_mfma_selftest(robo_ctx* ctx, double* out_err) {
             double s = 0.0;
             for (int k = 0; k < 4; ++k) s += hA[i * 4 + k] * hB[k * 16 + j];
             const double e = s - hC[i * 16 + j];
+            if ((e < 0 ? -e : e) > err) err = e < 0 ? -e : e;
+        }
+    // the int8 form: asymmetric operands that reach -128 and 127, an asymmetric C operand; any difference is >= 1
+    signed char iA[16 * 64], iB[64 * 16];
+    int iC[256], iD[256];
+    for (int i = 0; i < 16 * 64; ++i) {
+        iA[i] = (signed char)((i * 37 + (i >> 6) * 11 + 5) % 256 - 128);
+        iB[i] = (signed char)((i * 91 + (i & 15) * 7 + 200) % 256 - 128);
+    }
+    for (int i = 0; i < 256; ++i) iC[i] = 1000 * (i >> 4) - 7 * (i & 15) - 3;
+    char* di = nullptr;
+    ROBO_HIP_CHECK(hipMalloc(&di, sizeof(iA) + sizeof(iB) + sizeof(iC)));
+    ROBO_HIP_CHECK(hipMemcpyAsync(di, iA, sizeof(iA), hipMemcpyHostToDevice, ctx->stream));
+    ROBO_HIP_CHECK(hipMemcpyAsync(di + sizeof(iA), iB, sizeof(iB), hipMemcpyHostToDevice, ctx->stream));
+    ROBO_HIP_CHECK(hipMemcpyAsync(di + sizeof(iA) + sizeof(iB), iC, sizeof(iC), hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(mfma_i8_layout_kernel, dim3(1), dim3(64), 0, ctx->stream, (const signed char*)di,
+                       (const signed char*)(di + sizeof(iA)), reinterpret_cast<int*>(di + sizeof(iA) + sizeof(iB)));
+    ROBO_HIP_CHECK(hipMemcpyAsync(iD, di + sizeof(iA) + sizeof(iB), sizeof(iD), hipMemcpyDeviceToHost, ctx->stream));
+    ROBO_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    ROBO_HIP_CHECK(hipFree(di));
+    for (int i = 0; i < 16; ++i)
+        for (int j = 0; j < 16; ++j) {
+            int s = iC[i * 16 + j];
+            for (int k = 0; k < 64; ++k) s += (int)iA[i * 64 + k] * (int)iB[k * 16 + j];
+            const double e = (double)s - (double)iD[i * 16 + j];
             if ((e < 0 ? -e : e) > err) err = e < 0 ? -e : e;
         }
     *out_err = err;

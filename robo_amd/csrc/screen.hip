@@ -161,6 +161,48 @@
 //   launch_screen_bounds, unchanged (count, probe, cap, fall-back, screen_skip), and the factor's first stage pauses for
 //   1, 2, 4, ... eligible calls (reset by a new fit, back to 1 after a success): a regime the first stage cannot decide pays
 //   its kernel a vanishing number of times.
+//
+// The integer form (screen_bounds_dot_int_kernel; the first stage only, D <= 16).  The first stage rounds r2 to a float, so
+// the fp64 matrix pipe's only job there is to avoid the cancellation in |a|^2 + |b|^2 - 2 a.b; v_mfma_i32_16x16x64_i8
+// accumulates in int32 with no rounding at all and holds the pipe 16 cycles against 64 (measured: NOTES.md).
+//   Grid (per fit_gen, screen_dot_prep_kernel).  H = max_jd |x_jd - ctr_d| over the centred scaled training rows;
+//   h = 2 H / SD_INT_GRID, SD_INT_GRID = 8 355 000: +-2 H (candidates are drawn from the box of the data, whose centre is not
+//   the rows' mid-range) lies inside +-SD_INT_AMAX = 127 (2^16 + 2^8 + 1), the largest integer three balanced digits hold.
+//   A = rint(a / h) = A0 2^16 + A1 2^8 + A2, digits in [-128, 127] (the sign-extended low byte of what is left).  Rows with no
+//   extent (H = 0: one row) have no grid of their own: the rule refuses, key 1 takes H = 1/2.
+//   Operands.  Lane group g = l >> 4 of the A operand holds digit g of the row in dimensions 0 .. 15 (group 3: zeros), once
+//   per fit (screen_int_pack_kernel): ONE 16-byte LDS read per lane and tile serves four products whose B operands, built
+//   once per candidate, are [B0 0 0 0], [B1 B0 0 0], [B2 B1 B0 0], [0 B2 B1 0]:
+//       S0 = sum A0 B0 (2^32)   S1 = sum A0 B1 + A1 B0 (2^24)   S2 = sum A0 B2 + A1 B1 + A2 B0 (2^16)   S3 = sum A1 B2 + A2 B1 (2^8)
+//   in units of h^2; |S2| <= 3 x 16 x 2^14, no level leaves int32.  S4 = sum A2 B2 is dropped.
+//   Combine.  T0 = 256 S0 + S1, T1 = 256 S2 + S3 (int32), P = 2^16 T0 + T1, u = (|A|^2 + |B|^2 + SD_INT_OFF) - 512 P in fp64:
+//   all integers below 2^53, so u = |A - B|^2 + 2 S4 + SD_INT_OFF EXACTLY.  SD_INT_OFF = 2^19 >= 2 |S4| (D <= 16, digits
+//   <= 2^7) is added to |B|^2 once per candidate: u >= 0 always, no clamp; it and S4 together move u by [0, 2^20].
+//   t = 5 h^2 u (RBF: x = -h^2 u / 2): one fp64 rounding, then screen_single_cov, the single finish's float part unchanged.
+//   Per pair 17 instructions (the fp64-MFMA form: 11): 2 v_lshl_add_u32, 2 v_cvt_f64_i32, v_fmac_f64, v_add_f64, v_fmac_f64,
+//   v_mul_f64, and the 9 from v_cvt_f32_f64 on.
+//   Error of that k~, in units of amp, next to SD_SINGLE_EPS (which covers everything from the float conversion on).
+//     grid       a = h A + e_a, |e_a,d| <= h / 2 (the rounding of the centring, u |a_d|, and of a x fl(1 / h), 2^-29 h, are
+//                inside the slack of the constants below); likewise b.  With r~ = h |A - B|:  |r~ - r| <= |e_a - e_b|_2 <=
+//                sqrt(D) h (triangle inequality), and k is Lipschitz in r:  Matern-5/2  |dk/dr| = (sqrt 5 / 3) s (1 + s) e^-s
+//                <= 0.6261 (at s = (1 + sqrt 5) / 2);  RBF  |dk/dr| = r e^(-r^2 / 2) <= e^(-1/2) = 0.6066.
+//                |dk| <= c1 sqrt(D) h,  c1 = 0.63 (Matern-5/2), 0.61 (RBF):  1.5e-7 at the headline (H = 0.25, h = 6.0e-8).
+//     S4, offset r2 moves by at most 2^20 h^2 and |dk/dr2| <= c2 = 5/6 (1/2):  c2 2^20 h^2 = 3e-9 at the headline.
+//     product    5 h^2 as a double and t: 3 u relative in t, |dk/d ln t| <= 0.47:  2e-16.
+//   SD_INT eps = c1 sqrt(D) h + c2 2^20 h^2 is per fit (st[SD_INT + 2]); candidate c's delta gains, in place of the fp64 dot
+//   form's r2 term (which no longer applies),
+//       SCREEN_SINGLE_SAFETY (SD_SINGLE_EPS + eps_c) |y_std| sum_j |amp alpha_j|
+//   with eps_c = that figure;  = 1 for a FAR candidate -- a finite coordinate beyond +-SD_INT_AMAX h is clamped to it, and k~,
+//   k both lie in [0, 1]: a finite, rigorous, vacuous bound (U_c is then huge: a survivor in practice);  = NaN for a
+//   non-finite coordinate (the integer conversion would not propagate it): both bounds NaN, a survivor.  More than a tile of
+//   either kind makes the first stage miss and pause through the cascade's own path.
+//   The rule (screen_int_wanted).  acq_screen_int: -1 the rule, 0 never, 1 wherever the first stage runs and D <= 16.  Under
+//   the rule: 8 < D <= 16 (four k-steps of the fp64 form; at D = 8 the integer form measured no faster), the rows have an
+//   extent, and the stage's WHOLE term stays within SCREEN_SINGLE_MAX:
+//       SCREEN_SINGLE_SAFETY (SD_SINGLE_EPS + eps) sqrt(amp) sum_j |alpha_j| <= 0.5               (the headline's fit: 0.39)
+//   Otherwise the fp64-MFMA first stage runs under its own rule.  robo_cand_last_screen_form reports the form;
+//   bounds_kernel() keeps naming the dot kernel's family.  Measured (tests/test_acq_screen_int.py): on the grid the error is the
+//   float finish's alone (1.3e-7), off it 1.0e-7 against 7.8e-7 allowed at D = 16.
 #include <cmath>
 
 #include "api_internal.h"
@@ -371,13 +413,22 @@ __device__ __forceinline__ double screen_block_reduce(double x, double* sh, int 
 }
 
 // st[1] = sum_j |alpha_j|, st[2] = max_j |x_j - ctr|^2, st[3] = sum_d max_j (x_jd - ctr_d)^2, st[SD_CTR + d] = ctr_d (mid-range)
+// and the integer form's grid (header: "The integer form"): st[SD_INT] = h, + 1: 1 / h, + 2: its covariance error in units of
+// amp, + 3: H = max_jd |x_jd - ctr_d| (0: the rows have no extent and the grid is the fall-back's, which only key 1 takes)
 constexpr int SD_CTR = 4;
+constexpr int SD_INT = SD_CTR + SCREEN_DOT_MAX_D;
+constexpr int SD_STATS = SD_INT + 4;
+constexpr int SD_INT_MAX_D = 16;                 // one lane group of 16 bytes per digit
+constexpr double SD_INT_AMAX = 8355711.0;        // 127 (2^16 + 2^8 + 1): the largest |A| three balanced digits hold
+constexpr double SD_INT_GRID = 8355000.0;        // 2 H / h: +-2 H lies inside +-AMAX with room for the roundings of the centring
+constexpr double SD_INT_OFF = 1048576.0 / 2;     // 2^19 >= 2 |S4| at D <= 16: added to |B|^2, keeps the integer r2 >= 0 without S4
+constexpr double SD_INT_H0 = 0.5;                // H of the fall-back grid
 __global__ __launch_bounds__(256) void screen_dot_prep_kernel(const double* __restrict__ alpha, const double* __restrict__ Xs,
-                                                              int D, int n, double* __restrict__ st) {
+                                                              int D, int n, int matern, double* __restrict__ st) {
     __shared__ double sh[256];
     __shared__ double sc[SCREEN_DOT_MAX_D];
     const double inf = __builtin_huge_val();
-    double ext = 0.0;
+    double ext = 0.0, H = 0.0;
     for (int d = 0; d < D; ++d) {
         double hi = -inf, nlo = -inf;
         for (int j = threadIdx.x; j < n; j += 256) {
@@ -389,6 +440,7 @@ __global__ __launch_bounds__(256) void screen_dot_prep_kernel(const double* __re
         nlo = screen_block_reduce<256>(nlo, sh, 1);
         const double c = 0.5 * (hi - nlo), h = hi - c, l = c + nlo;
         ext += fmax(h * h, l * l);
+        H = fmax(H, fmax(h, l));
         if (threadIdx.x == 0) sc[d] = c;
     }
     __syncthreads();
@@ -408,6 +460,13 @@ __global__ __launch_bounds__(256) void screen_dot_prep_kernel(const double* __re
         st[1] = a;
         st[2] = r;
         st[3] = ext;
+        // the grid and its bound: c1 sqrt(D) h + c2 2^20 h^2 (the header's derivation)
+        const bool extent = H > 0.0 && H < inf;
+        const double hs = 2.0 * (extent ? H : SD_INT_H0) / SD_INT_GRID;
+        st[SD_INT] = hs;
+        st[SD_INT + 1] = 1.0 / hs;
+        st[SD_INT + 2] = (matern ? 0.63 : 0.61) * sqrt((double)D) * hs + (matern ? 5.0 / 6.0 : 0.5) * 2.0 * SD_INT_OFF * hs * hs;
+        st[SD_INT + 3] = extent ? H : 0.0;
     }
     if ((int)threadIdx.x < D) st[SD_CTR + threadIdx.x] = sc[threadIdx.x];
 }
@@ -436,6 +495,46 @@ __global__ __launch_bounds__(256) void screen_dot_pack_kernel(const double* __re
         const int slot = (tile >> 3) * 2 * NB + (tile & 7) * 16 + (l & 3) * 4 + (l >> 2);
         apack[slot] = real ? amp * alpha[row] : 0.0;
         apack[slot + NB] = nb;
+    }
+}
+
+// The integer form's operands (header: "The integer form").  A = A0 2^16 + A1 2^8 + A2 with balanced digits in [-128, 127]:
+// each digit is the sign-extended low byte of what the digits below it leave.
+__device__ __forceinline__ void screen_int_digits(int A, int& d0, int& d1, int& d2) {
+    d2 = (int)(signed char)A;
+    A = (A - d2) >> 8;
+    d1 = (int)(signed char)A;
+    d0 = (A - d1) >> 8;
+}
+// byte d & 3 of word d >> 2: dimension d
+__device__ __forceinline__ void screen_int_put(v4i& v, int d, int digit) { v[d >> 2] |= (digit & 255) << (8 * (d & 3)); }
+
+// one workgroup per 64 rows (4 tiles of 16), as the pack above:
+//     rows   [tile of 16 rows][lane l]  =  16 bytes: digit g = l >> 4 of row 16 tile + (l & 15) in dimensions 0 .. 15 (g = 3: zeros)
+//     alpha  [stage of 128 rows][0][row]  =  amp alpha in natural order (the rows of lane l's D registers are 4 (l >> 4) + r)
+//     norms  [stage of 128 rows][1][row]  =  |A|^2, an integer below 2^50
+__global__ __launch_bounds__(256) void screen_int_pack_kernel(const double* __restrict__ alpha, const double* __restrict__ Xs,
+                                                              const double* __restrict__ st, double amp, int D, int n,
+                                                              v4i* __restrict__ rows, double* __restrict__ apack) {
+    const int tile = blockIdx.x * 4 + (threadIdx.x >> 6), l = threadIdx.x & 63, g = l >> 4;
+    const int row = tile * 16 + (l & 15);
+    const bool real = row < n;
+    v4i v = {0, 0, 0, 0};
+    double na = 0.0;
+    if (real)
+        for (int d = 0; d < D; ++d) {
+            // (|q| <= GRID / 2 by the choice of h; the clamp keeps a fit whose rows are not finite inside the digits' range)
+            const double q = fmax(fmin(rint((Xs[(size_t)row * D + d] - st[SD_CTR + d]) * st[SD_INT + 1]), SD_INT_AMAX), -SD_INT_AMAX);
+            int dg[3];
+            screen_int_digits((int)q, dg[0], dg[1], dg[2]);
+            if (g < 3) screen_int_put(v, d, dg[g]);
+            na = fma(q, q, na);
+        }
+    rows[(size_t)tile * 64 + l] = v;
+    if (g == 0) {
+        const int slot = (tile >> 3) * 2 * NB + (tile & 7) * 16 + l;
+        apack[slot] = real ? amp * alpha[row] : 0.0;
+        apack[slot + NB] = na;
     }
 }
 
@@ -552,21 +651,24 @@ __device__ __forceinline__ void screen_dot_finish_lean(const v4d acc, double nc,
 constexpr double SD_SINGLE_EPS = 6.3e-7;
 constexpr double SCREEN_SINGLE_SAFETY = 1.5;
 constexpr double SCREEN_SINGLE_MAX = 0.5;     // of the prior standard deviation: the most the first stage's term may add to delta
+// k~ / amp from t = 5 r2 (RBF: from x = -r2 / 2) as a float: the part both first-stage forms share
+template <int KIND>
+__device__ __forceinline__ float screen_single_cov(float tx) {
+    if (KIND == ROBO_KERNEL_MATERN52_ARD) {
+        const float s = hw_sqrt_f32(tx);
+        const float q = fmaf(tx, 0.333333333f, 1.0f + s);
+        return q * hw_exp2_f32(s * -1.44269504f);
+    }
+    return hw_exp2_f32(tx * 1.44269504f);
+}
+
 template <int KIND>
 __device__ __forceinline__ void screen_dot_finish_single(const v4d acc, double nc, const double* __restrict__ al, double (&dot)[4]) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-        float kv;
-        if (KIND == ROBO_KERNEL_MATERN52_ARD) {
-            const float t = (float)fmax(fma(5.0, acc[r], nc), 5.0 * SD_R2_MIN);
-            const float s = hw_sqrt_f32(t);
-            const float q = fmaf(t, 0.333333333f, 1.0f + s);
-            kv = q * hw_exp2_f32(s * -1.44269504f);
-        } else {
-            const float x = (float)fmin(fma(-0.5, acc[r], nc), -0.5 * SD_R2_MIN);
-            kv = hw_exp2_f32(x * 1.44269504f);
-        }
-        dot[r] = fma((double)kv, al[r], dot[r]);
+        const float tx = KIND == ROBO_KERNEL_MATERN52_ARD ? (float)fmax(fma(5.0, acc[r], nc), 5.0 * SD_R2_MIN)
+                                                          : (float)fmin(fma(-0.5, acc[r], nc), -0.5 * SD_R2_MIN);
+        dot[r] = fma((double)screen_single_cov<KIND>(tx), al[r], dot[r]);
     }
 }
 
@@ -659,6 +761,127 @@ __global__ __launch_bounds__(256) void screen_bounds_dot_kernel(const double* __
                        SCREEN_DOT_SAFETY * fabs(y_std) * fabs(cp.amp) * ck * r2_err * alpha_norm[1];
         if (FINISH != SD_FULL) delta += SCREEN_LEAN_SAFETY * SD_LEAN_EPS * fabs(y_std) * fabs(cp.amp) * alpha_norm[1];
         if (FINISH == SD_SINGLE) delta += SCREEN_SINGLE_SAFETY * SD_SINGLE_EPS * fabs(y_std) * fabs(cp.amp) * alpha_norm[1];
+        double u, l;
+        screen_bounds(acq_kind, par, eta, mt, delta, v_prior, u, l);
+        up[i] = u;
+        lo[i] = l;
+        if (!isnan(l)) lmax = l;
+    }
+    lmax = screen_block_max(lmax, sMx);
+    if (tid == 0) atomicMax(bkey, screen_key(lmax));
+}
+
+// ---- the first stage's bounds, integer form (header: "The integer form") -------------------------------------------------------
+// The same arguments, workgroup shape, stage loop and reduction as screen_bounds_dot_kernel<KIND, 4, SD_SINGLE>; Xs = the int8
+// rows, alpha = the integer form's amp alpha and |A|^2.  A wave holds its 16 candidates' digits as the B operands of the four
+// levels for the whole sweep; per 16 x 16 pair tile one 16-byte LDS read and four v_mfma_i32_16x16x64_i8.  Per pair, in front of
+// the conversion to float: T0 = 256 S0 + S1, T1 = 256 S2 + S3 (v_lshl_add_u32), two conversions, P = 2^16 T0 + T1, |A|^2 + |B|^2,
+// u = that - 512 P, t = 5 h^2 u: every value an integer below 2^53 up to the last product.
+template <int KIND>
+__global__ __launch_bounds__(256) void screen_bounds_dot_int_kernel(const double* __restrict__ Xcs, const v4i* __restrict__ Xs,
+                                                                    const double* __restrict__ alpha,
+                                                                    const double* __restrict__ alpha_norm, CovParams cp, int n,
+                                                                    long long m, double mean_c, double y_mean, double y_std,
+                                                                    int acq_kind, double par, double eta, double* __restrict__ up,
+                                                                    double* __restrict__ lo, unsigned long long* __restrict__ bkey) {
+    __shared__ double sMx[4];
+    constexpr int TILES = SD_STAGE / 16, STAGE_VECS = TILES * 64, PER = STAGE_VECS / 256;
+    __shared__ v4i sA[STAGE_VECS];
+    __shared__ __attribute__((aligned(32))) double sAN[2 * SD_STAGE];      // amp alpha | |A|^2 of the stage's rows
+    const double *sAl = sAN, *sNj = sAN + SD_STAGE;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, D = cp.dim;
+    const long long i = (long long)blockIdx.x * SD_CAND + wave * 16 + (lane & 15);
+    const bool live = i < m;
+    const long long ii = live ? i : 0;
+    // the candidate's digits (every lane of a column forms all three); a coordinate beyond the digits' range is clamped and
+    // marks the candidate FAR, a NaN or infinite one marks it LOST: its own term of delta below
+    const double inv_h = alpha_norm[SD_INT + 1];
+    v4i B0 = {0, 0, 0, 0}, B1 = {0, 0, 0, 0}, B2 = {0, 0, 0, 0};
+    double nb = SD_INT_OFF;
+    bool far = false, lost = false;
+#pragma unroll
+    for (int d = 0; d < SD_INT_MAX_D; ++d) {
+        if (d < D) {
+            const double q = rint((Xcs[ii * D + d] - alpha_norm[SD_CTR + d]) * inv_h);
+            const bool fin = fabs(q) < __builtin_huge_val();            // false for NaN and the infinities
+            const double qc = fin ? fmax(fmin(q, SD_INT_AMAX), -SD_INT_AMAX) : 0.0;
+            lost = lost || !fin;
+            far = far || qc != q;
+            int d0, d1, d2;
+            screen_int_digits((int)qc, d0, d1, d2);
+            screen_int_put(B0, d, d0);
+            screen_int_put(B1, d, d1);
+            screen_int_put(B2, d, d2);
+            nb = fma(qc, qc, nb);
+        }
+    }
+    // the four levels' B operands: lane group g of the rows holds digit g, so level S_k pairs it with digit k - g
+    const v4i zero = {0, 0, 0, 0};
+    const v4i bop0 = g == 0 ? B0 : zero;
+    const v4i bop1 = g == 0 ? B1 : g == 1 ? B0 : zero;
+    const v4i bop2 = g == 0 ? B2 : g == 1 ? B1 : g == 2 ? B0 : zero;
+    const v4i bop3 = g == 1 ? B2 : g == 2 ? B1 : zero;
+    const double hs = alpha_norm[SD_INT];
+    const double scale = KIND == ROBO_KERNEL_MATERN52_ARD ? 5.0 * hs * hs : -0.5 * hs * hs;
+    const int nst = (n + SD_STAGE - 1) / SD_STAGE;
+    v4i pa[PER];
+#pragma unroll
+    for (int e = 0; e < PER; ++e) pa[e] = Xs[e * 256 + tid];
+    double pan = alpha[tid];
+    double dot[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int s = 0; s < nst; ++s) {
+        __syncthreads();
+#pragma unroll
+        for (int e = 0; e < PER; ++e) sA[e * 256 + tid] = pa[e];
+        sAN[tid] = pan;
+        __syncthreads();
+        if (s + 1 < nst) {
+            const v4i* nx = Xs + (size_t)(s + 1) * STAGE_VECS;
+#pragma unroll
+            for (int e = 0; e < PER; ++e) pa[e] = nx[e * 256 + tid];
+            pan = alpha[(s + 1) * 2 * SD_STAGE + tid];
+        }
+        v4i a = sA[lane];
+        v4i s0 = mfma_i8(a, bop0, zero), s1 = mfma_i8(a, bop1, zero), s2 = mfma_i8(a, bop2, zero), s3 = mfma_i8(a, bop3, zero);
+#pragma unroll
+        for (int t = 0; t < TILES; ++t) {
+            v4i n0 = s0, n1 = s1, n2 = s2, n3 = s3;
+            if (t + 1 < TILES) {
+                a = sA[(t + 1) * 64 + lane];
+                n0 = mfma_i8(a, bop0, zero);
+                n1 = mfma_i8(a, bop1, zero);
+                n2 = mfma_i8(a, bop2, zero);
+                n3 = mfma_i8(a, bop3, zero);
+            }
+            const double* nj = sNj + t * 16 + g * 4;
+            const double* al = sAl + t * 16 + g * 4;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int t0 = s0[r] * 256 + s1[r], t1 = s2[r] * 256 + s3[r];
+                const double p = fma((double)t0, 65536.0, (double)t1);
+                const double u = fma(p, -512.0, nj[r] + nb);
+                dot[r] = fma((double)screen_single_cov<KIND>((float)(u * scale)), al[r], dot[r]);
+            }
+            s0 = n0;
+            s1 = n1;
+            s2 = n2;
+            s3 = n3;
+        }
+    }
+    double mu = (dot[0] + dot[1]) + (dot[2] + dot[3]);
+    mu += __shfl_xor(mu, 16);
+    mu += __shfl_xor(mu, 32);
+    double lmax = -__builtin_huge_val();
+    if (g == 0 && live) {
+        const double kself = cp.amp;
+        double mt = mu + mean_c;
+        mt = mt * y_std + y_mean;
+        const double v_prior = kself * (y_std * y_std);
+        // |k~ - k| / amp: the grid's bound; 1 for a clamped candidate (both lie in [0, 1]); NaN for a lost one: a survivor
+        const double eps_c = lost ? __builtin_nan("") : far ? 1.0 : alpha_norm[SD_INT + 2];
+        const double delta = SCREEN_DELTA_REL * (fabs(y_mean) + fabs(y_std) * (fabs(mean_c) + sqrt(fabs(kself)) * alpha_norm[0])) +
+                             (SCREEN_LEAN_SAFETY * SD_LEAN_EPS + SCREEN_SINGLE_SAFETY * (SD_SINGLE_EPS + eps_c)) * fabs(y_std) *
+                                 fabs(cp.amp) * alpha_norm[1];
         double u, l;
         screen_bounds(acq_kind, par, eta, mt, delta, v_prior, u, l);
         up[i] = u;
@@ -812,7 +1035,9 @@ static int screen_dot_ks(const robo_gp* g) {
 static int alpha_ensure(robo_gp* g) {
     const size_t np = (size_t)g->n_pad_max;
     const int ks = screen_dot_ks(g);
-    const size_t dot_doubles = ks ? SD_CTR + SCREEN_DOT_MAX_D + 2 * np + np * 4 * (size_t)ks : 0;
+    // ... and, for D <= SD_INT_MAX_D, the integer form's [amp alpha and |A|^2 (2 n_pad_max) | int8 rows (n_pad_max x 64 bytes)]
+    const bool ints = ks && g->dim <= SD_INT_MAX_D;
+    const size_t dot_doubles = ks ? SD_STATS + 2 * np + np * 4 * (size_t)ks + (ints ? 2 * np + 8 * np : 0) : 0;
     if (!g->d_alpha) ROBO_TRY(dev_alloc(&g->d_alpha, 2 * np + 8 + dot_doubles));
     if (g->alpha_gen == g->fit_gen) return ROBO_OK;
     robo_ctx* c = g->ctx;
@@ -824,22 +1049,33 @@ static int alpha_ensure(robo_gp* g) {
     double* stats = g->d_alpha + 2 * np;
     hipLaunchKernelGGL(screen_alpha_norm_kernel, dim3(1), dim3(256), 0, st, (const double*)a, (const double*)g->d_Xs, g->cov,
                        g->n, stats);
-    g->dot_extent = g->dot_alpha_sum = 0.0;
+    g->dot_extent = g->dot_alpha_sum = g->int_step = g->int_eps = 0.0;
     if (ks) {
-        double* apack = stats + SD_CTR + SCREEN_DOT_MAX_D;
+        double* apack = stats + SD_STATS;
         const int nst = (g->n + SD_STAGE - 1) / SD_STAGE;
         hipLaunchKernelGGL(screen_dot_prep_kernel, dim3(1), dim3(256), 0, st, (const double*)a, (const double*)g->d_Xs, g->dim,
-                           g->n, stats);
+                           g->n, g->kind == ROBO_KERNEL_MATERN52_ARD ? 1 : 0, stats);
         hipLaunchKernelGGL(screen_dot_pack_kernel, dim3((unsigned)(nst * SD_STAGE / 64)), dim3(256), 0, st, (const double*)a,
                            (const double*)g->d_Xs, (const double*)stats, g->cov.amp, g->dim, ks, g->n, apack + 2 * np, apack);
+        if (ints) {
+            double* ipack = apack + 2 * np + np * 4 * (size_t)ks;
+            hipLaunchKernelGGL(screen_int_pack_kernel, dim3((unsigned)(nst * SD_STAGE / 64)), dim3(256), 0, st, (const double*)a,
+                               (const double*)g->d_Xs, (const double*)stats, g->cov.amp, g->dim, g->n,
+                               reinterpret_cast<v4i*>(ipack + 2 * np), ipack);
+        }
         ROBO_LAUNCH_CHECK();
-        // the centred extent decides between the two kernels on the host, sum_j |alpha_j| between the two finishes: one
-        // small copy per fit_gen
+        // the centred extent decides between the two kernels on the host, sum_j |alpha_j| between the finishes, the grid's
+        // bound between the first stage's two forms: one small copy per fit_gen
+        static_assert(SD_STATS - 1 <= 48, "the pinned block's tail");
         double* hp = c->h_pinned + MAX_DIM + 16;
-        ROBO_HIP_CHECK(hipMemcpyAsync(hp, stats + 1, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+        ROBO_HIP_CHECK(hipMemcpyAsync(hp, stats + 1, (SD_STATS - 1) * sizeof(double), hipMemcpyDeviceToHost, st));
         ROBO_HIP_CHECK(hipStreamSynchronize(st));
         g->dot_alpha_sum = hp[0];
         g->dot_extent = hp[2];
+        if (ints) {
+            g->int_step = hp[SD_INT - 1];
+            g->int_eps = hp[SD_INT + 3 - 1] > 0.0 ? hp[SD_INT + 2 - 1] : 0.0;      // no extent: no rule-admitted grid
+        }
     }
     ROBO_LAUNCH_CHECK();
     g->alpha_gen = g->fit_gen;
@@ -875,6 +1111,20 @@ static bool screen_single_wanted(const robo_gp* g) {
     return term <= SCREEN_SINGLE_MAX;            // (a NaN sum: no first stage)
 }
 
+// whether that first stage takes its squared distances from the int8 products (header: "The integer form"); the caller has
+// asked screen_single_wanted
+static bool screen_int_wanted(const robo_gp* g) {
+    const int t = g->ctx->tune.acq_screen_int;
+    if (t == 0 || g->dim > SD_INT_MAX_D || !(g->int_step > 0.0)) return false;
+    if (t > 0) return true;
+    // measured: at D <= 8 the fp64 form needs one or two k-steps per pair tile and the integer form's four products and six
+    // more instructions per pair do not clear the rule (config 2: 53.1 against 54.1 us); it pays from four k-steps on
+    if (screen_dot_ks(g) != 4) return false;
+    if (!(g->int_eps > 0.0)) return false;       // rows without an extent: no grid of their own
+    const double term = SCREEN_SINGLE_SAFETY * (SD_SINGLE_EPS + g->int_eps) * std::sqrt(std::fabs(g->cov.amp)) * g->dot_alpha_sum;
+    return term <= SCREEN_SINGLE_MAX;            // (a NaN sum: the fp64-MFMA form, under its own rule)
+}
+
 static int screen_buffers(robo_cand* k) {
     const size_t mp = (size_t)k->m_pad;
     if (!k->d_scr_up) ROBO_TRY(dev_alloc(&k->d_scr_up, mp));
@@ -899,10 +1149,30 @@ static int launch_screen_bounds(robo_gp* g, robo_cand* k, int kind, double par, 
     const dim3 grid((unsigned)((k->m + SC_CAND - 1) / SC_CAND));
     const double* alpha = g->d_alpha + (size_t)g->n_pad_max;
     const double* anorm = g->d_alpha + 2 * (size_t)g->n_pad_max;
+    k->scr_int = 0;
+    k->scr_int_step = 0.0;
     if (screen_dot_wanted(g)) {
-        const double* apack = anorm + SD_CTR + SCREEN_DOT_MAX_D;
+        const double* apack = anorm + SD_STATS;
         const double* rows = apack + 2 * (size_t)g->n_pad_max;
         const dim3 dgrid((unsigned)((k->m + SD_CAND - 1) / SD_CAND));
+        if (single && screen_int_wanted(g)) {
+            // the first stage's integer form; reported as the dot kernel's family (robo_cand_last_screen_form tells the form)
+            const double* ipack = rows + (size_t)g->n_pad_max * 4 * screen_dot_ks(g);
+            const v4i* irows = reinterpret_cast<const v4i*>(ipack + 2 * (size_t)g->n_pad_max);
+#define ROBO_SCREEN_INT_CALL(KIND)                                                                                              \
+    hipLaunchKernelGGL((screen_bounds_dot_int_kernel<KIND>), dgrid, dim3(256), 0, c->stream, (const double*)k->d_Xcs, irows, ipack, \
+                       anorm, g->cov, g->n, (long long)k->m, g->mean_c, g->y_mean, g->y_std, kind, par, eta, k->d_scr_up,      \
+                       k->d_scr_lo, bkey)
+            if (g->kind == ROBO_KERNEL_MATERN52_ARD) ROBO_SCREEN_INT_CALL(ROBO_KERNEL_MATERN52_ARD);
+            else ROBO_SCREEN_INT_CALL(ROBO_KERNEL_RBF_ARD);
+#undef ROBO_SCREEN_INT_CALL
+            ROBO_LAUNCH_CHECK();
+            k->scr_bounds_kernel = "screen_bounds_dot_kernel";
+            k->scr_finish = screen_lean_wanted(g) ? ROBO_SCREEN_FINISH_LEAN : ROBO_SCREEN_FINISH_FULL;
+            k->scr_int = 1;
+            k->scr_int_step = g->int_step;
+            return ROBO_OK;
+        }
 #define ROBO_SCREEN_DOT_CALL(KIND, KS, LEAN)                                                                                  \
     hipLaunchKernelGGL((screen_bounds_dot_kernel<KIND, KS, LEAN>), dgrid, dim3(256), 0, c->stream, (const double*)k->d_Xcs, rows,  \
                        apack, anorm, g->cov, g->n, (long long)k->m, g->mean_c, g->y_mean, g->y_std, kind, par, eta,          \
@@ -987,6 +1257,8 @@ int acq_sweep_best(robo_gp* g, int32_t kind, double par, double eta, robo_cand* 
         k->scr_tail_fused = false;
         k->scr_first_stage = 0;
         k->scr_first_kept = 0;
+        k->scr_int = 0;
+        k->scr_int_step = 0.0;
     }
     if (want_values || !screen_eligible(g, k, kind, par, eta)) return acq_sweep(&g, 1, false, kind, par, &eta, k, allow_chain);
     if (g->screen_gen != g->fit_gen) {
@@ -1041,8 +1313,12 @@ int acq_sweep_best(robo_gp* g, int32_t kind, double par, double eta, robo_cand* 
             k->scr_first_stage = 2;
             g->single_skip = g->single_backoff;
             if (g->single_backoff < (1 << 20)) g->single_backoff *= 2;
+            const int first_int = k->scr_int;
+            const double first_step = k->scr_int_step;
             ROBO_TRY(launch_screen_bounds(g, k, kind, par, eta));
             ROBO_TRY(count_survivors());
+            k->scr_int = first_int;                // the form reported is the first stage's
+            k->scr_int_step = first_step;
         }
     }
     k->scr_n = k->m;
@@ -1149,6 +1425,13 @@ int32_t robo_cand_last_screen_first(robo_cand* k, int32_t* out_stage, int64_t* o
     if (!k) return ROBO_BAD_ARGUMENT;
     if (out_stage) *out_stage = k->scr_first_stage;
     if (out_kept) *out_kept = k->scr_first_kept;
+    return ROBO_OK;
+}
+
+int32_t robo_cand_last_screen_form(robo_cand* k, int32_t* out_form, double* out_step) {
+    if (!k) return ROBO_BAD_ARGUMENT;
+    if (out_form) *out_form = k->scr_int ? ROBO_SCREEN_FORM_INT8 : ROBO_SCREEN_FORM_FP64;
+    if (out_step) *out_step = k->scr_int_step;
     return ROBO_OK;
 }
 
