@@ -82,7 +82,7 @@ int32_t robo_ctx_destroy(robo_ctx* ctx);
 int32_t robo_ctx_live_count(int32_t* out_n);
 int32_t robo_ctx_synchronize(robo_ctx* ctx);
 int32_t robo_ctx_device_name(robo_ctx* ctx, char* buf, int32_t buf_len);
-/* HIP-event timing on the context's stream (what bench.py uses).  There are 34 slots, 0 .. 33.  Slots 0 .. 18 are the
+/* HIP-event timing on the context's stream (what bench.py uses).  There are 36 slots, 0 .. 35.  Slots 0 .. 18 are the
  * caller's; the library records the others itself (csrc/common.h names them; a pair is shared by calls that never run
  * inside one another):
  *   19 .. 23  the phases of robo_gp_fit: 19 -> 21 gram kernel, 20 -> 21 gram phase, 21 -> 22 Cholesky, 22 -> 23
@@ -97,7 +97,8 @@ int32_t robo_ctx_device_name(robo_ctx* ctx, char* buf, int32_t buf_len);
  *   30, 31    what follows the sweeps: the envelope kernel of robo_kg_eval_cand and the element-wise half of
  *             robo_mes_eval_cand (last sample each), the strip kernel of robo_ehvi_eval_cand, the passes of the path kernel
  *             (robo_paths_eval_cand, robo_paths_refine_cand), the fold kernel of robo_qei_batch_cand's last pick.
- *   32, 33    the fold kernel of robo_cei_eval_cand.                                                                    */
+ *   32, 33    the fold kernel of robo_cei_eval_cand.
+ *   34, 35    the box kernel of robo_ehvi_box_eval_cand.                                                                */
 int32_t robo_ctx_event_record(robo_ctx* ctx, int32_t slot);
 int32_t robo_ctx_event_elapsed_ms(robo_ctx* ctx, int32_t slot_begin, int32_t slot_end, float* out_ms);
 int32_t robo_ctx_set_phase_events(robo_ctx* ctx, int32_t on);
@@ -668,6 +669,51 @@ int32_t robo_ehvi_eval_cand(robo_gp* gp1, robo_gp* gp2, robo_cand* cand, const d
 int32_t robo_ehvi_eval_moments(robo_ctx* ctx, int64_t m, const double* mean1, const double* var1, const double* mean2,
                                const double* var2, const double* front, int32_t P, const double* ref, double* out_ehvi,
                                double* out_max, int64_t* out_argmax, uint32_t* out_flags);
+
+/* ---- expected hypervolume improvement for two to four objectives (box decomposition; not in the reference).  All K
+ * objectives are minimised, their posteriors N(mu_k, s_k^2) independent.
+ *   Bounds.     Per objective k, n_bounds[k] values t_k[0] = -inf < t_k[1] < .. < t_k[n_k - 1]: the distinct front
+ *               coordinates below the reference point, -inf in front and ref_k last; 2 <= n_k <= ROBO_EHVI_BOX_MAX_BOUNDS.
+ *               bounds holds them concatenated, objective after objective (sum_k n_k doubles).
+ *   Boxes.      B boxes [t_k[lo_bk], t_k[hi_bk]) over k with lo_bk < hi_bk < n_k, as uint16 pairs (lo, hi), row-major
+ *               B x K x 2; 1 <= B <= ROBO_EHVI_BOX_MAX_BOXES.  THAT THE BOXES PARTITION the region below ref which the front
+ *               does not dominate IS THE CALLER'S CONTRACT: the library checks the indices only (any family of boxes gives
+ *               the sum below).
+ *   Value.      g(b; mu, s) = E[(b - y)^+] exactly as in robo_ehvi_eval_cand (g(-inf) = +0; s == 0: max(b - mu, 0); the
+ *               erfcx tail, exactly 0 for z < -36), evaluated once per (candidate, bound), and
+ *                 EHVI = sum_{b=0}^{B-1} prod_{k=0}^{K-1} [ g(t_k[hi_bk]; mu_k, s_k) - g(t_k[lo_bk]; mu_k, s_k) ],  every factor >= 0.
+ *               With K = 2 and the strips as boxes this is robo_ehvi_eval_cand's rule (equal within the bounds, not in bits).
+ *   Order.      A factor is the difference of two rounded g; one that comes out negative counts as 0, a NaN stays.  A box's
+ *               product runs in objective order k = 0 .. K - 1.  The boxes b = l, l + 16, l + 32, .. are added in ascending
+ *               b into partial sum l (l = 0 .. 15) by a compensated (Kahan) sum; the 16 partial sums are added in ascending
+ *               l, compensated again.  Every operation is rounded once and never contracted, and the order depends on nothing
+ *               but K, the bounds and the boxes: a value's bits do not depend on the batch position, on m, on the chunking
+ *               or on which of the two entry points produced it.
+ *   Edges.      A NaN among the 2 K moments (or a negative variance): NaN and ROBO_FLAG_NAN.  Any s_k == 0 (the moments form
+ *               only: the fused form's variances are floored at DBL_EPSILON): ROBO_FLAG_ZERO_SIGMA, the value by the max
+ *               branch (not zeroed).  argmax follows np.argmax (first index, NaN maximal) through the sweep's own reduction.
+ * The fused form runs the K sweeps over cand, each chunked by the candidate workspace, into the rows of the handle's sample
+ * tables, then the box kernel, the reduction and the read-back with one synchronisation.  The GPs may differ in kernel kind,
+ * hyper-parameters, N and output normalisation.  out_ehvi (m) is nullable; out_trace, nullable, m x 2 K: per candidate mu_0,
+ * var_0, .. mu_{K-1}, var_{K-1} as the kernel read them (what robo_gp_predict_cand returns).  Later calls on the same handles
+ * return what they return on fresh ones.
+ * K outside 2 .. ROBO_EHVI_BOX_MAX_OBJ, an n_bounds[k] outside 2 .. ROBO_EHVI_BOX_MAX_BOUNDS, B outside 1 ..
+ * ROBO_EHVI_BOX_MAX_BOXES, a first bound that is not -inf, a later bound that is not finite, bounds that are not strictly
+ * ascending, a box with lo >= hi or hi >= n_bounds[k], a NULL required pointer, GPs or cand on different contexts:
+ * ROBO_BAD_ARGUMENT; a GP whose dim is not cand's: ROBO_BAD_SHAPE; a GP that is not fitted: ROBO_NOT_FITTED -- all before
+ * anything is launched.
+ * Event slots 34 and 35 bracket the box kernel, under the condition of slots 24..27.                                    */
+#define ROBO_EHVI_BOX_MAX_OBJ 4
+#define ROBO_EHVI_BOX_MAX_BOUNDS 258 /* per objective: -inf, <= 256 distinct coordinates, ref */
+#define ROBO_EHVI_BOX_MAX_BOXES 65536
+int32_t robo_ehvi_box_eval_cand(robo_gp* const* gps, int32_t K, robo_cand* cand, const double* bounds,
+                                const int32_t* n_bounds, const uint16_t* boxes, int32_t B, double* out_ehvi /* nullable */,
+                                double* out_max, int64_t* out_argmax, uint32_t* out_flags, double* out_trace /* nullable */);
+/* the box kernel alone for any models' moments: mean, var (K x m, row-major).  Equals the fused call bit for bit when fed
+ * the fused call's own trace.                                                                                           */
+int32_t robo_ehvi_box_eval_moments(robo_ctx* ctx, int64_t m, int32_t K, const double* mean, const double* var,
+                                   const double* bounds, const int32_t* n_bounds, const uint16_t* boxes, int32_t B,
+                                   double* out_ehvi, double* out_max, int64_t* out_argmax, uint32_t* out_flags);
 
 /* ---- constrained expected improvement (Schonlau, Welch & Jones 1998; Gardner et al. 2014; Gelbart, Snoek & Adams 2014; not
  * in the reference): expected improvement weighted by the probability that C black-box constraints hold, each modelled by a

@@ -32,6 +32,7 @@ FANTASY_KINDS = {"kriging_believer": 0, "constant_liar": 1}   # robo_acq_batch_*
 MES_MAX_K = 128                                  # robo_mes_*: cap on the sampled minima per model
 KG_MAX_DISC = 64                                 # robo_kg_*: cap on the discretisation points of the knowledge gradient
 EHVI_MAX_FRONT = 4096                            # robo_ehvi_*: cap on the points of the Pareto front
+EHVI_BOX_MAX_OBJ, EHVI_BOX_MAX_BOUNDS, EHVI_BOX_MAX_BOXES = 4, 258, 65536     # robo_ehvi_box_*: objectives, bounds each, boxes
 CEI_MAX_CONSTRAINTS = 16                         # robo_cei_*: cap on the constraints of constrained expected improvement
 PATHS_MAX = 64                                   # robo_paths_*: cap on the sample paths of one object
 PATHS_MAX_FEATURES = 4096                        # ... and on its random Fourier features
@@ -61,7 +62,7 @@ SYMBOLS = [
     "robo_acq_batch_cand", "robo_acq_batch_marginal_cand", "robo_qei_batch_cand", "robo_qei_batch_marginal_cand",
     "robo_mes_eval_cand", "robo_mes_eval_marginal_cand", "robo_mes_sample_min_moments", "robo_mes_eval_moments",
     "robo_kg_eval_cand", "robo_kg_eval_marginal_cand", "robo_kg_eval_moments",
-    "robo_ehvi_eval_cand", "robo_ehvi_eval_moments",
+    "robo_ehvi_eval_cand", "robo_ehvi_eval_moments", "robo_ehvi_box_eval_cand", "robo_ehvi_box_eval_moments",
     "robo_cei_eval_cand", "robo_cei_eval_moments", "robo_cei_refine_cand",
     "robo_paths_create", "robo_paths_eval_cand", "robo_paths_destroy", "robo_paths_descend", "robo_paths_refine_cand",
     "robo_ig_eval_cand", "robo_ig_eval_per_cost_cand", "robo_ig_eval_moments", "robo_gp_cross_cov",
@@ -257,6 +258,10 @@ def lib():
         "robo_ehvi_eval_cand": [vp, vp, vp, _dp, i32, _dp, _dp, _dp, C.POINTER(i64), C.POINTER(C.c_uint32), _dp],
         "robo_ehvi_eval_moments": [vp, i64, _dp, _dp, _dp, _dp, _dp, i32, _dp, _dp, _dp, C.POINTER(i64),
                                    C.POINTER(C.c_uint32)],
+        "robo_ehvi_box_eval_cand": [pp, i32, vp, _dp, C.POINTER(i32), C.POINTER(C.c_uint16), i32, _dp, _dp, C.POINTER(i64),
+                                    C.POINTER(C.c_uint32), _dp],
+        "robo_ehvi_box_eval_moments": [vp, i64, i32, _dp, _dp, _dp, C.POINTER(i32), C.POINTER(C.c_uint16), i32, _dp, _dp,
+                                       C.POINTER(i64), C.POINTER(C.c_uint32)],
         "robo_cei_eval_cand": [vp, pp, i32, _dp, i32, dbl, dbl, i32, vp, _dp, _dp, C.POINTER(i64), C.POINTER(C.c_uint32),
                                _dp],
         "robo_cei_eval_moments": [vp, i64, i32, _dp, _dp, _dp, _dp, _dp, i32, dbl, dbl, i32, _dp, _dp, C.POINTER(i64),
@@ -414,7 +419,7 @@ def mcmc_draws(random_state, n_steps, half):
 
 
 class Context(object):
-    """robo_ctx: one device, one HIP stream, 34 event slots."""
+    """robo_ctx: one device, one HIP stream, 36 event slots."""
 
     def __init__(self, device=0, stream=None):
         self._h = C.c_void_p()
@@ -988,6 +993,19 @@ class DeviceGP(object):
                                         _arr(trace) if trace is not None else None))
         return EHVIResult(out, *best.values(), trace)
 
+    def ehvi_box(self, other_gps, cand, bounds, boxes, want_values=True, diagnostics=False):
+        """expected hypervolume improvement of ``cand`` over K = 2 .. 4 objectives, this GP the first and ``other_gps`` the
+        rest, from the per-objective bounds and the boxes of util.pareto.nondominated_boxes (robo_ehvi_box_eval_cand)
+        -> EHVIResult with trace (m, 2 K)"""
+        gps = [self] + list(other_gps)
+        tail = _ehvi_box_tail(bounds, boxes, len(gps))
+        out = np.empty(cand.m) if want_values else None
+        trace = np.empty((cand.m, 2 * len(gps))) if diagnostics else None
+        best = _Best()
+        check(lib().robo_ehvi_box_eval_cand(_handles(gps), len(gps), cand._h, *tail[:4], _arr(out) if want_values else None,
+                                            *best.refs, _arr(trace) if trace is not None else None))
+        return EHVIResult(out, *best.values(), trace)
+
     def cei(self, constraint_gps, cand, thresholds, kind, par, eta, want_values=True, diagnostics=False):
         """constrained expected improvement of ``cand`` with this GP as the objective and ``constraint_gps`` (C of them) as
         the constraints c_k(x) <= thresholds[k]; kind "ei" or "log_ei"; eta None: no feasible incumbent yet, the probability
@@ -1138,7 +1156,7 @@ def kg_from_moments(ctx, s, v, mean, disc_mean, sn2, include_self=True):
 
 class EHVIResult(object):
     """values (m,) or None, max, argmax, flags; with diagnostics: trace (m, 4) = per candidate mean1, var1, mean2, var2 as
-    the kernel read them (include/robo_hip.h)"""
+    the kernel read them (include/robo_hip.h); the box form's trace is (m, 2 K), a (mean, var) pair per objective"""
 
     def __init__(self, values, max, argmax, flags, trace=None):
         self.values, self.max, self.argmax, self.flags, self.trace = values, float(max), int(argmax), int(flags), trace
@@ -1165,6 +1183,38 @@ def ehvi_from_moments(ctx, mean1, var1, mean2, var2, front, ref):
     best = _Best()
     check(lib().robo_ehvi_eval_moments(ctx._h, mean1.shape[0], _arr(mean1), _arr(var1), _arr(mean2), _arr(var2), _arr(front),
                                        front.shape[0], _arr(ref), _arr(out), *best.refs))
+    return (out,) + best.values()
+
+
+def _ehvi_box_tail(bounds, boxes, K):
+    """(bounds pointer, n_bounds pointer, boxes pointer, B, the arrays behind them) of the box entry points: ``bounds`` a
+    list of K ascending fp64 arrays beginning with -inf, ``boxes`` (B, K, 2) integer index pairs"""
+    bounds = [_f64(b).reshape(-1) for b in bounds]
+    if len(bounds) != K:
+        raise ValueError("%d arrays of bounds for %d objectives" % (len(bounds), K))
+    boxes = np.asarray(boxes)
+    if boxes.ndim != 3 or boxes.shape[1:] != (K, 2):
+        raise ValueError("boxes must be (B, %d, 2), got %r" % (K, boxes.shape))
+    if boxes.size and (boxes.min() < 0 or boxes.max() > 65535):
+        raise ValueError("box indices must fit 16 bits")
+    flat = _f64(np.concatenate(bounds)) if bounds else np.zeros(1)
+    n = np.ascontiguousarray([b.shape[0] for b in bounds], dtype=np.int32)
+    b16 = np.ascontiguousarray(boxes, dtype=np.uint16)
+    return (_arr(flat), n.ctypes.data_as(C.POINTER(C.c_int32)), b16.ctypes.data_as(C.POINTER(C.c_uint16)), boxes.shape[0],
+            (flat, n, b16))
+
+
+def ehvi_box_from_moments(ctx, means, vars, bounds, boxes):
+    """the box kernel of the expected hypervolume improvement alone on the device for the moments of any K = 2 .. 4 models
+    (robo_ehvi_box_eval_moments): means, vars (K, m), the bounds and boxes of util.pareto.nondominated_boxes
+    -> (values, max, argmax, flags)"""
+    means, vars = _f64(means), _f64(vars)
+    assert means.ndim == 2 and vars.shape == means.shape
+    tail = _ehvi_box_tail(bounds, boxes, means.shape[0])
+    out = np.empty(means.shape[1])
+    best = _Best()
+    check(lib().robo_ehvi_box_eval_moments(ctx._h, means.shape[1], means.shape[0], _arr(means), _arr(vars), *tail[:4],
+                                           _arr(out), *best.refs))
     return (out,) + best.values()
 
 

@@ -232,6 +232,9 @@ int32_t robo_gp_fit(robo_gp* g, const double* theta, double mean_c, double* out_
     }
     robo_ctx* c = g->ctx;
     g->fitted = false;
+    // The runtime keeps a failed call's error with the thread until somebody asks for it: one the APPLICATION left behind
+    // (hipHostRegister declining a pageable buffer, as bench.py --full tries before it refits) is not this fit's launch failing
+    (void)hipGetLastError();
     // event slots 20..23: 20 -> 21 gram build, 21 -> 22 Cholesky, 22 -> 23 log-likelihood reduce
     const bool ev = phase_events_on(c, nullptr);
     if (ev) ROBO_TRY(record_phase(c, EV_FIT_BEGIN));

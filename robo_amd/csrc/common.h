@@ -513,7 +513,9 @@ enum RoboEventSlot {
     EV_FOLD_END = 31,         //   EHVI's strip kernel, the passes of the path kernel, q-EI's fold kernel of the last pick
     EV_CEI_BEGIN = 32,        // constrained EI's fold kernel
     EV_CEI_END = 33,
-    EV_LAST = EV_CEI_END
+    EV_EHVI_BOX_BEGIN = 34,   // the box kernel of robo_ehvi_box_eval_cand
+    EV_EHVI_BOX_END = 35,
+    EV_LAST = EV_EHVI_BOX_END
 };
 constexpr int ROBO_EVENT_SLOTS = EV_LAST + 1;
 constexpr int ROBO_CHAIN_SLOTS = 16;    // chained solves whose time-out words may be in flight between two synchronisations
@@ -655,7 +657,8 @@ struct robo_cand {
     size_t f_cap, q_cap, g_cap;
     double* d_kg;       // knowledge gradient (lazy, grows): [S x 64 discretisation means | S x m x (nb + 2) trace]; the expected
                         // hypervolume improvement's [front (4096 x 2) | m x 4 trace] (api_ehvi.hip); constrained EI's trace
-                        // (m x (2 (C + 1) + 2)) or, in the moments form, the constraints' [means (C x m) | vars (C x m)]
+                        // (m x (2 (C + 1) + 2)) or, in the moments form, the constraints' [means (C x m) | vars (C x m)];
+                        // the box form's [bounds | box words | m x 2 K trace or the moments' means, vars] (api_ehvi_box.hip)
     size_t kg_cap;
     double* h_igkey;    // host copy of the EP state whose device form d_G / d_igc hold (compared in full before an upload
     size_t igkey_len;   // is skipped: compute() is called many times per update(), information_gain.py:87-125 / :153-167)
@@ -860,6 +863,16 @@ int launch_kg(robo_ctx* ctx, const double* d_S, const double* d_var, const doubl
 int launch_ehvi(robo_ctx* ctx, const double* d_mean1, const double* d_var1, const double* d_mean2, const double* d_var2,
                 const double* d_front, int P, double r1, double r2, int64_t m, double* d_out, unsigned* d_flags,
                 double* d_trace);
+// ehvi_box.hip: the expected hypervolume improvement of candidates c < m over K = 2 .. 4 objectives (row k of the moments at
+// d_mean / d_var + k * stride) from the concatenated bounds (sh.rows doubles) and the B boxes' index words (B x K,
+// lo | hi << 16: the caller's uint16 pairs) into d_out; d_trace (m x 2 K: mean_0, var_0, .. mean_{K-1}, var_{K-1}) nullable
+struct EhviBoxShape {
+    int K, rows;                           // rows = sum_k n_bounds[k]
+    int base[ROBO_EHVI_BOX_MAX_OBJ];       // first row of objective k; rows for k >= K
+};
+int launch_ehvi_box(robo_ctx* ctx, const double* d_mean, const double* d_var, int64_t stride, const EhviBoxShape& sh,
+                    const double* d_bounds, const unsigned* d_boxes, int B, int64_t m, double* d_out, unsigned* d_flags,
+                    double* d_trace);
 // cei.hip: EI weighted by the probability of feasibility of candidates c < m from the objective's moments and the C
 // constraints' (row k at d_means / d_vars + k * stride) into d_out; the thresholds travel as a kernel argument;
 // d_trace (m x (2 (C + 1) + 2): the moments, L, the objective factor) nullable

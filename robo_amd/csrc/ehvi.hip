@@ -11,22 +11,11 @@
 // loads: no LDS, no barrier.  A candidate's strips are summed in index order i = 0 .. P with the boundary value
 // g(a_i) carried in a register, by a compensated sum; every operation of it is rounded once and never contracted (rn_*),
 // so the same four moments give the same bits at any batch position, for any m and in either entry point.
-#include "common.h"
-#include "kern_math.h"
+#include "ehvi_dev.h"
 
 namespace robo {
 
 constexpr int EHVI_WG = 64;      // one wavefront per workgroup: 65 536 candidates are four workgroups per CU
-
-__device__ __forceinline__ double ehvi_nan() { return __longlong_as_double(0x7FF8000000000000LL); }
-
-// g(b; mu, s) = E[(b - y)^+], y ~ N(mu, s^2); s == 0: max(b - mu, 0)
-__device__ __forceinline__ double ehvi_g(double b, double mu, double s) {
-    const double d = rn_sub(b, mu);
-    if (s == 0.0) return fmax(d, 0.0);
-    const double z = rn_div(d, s);
-    return rn_mul(s, rn_add(fmax(z, 0.0), norm_tail_mean(fabs(z))));
-}
 
 __global__ __launch_bounds__(EHVI_WG) void ehvi_kernel(const double* __restrict__ mean1, const double* __restrict__ var1,
                                                        const double* __restrict__ mean2, const double* __restrict__ var2,

@@ -1,4 +1,4 @@
-"""``multi_objective_optimization``: Bayesian optimisation of two objectives at once by the expected hypervolume
+"""``multi_objective_optimization``: Bayesian optimisation of two to four objectives at once by the expected hypervolume
 improvement over the observed Pareto front (not in the reference, whose front ends all take a scalar objective).
 
 One model per objective, each built as ``bayesian_optimization`` builds its model:
@@ -6,43 +6,48 @@ One model per objective, each built as ``bayesian_optimization`` builds its mode
     kernel   2 * Matern52Kernel(ones(D), ndim=D)
     prior    DefaultPrior(len(kernel) + 1)
     model    GaussianProcess | GaussianProcessMCMC(n_hypers = 3 * len(kernel), made even)
-    acq      EHVI over the pair: two native "gp" models take the fused device call, "gp_mcmc" enters with its mixture moments
+    acq      EHVI over the models: native "gp" models take the fused device call, "gp_mcmc" enters with its mixture moments
     maximiser RandomSampling | DeviceRandomSampling ("gp" only)
 
 The loop is this module's own (solver.BayesianOptimization assumes a scalar y): ``n_init`` Latin-hypercube points, then per
-iteration both models are refitted, the front is updated and EHVI is maximised.
+iteration every model is refitted, the front is updated and EHVI is maximised.
 """
 import numpy as np
 
 from robo_amd.acquisition_functions import EHVI
 from robo_amd.fmin import _multi_output
 from robo_amd.maximizers import DeviceRandomSampling, RandomSampling
-from robo_amd.util.pareto import hypervolume_2d, pareto_front_2d
+from robo_amd.util.pareto import hypervolume, hypervolume_2d, pareto_front, pareto_front_2d
 
 
 def multi_objective_optimization(objective_function, lower, upper, ref_point, num_iterations=30, n_init=3, maximizer="random",
                                  model_type="gp", n_candidates=500, rng=None, hyper_optimizer="host", n_restarts=8,
                                  chain_length=200, burnin_steps=100):
-    """Minimise both values of ``objective_function(x) -> (f1, f2)`` over the box [lower, upper] -> dict with X, Y (every
-    evaluation), pareto_X, pareto_Y (the front of Y inside ``ref_point``, sorted by f1), hypervolume (after every
-    evaluation), runtime and overhead (per evaluation).  ``num_iterations`` counts the ``n_init`` initial points."""
+    """Minimise all values of ``objective_function(x) -> (f1, .., fK)``, K = len(ref_point) in 2 .. 4, over the box
+    [lower, upper] -> dict with X, Y (every evaluation), pareto_X, pareto_Y (the front of Y inside ``ref_point``, sorted by
+    f1; for K > 2 in lexicographic order), hypervolume (after every evaluation), runtime and overhead (per evaluation).
+    ``num_iterations`` counts the ``n_init`` initial points."""
     lower, upper = np.asarray(lower, dtype=np.float64), np.asarray(upper, dtype=np.float64)
-    ref_point = np.array(ref_point, dtype=np.float64).reshape(2)
-    rng, models = _multi_output.output_models(2, lower, upper, num_iterations, n_init, maximizer, model_type, rng,
+    ref_point = np.array(ref_point, dtype=np.float64).reshape(-1)
+    K = ref_point.shape[0]
+    if not 2 <= K <= 4:
+        raise ValueError("ref_point has %d entries: two to four objectives" % K)
+    front_of, volume_of = (pareto_front_2d, hypervolume_2d) if K == 2 else (pareto_front, hypervolume)
+    rng, models = _multi_output.output_models(K, lower, upper, num_iterations, n_init, maximizer, model_type, rng,
                                               hyper_optimizer, n_restarts, chain_length, burnin_steps, acq_name="EHVI",
-                                              fused_over="two 'gp' models")
+                                              fused_over="%s 'gp' models" % ("two", "two", "two", "three", "four")[K])
     acq = EHVI(models, ref_point)
     cls = RandomSampling if maximizer == "random" else DeviceRandomSampling
     max_func = cls(acq, lower, upper, n_samples=n_candidates, rng=rng)
     hv = []
 
     def record(X, Y):
-        hv.append(hypervolume_2d(pareto_front_2d(np.array(Y), ref_point)[0], ref_point))
+        hv.append(volume_of(front_of(np.array(Y), ref_point)[0], ref_point))
         return "hypervolume %f" % hv[-1]
 
     X, Y, runtime, overhead = _multi_output.run(objective_function, lower, upper, models, acq, max_func, num_iterations,
-                                                n_init, rng, "two values", record)
+                                                n_init, rng, ("two", "two", "two", "three", "four")[K] + " values", record)
     Xa, Ya = np.array(X), np.array(Y)
-    front, idx = pareto_front_2d(Ya, ref_point)
+    front, idx = front_of(Ya, ref_point)
     return {"X": [x.tolist() for x in X], "Y": [y.tolist() for y in Y], "pareto_X": Xa[idx], "pareto_Y": front,
             "hypervolume": hv, "runtime": runtime, "overhead": overhead}
