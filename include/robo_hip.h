@@ -910,6 +910,60 @@ int32_t robo_paths_refine_cand(robo_paths* p, robo_cand* cand, int32_t n_starts,
                                int64_t* out_start_index /* S: row in cand, -1 when no start */, uint32_t* out_flags,
                                int64_t* out_starts /* S x n_starts, nullable */, double* out_trace /* nullable */);
 
+/* ---- Bayesian linear regression on basis features (Bishop 3.3 / 3.5; robo/models/bayesian_linear_regression.py): the model
+ * whose cost is linear in the number of observations.  With Phi (n x F) the features of the inputs,
+ *     A = beta Phi^T Phi + alpha I,   m = beta A^-1 Phi^T y,   mean(x) = m . phi(x),   var(x) = 1 / beta + phi(x)^T A^-1 phi(x).
+ *   Features.   ROBO_BLR_FEAT_GIVEN: the caller passes Phi rows (F doubles each) wherever "rows" appears below.  The other kinds
+ *               take raw rows (dim doubles each) and the features exist in LDS only: LINEAR [x, 1] (F = dim + 1), QUADRATIC
+ *               [x^2, x, 1] (F = 2 dim + 1), RFF scale cos(x . omega_f + phase_f) with omega (dim x F, row-major), phase (F).
+ *   Statistics. robo_blr_set_data reduces the n rows to G = Phi^T Phi, b = Phi^T y, yy = y^T y: one workgroup per chunk of
+ *               1024 rows, Phi^T Phi on the fp64 matrix instruction in row order, the chunks' partial sums added in chunk
+ *               order.  No atomics: the bits of G, b, yy depend on the data alone -- not on the workspace (which only bounds
+ *               how many partials exist at a time), the device or the call.  It then factors G = Q diag(lambda) Q^T by a
+ *               two-sided cyclic Jacobi iteration (negative lambda clamped to 0; a pair counts as converged at
+ *               |g_pq| <= 4 eps max(sqrt(|g_pp g_qq|), eps trace G); 40 sweeps without convergence: ROBO_RUNTIME_ERROR) and
+ *               keeps Q, lambda and c = Q^T b.  One synchronisation.  n is bounded by memory only.
+ *   Likelihood. With t_j = beta lambda_j + alpha:  log det A = sum_j log t_j,  m^T m = beta^2 sum_j c_j^2 / t_j^2,
+ *               |y - Phi m|^2 = yy - beta sum_j c_j^2 (beta lambda_j + 2 alpha) / t_j^2, clamped at 0.  Form 1 is Bishop (3.86);
+ *               form 0 is the reference's expression as written (bayesian_linear_regression.py:105-110), whose residual term
+ *               is the UNSQUARED norm.  No prior is added.  One lane per pair: a pair's value does not depend on S.  The
+ *               residual comes from sufficient statistics, so its absolute error is of the order eps beta yy.
+ *   Sweep.      psi = Q^T phi(x) once per candidate (matrix instruction, features in index order), then for every sample s
+ *               mean_s = sum_j psi_j beta_s c_j / t_sj and var_s = 1 / beta_s + sum_j psi_j^2 / t_sj (j ascending), then the
+ *               reference's mixture (predict, :244-252): the average of the means and of the variances over the samples, the
+ *               variance clipped at eps from below.  A candidate's bits do not depend on its position, on m or on the other
+ *               candidates.  A NaN coordinate gives NaN.
+ * robo_blr_acq_eval_cand is the sweep followed by robo_acq_eval_moments' kernels on the device-resident moments: the same
+ * values, argmax rule and flags, one synchronisation.  out_per_sample (nullable): [means (S x m) | variances (S x m)].
+ * F outside 1 .. 128, dim outside 1 .. 64, a kind outside 0 .. 3, F not the kind's count, non-finite omega / phase / scale,
+ * S outside 1 .. 64 (robo_blr_set_hypers), alpha or beta not positive and finite, n < 1, m < 1, a NULL required pointer,
+ * a NaN or an infinity in the training rows or targets (found on the device, in trace G + yy, before the eigensolver runs):
+ * ROBO_BAD_ARGUMENT.  Event slots: robo_blr_set_data records 30 -> 31 around the statistics and sum kernels and 31 -> 29
+ * around the eigensolver when the phase events are switched on; the sweep kernel is bracketed by 30 -> 31 under the
+ * condition of slots 24..27.  A call before robo_blr_set_data (or, for the sweep, before robo_blr_set_hypers): ROBO_NOT_FITTED.
+ * robo_blr_set_data forgets the hyper-parameter samples.  robo_blr_destroy(NULL) is harmless.                               */
+#define ROBO_BLR_FEAT_GIVEN 0
+#define ROBO_BLR_FEAT_LINEAR 1
+#define ROBO_BLR_FEAT_QUADRATIC 2
+#define ROBO_BLR_FEAT_RFF 3
+#define ROBO_BLR_MAX_FEATURES 128
+#define ROBO_BLR_MAX_DIM 64
+#define ROBO_BLR_MAX_SAMPLES 64
+typedef struct robo_blr robo_blr; /* one data set's sufficient statistics, their eigenpairs and the hyper-parameter samples */
+int32_t robo_blr_create(robo_ctx* ctx, int32_t feat_kind, int32_t dim, int32_t F, const double* omega /* kind 3 */,
+                        const double* phase /* kind 3 */, double scale /* kind 3 */, robo_blr** out);
+int32_t robo_blr_destroy(robo_blr* blr);
+int32_t robo_blr_set_data(robo_blr* blr, const double* rows, const double* y, int64_t n);
+/* every output nullable: G (F x F), b (F), yy (1), lambda (F), Q (F x F, column j the eigenvector of lambda_j) */
+int32_t robo_blr_get_stats(robo_blr* blr, double* out_G, double* out_b, double* out_yy, double* out_lambda, double* out_Q);
+int32_t robo_blr_loglik_batch(robo_blr* blr, int32_t S, const double* log_alpha_beta /* S x 2 */, int32_t form,
+                              double* out /* S */);
+int32_t robo_blr_set_hypers(robo_blr* blr, int32_t S, const double* alpha_beta /* S x 2 */);
+int32_t robo_blr_predict(robo_blr* blr, const double* rows, int64_t m, double* out_mean, double* out_var,
+                         double* out_per_sample /* nullable */);
+int32_t robo_blr_acq_eval_cand(robo_blr* blr, int32_t acq_kind, double par, double eta, const double* rows, int64_t m,
+                               double* out_acq /* nullable */, double* out_max, int64_t* out_argmax, uint32_t* out_flags);
+
 /* ---- entropy search: replaces InformationGain.innovations/_dh_fun/compute ---------------
  * (robo/acquisition_functions/information_gain.py:87-125,169-203,253-272), batched over candidates.
  * rep: the Nb <= 64 representer points as a candidate batch (same normalised space).  The EP

@@ -34,6 +34,9 @@ KG_MAX_DISC = 64                                 # robo_kg_*: cap on the discret
 EHVI_MAX_FRONT = 4096                            # robo_ehvi_*: cap on the points of the Pareto front
 EHVI_BOX_MAX_OBJ, EHVI_BOX_MAX_BOUNDS, EHVI_BOX_MAX_BOXES = 4, 258, 65536     # robo_ehvi_box_*: objectives, bounds each, boxes
 CEI_MAX_CONSTRAINTS = 16                         # robo_cei_*: cap on the constraints of constrained expected improvement
+BLR_FEATURE_KINDS = {"given": 0, "linear": 1, "quadratic": 2, "rff": 3}   # robo_blr_create
+BLR_MAX_FEATURES, BLR_MAX_DIM, BLR_MAX_SAMPLES = 128, 64, 64
+BLR_CHUNK, BLR_TILE = 1024, 64                  # rows per workgroup of the statistics kernel; candidates per workgroup of the sweep
 PATHS_MAX = 64                                   # robo_paths_*: cap on the sample paths of one object
 PATHS_MAX_FEATURES = 4096                        # ... and on its random Fourier features
 PATHS_MAX_STARTS = 1024                          # robo_paths_refine_cand: cap on n_starts (per path)
@@ -64,6 +67,8 @@ SYMBOLS = [
     "robo_kg_eval_cand", "robo_kg_eval_marginal_cand", "robo_kg_eval_moments",
     "robo_ehvi_eval_cand", "robo_ehvi_eval_moments", "robo_ehvi_box_eval_cand", "robo_ehvi_box_eval_moments",
     "robo_cei_eval_cand", "robo_cei_eval_moments", "robo_cei_refine_cand",
+    "robo_blr_create", "robo_blr_destroy", "robo_blr_set_data", "robo_blr_get_stats", "robo_blr_loglik_batch",
+    "robo_blr_set_hypers", "robo_blr_predict", "robo_blr_acq_eval_cand",
     "robo_paths_create", "robo_paths_eval_cand", "robo_paths_destroy", "robo_paths_descend", "robo_paths_refine_cand",
     "robo_ig_eval_cand", "robo_ig_eval_per_cost_cand", "robo_ig_eval_moments", "robo_gp_cross_cov",
     "robo_ep_joint_min", "robo_pmin_mc", "robo_igmc_eval_cand", "robo_igmc_eval_moments",
@@ -268,6 +273,14 @@ def lib():
                                   C.POINTER(C.c_uint32)],
         "robo_cei_refine_cand": [vp, pp, i32, _dp, i32, dbl, dbl, i32, vp, i32, i32, dbl, _dp, _dp, C.POINTER(i64),
                                  C.POINTER(C.c_uint32), C.POINTER(i64), _dp],
+        "robo_blr_create": [vp, i32, i32, i32, _dp, _dp, dbl, pp],
+        "robo_blr_destroy": [vp],
+        "robo_blr_set_data": [vp, _dp, _dp, i64],
+        "robo_blr_get_stats": [vp, _dp, _dp, _dp, _dp, _dp],
+        "robo_blr_loglik_batch": [vp, i32, _dp, i32, _dp],
+        "robo_blr_set_hypers": [vp, i32, _dp],
+        "robo_blr_predict": [vp, _dp, i64, _dp, _dp, _dp],
+        "robo_blr_acq_eval_cand": [vp, i32, dbl, dbl, _dp, i64, _dp, _dp, C.POINTER(i64), C.POINTER(C.c_uint32)],
         "robo_paths_create": [vp, i32, i32, _dp, _dp, _dp, _dp, pp],
         "robo_paths_eval_cand": [vp, vp, _dp, _dp, C.POINTER(i64), C.POINTER(C.c_uint32)],
         "robo_paths_destroy": [vp],
@@ -1357,6 +1370,90 @@ class PosteriorPaths(object):
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
             self._owner.robo_paths_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DeviceBLR(object):
+    """robo_blr: Bayesian linear regression on basis features (include/robo_hip.h).  ``rows`` are feature rows (n, F) for
+    kind "given" and raw inputs (n, dim) otherwise."""
+
+    def __init__(self, ctx, kind, dim, n_features, omega=None, phase=None, scale=0.0):
+        self._h = None
+        self.ctx, self.kind, self.dim, self.n_features = ctx, kind, int(dim), int(n_features)
+        self.width = self.n_features if kind == "given" else self.dim
+        self.n_samples = 0
+        if kind == "rff":
+            omega, phase = _f64(omega, (self.dim, self.n_features)), _f64(phase, (self.n_features,))
+        self._owner = lib()
+        h = C.c_void_p()
+        check(self._owner.robo_blr_create(ctx._h, BLR_FEATURE_KINDS[kind], self.dim, self.n_features,
+                                          _arr(omega) if kind == "rff" else None, _arr(phase) if kind == "rff" else None,
+                                          float(scale), C.byref(h)))
+        self._h = h
+
+    def _rows(self, rows):
+        rows = _f64(rows)
+        if rows.ndim != 2 or rows.shape[1] != self.width:
+            raise RoboBadShape("rows must be (n, %d), got %r" % (self.width, rows.shape))
+        return rows
+
+    def set_data(self, rows, y):
+        rows = self._rows(rows)
+        y = _f64(y, (rows.shape[0],))
+        self.n_samples = 0
+        check(lib().robo_blr_set_data(self._h, _arr(rows), _arr(y), rows.shape[0]))
+
+    def stats(self):
+        """-> G (F, F), b (F,), yy, lambda (F,), Q (F, F)"""
+        F = self.n_features
+        G, b, yy, lam, Q = np.empty((F, F)), np.empty(F), C.c_double(0), np.empty(F), np.empty((F, F))
+        check(lib().robo_blr_get_stats(self._h, _arr(G), _arr(b), C.byref(yy), _arr(lam), _arr(Q)))
+        return G, b, yy.value, lam, Q
+
+    def loglik(self, log_alpha_beta, form=0):
+        """marginal log-likelihoods (no prior) of (S, 2) pairs (log alpha, log beta); form 0: the reference's expression as
+        written, form 1: Bishop (3.86)"""
+        th = _f64(log_alpha_beta)
+        if th.ndim != 2 or th.shape[1] != 2:
+            raise RoboBadShape("log_alpha_beta must be (S, 2), got %r" % (th.shape,))
+        out = np.empty(th.shape[0])
+        check(lib().robo_blr_loglik_batch(self._h, th.shape[0], _arr(th), int(form), _arr(out)))
+        return out
+
+    def set_hypers(self, alpha_beta):
+        ab = _f64(alpha_beta)
+        if ab.ndim != 2 or ab.shape[1] != 2:
+            raise RoboBadShape("alpha_beta must be (S, 2), got %r" % (ab.shape,))
+        check(lib().robo_blr_set_hypers(self._h, ab.shape[0], _arr(ab)))
+        self.n_samples = ab.shape[0]
+
+    def predict(self, rows, per_sample=False):
+        """-> mixture (mean, var) [, per-sample means (S, m), variances (S, m)]"""
+        rows = self._rows(rows)
+        m = rows.shape[0]
+        mean, var = np.empty(m), np.empty(m)
+        ps = np.empty((2, max(self.n_samples, 1), m)) if per_sample else None
+        check(lib().robo_blr_predict(self._h, _arr(rows), m, _arr(mean), _arr(var), _arr(ps) if per_sample else None))
+        return (mean, var, ps[0], ps[1]) if per_sample else (mean, var)
+
+    def acq(self, kind, par, eta, rows, want_values=True):
+        """sweep + closed-form acquisition + argmax in one call (robo_blr_acq_eval_cand) -> (values, max, argmax, flags)"""
+        rows = self._rows(rows)
+        out = np.empty(rows.shape[0]) if want_values else None
+        best = _Best()
+        check(lib().robo_blr_acq_eval_cand(self._h, ACQ_KINDS[kind], float(par), float(eta), _arr(rows), rows.shape[0],
+                                           _arr(out) if want_values else None, *best.refs))
+        return (out,) + best.values()
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            self._owner.robo_blr_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -292,6 +292,11 @@ class ClosedFormAcquisition(BaseAcquisitionFunction):
     def _is_native(self):
         return hasattr(self.model, "acquisition") and hasattr(self.model, "gp")
 
+    def _has_fused_call(self):
+        """a device GP, or another device model with the same fused ``acquisition`` call (Bayesian linear regression:
+        robo_blr_acq_eval_cand); refine, select_batch and the candidate shard stay the GP's"""
+        return self._is_native() or getattr(self.model, "device_acquisition", False)
+
     def _eta(self, eta):
         if not self.needs_eta:
             return 0.0
@@ -302,7 +307,7 @@ class ClosedFormAcquisition(BaseAcquisitionFunction):
     def _evaluate(self, X, eta):
         """-> (values (N,), flags)"""
         eta = self._eta(eta)
-        if self._is_native():
+        if self._has_fused_call():
             vals, mx, am, flags = self.model.acquisition(self.kind, self.par, eta, X)
         else:
             m, v = self.model.predict(X)
@@ -315,7 +320,7 @@ class ClosedFormAcquisition(BaseAcquisitionFunction):
     def argmax(self, X, eta=None):
         """Index of the best candidate without copying the values back (large-M maximisers)."""
         eta = self._eta(eta)
-        if self._is_native():
+        if self._has_fused_call():
             _, mx, am, flags = self.model.acquisition(self.kind, self.par, eta, X, want_values=False)
             self.last_max, self.last_argmax = mx, am
             if self.kind == "ei":

@@ -6,6 +6,7 @@ without george, pybnn and pyrfr: :2,5,8,11), wired to the MI355X GP path:
     prior    DefaultPrior(len(kernel) + 1)                   (:83)
     n_hypers 3 * len(kernel), made even                      (:85-87)
     model    GaussianProcess | GaussianProcessMCMC(chain_length=200, burnin_steps=100)  (:89-100)
+             | BayesianLinearRegression on basis features ("blr"; not a choice of the reference's front end)
     acq      EI | LogEI | PI | LCB, wrapped in MarginalizationGPMCMC for gp_mcmc       (:114-129)
              | MES | KnowledgeGradient | ThompsonSampling (not in the reference; Thompson sampling marginalises over
              the hyper-parameter samples itself and is not wrapped)
@@ -13,8 +14,7 @@ without george, pybnn and pyrfr: :2,5,8,11), wired to the MI355X GP path:
     maximiser RandomSampling | SciPyOptimizer | DifferentialEvolution                    (:131-139)
               | DeviceRandomSampling | DeviceGradientAscent (not in the reference)
 
-Model types other than the two GP ones (rf / bohamiann / dngo) are outside this project's hot path
-(SURVEY.md section 2, rows 6, 8).
+The model types rf / bohamiann / dngo are outside this project's hot path.
 """
 import logging
 
@@ -27,6 +27,7 @@ from robo_amd.kernels import Matern52Kernel
 from robo_amd.maximizers import (DeviceGradientAscent, DeviceRandomSampling, DifferentialEvolution, RandomSampling,
                                  SciPyOptimizer)
 from robo_amd.models import GaussianProcess, GaussianProcessMCMC
+from robo_amd.models.bayesian_linear_regression import BayesianLinearRegression, quadratic_basis_func
 from robo_amd.priors import DefaultPrior
 from robo_amd.solver import BayesianOptimization
 
@@ -37,7 +38,7 @@ def bayesian_optimization(objective_function, lower, upper, num_iterations=30, X
                           maximizer="random", acquisition_func="log_ei", model_type="gp_mcmc", n_init=3, rng=None,
                           output_path=None, n_candidates=500, chain_length=200, burnin_steps=100, n_gpus=None,
                           devices=None, batch_size=1, fantasy="kriging_believer", liar="min", evaluate_batch=None,
-                          hyper_optimizer="host", n_restarts=8, n_features=1024, n_mc=128):
+                          hyper_optimizer="host", n_restarts=8, n_features=1024, n_mc=128, basis=None):
     """Minimise ``objective_function`` over the box [lower, upper] -> dict with x_opt, f_opt,
     incumbents, incumbent_values, runtime, overhead, X, y (same keys as the reference).
 
@@ -55,6 +56,13 @@ def bayesian_optimization(objective_function, lower, upper, num_iterations=30, X
     minimiser of one posterior sample path over the candidates, so ``batch_size=q`` proposes one point per path from one
     call: ``fantasy`` and ``liar`` are ignored (a path needs no fantasies).  With ``model_type="gp_mcmc"`` every path
     draws its own hyper-parameter sample.  One device only.
+
+    ``model_type="blr"``: Bayesian linear regression on the features ``basis`` -- ``linear_basis_func``,
+    ``quadratic_basis_func`` (the default), a ``RandomFourierBasis`` (an approximate GP, linear in the number of
+    observations) or any callable rows -> features (models/bayesian_linear_regression.py) -- with (alpha, beta) sampled by
+    the ensemble sampler (``chain_length``, ``burnin_steps``, 20 walkers).  ``acquisition_func`` is one of ei / log_ei / pi
+    / lcb and ``maximizer`` a host one; every maximisation over a candidate batch is one fused device call
+    (robo_blr_acq_eval_cand).  One device, ``batch_size=1``.
 
     ``fantasy="joint"`` (``acquisition_func="ei"`` only): the proposals of a round are picked by joint Monte-Carlo batch
     EI over ``n_mc`` scenarios drawn from this call's rng (``EI.select_batch``); ``liar`` is ignored.  Any other
@@ -91,8 +99,18 @@ def bayesian_optimization(objective_function, lower, upper, num_iterations=30, X
         model = GaussianProcessMCMC(kernel, prior=prior, n_hypers=n_hypers, chain_length=chain_length,
                                     burnin_steps=burnin_steps, normalize_input=True, normalize_output=False,
                                     rng=rng, lower=lower, upper=upper, devices=devices)
+    elif model_type == "blr":
+        if acquisition_func not in ("ei", "log_ei", "pi", "lcb") or maximizer not in ("random", "scipy",
+                                                                                    "differential_evolution") \
+                or devices or batch_size != 1 or hyper_optimizer != "host":
+            raise ValueError("model_type='blr' takes acquisition_func ei / log_ei / pi / lcb, a host maximizer (random / scipy "
+                             "/ differential_evolution), one device and batch_size=1")
+        model = BayesianLinearRegression(basis_func=quadratic_basis_func if basis is None else basis, rng=rng,
+                                         chain_length=chain_length, burnin_steps=burnin_steps)
     else:
-        raise ValueError("'{}' is not a valid model (robo_amd provides 'gp' and 'gp_mcmc')".format(model_type))
+        raise ValueError("'{}' is not a valid model (robo_amd provides 'gp', 'gp_mcmc' and 'blr')".format(model_type))
+    if basis is not None and model_type != "blr":
+        raise ValueError("basis=... applies to model_type='blr'")
 
     # "mes": max-value entropy search; its draws (discretisation, uniforms) come from this call's rng
     # "kg": knowledge gradient over a discretisation drawn from this call's rng as well
