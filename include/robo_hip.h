@@ -144,7 +144,9 @@ int32_t robo_ctx_set_phase_events(robo_ctx* ctx, int32_t on);
  * robo_gp_predict[_cand], robo_gp_predict_cov, robo_acq_eval[_cand] and robo_acq_eval_marginal_cand, bit-identical
  * results; a launch whose hand-off times out is repeated by launches, the context stays off the chain until this key is
  * set again, and robo_last_error_string says so although the call succeeds), trsm_chain_max_wg (the automatic rule:
- * while 16-candidate tiles x block rows <= this many times the CU count), trsm_chain_spin_limit (tests only).           */
+ * while 16-candidate tiles x block rows <= this many times the CU count), trsm_chain_spin_limit (tests only),
+ * mlp_fused (robo_mlp_train on at most 1024 rows: 1: every step of the call in ONE single-workgroup launch; -1 = default
+ * and 0: two launches per step, which was measured faster; the same bits either way).                                  */
 int32_t robo_ctx_set_tuning(robo_ctx* ctx, const char* key, int64_t value);
 const char* robo_last_error_string(void);
 const char* robo_version_string(void);
@@ -946,6 +948,7 @@ int32_t robo_paths_refine_cand(robo_paths* p, robo_cand* cand, int32_t n_starts,
 #define ROBO_BLR_FEAT_LINEAR 1
 #define ROBO_BLR_FEAT_QUADRATIC 2
 #define ROBO_BLR_FEAT_RFF 3
+#define ROBO_BLR_FEAT_MLP 4 /* the last hidden layer of a trained robo_mlp: robo_blr_create_mlp, below */
 #define ROBO_BLR_MAX_FEATURES 128
 #define ROBO_BLR_MAX_DIM 64
 #define ROBO_BLR_MAX_SAMPLES 64
@@ -963,6 +966,54 @@ int32_t robo_blr_predict(robo_blr* blr, const double* rows, int64_t m, double* o
                          double* out_per_sample /* nullable */);
 int32_t robo_blr_acq_eval_cand(robo_blr* blr, int32_t acq_kind, double par, double eta, const double* rows, int64_t m,
                                double* out_acq /* nullable */, double* out_max, int64_t* out_argmax, uint32_t* out_flags);
+
+/* ---- DNGO's basis: a small tanh network trained on the device (Snoek et al. 2015, "Scalable Bayesian Optimization Using Deep
+ * Neural Networks"), whose last hidden layer is the Bayesian linear regression's fifth feature kind.
+ *   Model.      dim inputs (1 .. 64), n_layers (1 .. 3) hidden tanh layers of one width H (1 .. 64), one linear output.
+ *   Parameters. One packed vector of P doubles: per hidden layer l  W_l (in_l x H, row-major, W[i][j] = input i -> unit j;
+ *               in_1 = dim, in_l = H), then b_l (H); then w_out (H), b_out (1).  The caller supplies the start parameters
+ *               (robo_mlp_set_params, which also clears Adam's moments and step count): a run is a function of its arguments.
+ *   Loss.       (1 / n) sum_i (f(x_i) - y_i)^2 + l2 sum w^2, the second sum over the weights only, not the biases.
+ *   Optimiser.  Full-batch Adam, beta1 = 0.9, beta2 = 0.999, eps = 1e-8:  m <- beta1 m + (1 - beta1) g,
+ *               v <- beta2 v + (1 - beta2) g^2,  p <- p - lr (m / (1 - beta1^t)) / (sqrt(v / (1 - beta2^t)) + eps), t counted
+ *               from the last robo_mlp_set_params: n_steps = a and then b equals a + b in one call.
+ *   Order.      One workgroup per chunk of 1024 rows, the rows in tiles of 16: forward layer by layer on the fp64 matrix
+ *               instruction (contraction in index order), backward delta_L = 2 (f - y) / n  w_out (1 - a_L^2),
+ *               delta_(l-1) = (delta_l W_l^T) (1 - a_(l-1)^2), dW_l += a_(l-1)^T delta_l in row order; one partial per chunk,
+ *               the partials added in chunk order by one workgroup that also adds the l2 terms and applies Adam.  No atomics:
+ *               the bits of every step depend on the data, the start parameters and n -- not on the workspace (which only
+ *               bounds how many partials exist at a time), the device or the call.  One synchronisation per call.  With
+ *               n <= 1024 the whole loop can run in ONE launch (tuning key mlp_fused: 1 there; -1 = default and 0 the per-step
+ *               launches, measured faster on the MI355X); both forms call the same device functions and make the same bits.
+ * robo_mlp_train: n_steps = 0 evaluates the loss and the gradient and changes nothing.  out_loss (n_steps + 1, nullable): the
+ * loss at the parameters before each step and after the last; out_grad (P, nullable): the gradient at the start parameters;
+ * out_trace ((n_steps + 1) x P, nullable): the parameters before each step and after the last.  robo_mlp_forward:
+ * out_features (m x (H + 1), nullable) = [a_L(x), 1], out_value (m, nullable) = a_L . w_out + b_out; a row's bits do not depend
+ * on its position or on m.  robo_blr_create_mlp makes a Bayesian linear regression handle of kind ROBO_BLR_FEAT_MLP with
+ * F = H + 1 from a COPY of the network's current parameters: later training does not move it.  Its rows are raw inputs and
+ * the features exist in LDS only, in robo_blr_set_data and in the sweep.
+ * A shape out of range, lr not positive and finite, l2 negative or not finite, n < 1, m < 1, n_steps < 0, a NULL required
+ * pointer, non-finite parameters -- all decided before anything is launched -- and a loss at the start parameters that is not
+ * finite (the data are bad): ROBO_BAD_ARGUMENT.  A loss that leaves the finite numbers later (the run diverged):
+ * ROBO_NUMERIC_ERROR, the parameters, moments and step count left as they were before the step that produced it; out_loss
+ * and out_trace hold the entries up to those parameters' and NaN after them.  A call
+ * before robo_mlp_set_params: ROBO_NOT_FITTED.  Event slots: robo_mlp_train records 30 -> 31 around its steps' kernels and, in the
+ * per-step form, 28 -> 29 around the call's first gradient launch when the phase events are switched on.  robo_mlp_destroy(NULL) is harmless.                                                            */
+#define ROBO_MLP_MAX_DIM 64
+#define ROBO_MLP_MAX_WIDTH 64
+#define ROBO_MLP_MAX_LAYERS 3
+typedef struct robo_mlp robo_mlp;
+int32_t robo_mlp_create(robo_ctx* ctx, int32_t dim, int32_t n_layers, int32_t width, robo_mlp** out);
+int32_t robo_mlp_destroy(robo_mlp* mlp);
+int32_t robo_mlp_param_count(robo_mlp* mlp, int64_t* out_P);
+int32_t robo_mlp_set_params(robo_mlp* mlp, const double* params /* P */);
+int32_t robo_mlp_get_params(robo_mlp* mlp, double* out_params /* P */);
+int32_t robo_mlp_train(robo_mlp* mlp, const double* rows /* n x dim */, const double* y /* n */, int64_t n, int32_t n_steps,
+                       double lr, double l2, double* out_loss /* n_steps + 1, nullable */, double* out_grad /* P, nullable */,
+                       double* out_trace /* (n_steps + 1) x P, nullable */);
+int32_t robo_mlp_forward(robo_mlp* mlp, const double* rows /* m x dim */, int64_t m,
+                         double* out_features /* m x (H + 1), nullable */, double* out_value /* m, nullable */);
+int32_t robo_blr_create_mlp(robo_ctx* ctx, robo_mlp* mlp, robo_blr** out);
 
 /* ---- entropy search: replaces InformationGain.innovations/_dh_fun/compute ---------------
  * (robo/acquisition_functions/information_gain.py:87-125,169-203,253-272), batched over candidates.

@@ -34,8 +34,9 @@ KG_MAX_DISC = 64                                 # robo_kg_*: cap on the discret
 EHVI_MAX_FRONT = 4096                            # robo_ehvi_*: cap on the points of the Pareto front
 EHVI_BOX_MAX_OBJ, EHVI_BOX_MAX_BOUNDS, EHVI_BOX_MAX_BOXES = 4, 258, 65536     # robo_ehvi_box_*: objectives, bounds each, boxes
 CEI_MAX_CONSTRAINTS = 16                         # robo_cei_*: cap on the constraints of constrained expected improvement
-BLR_FEATURE_KINDS = {"given": 0, "linear": 1, "quadratic": 2, "rff": 3}   # robo_blr_create
+BLR_FEATURE_KINDS = {"given": 0, "linear": 1, "quadratic": 2, "rff": 3, "mlp": 4}   # robo_blr_create, robo_blr_create_mlp
 BLR_MAX_FEATURES, BLR_MAX_DIM, BLR_MAX_SAMPLES = 128, 64, 64
+MLP_MAX_DIM, MLP_MAX_WIDTH, MLP_MAX_LAYERS = 64, 64, 3                     # robo_mlp_create
 BLR_CHUNK, BLR_TILE = 1024, 64                  # rows per workgroup of the statistics kernel; candidates per workgroup of the sweep
 PATHS_MAX = 64                                   # robo_paths_*: cap on the sample paths of one object
 PATHS_MAX_FEATURES = 4096                        # ... and on its random Fourier features
@@ -69,6 +70,8 @@ SYMBOLS = [
     "robo_cei_eval_cand", "robo_cei_eval_moments", "robo_cei_refine_cand",
     "robo_blr_create", "robo_blr_destroy", "robo_blr_set_data", "robo_blr_get_stats", "robo_blr_loglik_batch",
     "robo_blr_set_hypers", "robo_blr_predict", "robo_blr_acq_eval_cand",
+    "robo_mlp_create", "robo_mlp_destroy", "robo_mlp_param_count", "robo_mlp_set_params", "robo_mlp_get_params",
+    "robo_mlp_train", "robo_mlp_forward", "robo_blr_create_mlp",
     "robo_paths_create", "robo_paths_eval_cand", "robo_paths_destroy", "robo_paths_descend", "robo_paths_refine_cand",
     "robo_ig_eval_cand", "robo_ig_eval_per_cost_cand", "robo_ig_eval_moments", "robo_gp_cross_cov",
     "robo_ep_joint_min", "robo_pmin_mc", "robo_igmc_eval_cand", "robo_igmc_eval_moments",
@@ -281,6 +284,14 @@ def lib():
         "robo_blr_set_hypers": [vp, i32, _dp],
         "robo_blr_predict": [vp, _dp, i64, _dp, _dp, _dp],
         "robo_blr_acq_eval_cand": [vp, i32, dbl, dbl, _dp, i64, _dp, _dp, C.POINTER(i64), C.POINTER(C.c_uint32)],
+        "robo_mlp_create": [vp, i32, i32, i32, pp],
+        "robo_mlp_destroy": [vp],
+        "robo_mlp_param_count": [vp, C.POINTER(i64)],
+        "robo_mlp_set_params": [vp, _dp],
+        "robo_mlp_get_params": [vp, _dp],
+        "robo_mlp_train": [vp, _dp, _dp, i64, i32, dbl, dbl, _dp, _dp, _dp],
+        "robo_mlp_forward": [vp, _dp, i64, _dp, _dp],
+        "robo_blr_create_mlp": [vp, vp, pp],
         "robo_paths_create": [vp, i32, i32, _dp, _dp, _dp, _dp, pp],
         "robo_paths_eval_cand": [vp, vp, _dp, _dp, C.POINTER(i64), C.POINTER(C.c_uint32)],
         "robo_paths_destroy": [vp],
@@ -1379,11 +1390,78 @@ class PosteriorPaths(object):
             pass
 
 
+class DeviceMLP(object):
+    """robo_mlp: a tanh network of ``n_layers`` hidden layers of ``width`` units trained by full-batch Adam on the device
+    (include/robo_hip.h); the parameters are one packed vector (``n_params``)"""
+
+    def __init__(self, ctx, dim, n_layers, width):
+        self._h = None
+        self.ctx, self.dim, self.n_layers, self.width = ctx, int(dim), int(n_layers), int(width)
+        self._owner = lib()
+        h, P = C.c_void_p(), C.c_int64(0)
+        check(self._owner.robo_mlp_create(ctx._h, self.dim, self.n_layers, self.width, C.byref(h)))
+        self._h = h
+        check(self._owner.robo_mlp_param_count(h, C.byref(P)))
+        self.n_params = int(P.value)
+
+    def _rows(self, rows):
+        rows = _f64(rows)
+        if rows.ndim != 2 or rows.shape[1] != self.dim:
+            raise RoboBadShape("rows must be (n, %d), got %r" % (self.dim, rows.shape))
+        return rows
+
+    def set_params(self, params):
+        check(lib().robo_mlp_set_params(self._h, _arr(_f64(params, (self.n_params,)))))
+
+    @property
+    def params(self):
+        out = np.empty(self.n_params)
+        check(lib().robo_mlp_get_params(self._h, _arr(out)))
+        return out
+
+    def train(self, rows, y, n_steps, lr=0.01, l2=0.0, want_grad=False, want_trace=False):
+        """-> losses (n_steps + 1,), the gradient at the start parameters (P,) or None, the parameters before every step and
+        after the last (n_steps + 1, P) or None.  A run that diverges raises FloatingPointError; its ``partial`` holds the same
+        three, NaN past the last finite step."""
+        rows = self._rows(rows)
+        y = _f64(y, (rows.shape[0],))
+        n_steps = int(n_steps)
+        loss = np.full(max(n_steps, 0) + 1, np.nan)
+        grad = np.empty(self.n_params) if want_grad else None
+        trace = np.full((max(n_steps, 0) + 1, self.n_params), np.nan) if want_trace else None
+        status = lib().robo_mlp_train(self._h, _arr(rows), _arr(y), rows.shape[0], n_steps, float(lr), float(l2), _arr(loss),
+                                      _arr(grad) if want_grad else None, _arr(trace) if want_trace else None)
+        if status == NUMERIC_ERROR:
+            err = FloatingPointError(last_error())
+            err.partial = (loss, grad, trace)
+            raise err
+        check(status)
+        return loss, grad, trace
+
+    def forward(self, rows):
+        """-> features [a_L, 1] (m, width + 1), value (m,)"""
+        rows = self._rows(rows)
+        feat, value = np.empty((rows.shape[0], self.width + 1)), np.empty(rows.shape[0])
+        check(lib().robo_mlp_forward(self._h, _arr(rows), rows.shape[0], _arr(feat), _arr(value)))
+        return feat, value
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            self._owner.robo_mlp_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class DeviceBLR(object):
     """robo_blr: Bayesian linear regression on basis features (include/robo_hip.h).  ``rows`` are feature rows (n, F) for
-    kind "given" and raw inputs (n, dim) otherwise."""
+    kind "given" and raw inputs (n, dim) otherwise.  Kind "mlp" takes a DeviceMLP and copies its parameters as they are now."""
 
-    def __init__(self, ctx, kind, dim, n_features, omega=None, phase=None, scale=0.0):
+    def __init__(self, ctx, kind, dim, n_features, omega=None, phase=None, scale=0.0, mlp=None):
         self._h = None
         self.ctx, self.kind, self.dim, self.n_features = ctx, kind, int(dim), int(n_features)
         self.width = self.n_features if kind == "given" else self.dim
@@ -1392,9 +1470,14 @@ class DeviceBLR(object):
             omega, phase = _f64(omega, (self.dim, self.n_features)), _f64(phase, (self.n_features,))
         self._owner = lib()
         h = C.c_void_p()
-        check(self._owner.robo_blr_create(ctx._h, BLR_FEATURE_KINDS[kind], self.dim, self.n_features,
-                                          _arr(omega) if kind == "rff" else None, _arr(phase) if kind == "rff" else None,
-                                          float(scale), C.byref(h)))
+        if kind == "mlp":
+            if mlp is None or (mlp.dim, mlp.width + 1) != (self.dim, self.n_features):
+                raise ValueError("kind 'mlp' takes mlp=DeviceMLP of this dim with n_features - 1 units")
+            check(self._owner.robo_blr_create_mlp(ctx._h, mlp._h, C.byref(h)))
+        else:
+            check(self._owner.robo_blr_create(ctx._h, BLR_FEATURE_KINDS[kind], self.dim, self.n_features,
+                                              _arr(omega) if kind == "rff" else None, _arr(phase) if kind == "rff" else None,
+                                              float(scale), C.byref(h)))
         self._h = h
 
     def _rows(self, rows):

@@ -26,6 +26,23 @@ static void blr_free(robo_blr* h) {
     ctx_release(c);
 }
 
+// the statistics, eigenpairs and hyper-parameter tables of a handle whose feature map is set
+static int blr_alloc_model(robo_blr* h) {
+    const int FP = h->ft.FP;
+    const size_t stats = blr_part_stride(FP), model = stats + (size_t)FP * FP + 2 * FP;
+    const size_t hyp = 3 * ROBO_BLR_MAX_SAMPLES + 2 * (size_t)ROBO_BLR_MAX_SAMPLES * FP;
+    ROBO_TRY(dev_alloc(&h->d_model, model));
+    ROBO_TRY(dev_alloc(&h->d_hyp, hyp));
+    ROBO_TRY(dev_alloc(&h->d_status, 2));
+    h->d_Qt = h->d_model + stats;
+    h->d_lam = h->d_Qt + (size_t)FP * FP;
+    h->d_c = h->d_lam + FP;
+    h->d_invb = h->d_hyp + 2 * ROBO_BLR_MAX_SAMPLES;
+    h->d_wm = h->d_invb + ROBO_BLR_MAX_SAMPLES;
+    h->d_wv = h->d_wm + (size_t)ROBO_BLR_MAX_SAMPLES * FP;
+    return ROBO_OK;
+}
+
 static int blr_ready(const robo_blr* h, bool hypers) {
     if (!h->has_data || (hypers && !h->has_hypers)) {
         set_error("Model has to be trained first!");
@@ -116,21 +133,51 @@ int32_t robo_blr_create(robo_ctx* ctx, int32_t feat_kind, int32_t dim, int32_t F
         ft.omega = h->d_feat;
         ft.phase = h->d_feat + (size_t)ft.DP * FP;
     }
-    const size_t stats = blr_part_stride(FP), model = stats + (size_t)FP * FP + 2 * FP;
-    const size_t hyp = 3 * ROBO_BLR_MAX_SAMPLES + 2 * (size_t)ROBO_BLR_MAX_SAMPLES * FP;
-    if (st == ROBO_OK) st = dev_alloc(&h->d_model, model);
-    if (st == ROBO_OK) st = dev_alloc(&h->d_hyp, hyp);
-    if (st == ROBO_OK) st = dev_alloc(&h->d_status, 2);
+    if (st == ROBO_OK) st = blr_alloc_model(h);
     if (st != ROBO_OK) {
         blr_free(h);
         return st;
     }
-    h->d_Qt = h->d_model + stats;
-    h->d_lam = h->d_Qt + (size_t)FP * FP;
-    h->d_c = h->d_lam + FP;
-    h->d_invb = h->d_hyp + 2 * ROBO_BLR_MAX_SAMPLES;
-    h->d_wm = h->d_invb + ROBO_BLR_MAX_SAMPLES;
-    h->d_wv = h->d_wm + (size_t)ROBO_BLR_MAX_SAMPLES * FP;
+    *out = h;
+    return ROBO_OK;
+}
+
+// kind 4: the features are the last hidden layer of `mlp` and a constant, from a copy of its padded parameters taken here
+int32_t robo_blr_create_mlp(robo_ctx* ctx, robo_mlp* mlp, robo_blr** out) {
+    if (!ctx || !mlp || !out) return ROBO_BAD_ARGUMENT;
+    if (!mlp->has_params) {
+        set_error("%s: the network's parameters have to be set first", BLR_LABEL);
+        return ROBO_NOT_FITTED;
+    }
+    if (mlp->ctx->device != ctx->device) {
+        set_error("%s: the network lives on device %d, the context on device %d", BLR_LABEL, mlp->ctx->device, ctx->device);
+        return ROBO_BAD_ARGUMENT;
+    }
+    ROBO_HIP_CHECK(hipSetDevice(ctx->device));
+    robo_blr* h = new robo_blr();
+    memset(h, 0, sizeof(*h));
+    h->ctx = ctx;
+    ctx_retain(ctx);
+    BlrFeat& ft = h->ft;
+    ft.kind = ROBO_BLR_FEAT_MLP;
+    ft.dim = mlp->net.dim;
+    ft.F = mlp->net.H + 1;
+    ft.FP = ft.F <= 16 ? 16 : ft.F <= 32 ? 32 : ft.F <= 64 ? 64 : 128;
+    ft.DP = mlp->net.DP;
+    ft.mlp = mlp->net;
+    const size_t len = (size_t)mlp_pad_len(mlp->net);
+    int st = dev_alloc(&h->d_feat, len);
+    // on the network's own stream, behind its last training call, and complete before anything else can touch either side
+    if (st == ROBO_OK && (hipMemcpyAsync(h->d_feat, mlp->d_pad, len * sizeof(double), hipMemcpyDeviceToDevice,
+                                         mlp->ctx->stream) != hipSuccess ||
+                          hipStreamSynchronize(mlp->ctx->stream) != hipSuccess))
+        st = ROBO_RUNTIME_ERROR;
+    ft.mlp.pad = h->d_feat;
+    if (st == ROBO_OK) st = blr_alloc_model(h);
+    if (st != ROBO_OK) {
+        blr_free(h);
+        return st;
+    }
     *out = h;
     return ROBO_OK;
 }

@@ -19,7 +19,7 @@ namespace robo {
 
 // ---- G = Phi^T Phi, b = Phi^T y, yy = y^T y per chunk -------------------------------------------------------------------------
 // NT = FP / 16.  The four waves own the quadrants of the FP x FP tile grid (NT = 1: wave 0 alone owns the one tile).
-template <int NT>
+template <int NT, bool NET>
 __global__ __launch_bounds__(WG) void blr_stats_kernel(BlrFeat ft, const double* __restrict__ rows,
                                                        const double* __restrict__ y, long long n, long long c0,
                                                        double* __restrict__ part) {
@@ -49,7 +49,7 @@ __global__ __launch_bounds__(WG) void blr_stats_kernel(BlrFeat ft, const double*
             if (tid < BK) sy[(t + 1) % 3][tid] = r0 + BK + tid < end ? y[r0 + BK + tid] : 0.0;
         }
         double* cur = sphi[t & 1];
-        blr_features(ft, rows, r0, BK, end, sx[t & 1], cur, 1, LDS_LD);
+        blr_features<NET>(ft, rows, r0, BK, end, sx[t & 1], cur, 1, LDS_LD);
         __syncthreads();
         if (live) {
             const double* pa = cur + (wy * H * 16 + (lane & 15)) * LDS_LD + (lane >> 4);
@@ -254,7 +254,7 @@ __global__ __launch_bounds__(WG) void blr_hypers_kernel(const double* __restrict
 // features per stage of Q^T).  The fold: thread (candidate, group g) takes the samples g, g + 4, .. with the features in index
 // order; the mixture adds the four groups' sums in group order.  Nothing a candidate's values are made of depends on its
 // row, on m or on the other candidates.
-template <int NT>
+template <int NT, bool NET>
 __global__ __launch_bounds__(WG) void blr_sweep_kernel(BlrFeat ft, const double* __restrict__ rows, long long m,
                                                        const double* __restrict__ Qt, const double* __restrict__ wm,
                                                        const double* __restrict__ wv, const double* __restrict__ invb, int S,
@@ -271,7 +271,7 @@ __global__ __launch_bounds__(WG) void blr_sweep_kernel(BlrFeat ft, const double*
     Tile4 rq = tile_load_regs<FP>(Qt, FP, 0);
     tile_store_lds<FP>(sq[0], rq);
     __syncthreads();
-    blr_features(ft, rows, row0, BLR_TC, m, sx, sp, PLD, 1);
+    blr_features<NET>(ft, rows, row0, BLR_TC, m, sx, sp, PLD, 1);
     __syncthreads();
     v4d acc[NT];
 #pragma unroll
@@ -338,18 +338,29 @@ __global__ __launch_bounds__(WG) void blr_sweep_kernel(BlrFeat ft, const double*
 }
 
 // ---- launchers ---------------------------------------------------------------------------------------------------------------
-#define BLR_BY_NT(FP, CALL)            \
+#define BLR_BY_NT(FP, ...)             \
     switch ((FP) / 16) {               \
-        case 1: { constexpr int NT = 1; CALL; } break; \
-        case 2: { constexpr int NT = 2; CALL; } break; \
-        case 4: { constexpr int NT = 4; CALL; } break; \
-        default: { constexpr int NT = 8; CALL; } break; \
+        case 1: { constexpr int NT = 1; __VA_ARGS__; } break; \
+        case 2: { constexpr int NT = 2; __VA_ARGS__; } break; \
+        case 4: { constexpr int NT = 4; __VA_ARGS__; } break; \
+        default: { constexpr int NT = 8; __VA_ARGS__; } break; \
+    }
+// NET: feature kind 4, the only instantiations that hold the network's loader and take its dynamic LDS
+#define BLR_BY_KIND(FT, ...)                                                       \
+    if ((FT).kind == ROBO_BLR_FEAT_MLP) {                                          \
+        constexpr bool NET = true;                                                 \
+        constexpr size_t LDS = MLP_ACT_BYTES;                                      \
+        BLR_BY_NT((FT).FP, __VA_ARGS__)                                            \
+    } else {                                                                       \
+        constexpr bool NET = false;                                                \
+        constexpr size_t LDS = 0;                                                  \
+        BLR_BY_NT((FT).FP, __VA_ARGS__)                                            \
     }
 
 int launch_blr_stats(robo_ctx* ctx, const BlrFeat& ft, const double* d_rows, const double* d_y, long long n, long long c0,
                      int nc, double* d_part) {
-    BLR_BY_NT(ft.FP, hipLaunchKernelGGL(HIP_KERNEL_NAME(blr_stats_kernel<NT>), dim3(nc), dim3(WG), 0, ctx->stream, ft, d_rows,
-                                        d_y, n, c0, d_part));
+    BLR_BY_KIND(ft, hipLaunchKernelGGL(HIP_KERNEL_NAME(blr_stats_kernel<NT, NET>), dim3(nc), dim3(WG), LDS, ctx->stream, ft,
+                                       d_rows, d_y, n, c0, d_part));
     ROBO_LAUNCH_CHECK();
     return ROBO_OK;
 }
@@ -389,8 +400,8 @@ int launch_blr_sweep(robo_ctx* ctx, const BlrFeat& ft, const double* d_rows, lon
                      const double* d_wm, const double* d_wv, const double* d_invb, int S, double* d_mean, double* d_var,
                      double* d_per_sample) {
     const unsigned blocks = (unsigned)((m + BLR_TC - 1) / BLR_TC);
-    BLR_BY_NT(ft.FP, hipLaunchKernelGGL(HIP_KERNEL_NAME(blr_sweep_kernel<NT>), dim3(blocks), dim3(WG), 0, ctx->stream, ft,
-                                        d_rows, m, d_Qt, d_wm, d_wv, d_invb, S, d_mean, d_var, d_per_sample));
+    BLR_BY_KIND(ft, hipLaunchKernelGGL(HIP_KERNEL_NAME(blr_sweep_kernel<NT, NET>), dim3(blocks), dim3(WG), LDS, ctx->stream, ft,
+                                       d_rows, m, d_Qt, d_wm, d_wv, d_invb, S, d_mean, d_var, d_per_sample));
     ROBO_LAUNCH_CHECK();
     return ROBO_OK;
 }

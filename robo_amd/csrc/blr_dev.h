@@ -3,6 +3,7 @@
 #pragma once
 #include "common.h"
 #include "gemm_f64.h"
+#include "mlp_dev.h"
 
 namespace robo {
 
@@ -21,7 +22,9 @@ struct BlrFeat {
     const double* omega;     // kind 3: DP x FP, pad rows and columns zero
     const double* phase;     // kind 3: FP
     double scale;
+    MlpNet mlp;              // kind 4: the layer shape and the handle's own padded copy of the parameters (mlp_dev.h)
 };
+static_assert(BLR_XLD == MLP_LD, "mlp_features reads the staged rows of blr_stage_x");
 inline int blr_row_width(const BlrFeat& ft) { return ft.kind == ROBO_BLR_FEAT_GIVEN ? ft.F : ft.dim; }
 inline size_t blr_part_stride(int FP) { return (size_t)FP * FP + FP + 8; }   // [G | b | yy] of one chunk
 
@@ -39,10 +42,17 @@ __device__ __forceinline__ void blr_stage_x(const BlrFeat& ft, const double* __r
 // phi(row0 + r)[f] -> dst[r * sr + f * sf] for r < rows (a multiple of 16), f < FP; rows past `limit` and features past F
 // are 0.  Kinds 1 and 2 read the staged rows; kind 3 forms x . omega_f on the matrix pipe (one 16 x 16 tile of arguments
 // per wave and step, coordinates in index order) and leaves scale cos(x . omega_f + phase_f); kind 0 copies the caller's
-// row.  A value depends on its own row alone.  Ends without a barrier.
+// row; kind 4 is the network's last hidden layer and a constant (mlp_features: barriers inside, so every thread of the
+// workgroup reaches the loader).  A value depends on its own row alone.  Ends without a barrier.  NET says at compile time
+// that the kind is 4: the kernels of kinds 0..3 are instantiated without the network's code and stay what they were.
+template <bool NET>
 __device__ __forceinline__ void blr_features(const BlrFeat& ft, const double* __restrict__ src, long long row0, int rows,
                                              long long limit, const double* xs, double* dst, int sr, int sf) {
     const int D = ft.dim, F = ft.F, FP = ft.FP;
+    if constexpr (NET) {
+        mlp_features(ft.mlp, row0, rows, limit, xs, dst, sr, sf, FP);
+        return;
+    }
     if (ft.kind == ROBO_BLR_FEAT_RFF) {
         const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nf = FP / 16, tiles = (rows / 16) * nf;
         for (int u = wave; u < tiles; u += WG / 64) {
@@ -94,7 +104,7 @@ int launch_blr_sweep(robo_ctx* ctx, const BlrFeat& ft, const double* d_rows, lon
 struct robo_blr {
     robo_ctx* ctx;
     robo::BlrFeat ft;            // (omega / phase point into d_feat)
-    double* d_feat;              // kind 3: [omega (DP x FP) | phase (FP)]
+    double* d_feat;              // kind 3: [omega (DP x FP) | phase (FP)]; kind 4: the padded parameters
     long long n;
     bool has_data, has_hypers;
     int S;

@@ -42,6 +42,17 @@ class RandomFourierBasis(object):
         return self.scale * np.cos(np.dot(x, self.omega) + self.phase)
 
 
+class NetworkBasis(object):
+    """the last hidden layer of a trained ``_lib.DeviceMLP`` and a constant (models/dngo.py).  The model copies the
+    network's parameters when it builds its device handle, and builds a new one whenever ``version`` has moved."""
+
+    def __init__(self, mlp):
+        self.mlp, self.version = mlp, 0
+
+    def __call__(self, x):
+        return self.mlp.forward(x)[0]
+
+
 class BayesianLinearRegression(BaseModel):
 
     def __init__(self, alpha=1, beta=1000, basis_func=linear_basis_func, prior=None, do_mcmc=True, n_hypers=20,
@@ -67,7 +78,9 @@ class BayesianLinearRegression(BaseModel):
     # ---- the device handle ---------------------------------------------------------------------------------------------
     def _rows(self, X):
         """what the device takes for X: the raw rows for the device feature kinds, else the host's feature rows"""
-        if self.basis_func in (linear_basis_func, quadratic_basis_func) or isinstance(self.basis_func, RandomFourierBasis):
+        if self.basis_func in (linear_basis_func, quadratic_basis_func):
+            return X
+        if isinstance(self.basis_func, (RandomFourierBasis, NetworkBasis)):
             return X
         return X if self.basis_func is None else self.basis_func(X)
 
@@ -80,12 +93,16 @@ class BayesianLinearRegression(BaseModel):
             key = ("quadratic", D, 2 * D + 1)
         elif isinstance(b, RandomFourierBasis):
             key = ("rff", D, b.omega.shape[1])
+        elif isinstance(b, NetworkBasis):
+            key = ("mlp", D, b.mlp.width + 1, b.version)
         else:
             key = ("given", 1, self._rows(X[:1]).shape[1])
         if self._dev is None or self._dev_key != key:
             ctx = self._ctx or _lib.default_context()
             rff = dict(omega=b.omega, phase=b.phase, scale=b.scale) if key[0] == "rff" else {}
-            self._dev, self._dev_key = _lib.DeviceBLR(ctx, *key, **rff), key
+            if key[0] == "mlp":
+                rff = dict(mlp=b.mlp)
+            self._dev, self._dev_key = _lib.DeviceBLR(ctx, *key[:3], **rff), key
         return self._dev
 
     # ---- the reference's methods ------------------------------------------------------------------------------------------
