@@ -146,7 +146,8 @@ int32_t robo_ctx_set_phase_events(robo_ctx* ctx, int32_t on);
  * set again, and robo_last_error_string says so although the call succeeds), trsm_chain_max_wg (the automatic rule:
  * while 16-candidate tiles x block rows <= this many times the CU count), trsm_chain_spin_limit (tests only),
  * mlp_fused (robo_mlp_train on at most 1024 rows: 1: every step of the call in ONE single-workgroup launch; -1 = default
- * and 0: two launches per step, which was measured faster; the same bits either way).                                  */
+ * and 0: two launches per step, which was measured faster; the same bits either way), bnn_launch_steps (robo_bnn_run:
+ * SGHMC steps per launch of the chain kernel, default 2048; the same bits whatever the value).                           */
 int32_t robo_ctx_set_tuning(robo_ctx* ctx, const char* key, int64_t value);
 const char* robo_last_error_string(void);
 const char* robo_version_string(void);
@@ -1014,6 +1015,76 @@ int32_t robo_mlp_train(robo_mlp* mlp, const double* rows /* n x dim */, const do
 int32_t robo_mlp_forward(robo_mlp* mlp, const double* rows /* m x dim */, int64_t m,
                          double* out_features /* m x (H + 1), nullable */, double* out_value /* m, nullable */);
 int32_t robo_blr_create_mlp(robo_ctx* ctx, robo_mlp* mlp, robo_blr** out);
+
+/* ---- BOHAMIANN: a Bayesian neural network sampled by scale-adapted SGHMC on the device (Springenberg et al. 2016, "Bayesian
+ * Optimization with Robust Bayesian Neural Networks"; robo/models/wrapper_bohamiann.py).  The contract is the paper's sampler
+ * as written here, with the library's own counter-based draws.
+ *   Model.      robo_mlp's network (dim 1 .. 64, 1 .. 3 hidden tanh layers of width 1 .. 64, one linear output) and one more
+ *               free scalar l, the log noise variance.  A chain's parameters are the packed P doubles of robo_mlp followed by
+ *               l: P + 1 (robo_bnn_param_count).  n_chains (1 .. 64) independent chains run side by side.
+ *   Potential.  For a mini-batch B of the n training rows
+ *                 U = (1 / |B|) sum_{i in B} (l + (y_i - f(x_i))^2 exp(-l)) / 2
+ *                     + (1 / n) ((l - ln mu_l)^2 / (2 s_l) + lambda / 2 sum_e p_e^2),   the last sum over all P network entries.
+ *   Gradient.   The error that goes back from row i is (exp(-l) (f(x_i) - y_i)) / |B| through robo_mlp's backward pass (rows in
+ *               batch order, 16 at a time); g_e = that sum + (lambda / n) p_e;
+ *               g_l = 0.5 (1 - (sum_i (f - y)^2 / |B|) exp(-l)) + (l - ln mu_l) (1 / (s_l n)).
+ *   Step.       With eps = lr / sqrt(n), eps2 = eps eps, eps4 = eps2 eps2, c2 = (2 eps2) mdecay, for every entry, at global step
+ *               count t (from 0 at robo_bnn_set_state), every operation rounded once and in this order:
+ *                 if t < n_burn_in:  r = 1 / (tau + 1);  tau <- (tau + 1) - (tau (gbar gbar)) / V;
+ *                                    gbar <- gbar + r (g - gbar);  V <- V + r (g g - V)
+ *                 M = 1 / (sqrt(V) + 1e-16);  sigma = sqrt(max(c2 M - eps4, 1e-16))
+ *                 v <- ((v - (eps2 M) g) - mdecay v) + sigma xi;   p <- p + v
+ *               from tau = gbar = V = 1, v = 0.  After the burn-in V stands, so M and sigma are formed once and read afterwards.
+ *   Draws.      Philox-4x32-10 under the key `seed` on the counter (t low word, t high word, chain, w):  w = the entry's index
+ *               in the packed vector for xi = sqrt(-2 log(1 - u1)) cos(2 pi u2), (u1, u2) the block's two 53-bit uniforms;
+ *               w = 2^31 + slot for the row index floor(u1 n) of slot `slot` of the mini-batch.  All chains of a step share
+ *               nothing: a draw is a function of (seed, chain, t, entry).  Both draws are also taken from the caller: idx
+ *               (n_steps x batch, shared by the chains) and xi (n_steps x n_chains x (P + 1)), each nullable on its own.
+ *   Samples.    After step count T = t + 1 with T > n_burn_in and (T - n_burn_in) a multiple of keep_every the chains' (p, l)
+ *               are appended to the sample table, chain-major inside a step, step-major overall; the table holds
+ *               ROBO_BNN_MAX_SAMPLES entries and a full table takes no more.
+ *   Order.      One workgroup per chain, many steps per launch: the weights live in LDS and are updated there by the lane
+ *               that holds the entry's gradient in its matrix-instruction accumulator; the sampler state lives in memory in a
+ *               layout private to the device.  No atomics.  A long run is split into launches of bounded length (tuning key
+ *               bnn_launch_steps) with nothing between them; the bits do not depend on the split, on n_chains (chain c of C
+ *               equals the same chain run alone with the same draws) or on how a run is divided into calls: the step count
+ *               continues, n_steps = a and then b equals a + b.
+ *   Prediction. f_s(x) for every kept sample s exactly as robo_mlp_forward forms it; mean and M2 by Welford's update in sample
+ *               order (d = f - mean; mean <- mean + d / k; M2 <- M2 + d (f - mean)); var = M2 / S, plus (add_noise) the mean of
+ *               exp(l_s) in sample order; then mean y_std + y_mean and var (y_std y_std), the variance clipped at eps from
+ *               below as robo_blr_predict clips it.  A candidate's bits do not depend on its position, on m or on the other
+ *               candidates.  A NaN coordinate gives NaN.
+ * robo_bnn_run: out_trace ((n_steps + 1) x n_chains x 5 x (P + 1), nullable): [p, l | v | tau | gbar | V] of every chain before
+ * each step and after the last; out_status (n_chains, nullable): 0, or 1 for a chain one of whose parameters left the finite
+ * numbers.  Such a chain ends there: the call returns ROBO_NUMERIC_ERROR, the samples kept before that step stay, the trace
+ * reads NaN where the chain wrote nothing, and robo_bnn_set_state has to come before the next run.  robo_bnn_set_state resets
+ * the sampler state, the step count and the sample table.  robo_bnn_set_samples fills the table from the caller (a restored
+ * model; the sweep without a chain).  robo_bnn_acq_eval_cand is the sweep followed by robo_acq_eval_moments' kernels on the
+ * device-resident moments: the same values, argmax rule and flags, one synchronisation.  out_per_sample (nullable): S x m.
+ * A shape or a count out of range, lr, mdecay, mu_l, s_l not positive and finite, lambda negative or not finite, y_std not
+ * positive, a row index outside 0 .. n - 1, non-finite rows, targets, start parameters or samples, a NULL required pointer:
+ * ROBO_BAD_ARGUMENT.  robo_bnn_run before robo_bnn_set_state, a sweep on an empty table: ROBO_NOT_FITTED.  All decided before
+ * anything is launched.  Event slots: 30 -> 31 around the chain launches (phase events on) and around the sweep kernel under
+ * the condition of slots 24..27.  robo_bnn_destroy(NULL) is harmless.                                                       */
+#define ROBO_BNN_MAX_CHAINS 64
+#define ROBO_BNN_MAX_BATCH 64
+#define ROBO_BNN_MAX_SAMPLES 512
+typedef struct robo_bnn robo_bnn;
+int32_t robo_bnn_create(robo_ctx* ctx, int32_t dim, int32_t n_layers, int32_t width, int32_t n_chains, robo_bnn** out);
+int32_t robo_bnn_destroy(robo_bnn* bnn);
+int32_t robo_bnn_param_count(robo_bnn* bnn, int64_t* out_count /* P + 1 */);
+int32_t robo_bnn_set_state(robo_bnn* bnn, const double* params /* n_chains x (P + 1) */);
+int32_t robo_bnn_run(robo_bnn* bnn, const double* rows /* n x dim */, const double* y /* n */, int64_t n, int32_t n_steps,
+                     int32_t n_burn_in, int32_t keep_every, int32_t batch, double lr, double mdecay, double prior_mu,
+                     double prior_s, double prior_lambda, uint64_t seed, const int32_t* idx /* nullable */,
+                     const double* xi /* nullable */, double* out_trace /* nullable */, int32_t* out_status /* nullable */);
+int32_t robo_bnn_get_samples(robo_bnn* bnn, int32_t* out_count, double* out_samples /* count x (P + 1), nullable */);
+int32_t robo_bnn_set_samples(robo_bnn* bnn, int32_t count, const double* samples /* count x (P + 1) */);
+int32_t robo_bnn_set_output_transform(robo_bnn* bnn, double y_mean, double y_std, int32_t add_noise);
+int32_t robo_bnn_predict(robo_bnn* bnn, const double* rows /* m x dim */, int64_t m, double* out_mean, double* out_var,
+                         double* out_per_sample /* nullable */);
+int32_t robo_bnn_acq_eval_cand(robo_bnn* bnn, int32_t acq_kind, double par, double eta, const double* rows, int64_t m,
+                               double* out_acq /* nullable */, double* out_max, int64_t* out_argmax, uint32_t* out_flags);
 
 /* ---- entropy search: replaces InformationGain.innovations/_dh_fun/compute ---------------
  * (robo/acquisition_functions/information_gain.py:87-125,169-203,253-272), batched over candidates.

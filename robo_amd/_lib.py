@@ -37,7 +37,8 @@ CEI_MAX_CONSTRAINTS = 16                         # robo_cei_*: cap on the constr
 BLR_FEATURE_KINDS = {"given": 0, "linear": 1, "quadratic": 2, "rff": 3, "mlp": 4}   # robo_blr_create, robo_blr_create_mlp
 BLR_MAX_FEATURES, BLR_MAX_DIM, BLR_MAX_SAMPLES = 128, 64, 64
 MLP_MAX_DIM, MLP_MAX_WIDTH, MLP_MAX_LAYERS = 64, 64, 3                     # robo_mlp_create
-BLR_CHUNK, BLR_TILE = 1024, 64                  # rows per workgroup of the statistics kernel; candidates per workgroup of the sweep
+BNN_MAX_CHAINS, BNN_MAX_BATCH, BNN_MAX_SAMPLES = 64, 64, 512               # robo_bnn_create, robo_bnn_run, the sample table
+BLR_CHUNK, BLR_TILE = 1024, 64                # rows per workgroup of the statistics kernel; candidates per workgroup of the sweep
 PATHS_MAX = 64                                   # robo_paths_*: cap on the sample paths of one object
 PATHS_MAX_FEATURES = 4096                        # ... and on its random Fourier features
 PATHS_MAX_STARTS = 1024                          # robo_paths_refine_cand: cap on n_starts (per path)
@@ -72,6 +73,9 @@ SYMBOLS = [
     "robo_blr_set_hypers", "robo_blr_predict", "robo_blr_acq_eval_cand",
     "robo_mlp_create", "robo_mlp_destroy", "robo_mlp_param_count", "robo_mlp_set_params", "robo_mlp_get_params",
     "robo_mlp_train", "robo_mlp_forward", "robo_blr_create_mlp",
+    "robo_bnn_create", "robo_bnn_destroy", "robo_bnn_param_count", "robo_bnn_set_state", "robo_bnn_run",
+    "robo_bnn_get_samples", "robo_bnn_set_samples", "robo_bnn_set_output_transform", "robo_bnn_predict",
+    "robo_bnn_acq_eval_cand",
     "robo_paths_create", "robo_paths_eval_cand", "robo_paths_destroy", "robo_paths_descend", "robo_paths_refine_cand",
     "robo_ig_eval_cand", "robo_ig_eval_per_cost_cand", "robo_ig_eval_moments", "robo_gp_cross_cov",
     "robo_ep_joint_min", "robo_pmin_mc", "robo_igmc_eval_cand", "robo_igmc_eval_moments",
@@ -292,6 +296,17 @@ def lib():
         "robo_mlp_train": [vp, _dp, _dp, i64, i32, dbl, dbl, _dp, _dp, _dp],
         "robo_mlp_forward": [vp, _dp, i64, _dp, _dp],
         "robo_blr_create_mlp": [vp, vp, pp],
+        "robo_bnn_create": [vp, i32, i32, i32, i32, pp],
+        "robo_bnn_destroy": [vp],
+        "robo_bnn_param_count": [vp, C.POINTER(i64)],
+        "robo_bnn_set_state": [vp, _dp],
+        "robo_bnn_run": [vp, _dp, _dp, i64, i32, i32, i32, i32, dbl, dbl, dbl, dbl, dbl, C.c_uint64, C.POINTER(i32), _dp, _dp,
+                         C.POINTER(i32)],
+        "robo_bnn_get_samples": [vp, C.POINTER(i32), _dp],
+        "robo_bnn_set_samples": [vp, i32, _dp],
+        "robo_bnn_set_output_transform": [vp, dbl, dbl, i32],
+        "robo_bnn_predict": [vp, _dp, i64, _dp, _dp, _dp],
+        "robo_bnn_acq_eval_cand": [vp, i32, dbl, dbl, _dp, i64, _dp, _dp, C.POINTER(i64), C.POINTER(C.c_uint32)],
         "robo_paths_create": [vp, i32, i32, _dp, _dp, _dp, _dp, pp],
         "robo_paths_eval_cand": [vp, vp, _dp, _dp, C.POINTER(i64), C.POINTER(C.c_uint32)],
         "robo_paths_destroy": [vp],
@@ -1448,6 +1463,109 @@ class DeviceMLP(object):
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
             self._owner.robo_mlp_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DeviceBNN(object):
+    """robo_bnn: ``n_chains`` scale-adapted SGHMC chains over the weights of DeviceMLP's network and a log noise variance,
+    their sample table and the ensemble sweep (include/robo_hip.h).  A chain's parameters are ``n_params`` = P + 1 doubles."""
+
+    def __init__(self, ctx, dim, n_layers, width, n_chains=1):
+        self._h = None
+        self.ctx, self.dim, self.n_layers, self.width, self.n_chains = ctx, int(dim), int(n_layers), int(width), int(n_chains)
+        self._owner = lib()
+        h, P = C.c_void_p(), C.c_int64(0)
+        check(self._owner.robo_bnn_create(ctx._h, self.dim, self.n_layers, self.width, self.n_chains, C.byref(h)))
+        self._h = h
+        check(self._owner.robo_bnn_param_count(h, C.byref(P)))
+        self.n_params = int(P.value)
+
+    def _rows(self, rows):
+        rows = _f64(rows)
+        if rows.ndim != 2 or rows.shape[1] != self.dim:
+            raise RoboBadShape("rows must be (n, %d), got %r" % (self.dim, rows.shape))
+        return rows
+
+    def set_state(self, params):
+        check(lib().robo_bnn_set_state(self._h, _arr(_f64(params, (self.n_chains, self.n_params)))))
+
+    def run(self, rows, y, n_steps, n_burn_in, keep_every=100, batch=20, lr=1e-2, mdecay=0.05, prior_mu=1e-6, prior_s=0.01,
+            prior_lambda=1.0, seed=0, idx=None, xi=None, want_trace=False):
+        """-> the trace (n_steps + 1, n_chains, 5, n_params) of [p, l | v | tau | gbar | V] or None.  A chain that leaves the
+        finite numbers raises FloatingPointError; its ``partial`` holds the trace and ``status`` the chains' verdicts."""
+        rows = self._rows(rows)
+        y = _f64(y, (rows.shape[0],))
+        n_steps = int(n_steps)
+        if idx is not None:
+            idx = np.ascontiguousarray(idx, dtype=np.int32)
+            if idx.shape != (n_steps, int(batch)):
+                raise RoboBadShape("idx must be (%d, %d), got %r" % (n_steps, batch, idx.shape))
+        if xi is not None:
+            xi = _f64(xi, (n_steps, self.n_chains, self.n_params))
+        trace = np.full((max(n_steps, 0) + 1, self.n_chains, 5, self.n_params), np.nan) if want_trace else None
+        status = np.zeros(self.n_chains, dtype=np.int32)
+        i32p = C.POINTER(C.c_int32)
+        code = lib().robo_bnn_run(self._h, _arr(rows), _arr(y), rows.shape[0], n_steps, int(n_burn_in), int(keep_every),
+                                  int(batch), float(lr), float(mdecay), float(prior_mu), float(prior_s), float(prior_lambda),
+                                  int(seed), idx.ctypes.data_as(i32p) if idx is not None else None,
+                                  _arr(xi) if xi is not None else None, _arr(trace) if want_trace else None,
+                                  status.ctypes.data_as(i32p))
+        if code == NUMERIC_ERROR:
+            err = FloatingPointError(last_error())
+            err.partial, err.status = trace, status
+            raise err
+        check(code)
+        return trace
+
+    @property
+    def n_samples(self):
+        count = C.c_int32(0)
+        check(lib().robo_bnn_get_samples(self._h, C.byref(count), None))
+        return int(count.value)
+
+    @property
+    def samples(self):
+        count = C.c_int32(self.n_samples)
+        out = np.empty((count.value, self.n_params))
+        check(lib().robo_bnn_get_samples(self._h, C.byref(count), _arr(out) if count.value else None))
+        return out
+
+    def set_samples(self, samples):
+        samples = _f64(samples)
+        if samples.ndim != 2 or samples.shape[1] != self.n_params:
+            raise RoboBadShape("samples must be (S, %d), got %r" % (self.n_params, samples.shape))
+        check(lib().robo_bnn_set_samples(self._h, samples.shape[0], _arr(samples)))
+
+    def set_output_transform(self, y_mean=0.0, y_std=1.0, add_noise=False):
+        check(lib().robo_bnn_set_output_transform(self._h, float(y_mean), float(y_std), int(bool(add_noise))))
+
+    def predict(self, rows, per_sample=False):
+        """-> (mean, var) [, every sample's value (S, m)]"""
+        rows = self._rows(rows)
+        m = rows.shape[0]
+        mean, var = np.empty(m), np.empty(m)
+        ps = np.empty((self.n_samples, m)) if per_sample else None
+        check(lib().robo_bnn_predict(self._h, _arr(rows), m, _arr(mean), _arr(var), _arr(ps) if per_sample else None))
+        return (mean, var, ps) if per_sample else (mean, var)
+
+    def acq(self, kind, par, eta, rows, want_values=True):
+        """sweep + closed-form acquisition + argmax in one call (robo_bnn_acq_eval_cand) -> (values, max, argmax, flags)"""
+        rows = self._rows(rows)
+        out = np.empty(rows.shape[0]) if want_values else None
+        best = _Best()
+        check(lib().robo_bnn_acq_eval_cand(self._h, ACQ_KINDS[kind], float(par), float(eta), _arr(rows), rows.shape[0],
+                                           _arr(out) if want_values else None, *best.refs))
+        return (out,) + best.values()
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            self._owner.robo_bnn_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -12,6 +12,7 @@
 // the launch geometry.
 #include "common.h"
 #include "kern_math.h"
+#include "philox.h"
 #include "post_dev.h"
 
 namespace robo {
@@ -279,13 +280,7 @@ int launch_mixture(robo_cand* cand, int S) {
 }
 
 // ---- Philox-4x32-10 counter-based uniforms (device-side candidate generation; the
-// large-M maximiser row of SURVEY.md section 8f) ---------------------------------------------
-__device__ __forceinline__ void philox_round(unsigned (&c)[4], unsigned k0, unsigned k1) {
-    const unsigned long long p0 = 0xD2511F53ull * c[0], p1 = 0xCD9E8D57ull * c[2];
-    const unsigned n0 = (unsigned)(p1 >> 32) ^ c[1] ^ k0, n1 = (unsigned)p1;
-    const unsigned n2 = (unsigned)(p0 >> 32) ^ c[3] ^ k1, n3 = (unsigned)p0;
-    c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-}
+// large-M maximiser row of SURVEY.md section 8f); philox_round: philox.h ---------------------
 
 __global__ __launch_bounds__(256) void uniform_kernel(double* __restrict__ out, long long m, long long m_pad, int dim,
                                                       unsigned long long seed) {

@@ -73,6 +73,7 @@ static const TuneKey TUNE_KEYS[] = {
     {"trsm_chain_max_wg", nullptr, &Tuning::trsm_chain_max_wg, 4},
     {"trsm_chain_spin_limit", &Tuning::trsm_chain_spin_limit, nullptr, -1},
     {"mlp_fused", nullptr, &Tuning::mlp_fused, -1},
+    {"bnn_launch_steps", nullptr, &Tuning::bnn_launch_steps, 2048},
 };
 
 static void tune_set(Tuning* t, const TuneKey& k, long long v) {

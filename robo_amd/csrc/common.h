@@ -291,6 +291,8 @@ struct Tuning {
     int trsm_chain_max_wg;       // ... auto: while (16-candidate tiles x block rows) <= this many times the CU count (4: measured)
     int mlp_fused;               // robo_mlp_train on one chunk of rows (n <= 1024): every step in ONE launch (mlp_train_one_kernel): 1
                                  // wherever legal (there); -1 auto and 0 never (two launches per step: measured faster, NOTES.md)
+    int bnn_launch_steps;        // robo_bnn_run: SGHMC steps per launch of the chain kernel (2048: about 0.1 s at the default net; the
+                                 // bits do not depend on it; tests lower it)
     long long trsm_chain_spin_limit;   // TEST ONLY: polls before a consumer gives up (-1 = PROG_SPIN_LIMIT); 0 also keeps the
                                  // producers from publishing, so that the first wait of a launch fails at its first poll
 };

@@ -17,160 +17,41 @@
 
 namespace robo {
 
-// the LDS of a gradient workgroup: 3 x 64 x 65 weights (99 840 bytes), four activation tiles and two delta tiles of 16 x 65
-// (49 920), the biases, the output layer and the tile's targets and errors: 154 248 bytes (150.6 KiB) of gfx950's 160 KiB
-struct MlpLds {
-    double W[3][MLP_MAX * MLP_LD];
-    double act[4][MLP_TR * MLP_LD];
-    double del[2][MLP_TR * MLP_LD];
-    double b[3][MLP_MAX];
-    double wout[MLP_MAX];
-    double y[MLP_TR], err[MLP_TR], sq[MLP_TR];
-    double red[WG];
-    double bout;
-};
-
-// the packed parameters -> LDS, pad rows and columns zero
-__device__ __forceinline__ void mlp_stage_weights(const MlpNet& s, const double* p, MlpLds& m) {
-    const int tid = threadIdx.x;
-    for (int l = 0; l < s.L; ++l) {
-        const int in = mlp_in(s, l), kp = l == 0 ? s.IP : s.HP;
-        const double* W = p + mlp_w_off(s, l);
-        for (int e = tid; e < kp * s.HP; e += WG) {
-            const int i = e / s.HP, j = e - i * s.HP;
-            m.W[l][i * MLP_LD + j] = (i < in && j < s.H) ? W[i * s.H + j] : 0.0;
-        }
-        if (tid < s.HP) m.b[l][tid] = tid < s.H ? p[mlp_b_off(s, l) + tid] : 0.0;
-    }
-    if (tid < s.HP) m.wout[tid] = tid < s.H ? p[mlp_out_off(s) + tid] : 0.0;
-    if (tid == 0) m.bout = p[s.P - 1];
-    __syncthreads();
-}
-
 // rows [beg, end) -> out[0 .. P - 1] = d (sum of squared errors / n) / d p, out[P] = the sum of squared errors.  The weights
-// are in LDS (mlp_stage_weights).  Every thread of the workgroup calls it; ends on a barrier.
+// are in LDS (mlp_stage_weights); the tiles go through mlp_tile_grad (mlp_dev.h).  Every thread of the workgroup calls it;
+// ends on a barrier.
 __device__ __forceinline__ void mlp_chunk_grad(const MlpNet& s, MlpLds& m, const double* __restrict__ rows,
                                                const double* __restrict__ y, double n, long long beg, long long end,
                                                double* out) {
-#pragma clang fp contract(off)
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wy = wave >> 1, wx = wave & 1;
-    const int L = s.L, H = s.H, HP = s.HP, nt = HP / 16;
+    const int tid = threadIdx.x, lane = tid & 63, H = s.H;
     const int tiles = (int)((end - beg + MLP_TR - 1) / MLP_TR);
-    v4d acc[3][2][2];
-#pragma unroll
-    for (int l = 0; l < 3; ++l)
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) acc[l][i][j] = v4d{0.0, 0.0, 0.0, 0.0};
-    double gb[3] = {0.0, 0.0, 0.0};      // thread j < HP: d / d b_l[j]
-    double side = 0.0;                   // thread 64 + j: d / d w_out[j]; thread 128: d / d b_out; thread 129: squared errors
-
-    for (int t = 0; t < tiles; ++t) {
-        const long long r0 = beg + (long long)t * MLP_TR;
-        for (int e = tid; e < MLP_TR * s.IP; e += WG) {
-            const int r = e / s.IP, d = e - r * s.IP;
-            m.act[0][r * MLP_LD + d] = (r0 + r < end && d < s.dim) ? rows[(size_t)(r0 + r) * s.dim + d] : 0.0;
-        }
-        if (tid < MLP_TR) m.y[tid] = r0 + tid < end ? y[r0 + tid] : 0.0;
-        __syncthreads();
-        for (int l = 0; l < L; ++l) {                                        // a_(l+1) = tanh(a_l W_l + b_l)
-            for (int u = wave; u < nt; u += WG / 64) {
-                const v4d z = mlp_tile(m.act[l], MLP_LD, m.W[l], MLP_LD, l == 0 ? s.DP : HP, u * 16);
-                const int f = u * 16 + (lane & 15);
-                const double b = m.b[l][f];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) m.act[l + 1][((lane >> 4) + 4 * r) * MLP_LD + f] = tanh(z[r] + b);
-            }
-            __syncthreads();
-        }
-        if (tid < MLP_TR) {                                                  // f = a_L . w_out + b_out, units in index order
-            double f = m.bout;
-            for (int j = 0; j < H; ++j) f = fma(m.act[L][tid * MLP_LD + j], m.wout[j], f);
-            const double e = r0 + tid < end ? f - m.y[tid] : 0.0;
-            m.err[tid] = (2.0 * e) / n;
-            m.sq[tid] = e * e;
-        }
-        __syncthreads();
-        double* dl = m.del[L & 1];                                           // delta_L = 2 (f - y) / n  w_out (1 - a_L^2)
-        for (int e = tid; e < MLP_TR * HP; e += WG) {
-            const int r = e / HP, j = e - r * HP;
-            const double a = m.act[L][r * MLP_LD + j];
-            dl[r * MLP_LD + j] = (m.err[r] * m.wout[j]) * (1.0 - a * a);
-        }
-        if (tid >= 64 && tid < 64 + H) {
-            for (int r = 0; r < MLP_TR; ++r) side = fma(m.err[r], m.act[L][r * MLP_LD + tid - 64], side);
-        } else if (tid == 128) {
-            for (int r = 0; r < MLP_TR; ++r) side = side + m.err[r];
-        } else if (tid == 129) {
-            for (int r = 0; r < MLP_TR; ++r) side = side + m.sq[r];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int l = 2; l >= 0; --l) {                                       // (unrolled: acc and gb stay in registers)
-            if (l >= L) continue;
-            const double* dcur = m.del[(l + 1) & 1];
-            const double* aprev = m.act[l];
-            const int it = (l == 0 ? s.IP : HP) / 16, hi = (it + 1) / 2, hj = (nt + 1) / 2;
-#pragma unroll
-            for (int i = 0; i < 2; ++i)                                      // dW_l += a_l^T delta_(l+1): the wave's quadrant
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    const int I = wy * hi + i, J = wx * hj + j;
-                    if (i < hi && j < hj && I < it && J < nt) {
-#pragma unroll
-                        for (int k0 = 0; k0 < MLP_TR; k0 += 4)
-                            acc[l][i][j] = mfma_f64(aprev[(k0 + (lane >> 4)) * MLP_LD + I * 16 + (lane & 15)],
-                                                    dcur[(k0 + (lane >> 4)) * MLP_LD + J * 16 + (lane & 15)], acc[l][i][j]);
-                    }
-                }
-            if (tid < HP) {
-                double g = gb[l];
-                for (int r = 0; r < MLP_TR; ++r) g = g + dcur[r * MLP_LD + tid];
-                gb[l] = g;
-            }
-            if (l > 0) {                                                     // delta_l = (delta_(l+1) W_l^T) (1 - a_l^2)
-                double* dnext = m.del[l & 1];
-                for (int u = wave; u < nt; u += WG / 64) {
-                    v4d z = v4d{0.0, 0.0, 0.0, 0.0};
-                    for (int k0 = 0; k0 < HP; k0 += 4)
-                        z = mfma_f64(dcur[(lane & 15) * MLP_LD + k0 + (lane >> 4)],
-                                     m.W[l][(u * 16 + (lane & 15)) * MLP_LD + k0 + (lane >> 4)], z);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int e = ((lane >> 4) + 4 * r) * MLP_LD + u * 16 + (lane & 15);
-                        const double a = aprev[e];
-                        dnext[e] = z[r] * (1.0 - a * a);
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    }
+    MlpGrad G;
+    mlp_grad_zero(G);
+    for (int t = 0; t < tiles; ++t) mlp_tile_grad(s, m, rows, y, nullptr, beg + (long long)t * MLP_TR, end, 2.0, n, G);
 #pragma unroll
     for (int l = 0; l < 3; ++l) {
-        if (l < L) {
-            const int in = mlp_in(s, l), it = (l == 0 ? s.IP : HP) / 16, hi = (it + 1) / 2, hj = (nt + 1) / 2;
+        if (l < s.L) {
+            const int in = mlp_in(s, l);
             double* gW = out + mlp_w_off(s, l);
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
-                    const int I = wy * hi + i, J = wx * hj + j;
-                    if (i < hi && j < hj && I < it && J < nt) {
+                    int I, J;
+                    if (mlp_owned_tile(s, l, i, j, I, J)) {
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
                             const int row = I * 16 + (lane >> 4) + 4 * r, col = J * 16 + (lane & 15);
-                            if (row < in && col < H) gW[row * H + col] = acc[l][i][j][r];
+                            if (row < in && col < H) gW[row * H + col] = G.acc[l][i][j][r];
                         }
                     }
                 }
-            if (tid < H) out[mlp_b_off(s, l) + tid] = gb[l];
+            if (tid < H) out[mlp_b_off(s, l) + tid] = G.gb[l];
         }
     }
-    if (tid >= 64 && tid < 64 + H) out[mlp_out_off(s) + tid - 64] = side;
-    else if (tid == 128) out[s.P - 1] = side;
-    else if (tid == 129) out[s.P] = side;
+    if (tid >= 64 && tid < 64 + H) out[mlp_out_off(s) + tid - 64] = G.side;
+    else if (tid == 128) out[s.P - 1] = G.side;
+    else if (tid == 129) out[s.P] = G.side;
     __syncthreads();
 }
 
@@ -267,23 +148,8 @@ __global__ __launch_bounds__(WG) void mlp_train_one_kernel(MlpTrain a) {
 }
 
 __global__ __launch_bounds__(WG) void mlp_pack_kernel(MlpNet s, const double* __restrict__ p, double* __restrict__ pad) {
-    const int len = mlp_pad_len(s), tail = mlp_pad_off(s, s.L);
-    for (int e = blockIdx.x * WG + threadIdx.x; e < len; e += gridDim.x * WG) {
-        double v = 0.0;
-        if (e >= tail) {
-            const int j = e - tail;
-            v = j == s.HP ? p[s.P - 1] : (j < s.H ? p[mlp_out_off(s) + j] : 0.0);
-        } else {
-            int l = 0;
-            while (l + 1 < s.L && e >= mlp_pad_off(s, l + 1)) ++l;
-            const int o = e - mlp_pad_off(s, l), kp = mlp_kp(s, l), i = o / s.HP, j = o - i * s.HP;
-            if (j < s.H) {
-                if (i < mlp_in(s, l)) v = p[mlp_w_off(s, l) + i * s.H + j];
-                else if (i == kp) v = p[mlp_b_off(s, l) + j];
-            }
-        }
-        pad[e] = v;
-    }
+    const int len = mlp_pad_len(s);
+    for (int e = blockIdx.x * WG + threadIdx.x; e < len; e += gridDim.x * WG) pad[e] = mlp_pad_entry(s, p, e);
 }
 
 // rows [64 b, 64 b + 64): the features [a_L, 1] (nullable) and the value a_L . w_out + b_out (nullable), units in index order

@@ -14,8 +14,9 @@ without george, pybnn and pyrfr: :2,5,8,11), wired to the MI355X GP path:
     maximiser RandomSampling | SciPyOptimizer | DifferentialEvolution                    (:131-139)
               | DeviceRandomSampling | DeviceGradientAscent (not in the reference)
 
-The model types rf / bohamiann are outside this project's hot path.  DNGO is a device
-model (models/dngo.py) but not yet a model_type of this front end: build it and drive an acquisition with it directly.
+The model type rf is outside this project's hot path.  DNGO and BOHAMIANN are device models
+(models/dngo.py, models/bohamiann.py) but not model_types of this front end: build them and drive an acquisition and a
+maximiser with them through robo_amd.solver.BayesianOptimization.
 """
 import logging
 

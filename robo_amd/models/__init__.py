@@ -4,3 +4,5 @@ from robo_amd.models.gaussian_process_mcmc import GaussianProcessMCMC  # noqa: F
 from robo_amd.models.fabolas_gp import FabolasGP, FabolasGPMCMC  # noqa: F401
 from robo_amd.models.bayesian_linear_regression import BayesianLinearRegression, RandomFourierBasis  # noqa: F401
 from robo_amd.models.dngo import DNGO  # noqa: F401
+from robo_amd.models.bohamiann import Bohamiann  # noqa: F401
+from robo_amd.models.wrapper_bohamiann import WrapperBohamiann  # noqa: F401
