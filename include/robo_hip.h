@@ -436,6 +436,62 @@ int32_t robo_acq_refine_marginal_cand(robo_gp* const* gps, int32_t S, int32_t ac
                                       double* out_value, int64_t* out_start_index, uint32_t* out_flags,
                                       int64_t* out_starts, double* out_trace);
 
+/* ---- CMA-ES over the acquisition (the reference's robo/maximizers/cmaes.py drives the `cma` package from the host, one
+ * 1 x dim acquisition call per function value): sweep over `cand` exactly as robo_acq_eval_cand; the n_instances (R, 1 .. 64)
+ * best candidates -- robo_acq_refine_cand's rule: descending value, ties by ascending index, NaN never -- become the initial
+ * means m of R independent instances of Hansen's (mu/mu_w, lambda)-CMA-ES with positive weights, which run n_generations
+ * generations in lock step in the box [0, 1]^dim of the GP's normalised input space, all on the device.  2 <= dim <= 64,
+ * 4 <= lambda <= 64.  With n = dim: mu = lambda / 2, w_i ~ ln((lambda + 1) / 2) - ln i normalised to sum 1,
+ * mu_eff = 1 / sum w_i^2, c_sigma = (mu_eff + 2) / (n + mu_eff + 5),
+ * d_sigma = 1 + 2 max(0, sqrt((mu_eff - 1) / (n + 1)) - 1) + c_sigma, c_c = (4 + mu_eff / n) / (n + 4 + 2 mu_eff / n),
+ * c_1 = 2 / ((n + 1.3)^2 + mu_eff), c_mu = min(1 - c_1, 2 (mu_eff - 2 + 1 / mu_eff) / ((n + 2)^2 + mu_eff)),
+ * chi_n = sqrt(n) (1 - 1 / (4 n) + 1 / (21 n^2)).  C = A = A^-1 = I, p_sigma = p_c = 0, sigma = sigma0 at the start.
+ *   Ask.      y_i = A z_i (A = C^1/2, the SYMMETRIC square root), x_i = clip(m + sigma y_i, 0, 1), then y_i := (x_i - m) / sigma:
+ *             the update sees the repaired point.  z: [n_generations][R][lambda][dim] from the caller, or NULL: Philox-4x32-10
+ *             blocks on the counter (generation, instance, sample, pair) under the key `seed`, both Box-Muller branches
+ *             (cosine: coordinate 2 pair, sine: 2 pair + 1) of its two uniforms.
+ *   Values.   The posterior of all R lambda points as one batch per model, exactly as robo_acq_eval forms it for a batch of
+ *             that size; the acquisition value with robo_acq_eval_cand's guards; marginal form: summed in sample order, / S.
+ *   Tell.     Ranking: descending value, ties by ascending sample index, NaN last.  y_w = sum w_i y_(i:lambda);
+ *             m = clip(m + sigma y_w, 0, 1) (a mean of points of the box: only a rounding can put it outside);  p_sigma = (1 - c_sigma) p_sigma + sqrt(c_sigma (2 - c_sigma) mu_eff) A^-1 y_w;
+ *             h_sigma = [ |p_sigma| / sqrt(1 - (1 - c_sigma)^(2 (g + 1))) < (1.4 + 2 / (n + 1)) chi_n ];
+ *             p_c = (1 - c_c) p_c + h_sigma sqrt(c_c (2 - c_c) mu_eff) y_w;
+ *             C = (1 - c_1 - c_mu) C + c_1 (p_c p_c^T + (1 - h_sigma) c_c (2 - c_c) C) + c_mu sum w_i y_(i:lambda) y_(i:lambda)^T;
+ *             sigma *= exp((c_sigma / d_sigma) (|p_sigma| / chi_n - 1)).  After every eig_every-th generation (0: the
+ *             default max(1, floor(1 / (10 n (c_1 + c_mu))))) C = B Lambda B^T is decomposed (cyclic two-sided Jacobi) and
+ *             A = B sqrt(Lambda) B^T, A^-1 = B Lambda^-1/2 B^T; C, A and A^-1 are bit-symmetric.  An instance's best-so-far
+ *             (at first its start and the sweep's value) is replaced only by a strictly larger value.
+ *   Stops.    An instance stops with its best-so-far kept, and ROBO_FLAG_FROZEN is raised, when every value of a generation
+ *             is NaN or not finite (code 1: nothing is updated), an eigenvalue is <= 0 or not finite or the sweeps do not
+ *             converge (2), lambda_max / lambda_min > 1e14 (3) -- A and A^-1 then keep their last values --, the new sigma is
+ *             not finite (4) or below sigma_min (5).
+ * Result: the best-so-far of the best instance (first on ties): out_x (dim), *out_value, *out_instance (-1: every candidate
+ * was NaN), *out_flags = the sweep's flags | the generations' (ZERO_SIGMA / NEGATIVE_EI / NAN of their values, FROZEN).  The
+ * result is never below the sweep's maximum; n_generations = 0 returns the sweep's argmax, point and value.  With fewer
+ * eligible candidates than R the remaining instances stay unused.  An instance never looks at another one: with the
+ * caller's draws its trajectory does not depend on R or on its index.
+ * out_trace (nullable): [n_generations + 1][R][3 lambda dim + 2 lambda + 3 dim + 3 + 3 dim^2]; entry 0 is the state at the start,
+ * entry g + 1 generation g: z, x, repaired y (lambda x dim each), values, ranks (lambda each), then the state AFTER the tell:
+ * m, sigma, p_sigma, p_c, h_sigma, code (0 step taken, 1 .. 5 stopped here for the reason above, 6 stopped earlier, 7 unused;
+ * the sample columns of 6 and 7 are zero), C, A, A^-1 (dim x dim each).
+ * ROBO_BAD_ARGUMENT: a bad acq_kind, dim < 2 or > 64, lambda outside 4 .. 64, n_instances outside 1 .. 64, n_generations or
+ * eig_every < 0, sigma0 <= 0 or not finite, sigma_min < 0 or NaN, a Fabolas kernel (its fidelity column is not a box
+ * coordinate), a model handle given twice; ROBO_NOT_FITTED: a model that is not fitted; ROBO_BAD_SHAPE: cand's dim is not the
+ * GP's, or the R lambda rows do not fit the solve workspace.  One synchronisation per call; the state stays with gp (gps[0]).
+ * A caller's z (n_generations R lambda dim doubles) is uploaded up front from the caller's memory: from pageable memory that
+ * copy is staged by the runtime and may wait on the host, so only the Philox form (z = NULL) is strictly launches-only.     */
+int32_t robo_acq_cmaes_cand(robo_gp* gp, int32_t acq_kind, double par, double eta, robo_cand* cand, int32_t n_instances,
+                            int32_t lambda, int32_t n_generations, double sigma0, double sigma_min, int32_t eig_every,
+                            const double* z, uint64_t seed, double* out_x, double* out_value, int32_t* out_instance,
+                            uint32_t* out_flags, double* out_trace);
+/* the same for the mean over S fitted GPs (distinct handles; robo_acq_eval_marginal_cand's sweep): the points are scaled with
+ * every sample's length scales and solved against its factor.  S = 1 is robo_acq_cmaes_cand bit for bit.                    */
+int32_t robo_acq_cmaes_marginal_cand(robo_gp* const* gps, int32_t S, int32_t acq_kind, double par, const double* etas,
+                                     robo_cand* cand, int32_t n_instances, int32_t lambda, int32_t n_generations,
+                                     double sigma0, double sigma_min, int32_t eig_every, const double* z, uint64_t seed,
+                                     double* out_x, double* out_value, int32_t* out_instance, uint32_t* out_flags,
+                                     double* out_trace);
+
 /* ---- entropy search's representer points: the ensemble sampler's whole run on the device (the reference drives emcee from
  * the host around one acquisition value per walker, robo/acquisition_functions/information_gain.py:132-151).  One chain of
  * n_walkers (k, even, >= 2 dim) walkers in the CALLER's input space samples exp(acquisition) of the fitted gp inside the box

@@ -63,6 +63,7 @@ SYMBOLS = [
     "robo_cand_last_screen", "robo_cand_last_screen_finish", "robo_cand_last_screen_first", "robo_cand_last_screen_form",
     "robo_acq_screen_bounds",
     "robo_acq_refine_cand", "robo_acq_refine_marginal_cand",
+    "robo_acq_cmaes_cand", "robo_acq_cmaes_marginal_cand",
     "robo_rep_sample", "robo_rep_sample_batch",
     "robo_acq_batch_cand", "robo_acq_batch_marginal_cand", "robo_qei_batch_cand", "robo_qei_batch_marginal_cand",
     "robo_mes_eval_cand", "robo_mes_eval_marginal_cand", "robo_mes_sample_min_moments", "robo_mes_eval_moments",
@@ -246,6 +247,10 @@ def lib():
                                  C.POINTER(i64), _dp],
         "robo_acq_refine_marginal_cand": [pp, i32, i32, dbl, _dp, vp, i32, i32, dbl, _dp, _dp, C.POINTER(i64),
                                           C.POINTER(C.c_uint32), C.POINTER(i64), _dp],
+        "robo_acq_cmaes_cand": [vp, i32, dbl, dbl, vp, i32, i32, i32, dbl, dbl, i32, _dp, C.c_uint64, _dp, _dp, C.POINTER(i32),
+                                C.POINTER(C.c_uint32), _dp],
+        "robo_acq_cmaes_marginal_cand": [pp, i32, i32, dbl, _dp, vp, i32, i32, i32, dbl, dbl, i32, _dp, C.c_uint64, _dp, _dp,
+                                         C.POINTER(i32), C.POINTER(C.c_uint32), _dp],
         "robo_rep_sample": [vp, i32, dbl, dbl, _dp, _dp, i32, i32, i32, dbl, _dp, C.POINTER(i32), _dp, _dp, _dp, i32,
                             C.POINTER(i64), C.POINTER(C.c_uint32), _dp],
         "robo_rep_sample_batch": [pp, i32, i32, dbl, _dp, _dp, _dp, i32, i32, i32, dbl, _dp, C.POINTER(i32), _dp, _dp, _dp,
@@ -995,6 +1000,10 @@ class DeviceGP(object):
         -> RefineResult; see :func:`acq_refine`"""
         return acq_refine([self], kind, par, eta, cand, n_starts, n_steps, step0, diagnostics, marginal=False)
 
+    def cmaes(self, kind, par, eta, cand, n_instances=1, popsize=None, n_generations=100, sigma0=0.25, **how):
+        """sweep over ``cand`` + lock-step CMA-ES instances from its best rows on the device (robo_acq_cmaes_cand)
+        -> CMAESResult; see :func:`cmaes_marginal`"""
+        return cmaes_marginal([self], kind, par, eta, cand, n_instances, popsize, n_generations, sigma0, marginal=False, **how)
 
     def select_batch(self, kind, par, eta, cand, q, fantasy="kriging_believer", liar=0.0, diagnostics=False):
         """q greedy picks from ``cand`` with fantasised observations in between (robo_acq_batch_cand) -> BatchResult;
@@ -1753,6 +1762,56 @@ def acq_refine(gps, kind, par, eta, cand, n_starts=256, n_steps=50, step0=0.05, 
     fn = lib().robo_acq_refine_marginal_cand if marginal else lib().robo_acq_refine_cand
     return _refine_call(fn, _ensemble_head(gps, eta, marginal, ACQ_KINDS[kind], float(par)), cand, n_starts, n_steps, step0,
                         diagnostics)
+
+
+CMAES_MAX = 64                                   # robo_acq_cmaes_*: cap on dim, popsize and n_instances
+
+
+class CMAESResult(object):
+    """x (D,) in the GP's normalised input space, value, instance (the winning instance; -1: every candidate was NaN),
+    flags; with diagnostics the trace (T + 1, R, W) as a dict of views: z, x, y (T + 1, R, popsize, D), values, ranks
+    (T + 1, R, popsize), m, p_sigma, p_c (T + 1, R, D), sigma, h_sigma, code (T + 1, R), C, A, Ainv (T + 1, R, D, D); entry 0 is
+    the state at the start, entry g + 1 generation g with the state after its tell (include/robo_hip.h)"""
+
+    def __init__(self, x, value, instance, flags, trace=None):
+        self.x, self.value, self.instance, self.flags, self.trace = x, float(value), int(instance), int(flags), trace
+
+
+def cmaes_default_popsize(dim):
+    return 4 + int(np.floor(3 * np.log(dim)))
+
+
+def cmaes_trace_views(raw, D, L):
+    """the named columns of a raw trace (T + 1, R, W)"""
+    lead, out, at = raw.shape[:2], {}, 0
+    for name, shape in (("z", (L, D)), ("x", (L, D)), ("y", (L, D)), ("values", (L,)), ("ranks", (L,)), ("m", (D,)),
+                        ("sigma", ()), ("p_sigma", (D,)), ("p_c", (D,)), ("h_sigma", ()), ("code", ()), ("C", (D, D)),
+                        ("A", (D, D)), ("Ainv", (D, D))):
+        n = int(np.prod(shape, dtype=np.int64))
+        out[name] = raw[:, :, at:at + n].reshape(lead + shape)
+        at += n
+    assert at == raw.shape[2]
+    return out
+
+
+def cmaes_marginal(gps, kind, par, eta, cand, n_instances=1, popsize=None, n_generations=100, sigma0=0.25, sigma_min=1e-12,
+                   eig_every=0, z=None, seed=0, diagnostics=False, marginal=True):
+    """the CMA-ES maximiser of a closed-form acquisition over device GPs (one: robo_acq_cmaes_cand; the mean over several
+    hyper-parameter samples: robo_acq_cmaes_marginal_cand).  eta: one incumbent value, or one per sample.  popsize None:
+    4 + floor(3 ln D).  z (n_generations, n_instances, popsize, D): the standard normal draws, or None: Philox under ``seed``."""
+    R, T, D = int(n_instances), int(n_generations), cand.dim
+    L = cmaes_default_popsize(D) if popsize is None else int(popsize)
+    if z is not None:
+        z = _f64(z, (T, R, L, D))
+    x = np.empty(D)
+    value, inst, flags = C.c_double(0), C.c_int32(0), C.c_uint32(0)
+    want = bool(diagnostics) and 1 <= R <= CMAES_MAX and 4 <= L <= CMAES_MAX and 2 <= D <= CMAES_MAX and T >= 0
+    raw = np.empty((T + 1, R, 3 * L * D + 2 * L + 3 * D + 3 + 3 * D * D)) if want else None
+    fn = lib().robo_acq_cmaes_marginal_cand if marginal else lib().robo_acq_cmaes_cand
+    check(fn(*_ensemble_head(gps, eta, marginal, ACQ_KINDS[kind], float(par)), cand._h, R, L, T, float(sigma0),
+             float(sigma_min), int(eig_every), None if z is None else _arr(z), int(seed), _arr(x), C.byref(value),
+             C.byref(inst), C.byref(flags), _arr(raw) if want else None))
+    return CMAESResult(x, value.value, inst.value, flags.value, cmaes_trace_views(raw, D, L) if want else None)
 
 
 def _refine_call(fn, head, cand, n_starts, n_steps, step0, diagnostics):

@@ -54,6 +54,11 @@ class BaseAcquisitionFunction(object):
         raise TypeError("%s has no gradient refinement on the device: refine() is available for EI, LogEI, PI and LCB "
                         "over a robo_amd GaussianProcess (or MarginalizationGPMCMC over them)" % self.__class__.__name__)
 
+    def cmaes(self, X, n_instances=1, popsize=None, n_generations=100, sigma0=0.25, seed=0):
+        """CMA-ES maximiser on the device: EI / LogEI / PI / LCB over robo_amd GP models only."""
+        raise TypeError("%s has no moments-only value for the device's CMA-ES: cmaes() is available for EI, LogEI, PI and LCB "
+                        "over a robo_amd GaussianProcess (or MarginalizationGPMCMC over them)" % self.__class__.__name__)
+
 
     def select_batch(self, X, q, fantasy="kriging_believer", liar=None, diagnostics=False):
         """Greedy batch of q proposals with fantasised picks: EI / LogEI / PI / LCB over robo_amd GP models only."""
@@ -126,11 +131,13 @@ def refine_model_check(model, who, what="refine"):
         raise Exception('Model has to be trained first!')
 
 
-def refine_finish(acq, kind, model, res, cand):
-    """shared tail of the refine() methods: the reference's EI guards on the sweep's flags, the point in the caller's
-    input space"""
-    acq.last_refine = res
-    acq.last_max, acq.last_argmax = res.value, res.start_index
+def refine_finish(acq, kind, model, res, cand, keep="last_refine"):
+    """shared tail of the refine() and cmaes() methods (``keep``: the attribute that holds the library's result): the
+    reference's EI guards on the sweep's flags, the point in the caller's input space"""
+    setattr(acq, keep, res)
+    acq.last_max = res.value
+    if hasattr(res, "start_index"):
+        acq.last_argmax = res.start_index
     x = res.x
     if kind == "ei":
         if res.flags & _lib.FLAG_ZERO_SIGMA:          # ei.py:72-74: the batch collapses to [[0]], argmax 0
@@ -344,6 +351,19 @@ class ClosedFormAcquisition(BaseAcquisitionFunction):
         with staged_candidates(model, X) as cand:       # (refine_model_check admits no model with a normalize() of its own)
             res = model.gp.refine(self.kind, self.par, self._eta(eta), cand, n_starts, n_steps, step0, diagnostics)
             return refine_finish(self, self.kind, model, res, cand)
+
+    def cmaes(self, X, n_instances=1, popsize=None, n_generations=100, sigma0=0.25, seed=0, eta=None, **how):
+        """The maximiser found by CMA-ES on the device (robo_acq_cmaes_cand): sweep over the candidates X (as for
+        ``refine``), the ``n_instances`` best of them become the means of as many independent (mu/mu_w, lambda)-CMA-ES
+        instances of ``popsize`` samples (None: 4 + floor(3 ln D)), which run ``n_generations`` generations in lock step
+        -> the best point seen, in the caller's input space.  ``last_cmaes`` keeps the library's result."""
+        model = self.model
+        refine_model_check(model, self.__class__.__name__, "cmaes")
+        model._materialise()
+        with staged_candidates(model, X) as cand:
+            res = model.gp.cmaes(self.kind, self.par, self._eta(eta), cand, n_instances, popsize, n_generations, sigma0,
+                                 seed=seed, **how)
+            return refine_finish(self, self.kind, model, res, cand, "last_cmaes")
 
     def select_batch(self, X, q, fantasy="kriging_believer", liar=None, diagnostics=False, eta=None, *, n_mc=128, z=None,
                      rng=None):

@@ -491,6 +491,30 @@ class MarginalizationGPMCMC(BaseAcquisitionFunction):
             res = _lib.acq_refine(gps, est[0].kind, est[0].par, eta, cand, n_starts, n_steps, step0, diagnostics)
             return refine_finish(self, est[0].kind, m0, res, cand)
 
+    def cmaes(self, X_test, n_instances=1, popsize=None, n_generations=100, sigma0=0.25, seed=0, **how):
+        """CMA-ES maximiser of the marginalised acquisition on the device (robo_acq_cmaes_marginal_cand): as
+        ClosedFormAcquisition.cmaes, the values averaged over the hyper-parameter samples in sample order."""
+        from robo_amd.acquisition_functions.base_acquisition import refine_finish, refine_model_check
+        if not isinstance(self.acquisition_func, ClosedFormAcquisition) or not self.estimators:
+            raise TypeError("MarginalizationGPMCMC.cmaes is available for EI, LogEI, PI and LCB only (got %s)"
+                            % type(self.acquisition_func).__name__)
+        if getattr(self.model, "devices", None) or self._shard() is not None:
+            raise NotImplementedError("MarginalizationGPMCMC.cmaes runs on one device; multi-device and multi-process "
+                                      "sharding of it is not implemented")
+        for e in self.estimators:
+            refine_model_check(e.model, "MarginalizationGPMCMC", "cmaes")
+            e.model._materialise()
+        est = self.estimators
+        gps = [e.model.gp for e in est]
+        if len({id(g.ctx) for g in gps}) != 1:
+            raise NotImplementedError("MarginalizationGPMCMC.cmaes: the sub-models live on several contexts")
+        eta = np.array([e._eta(None) for e in est])
+        m0 = est[0].model
+        with staged_candidates(m0, X_test) as cand:
+            res = _lib.cmaes_marginal(gps, est[0].kind, est[0].par, eta, cand, n_instances, popsize, n_generations, sigma0,
+                                      seed=seed, **how)
+            return refine_finish(self, est[0].kind, m0, res, cand, "last_cmaes")
+
     def select_batch(self, X_test, q, fantasy="kriging_believer", liar=None, diagnostics=False, *, n_mc=128, z=None,
                      rng=None):
         """Greedy batch of q proposals under the marginalised acquisition (robo_acq_batch_marginal_cand): as

@@ -64,6 +64,7 @@ int32_t robo_gp_destroy(robo_gp* g) {
     qei_free(g->qei);
     mes_free(g->mes);
     rep_free(g->rep);
+    cma_free(g->cma);
     hyper_free(g->hyper);
     hipFree(g->d_X);
     hipFree(g->d_Xs);

@@ -462,6 +462,54 @@ struct RepWork {
 };
 void rep_free(RepWork* w);
 
+// ---- CMA-ES over an acquisition (cmaes.hip, api_cmaes.hip) ---------------------------------------------------------------------
+// what the ask and tell kernels need of ONE model: the generation's R lambda points are written into that model's own
+// candidate handle (the one behind the host-array entry points) and their posterior is formed there by predict_scaled
+struct CmaModel {
+    const double* ism;              // [D] inverse square-root metrics of the fitted theta (robo_gp::d_theta)
+    double* Xcs;                    // (m_pad, D) the handle's scaled input rows
+    const double *mean, *var;       // (m_pad) the handle's transformed mean and floored variance
+    double eta;
+};
+constexpr int CMA_MAX = 64;         // D, lambda and R are at most this
+constexpr int CMA_LD = CMA_MAX + 2; // leading dimension of every matrix in LDS: 66 doubles = 132 words, off the 64-bank stride
+// frozen codes of an instance (the trace's last-but-state column; 0 = the generation's step was taken)
+enum CmaCode { CMA_LIVE = 0, CMA_ALL_BAD = 1, CMA_EIG_BAD = 2, CMA_EIG_COND = 3, CMA_SIGMA_BAD = 4, CMA_SIGMA_MIN = 5,
+               CMA_WAS_FROZEN = 6, CMA_UNUSED = 7 };
+// the state of one call: R instances of lambda samples in D dimensions; all arrays device memory of one block
+struct CmaState {
+    int R, D, L, mu, T, S, eig_every, kind;
+    long long m_pad;                // rows of a model's candidate handle (rows beyond R lambda replicate row 0)
+    double par, sigma0, sigma_min;
+    double cs, ds, cc, c1, cmu, mueff, chin, log1mcs;      // Hansen's constants for (n = D, lambda); log(1 - cs)
+    unsigned long long seed;
+    double *m, *sigma, *ps, *pc;    // [R][D], [R], [R][D], [R][D]
+    double *C, *A, *Ainv;           // [R][D][D] each, bit-symmetric
+    double *bestx, *bestf;          // [R][D], [R] best-so-far point and value
+    double *x, *y;                  // [R][L][D] the pending generation: points in the box, repaired steps (x - m) / sigma
+    int *gen, *frozen;              // [R] generations taken; CmaCode the instance stopped with (0: live)
+    unsigned* flags;                // ROBO_FLAG_* of the generations
+    double* out;                    // [D + 3]: point, value, instance, flags
+    const double* w;                // [mu] recombination weights
+    const double* z;                // [T][R][L][D] the caller's draws, or nullptr: Philox
+    const CmaModel* model;          // [S]
+    double* trace;                  // [T + 1][R][cma_trace_row(D, L)], or nullptr
+};
+// one trace row: z, x, y (L x D each), values, ranks (L each), m, sigma, p_sigma, p_c, h_sigma, code, C, A, A^-1
+__host__ __device__ inline size_t cma_trace_row(int D, int L) { return (size_t)3 * L * D + 2 * L + 3 * D + 3 + (size_t)3 * D * D; }
+struct CmaWork {
+    size_t bytes;                   // of d_block (dev_grow: grows, never shrinks)
+    char* d_block;                  // laid out anew by every call (cma_core's BlockLayout)
+    double* d_trace;
+    size_t trace_cap;               // doubles
+    RefineWork* sel;                // refine.hip's top-K selection state for R starts, kept between calls of one (R, D)
+};
+void cma_free(CmaWork* w);
+int launch_cma_init(robo_ctx* ctx, const CmaState& st, const RefineState& sel);
+int launch_cma_ask(robo_ctx* ctx, const CmaState& st, int g);
+int launch_cma_tell(robo_ctx* ctx, const CmaState& st, int g);
+int launch_cma_result(robo_ctx* ctx, const CmaState& st, unsigned* d_cand_flags);
+
 // ---- multi-start MAP optimisation of the hyper-parameters (hyperopt.hip) ------------------------------------------------------
 constexpr int HYPER_MAX_STARTS = 64, HYPER_MAX_HISTORY = 16;
 // everything a start carries between two launches; all arrays [K], [K][P] or [K][hist][P], device memory of one block
@@ -623,6 +671,7 @@ struct robo_gp {
     robo::MesWork* mes;             // state of robo_mes_eval_* (mes.hip), kept between calls of one (m, S, K)
     robo::RepWork* rep;             // state of robo_rep_sample* (represent.hip), kept with gps[0] between calls
     robo::HyperWork* hyper;         // workspace of robo_gp_grad_loglik_batch / robo_gp_optimize_hypers (hyperopt.hip)
+    robo::CmaWork* cma;             // state of robo_acq_cmaes_* (cmaes.hip), kept with gps[0] between calls
     // the acquisition screen (screen.hip), lazy: [scratch (n_pad_max) | alpha = L^-T z (n_pad_max) | sum_j |alpha_j| sqrt(k_jj),
     // then, for the kinds and D the dot-form bounds kernel takes, its per-fit inputs (screen.hip "The dot form")]
     double* d_alpha;

@@ -13,6 +13,7 @@ without george, pybnn and pyrfr: :2,5,8,11), wired to the MI355X GP path:
 
     maximiser RandomSampling | SciPyOptimizer | DifferentialEvolution                    (:131-139)
               | DeviceRandomSampling | DeviceGradientAscent (not in the reference)
+              | CMAES (the reference's fabolas / entropy_search front ends take it; here it runs on the device)
 
 The model type rf is outside this project's hot path.  DNGO and BOHAMIANN are device models
 (models/dngo.py, models/bohamiann.py) but not model_types of this front end: build them and drive an acquisition and a
@@ -26,7 +27,7 @@ from robo_amd.acquisition_functions import (EI, LCB, MES, PI, KnowledgeGradient,
                                             ThompsonSampling)
 from robo_amd.initial_design import init_latin_hypercube_sampling
 from robo_amd.kernels import Matern52Kernel
-from robo_amd.maximizers import (DeviceGradientAscent, DeviceRandomSampling, DifferentialEvolution, RandomSampling,
+from robo_amd.maximizers import (CMAES, DeviceGradientAscent, DeviceRandomSampling, DifferentialEvolution, RandomSampling,
                                  SciPyOptimizer)
 from robo_amd.models import GaussianProcess, GaussianProcessMCMC
 from robo_amd.models.bayesian_linear_regression import BayesianLinearRegression, quadratic_basis_func
@@ -133,6 +134,9 @@ def bayesian_optimization(objective_function, lower, upper, num_iterations=30, X
     elif maximizer == "device_gradient":
         # the same candidates; the best of them are refined by gradient ascent on the device (n_candidates = sweep size)
         max_func = DeviceGradientAscent(acq, lower, upper, n_samples=n_candidates, rng=rng)
+    elif maximizer == "cmaes":
+        # the same candidates; the best of them starts a CMA-ES instance on the device (n_candidates = sweep size)
+        max_func = CMAES(acq, lower, upper, verbose=False, n_samples=n_candidates, rng=rng)
     elif maximizer == "scipy":
         max_func = SciPyOptimizer(acq, lower, upper, rng=rng)
     elif maximizer == "differential_evolution":
