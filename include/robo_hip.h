@@ -492,6 +492,69 @@ int32_t robo_acq_cmaes_marginal_cand(robo_gp* const* gps, int32_t S, int32_t acq
                                      double* out_x, double* out_value, int32_t* out_instance, uint32_t* out_flags,
                                      double* out_trace);
 
+/* ---- DIRECT over the acquisition (the reference's robo/maximizers/direct.py drives the DIRECT package from the host, one
+ * 1 x dim acquisition call per function value): Jones, Perttunen and Stuckman's DIviding RECTangles in its original form,
+ * minimising f = -a over the box [0, 1]^dim of the GP's normalised input space, 1 <= dim <= 64, all on the device.  It takes
+ * no draws and no starting points: two calls give the same bits.  f = 0 where a == 0 (never -0), f = DBL_MAX where a is NaN,
+ * and f is clamped to [-DBL_MAX, DBL_MAX].
+ *   Rectangle. r has a centre c_r (dim doubles), levels l_r[i] (trisections along i: the side is 3^-l) and a value f_r.  The
+ *             levels of one rectangle differ by at most one: with k = min_i l[i] and p = #{i : l[i] = k + 1} its size class
+ *             is the INTEGER s = k dim + p.  Classes are integers; no two sizes are ever compared as floating-point numbers.
+ *   Tables.   Built on the host in fp64, every operation rounded once: delta[j] = 1 / 3^j (3^j exact), q[j] = delta[j] delta[j],
+ *             d[s] = 0.5 sqrt((dim - p) q[k] + p q[k + 1]) for s = 0 .. LMAX dim.  d is strictly decreasing in s (checked).
+ *             LMAX = ROBO_DIRECT_LMAX = 24: a rectangle with k = LMAX is not divisible.  delta[25] = 1.2e-12 is still 1e4 ulps
+ *             of a centre, and far below the resolution of a posterior whose length scales are bounded below.
+ *   Iteration 0 evaluates the centre 0.5 * 1 alone: rectangle 0, all levels 0.  Iteration t = 1, 2, ...:
+ *   1. Class minima.  For every non-empty class s with k < LMAX: (F_s, r_s), the lowest value and, at equal values, the
+ *             lowest rectangle index.  fmin is the lowest value of ALL rectangles, the best its lowest index.
+ *   2. Potentially optimal classes, all pairs over the classes of 1.; sub, div, mul, add below are single roundings, none fused:
+ *             K_hi(j) = min over i < j (d_i > d_j) of (F_i - F_j) / (d_i - d_j), +inf if there is none;
+ *             K_lo(j) = max(0, max over i > j (d_i < d_j) of (F_j - F_i) / (d_j - d_i)).
+ *             j is potentially optimal iff K_hi > 0, K_lo <= K_hi and (K_hi = +inf or the epsilon test passes):
+ *             fmin != 0:  eps <= t1 + t2, t1 = (fmin - F_j) / |fmin|, t2 = (d_j / |fmin|) K_hi;   fmin == 0:  F_j <= d_j K_hi.
+ *   3. Slots. The rectangles r_j of the potentially optimal classes in increasing j (largest first).  With k = k_j and
+ *             I = {i : l[i] = k} in increasing i, r_j gets 2 |I| consecutive slots: slot 2 q is c + delta[k + 1] e_i, slot
+ *             2 q + 1 is c - delta[k + 1] e_i for the q-th i of I (one add each; every point is strictly inside the box).  The
+ *             posterior batch has `batch` (B >= 2 dim) rows: a rectangle whose slots would pass B is deferred together with
+ *             all later ones (ROBO_DIRECT_DEFERRED); it stays in the store and is found again.  Unused rows copy row 0.
+ *   4. Posterior of the B rows per model, exactly as robo_acq_eval forms it for a batch of that size.
+ *   5. Divide.  The acquisition value of a used slot with robo_acq_eval_cand's guards; marginal form: summed in sample order,
+ *             / S.  w_i = min(f+, f-); the dimensions of I are ranked by (w_i, i) ascending.  The dimension of rank rho yields
+ *             two children: centres the two sampled points, levels the parent's with +1 on every dimension of rank <= rho.
+ *             The parent gets +1 on all of I.  The child of slot e is rectangle n_before + e; every value makes one rectangle.
+ *   6. Stops, each with its own bit of *out_flags: ROBO_DIRECT_STOP_BUDGET (evals >= max_evals when an iteration would start:
+ *             the iteration in hand is finished), ROBO_DIRECT_STOP_ITERS (max_iters iterations done), ROBO_DIRECT_STOP_CAPACITY
+ *             (n_rect + B > capacity when an iteration would start: it is not started), ROBO_DIRECT_STOP_NOTHING (no divisible
+ *             potentially optimal rectangle).  The host enqueues min(max_iters, ceil((max_evals - 1) / 2)) iterations in
+ *             advance; after a stop this call's own kernels return at their first load, the posterior of the B rows left in
+ *             the handles still runs (predict_scaled has no device-side predicate).
+ * Result: out_x (dim) the best rectangle's centre, *out_value its acquisition value a = -f, *out_evals the values taken
+ * (= rectangles), *out_iters the iterations t >= 1 that divided, *out_flags = the stop and deferral bits | ZERO_SIGMA /
+ * NEGATIVE_EI / NAN of the values.  capacity 0: max_evals + B, which never stops a run.  eps: Jones' 1e-4.
+ * out_trace (nullable): [T + 1][8 + B / 2 + B dim + B] then the store [capacity][2 dim + 1], T = the enqueued iterations.  Row
+ * t: ran (0 / 1), potentially optimal rectangles taken, slots used, n_before, evals after, fmin and best index when t started
+ * (0, -1 for t = 0), flags so far; the taken rectangles' indices (-1 beyond); the B points; the B acquisition values (0 in
+ * unused slots).  Store row r: centre, levels, f (zeros beyond the rectangles made).
+ * ROBO_BAD_ARGUMENT: a bad acq_kind, dim > 64, batch < 2 dim, odd or > 16384, max_evals < 1, max_iters < 0, capacity != 0 and
+ * < 1, eps < 0 or not finite, a Fabolas kernel, a model handle given twice; ROBO_NOT_FITTED: a model that is not fitted;
+ * ROBO_BAD_SHAPE: the samples differ in dim or n, or the B rows do not fit the solve workspace.  One synchronisation per
+ * call; the state stays with gp (gps[0]).                                                                                    */
+#define ROBO_DIRECT_LMAX 24
+#define ROBO_DIRECT_STOP_BUDGET 0x100u
+#define ROBO_DIRECT_STOP_ITERS 0x200u
+#define ROBO_DIRECT_STOP_CAPACITY 0x400u
+#define ROBO_DIRECT_STOP_NOTHING 0x800u
+#define ROBO_DIRECT_DEFERRED 0x1000u
+int32_t robo_acq_direct(robo_gp* gp, int32_t acq_kind, double par, double eta, int32_t max_evals, int32_t max_iters,
+                        int32_t batch, double eps, int32_t capacity, double* out_x, double* out_value, int32_t* out_evals,
+                        int32_t* out_iters, uint32_t* out_flags, double* out_trace);
+/* the same for the mean over S fitted GPs (distinct handles): the points are scaled with every sample's length scales and
+ * solved against its factor.  S = 1 is robo_acq_direct bit for bit.                                                          */
+int32_t robo_acq_direct_marginal(robo_gp* const* gps, int32_t S, int32_t acq_kind, double par, const double* etas,
+                                 int32_t max_evals, int32_t max_iters, int32_t batch, double eps, int32_t capacity,
+                                 double* out_x, double* out_value, int32_t* out_evals, int32_t* out_iters,
+                                 uint32_t* out_flags, double* out_trace);
+
 /* ---- entropy search's representer points: the ensemble sampler's whole run on the device (the reference drives emcee from
  * the host around one acquisition value per walker, robo/acquisition_functions/information_gain.py:132-151).  One chain of
  * n_walkers (k, even, >= 2 dim) walkers in the CALLER's input space samples exp(acquisition) of the fitted gp inside the box

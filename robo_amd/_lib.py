@@ -64,6 +64,7 @@ SYMBOLS = [
     "robo_acq_screen_bounds",
     "robo_acq_refine_cand", "robo_acq_refine_marginal_cand",
     "robo_acq_cmaes_cand", "robo_acq_cmaes_marginal_cand",
+    "robo_acq_direct", "robo_acq_direct_marginal",
     "robo_rep_sample", "robo_rep_sample_batch",
     "robo_acq_batch_cand", "robo_acq_batch_marginal_cand", "robo_qei_batch_cand", "robo_qei_batch_marginal_cand",
     "robo_mes_eval_cand", "robo_mes_eval_marginal_cand", "robo_mes_sample_min_moments", "robo_mes_eval_moments",
@@ -251,6 +252,10 @@ def lib():
                                 C.POINTER(C.c_uint32), _dp],
         "robo_acq_cmaes_marginal_cand": [pp, i32, i32, dbl, _dp, vp, i32, i32, i32, dbl, dbl, i32, _dp, C.c_uint64, _dp, _dp,
                                          C.POINTER(i32), C.POINTER(C.c_uint32), _dp],
+        "robo_acq_direct": [vp, i32, dbl, dbl, i32, i32, i32, dbl, i32, _dp, _dp, C.POINTER(i32), C.POINTER(i32),
+                            C.POINTER(C.c_uint32), _dp],
+        "robo_acq_direct_marginal": [pp, i32, i32, dbl, _dp, i32, i32, i32, dbl, i32, _dp, _dp, C.POINTER(i32), C.POINTER(i32),
+                                     C.POINTER(C.c_uint32), _dp],
         "robo_rep_sample": [vp, i32, dbl, dbl, _dp, _dp, i32, i32, i32, dbl, _dp, C.POINTER(i32), _dp, _dp, _dp, i32,
                             C.POINTER(i64), C.POINTER(C.c_uint32), _dp],
         "robo_rep_sample_batch": [pp, i32, i32, dbl, _dp, _dp, _dp, i32, i32, i32, dbl, _dp, C.POINTER(i32), _dp, _dp, _dp,
@@ -1004,6 +1009,10 @@ class DeviceGP(object):
         """sweep over ``cand`` + lock-step CMA-ES instances from its best rows on the device (robo_acq_cmaes_cand)
         -> CMAESResult; see :func:`cmaes_marginal`"""
         return cmaes_marginal([self], kind, par, eta, cand, n_instances, popsize, n_generations, sigma0, marginal=False, **how)
+
+    def direct(self, kind, par, eta, max_evals=400, max_iters=200, **how):
+        """DIRECT over the box [0, 1]^D on the device (robo_acq_direct) -> DirectResult; see :func:`direct_marginal`"""
+        return direct_marginal([self], kind, par, eta, max_evals, max_iters, marginal=False, **how)
 
     def select_batch(self, kind, par, eta, cand, q, fantasy="kriging_believer", liar=0.0, diagnostics=False):
         """q greedy picks from ``cand`` with fantasised observations in between (robo_acq_batch_cand) -> BatchResult;
@@ -1812,6 +1821,51 @@ def cmaes_marginal(gps, kind, par, eta, cand, n_instances=1, popsize=None, n_gen
              float(sigma_min), int(eig_every), None if z is None else _arr(z), int(seed), _arr(x), C.byref(value),
              C.byref(inst), C.byref(flags), _arr(raw) if want else None))
     return CMAESResult(x, value.value, inst.value, flags.value, cmaes_trace_views(raw, D, L) if want else None)
+
+
+DIRECT_LMAX = 24                                 # robo_acq_direct*: trisections per dimension (ROBO_DIRECT_LMAX)
+DIRECT_STOP_BUDGET, DIRECT_STOP_ITERS, DIRECT_STOP_CAPACITY, DIRECT_STOP_NOTHING, DIRECT_DEFERRED = \
+    0x100, 0x200, 0x400, 0x800, 0x1000
+
+
+class DirectResult(object):
+    """x (D,) in the GP's normalised input space, value, evals (= rectangles made), iters (iterations that divided), flags
+    (DIRECT_STOP_* | DIRECT_DEFERRED | FLAG_*); with diagnostics the trace as a dict: per enqueued iteration t (row 0: the
+    centre) ran, n_po, n_slots, n_before, evals, fmin, best, flags (T + 1,), po (T + 1, B / 2), x (T + 1, B, D), values
+    (T + 1, B); the store centres (capacity, D), levels (capacity, D), f (capacity,) (include/robo_hip.h)"""
+
+    def __init__(self, x, value, evals, iters, flags, trace=None):
+        self.x, self.value, self.evals, self.iters, self.flags, self.trace = x, float(value), int(evals), int(iters), int(flags), trace
+
+
+def direct_default_batch(dim):
+    return (16 * int(dim) + 63) // 64 * 64
+
+
+def direct_marginal(gps, kind, par, eta, max_evals=400, max_iters=200, batch=None, eps=1e-4, capacity=0, diagnostics=False,
+                    marginal=True):
+    """the DIRECT maximiser of a closed-form acquisition over device GPs (one: robo_acq_direct; the mean over several
+    hyper-parameter samples: robo_acq_direct_marginal).  eta: one incumbent value, or one per sample.  batch None:
+    16 D rounded up to a multiple of 64 rows per posterior batch.  capacity 0: max_evals + batch rectangles."""
+    D = gps[0].dim
+    B = direct_default_batch(D) if batch is None else int(batch)
+    E, T, cap = int(max_evals), min(int(max_iters), int(max_evals) // 2), int(capacity)
+    x = np.empty(D)
+    value, evals, iters, flags = C.c_double(0), C.c_int32(0), C.c_int32(0), C.c_uint32(0)
+    rows = cap if cap != 0 else E + B
+    want = bool(diagnostics) and 1 <= D <= 64 and 2 * D <= B <= 16384 and B % 2 == 0 and E >= 1 and T >= 0 and 1 <= rows <= 1 << 24
+    W = 8 + B // 2 + B * D + B
+    raw = np.empty((T + 1) * W + rows * (2 * D + 1)) if want else None
+    fn = lib().robo_acq_direct_marginal if marginal else lib().robo_acq_direct
+    check(fn(*_ensemble_head(gps, eta, marginal, ACQ_KINDS[kind], float(par)), E, int(max_iters), B, float(eps), cap, _arr(x),
+             C.byref(value), C.byref(evals), C.byref(iters), C.byref(flags), _arr(raw) if want else None))
+    trace = None
+    if want:
+        it, store = raw[:(T + 1) * W].reshape(T + 1, W), raw[(T + 1) * W:].reshape(rows, 2 * D + 1)
+        trace = dict(zip(("ran", "n_po", "n_slots", "n_before", "evals", "fmin", "best", "flags"), it[:, :8].T))
+        trace.update(po=it[:, 8:8 + B // 2], x=it[:, 8 + B // 2:W - B].reshape(T + 1, B, D), values=it[:, W - B:],
+                     centres=store[:, :D], levels=store[:, D:2 * D], f=store[:, 2 * D])
+    return DirectResult(x, value.value, evals.value, iters.value, flags.value, trace)
 
 
 def _refine_call(fn, head, cand, n_starts, n_steps, step0, diagnostics):

@@ -59,6 +59,10 @@ class BaseAcquisitionFunction(object):
         raise TypeError("%s has no moments-only value for the device's CMA-ES: cmaes() is available for EI, LogEI, PI and LCB "
                         "over a robo_amd GaussianProcess (or MarginalizationGPMCMC over them)" % self.__class__.__name__)
 
+    def direct(self, n_func_evals=400, n_iters=200, eps=1e-4, batch=None):
+        """DIRECT maximiser on the device: EI / LogEI / PI / LCB over robo_amd GP models only."""
+        raise TypeError("%s has no moments-only value for the device's DIRECT: direct() is available for EI, LogEI, PI and LCB "
+                        "over a robo_amd GaussianProcess (or MarginalizationGPMCMC over them)" % self.__class__.__name__)
 
     def select_batch(self, X, q, fantasy="kriging_believer", liar=None, diagnostics=False):
         """Greedy batch of q proposals with fantasised picks: EI / LogEI / PI / LCB over robo_amd GP models only."""
@@ -146,6 +150,17 @@ def refine_finish(acq, kind, model, res, cand, keep="last_refine"):
             raise ValueError
     lower, upper = np.asarray(model.lower, dtype=np.float64), np.asarray(model.upper, dtype=np.float64)
     return lower + (upper - lower) * x
+
+
+def direct_finish(acq, kind, model, res):
+    """shared tail of the direct() methods: there is no candidate batch to collapse to, so a floored variance leaves the
+    point as it is; a negative EI raises as everywhere else; the point in the caller's input space"""
+    acq.last_direct = res
+    acq.last_max = res.value
+    if kind == "ei" and res.flags & _lib.FLAG_NEGATIVE_EI:
+        raise ValueError
+    lower, upper = np.asarray(model.lower, dtype=np.float64), np.asarray(model.upper, dtype=np.float64)
+    return lower + (upper - lower) * res.x
 
 
 @contextlib.contextmanager
@@ -364,6 +379,17 @@ class ClosedFormAcquisition(BaseAcquisitionFunction):
             res = model.gp.cmaes(self.kind, self.par, self._eta(eta), cand, n_instances, popsize, n_generations, sigma0,
                                  seed=seed, **how)
             return refine_finish(self, self.kind, model, res, cand, "last_cmaes")
+
+    def direct(self, n_func_evals=400, n_iters=200, eps=1e-4, batch=None, eta=None, **how):
+        """The maximiser found by DIRECT on the device (robo_acq_direct): Jones' DIviding RECTangles over the model's
+        normalised box, ``n_func_evals`` values in at most ``n_iters`` iterations, ``batch`` posterior rows per iteration
+        (None: 16 D rounded up to 64) -> the best centre, in the caller's input space.  Deterministic: no draws, no
+        starting points.  ``last_direct`` keeps the library's result."""
+        model = self.model
+        refine_model_check(model, self.__class__.__name__, "direct")
+        model._materialise()
+        res = model.gp.direct(self.kind, self.par, self._eta(eta), n_func_evals, n_iters, eps=eps, batch=batch, **how)
+        return direct_finish(self, self.kind, model, res)
 
     def select_batch(self, X, q, fantasy="kriging_believer", liar=None, diagnostics=False, eta=None, *, n_mc=128, z=None,
                      rng=None):

@@ -515,6 +515,27 @@ class MarginalizationGPMCMC(BaseAcquisitionFunction):
                                       seed=seed, **how)
             return refine_finish(self, est[0].kind, m0, res, cand, "last_cmaes")
 
+    def direct(self, n_func_evals=400, n_iters=200, eps=1e-4, batch=None, **how):
+        """DIRECT maximiser of the marginalised acquisition on the device (robo_acq_direct_marginal): as
+        ClosedFormAcquisition.direct, the values averaged over the hyper-parameter samples in sample order."""
+        from robo_amd.acquisition_functions.base_acquisition import direct_finish, refine_model_check
+        if not isinstance(self.acquisition_func, ClosedFormAcquisition) or not self.estimators:
+            raise TypeError("MarginalizationGPMCMC.direct is available for EI, LogEI, PI and LCB only (got %s)"
+                            % type(self.acquisition_func).__name__)
+        if getattr(self.model, "devices", None) or self._shard() is not None:
+            raise NotImplementedError("MarginalizationGPMCMC.direct runs on one device; multi-device and multi-process "
+                                      "sharding of it is not implemented")
+        for e in self.estimators:
+            refine_model_check(e.model, "MarginalizationGPMCMC", "direct")
+            e.model._materialise()
+        est = self.estimators
+        gps = [e.model.gp for e in est]
+        if len({id(g.ctx) for g in gps}) != 1:
+            raise NotImplementedError("MarginalizationGPMCMC.direct: the sub-models live on several contexts")
+        eta = np.array([e._eta(None) for e in est])
+        res = _lib.direct_marginal(gps, est[0].kind, est[0].par, eta, n_func_evals, n_iters, eps=eps, batch=batch, **how)
+        return direct_finish(self, est[0].kind, est[0].model, res)
+
     def select_batch(self, X_test, q, fantasy="kriging_believer", liar=None, diagnostics=False, *, n_mc=128, z=None,
                      rng=None):
         """Greedy batch of q proposals under the marginalised acquisition (robo_acq_batch_marginal_cand): as

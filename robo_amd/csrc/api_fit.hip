@@ -65,6 +65,7 @@ int32_t robo_gp_destroy(robo_gp* g) {
     mes_free(g->mes);
     rep_free(g->rep);
     cma_free(g->cma);
+    dir_free(g->dir);
     hyper_free(g->hyper);
     hipFree(g->d_X);
     hipFree(g->d_Xs);

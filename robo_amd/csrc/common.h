@@ -510,6 +510,49 @@ int launch_cma_ask(robo_ctx* ctx, const CmaState& st, int g);
 int launch_cma_tell(robo_ctx* ctx, const CmaState& st, int g);
 int launch_cma_result(robo_ctx* ctx, const CmaState& st, unsigned* d_cand_flags);
 
+// ---- DIRECT over an acquisition (direct.hip, api_direct.hip) -------------------------------------------------------------------
+constexpr int DIR_MAX_DIM = 64;
+constexpr int DIR_LMAX = ROBO_DIRECT_LMAX;
+constexpr int DIR_NCLS_MAX = DIR_LMAX * DIR_MAX_DIM + 1;      // classes s = k D + p, k <= LMAX (p = 0 at k = LMAX)
+constexpr int DIR_CHUNK = 1024;     // rectangles per workgroup of the class-minima reduction (4 per lane)
+// the words of DirState::hdr
+enum DirHdr { DIR_N_RECT = 0, DIR_EVALS, DIR_ITERS, DIR_STOP, DIR_N_BEFORE, DIR_N_SLOTS, DIR_N_PO, DIR_BEST, DIR_HDR_WORDS };
+// the state of one call; all arrays device memory of one block.  The store is rectangle-major: a rectangle's centre is one
+// contiguous row (the emit kernel reads it, the divide kernel writes the children's, with consecutive lanes on consecutive d)
+struct DirState {
+    int D, S, kind, B, cap, T, max_evals, n_cls;       // n_cls = LMAX D + 1
+    long long m_pad;                // rows of a model's candidate handle (rows beyond the used slots replicate row 0)
+    double par, eps;
+    double* c;                      // [cap][D] centres
+    double* f;                      // [cap] values
+    double* x;                      // [B][D] the pending batch, unscaled
+    double* fbest;                  // [2]: fmin as the last merge found it, spare
+    double* out;                    // [D + 4]: point, value, evals, iters, flags
+    const double *dsz, *delta;      // [n_cls] sizes, [LMAX + 2] steps
+    unsigned long long* part_key;   // [G][n_cls] ordered keys of the workgroups' class minima
+    int* part_idx;                  // [G][n_cls] ... their rectangles (INT_MAX: empty)
+    int* cls;                       // [cap] size class of every rectangle
+    int *po_rect, *po_off;          // [B / 2] the iteration's taken rectangles and their first slots
+    int* hdr;                       // [DIR_HDR_WORDS]
+    unsigned* flags;                // ROBO_FLAG_* of the values
+    const CmaModel* model;          // [S]
+    unsigned char* lev;             // [cap][D] levels
+    double* trace;                  // [T + 1][dir_trace_row(D, B)] + [cap][2 D + 1], or nullptr
+};
+__host__ __device__ inline size_t dir_trace_row(int D, int B) { return (size_t)8 + B / 2 + (size_t)B * D + B; }
+struct DirWork {
+    size_t bytes;                   // of d_block (dev_grow: grows, never shrinks)
+    char* d_block;                  // laid out anew by every call (dir_core's BlockLayout)
+    double* d_trace;
+    size_t trace_cap;               // doubles
+};
+void dir_free(DirWork* w);
+int launch_dir_init(robo_ctx* ctx, const DirState& st);
+int launch_dir_classmin(robo_ctx* ctx, const DirState& st, int force);
+int launch_dir_select(robo_ctx* ctx, const DirState& st, int t);
+int launch_dir_divide(robo_ctx* ctx, const DirState& st, int t);
+int launch_dir_result(robo_ctx* ctx, const DirState& st);
+
 // ---- multi-start MAP optimisation of the hyper-parameters (hyperopt.hip) ------------------------------------------------------
 constexpr int HYPER_MAX_STARTS = 64, HYPER_MAX_HISTORY = 16;
 // everything a start carries between two launches; all arrays [K], [K][P] or [K][hist][P], device memory of one block
@@ -672,6 +715,7 @@ struct robo_gp {
     robo::RepWork* rep;             // state of robo_rep_sample* (represent.hip), kept with gps[0] between calls
     robo::HyperWork* hyper;         // workspace of robo_gp_grad_loglik_batch / robo_gp_optimize_hypers (hyperopt.hip)
     robo::CmaWork* cma;             // state of robo_acq_cmaes_* (cmaes.hip), kept with gps[0] between calls
+    robo::DirWork* dir;             // state of robo_acq_direct* (direct.hip), kept with gps[0] between calls
     // the acquisition screen (screen.hip), lazy: [scratch (n_pad_max) | alpha = L^-T z (n_pad_max) | sum_j |alpha_j| sqrt(k_jj),
     // then, for the kinds and D the dot-form bounds kernel takes, its per-fit inputs (screen.hip "The dot form")]
     double* d_alpha;

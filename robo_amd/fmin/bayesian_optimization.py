@@ -14,6 +14,7 @@ without george, pybnn and pyrfr: :2,5,8,11), wired to the MI355X GP path:
     maximiser RandomSampling | SciPyOptimizer | DifferentialEvolution                    (:131-139)
               | DeviceRandomSampling | DeviceGradientAscent (not in the reference)
               | CMAES (the reference's fabolas / entropy_search front ends take it; here it runs on the device)
+              | Direct (the reference's robo/maximizers/direct.py; here Jones' rule runs on the device)
 
 The model type rf is outside this project's hot path.  DNGO and BOHAMIANN are device models
 (models/dngo.py, models/bohamiann.py) but not model_types of this front end: build them and drive an acquisition and a
@@ -27,8 +28,8 @@ from robo_amd.acquisition_functions import (EI, LCB, MES, PI, KnowledgeGradient,
                                             ThompsonSampling)
 from robo_amd.initial_design import init_latin_hypercube_sampling
 from robo_amd.kernels import Matern52Kernel
-from robo_amd.maximizers import (CMAES, DeviceGradientAscent, DeviceRandomSampling, DifferentialEvolution, RandomSampling,
-                                 SciPyOptimizer)
+from robo_amd.maximizers import (CMAES, DeviceGradientAscent, DeviceRandomSampling, DifferentialEvolution, Direct,
+                                 RandomSampling, SciPyOptimizer)
 from robo_amd.models import GaussianProcess, GaussianProcessMCMC
 from robo_amd.models.bayesian_linear_regression import BayesianLinearRegression, quadratic_basis_func
 from robo_amd.priors import DefaultPrior
@@ -66,6 +67,10 @@ def bayesian_optimization(objective_function, lower, upper, num_iterations=30, X
     the ensemble sampler (``chain_length``, ``burnin_steps``, 20 walkers).  ``acquisition_func`` is one of ei / log_ei / pi
     / lcb and ``maximizer`` a host one; every maximisation over a candidate batch is one fused device call
     (robo_blr_acq_eval_cand).  One device, ``batch_size=1``.
+
+    ``maximizer="direct"``: Jones' DIviding RECTangles over the whole box on the device (maximizers/direct.py) with the
+    reference's budget of 400 values in at most 200 iterations.  It draws nothing and starts nowhere: ``n_candidates`` is
+    unused and the same model gives the same proposal.  ei / log_ei / pi / lcb over ``gp`` or ``gp_mcmc``, one device.
 
     ``fantasy="joint"`` (``acquisition_func="ei"`` only): the proposals of a round are picked by joint Monte-Carlo batch
     EI over ``n_mc`` scenarios drawn from this call's rng (``EI.select_batch``); ``liar`` is ignored.  Any other
@@ -137,12 +142,16 @@ def bayesian_optimization(objective_function, lower, upper, num_iterations=30, X
     elif maximizer == "cmaes":
         # the same candidates; the best of them starts a CMA-ES instance on the device (n_candidates = sweep size)
         max_func = CMAES(acq, lower, upper, verbose=False, n_samples=n_candidates, rng=rng)
+    elif maximizer == "direct":
+        # no candidates and no draws: DIviding RECTangles over the whole box on the device, the reference's budget
+        max_func = Direct(acq, lower, upper, verbose=False, rng=rng)
     elif maximizer == "scipy":
         max_func = SciPyOptimizer(acq, lower, upper, rng=rng)
     elif maximizer == "differential_evolution":
         max_func = DifferentialEvolution(acq, lower, upper, rng=rng)
     else:
-        raise ValueError("'{}' is not a valid function to maximize the acquisition function".format(maximizer))
+        raise ValueError("'{}' is not a valid function to maximize the acquisition function (random, device_random, "
+                         "device_gradient, cmaes, direct, scipy, differential_evolution)".format(maximizer))
 
     # batch_size > 1: rounds of batch_size proposals from one model fit (greedy selection with fantasised picks on the
     # device), evaluated one by one or by evaluate_batch(Xq) -> yq; batch_size = 1 is the reference's loop, untouched
