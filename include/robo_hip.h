@@ -1205,6 +1205,69 @@ int32_t robo_bnn_predict(robo_bnn* bnn, const double* rows /* m x dim */, int64_
 int32_t robo_bnn_acq_eval_cand(robo_bnn* bnn, int32_t acq_kind, double par, double eta, const double* rows, int64_t m,
                                double* out_acq /* nullable */, double* out_max, int64_t* out_argmax, uint32_t* out_flags);
 
+/* ---- a regression forest grown and swept on the device (robo/models/random_forest.py, whose trees come from pyrfr; the rule
+ * below is the library's own).
+ *   Data.       Rows X (n x dim), targets y (n); 1 <= n <= ROBO_RF_MAX_N, 1 <= dim <= 64, 1 <= n_trees <= ROBO_RF_MAX_TREES.
+ *               ybar = (sum of y in index order) / n, y_c = y - ybar.
+ *   Weights.    With bootstrapping tree t makes n_points (1 .. 2^20) draws r_j = min(floor(u_j n), n - 1) and w_i counts them;
+ *               u_j is the first 53-bit uniform of Philox-4x32-10 under the key `seed` on the counter (j, 0, t, 0x52460000), or
+ *               r_j = idx[t n_points + j] from the caller (idx nullable).  Without bootstrapping every w_i = 1.  Rows of weight
+ *               0 take no part in the tree.
+ *   Nodes.      A tree's nodes are numbered level by level, the root 0, the children of a level's splitting nodes in node
+ *               order, left = right - 1.  A node is a leaf if its weight W = sum w < min_samples_split, its depth (root 0)
+ *               has reached max_depth, its variance <= eps_purity, or no admissible split exists.
+ *   Splits.     The candidate features are all dim, or max_features of them drawn without replacement by a partial
+ *               Fisher-Yates shuffle of (0 .. dim - 1): step i swaps entry i with entry min(i + floor(u (dim - i)), dim - 1),
+ *               u from the counter (node, i, t, 0x52460001); the first max_features entries are the candidates (the node's
+ *               mask; 0 for a node that the first three rules stop).  Along a candidate feature the node's rows stand in
+ *               ascending order of (value, row index, -0 as +0); a split may sit behind position p if the values at p and
+ *               p + 1 differ and both sides weigh at least min_samples_leaf.  Its score is S_L^2 / W_L + S_R^2 / W_R with
+ *               S_L = sum w y_c over positions <= p, S_R = S - S_L, S the node's sum along feature 0's order.  The best score
+ *               wins; ties go to the lower feature, then the lower position.  threshold = 0.5 a + 0.5 b of the two values,
+ *               replaced by a unless a <= threshold < b; a row goes left iff x_f <= threshold.
+ *   Statistics. Every node: weight W, mean = S / W + ybar, var = sum w (y_c - S / W)^2 / W, the sums in feature 0's order.
+ *   Order.      One workgroup per tree; every sum is a segmented scan over the node's rows in a feature's order, whose
+ *               combination tree is fixed by the positions in the tree's list.  No atomics on doubles: a tree's bits depend
+ *               on (data, options, seed, t) alone -- not on n_trees, the device or the call.
+ *   Prediction. The leaf (mu_t, v_t) of every tree in tree order; mean and M2 by Welford's update (d = mu_t - mean;
+ *               mean <- mean + d / (t + 1); M2 <- M2 + d (mu_t - mean)); var = M2 / T, plus (total_variance) (sum v_t) / T,
+ *               clipped at eps from below as robo_blr_predict clips it.  A candidate's bits do not depend on its position, on
+ *               m or on the other candidates.  A NaN coordinate gives NaN (also in out_per_tree).
+ * robo_rf_fit: launches only (the presort, the trees), one synchronisation.  robo_rf_get_trees: out_counts (T) the nodes of
+ * every tree, out_stride the nodes' stride, out_nodes (T x stride, nullable).  robo_rf_set_trees installs node tables (a
+ * restored model): every count in 1 .. stride, stride <= 2 ROBO_RF_MAX_N - 1, a feature in -1 .. dim - 1, children of a
+ * split behind their parent and inside the tree, finite threshold, mean and var.  robo_rf_acq_eval_cand is the sweep followed
+ * by robo_acq_eval_moments' kernels on the device-resident moments: the same values, argmax rule and flags, one
+ * synchronisation.  out_per_tree (nullable): T x m leaf means.
+ * A shape or an option out of range (max_features outside 1 .. dim, min_samples_split < 1, min_samples_leaf < 1, max_depth < 0,
+ * eps_purity negative or not finite), non-finite rows or targets, a draw outside 0 .. n - 1, m < 1, a NULL required pointer:
+ * ROBO_BAD_ARGUMENT, decided before anything is launched.  A sweep or robo_rf_get_trees before robo_rf_fit / robo_rf_set_trees:
+ * ROBO_NOT_FITTED.  Event slots: 30 -> 31 around the fit's kernels (phase events on) and around the sweep kernel under the
+ * condition of slots 24..27.  robo_rf_destroy(NULL) is harmless.                                                            */
+#define ROBO_RF_MAX_N 4096
+#define ROBO_RF_MAX_TREES 128
+#define ROBO_RF_MAX_DIM 64
+typedef struct robo_rf robo_rf;
+typedef struct robo_rf_node {
+    double threshold, mean, var, weight;
+    uint64_t mask;                     /* the candidate features of the split search, bit f = feature f */
+    int32_t feature /* -1: a leaf */, left, right /* -1 in a leaf */, depth;
+} robo_rf_node;
+int32_t robo_rf_create(robo_ctx* ctx, int32_t dim, int32_t n_trees, int32_t do_bootstrapping, int32_t max_features,
+                       int32_t min_samples_split, int32_t min_samples_leaf, int32_t max_depth, double eps_purity,
+                       int32_t total_variance, robo_rf** out);
+int32_t robo_rf_destroy(robo_rf* rf);
+int32_t robo_rf_fit(robo_rf* rf, const double* rows /* n x dim */, const double* y /* n */, int64_t n, int32_t n_points,
+                    uint64_t seed, const int32_t* idx /* n_trees x n_points, nullable */);
+int32_t robo_rf_get_trees(robo_rf* rf, int32_t* out_counts /* n_trees */, int32_t* out_stride,
+                          robo_rf_node* out_nodes /* n_trees x stride, nullable */);
+int32_t robo_rf_set_trees(robo_rf* rf, const int32_t* counts /* n_trees */, int32_t stride,
+                          const robo_rf_node* nodes /* n_trees x stride */);
+int32_t robo_rf_predict(robo_rf* rf, const double* rows /* m x dim */, int64_t m, double* out_mean, double* out_var,
+                        double* out_per_tree /* nullable */);
+int32_t robo_rf_acq_eval_cand(robo_rf* rf, int32_t acq_kind, double par, double eta, const double* rows, int64_t m,
+                              double* out_acq /* nullable */, double* out_max, int64_t* out_argmax, uint32_t* out_flags);
+
 /* ---- entropy search: replaces InformationGain.innovations/_dh_fun/compute ---------------
  * (robo/acquisition_functions/information_gain.py:87-125,169-203,253-272), batched over candidates.
  * rep: the Nb <= 64 representer points as a candidate batch (same normalised space).  The EP

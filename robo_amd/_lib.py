@@ -38,6 +38,8 @@ BLR_FEATURE_KINDS = {"given": 0, "linear": 1, "quadratic": 2, "rff": 3, "mlp": 4
 BLR_MAX_FEATURES, BLR_MAX_DIM, BLR_MAX_SAMPLES = 128, 64, 64
 MLP_MAX_DIM, MLP_MAX_WIDTH, MLP_MAX_LAYERS = 64, 64, 3                     # robo_mlp_create
 BNN_MAX_CHAINS, BNN_MAX_BATCH, BNN_MAX_SAMPLES = 64, 64, 512               # robo_bnn_create, robo_bnn_run, the sample table
+RF_MAX_N, RF_MAX_TREES, RF_MAX_DIM = 4096, 128, 64                        # robo_rf_create, robo_rf_fit
+RF_STAGE_NODES = 768                          # a tree of at most this many nodes is walked in LDS by the forest's sweep
 BLR_CHUNK, BLR_TILE = 1024, 64                # rows per workgroup of the statistics kernel; candidates per workgroup of the sweep
 PATHS_MAX = 64                                   # robo_paths_*: cap on the sample paths of one object
 PATHS_MAX_FEATURES = 4096                        # ... and on its random Fourier features
@@ -78,6 +80,8 @@ SYMBOLS = [
     "robo_bnn_create", "robo_bnn_destroy", "robo_bnn_param_count", "robo_bnn_set_state", "robo_bnn_run",
     "robo_bnn_get_samples", "robo_bnn_set_samples", "robo_bnn_set_output_transform", "robo_bnn_predict",
     "robo_bnn_acq_eval_cand",
+    "robo_rf_create", "robo_rf_destroy", "robo_rf_fit", "robo_rf_get_trees", "robo_rf_set_trees", "robo_rf_predict",
+    "robo_rf_acq_eval_cand",
     "robo_paths_create", "robo_paths_eval_cand", "robo_paths_destroy", "robo_paths_descend", "robo_paths_refine_cand",
     "robo_ig_eval_cand", "robo_ig_eval_per_cost_cand", "robo_ig_eval_moments", "robo_gp_cross_cov",
     "robo_ep_joint_min", "robo_pmin_mc", "robo_igmc_eval_cand", "robo_igmc_eval_moments",
@@ -317,6 +321,13 @@ def lib():
         "robo_bnn_set_output_transform": [vp, dbl, dbl, i32],
         "robo_bnn_predict": [vp, _dp, i64, _dp, _dp, _dp],
         "robo_bnn_acq_eval_cand": [vp, i32, dbl, dbl, _dp, i64, _dp, _dp, C.POINTER(i64), C.POINTER(C.c_uint32)],
+        "robo_rf_create": [vp, i32, i32, i32, i32, i32, i32, i32, dbl, i32, pp],
+        "robo_rf_destroy": [vp],
+        "robo_rf_fit": [vp, _dp, _dp, i64, i32, C.c_uint64, C.POINTER(i32)],
+        "robo_rf_get_trees": [vp, C.POINTER(i32), C.POINTER(i32), vp],
+        "robo_rf_set_trees": [vp, C.POINTER(i32), i32, vp],
+        "robo_rf_predict": [vp, _dp, i64, _dp, _dp, _dp],
+        "robo_rf_acq_eval_cand": [vp, i32, dbl, dbl, _dp, i64, _dp, _dp, C.POINTER(i64), C.POINTER(C.c_uint32)],
         "robo_paths_create": [vp, i32, i32, _dp, _dp, _dp, _dp, pp],
         "robo_paths_eval_cand": [vp, vp, _dp, _dp, C.POINTER(i64), C.POINTER(C.c_uint32)],
         "robo_paths_destroy": [vp],
@@ -1584,6 +1595,94 @@ class DeviceBNN(object):
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
             self._owner.robo_bnn_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# robo_rf_node (include/robo_hip.h) as a NumPy record
+RF_NODE = np.dtype([("threshold", "f8"), ("mean", "f8"), ("var", "f8"), ("weight", "f8"), ("mask", "u8"), ("feature", "i4"),
+                    ("left", "i4"), ("right", "i4"), ("depth", "i4")])
+
+
+class DeviceForest(object):
+    """robo_rf: ``n_trees`` regression trees grown on the device, one workgroup each, and the sweep of candidates through them
+    (include/robo_hip.h)."""
+
+    def __init__(self, ctx, dim, n_trees=30, do_bootstrapping=True, max_features=None, min_samples_split=2, min_samples_leaf=1,
+                 max_depth=2048, eps_purity=1e-8, total_variance=True):
+        self._h = None
+        self.ctx, self.dim, self.n_trees = ctx, int(dim), int(n_trees)
+        self._owner = lib()
+        h = C.c_void_p()
+        check(self._owner.robo_rf_create(ctx._h, self.dim, self.n_trees, int(bool(do_bootstrapping)),
+                                         self.dim if max_features is None else int(max_features), int(min_samples_split),
+                                         int(min_samples_leaf), int(max_depth), float(eps_purity), int(bool(total_variance)),
+                                         C.byref(h)))
+        self._h = h
+
+    def _rows(self, rows):
+        rows = _f64(rows)
+        if rows.ndim != 2 or rows.shape[1] != self.dim:
+            raise RoboBadShape("rows must be (n, %d), got %r" % (self.dim, rows.shape))
+        return rows
+
+    def fit(self, rows, y, n_points=0, seed=0, idx=None):
+        """n_points = 0: as many draws as rows.  idx (n_trees, n_points): the bootstrap draws, instead of the device's own"""
+        rows = self._rows(rows)
+        y = _f64(y, (rows.shape[0],))
+        n_points = int(n_points) or rows.shape[0]
+        if idx is not None:
+            idx = np.ascontiguousarray(idx, dtype=np.int32)
+            if idx.shape != (self.n_trees, n_points):
+                raise RoboBadShape("idx must be (%d, %d), got %r" % (self.n_trees, n_points, idx.shape))
+        check(lib().robo_rf_fit(self._h, _arr(rows), _arr(y), rows.shape[0], n_points, int(seed),
+                                idx.ctypes.data_as(C.POINTER(C.c_int32)) if idx is not None else None))
+
+    @property
+    def trees(self):
+        """-> a list of n_trees record arrays of dtype RF_NODE, a tree's nodes in level order"""
+        counts, stride = np.zeros(self.n_trees, dtype=np.int32), C.c_int32(0)
+        i32p = C.POINTER(C.c_int32)
+        check(lib().robo_rf_get_trees(self._h, counts.ctypes.data_as(i32p), C.byref(stride), None))
+        nodes = np.zeros((self.n_trees, stride.value), dtype=RF_NODE)
+        check(lib().robo_rf_get_trees(self._h, counts.ctypes.data_as(i32p), C.byref(stride), nodes.ctypes.data))
+        return [nodes[t, :counts[t]].copy() for t in range(self.n_trees)]
+
+    def set_trees(self, trees):
+        if len(trees) != self.n_trees:
+            raise RoboBadShape("%d trees, the forest has %d" % (len(trees), self.n_trees))
+        counts = np.array([len(tr) for tr in trees], dtype=np.int32)
+        nodes = np.zeros((self.n_trees, max(int(counts.max()), 1)), dtype=RF_NODE)
+        for t, tr in enumerate(trees):
+            nodes[t, :counts[t]] = tr
+        check(lib().robo_rf_set_trees(self._h, counts.ctypes.data_as(C.POINTER(C.c_int32)), nodes.shape[1], nodes.ctypes.data))
+
+    def predict(self, rows, per_tree=False):
+        """-> (mean, var) [, every tree's leaf mean (n_trees, m)]"""
+        rows = self._rows(rows)
+        m = rows.shape[0]
+        mean, var = np.empty(m), np.empty(m)
+        pt = np.empty((self.n_trees, m)) if per_tree else None
+        check(lib().robo_rf_predict(self._h, _arr(rows), m, _arr(mean), _arr(var), _arr(pt) if per_tree else None))
+        return (mean, var, pt) if per_tree else (mean, var)
+
+    def acq(self, kind, par, eta, rows, want_values=True):
+        """sweep + closed-form acquisition + argmax in one call (robo_rf_acq_eval_cand) -> (values, max, argmax, flags)"""
+        rows = self._rows(rows)
+        out = np.empty(rows.shape[0]) if want_values else None
+        best = _Best()
+        check(lib().robo_rf_acq_eval_cand(self._h, ACQ_KINDS[kind], float(par), float(eta), _arr(rows), rows.shape[0],
+                                          _arr(out) if want_values else None, *best.refs))
+        return (out,) + best.values()
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            self._owner.robo_rf_destroy(self._h)
             self._h = None
 
     def __del__(self):

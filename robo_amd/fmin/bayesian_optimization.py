@@ -16,9 +16,9 @@ without george, pybnn and pyrfr: :2,5,8,11), wired to the MI355X GP path:
               | CMAES (the reference's fabolas / entropy_search front ends take it; here it runs on the device)
               | Direct (the reference's robo/maximizers/direct.py; here Jones' rule runs on the device)
 
-The model type rf is outside this project's hot path.  DNGO and BOHAMIANN are device models
-(models/dngo.py, models/bohamiann.py) but not model_types of this front end: build them and drive an acquisition and a
-maximiser with them through robo_amd.solver.BayesianOptimization.
+DNGO, BOHAMIANN and the random forest are device models (models/dngo.py, models/bohamiann.py, models/forest.py) but not
+model_types of this front end (rf keeps raising ValueError): build them and drive an acquisition and a maximiser with them
+through robo_amd.solver.BayesianOptimization.
 """
 import logging
 
