@@ -492,6 +492,64 @@ int32_t robo_acq_cmaes_marginal_cand(robo_gp* const* gps, int32_t S, int32_t acq
                                      double* out_x, double* out_value, int32_t* out_instance, uint32_t* out_flags,
                                      double* out_trace);
 
+/* ---- Differential evolution over the acquisition (the reference's robo/maximizers/differential_evolution.py drives SciPy from
+ * the host, one 1 x dim acquisition call per function value): n_instances (R, 1 .. 64) independent populations of popsize (NP,
+ * 4 .. 1024) members run n_generations generations of `best1bin` with dithered scale, SciPy's bound repair and deferred
+ * (whole-generation) updating in lock step, maximising over the box [0, 1]^dim of the GP's normalised input space, all on the
+ * device.  1 <= dim <= 64, NP dim <= 16384, R NP <= 16384.  Every operation named below is rounded once, none is fused.
+ *   Start.    cand holds exactly R NP rows: row r NP + i is member i of instance r.  The sweep over cand runs exactly as
+ *             robo_acq_eval_cand (marginal form: robo_acq_eval_marginal_cand) and gives the start values.  The best of an
+ *             instance is its largest value, ties to the lowest member index, NaN never; every value NaN: member 0.
+ *   Draws.    Generation g, instance r, member i.  u = NULL: Philox-4x32-10 blocks under the key `seed`, each giving two
+ *             uniforms of 53 bits; counter (g, r, 0xFFFFFFFF, 0): first uniform u_F; (g, r, i, 0): (u_a, u_b); (g, r, i, 1):
+ *             first uniform u_j; (g, r, i, 2 + p): the crossover uniforms of coordinates 2 p and 2 p + 1; (g, r, i, 2^31 + p):
+ *             their repair uniforms.  Otherwise u is [n_generations][R][1 + NP (3 + 2 dim)]: u_F, then per member u_a, u_b, u_j,
+ *             dim crossover uniforms, dim repair uniforms; every entry in [0, 1).
+ *   Trial.    F = f_lo + u_F (f_hi - f_lo) (sub, mul, add).  With idx(u, n) = min(floor(u n), n - 1) (the product can round up
+ *             to n): a = idx(u_a, NP - 1), a += (a >= i);  b = idx(u_b, NP - 2), with lo < hi the two of {i, a}: b += (b >= lo),
+ *             then b += (b >= hi);  jrand = idx(u_j, dim).  Coordinate d: crossover uniform < cr or d == jrand:
+ *             t_d = best_d + F (x_a,d - x_b,d) (sub, mul, add); otherwise t_d = x_i,d.  Repair (SciPy's _ensure_constraint): a
+ *             t_d outside [0, 1] or NaN is replaced by coordinate d's repair uniform.
+ *   Values.   The posterior of all R NP trial rows as one batch per model, scaled with that model's length scales, exactly as
+ *             robo_acq_eval forms it for a batch of that size; the acquisition value with robo_acq_eval_cand's guards; marginal
+ *             form: summed in sample order, / S.
+ *   Select.   Member i takes its trial iff the trial's value is no NaN and (the member's value is NaN or trial >= member); then
+ *             the best is formed anew.
+ *   Converge. SciPy's std <= atol + tol |mean| without the square root and in a fixed order: partial j (0 .. 255) sums the
+ *             values of the members i = j (mod 256) in increasing i from 0.0, the partials are added by the tree j += j + stride
+ *             for stride = 128 .. 1; mean = sum / NP; M2 in the same shape over (v - mean)^2 (sub, mul).  The instance has
+ *             converged iff every value is finite and M2 <= NP (atol + tol |mean|)^2 (mul, add, mul, mul).  The test follows
+ *             every select (as SciPy's: not the start).  A converged instance stops: ROBO_FLAG_FROZEN is raised, its later trial rows copy its best
+ *             point and nothing of it changes.  So does an instance all of whose trial values in a generation are NaN.
+ * Result: the best member of the instance with the largest best value (first on ties, NaN never): out_x (dim), *out_value,
+ * *out_instance (-1: every value was NaN; out_x is then member 0 of instance 0), out_generations (R, nullable: the generations
+ * each instance selected, the stopping one included), *out_flags = the sweep's flags | the generations' (ZERO_SIGMA /
+ * NEGATIVE_EI / NAN of their values, FROZEN).  The result is never below the sweep's maximum; n_generations = 0 returns the
+ * sweep's argmax.  There is no polishing step.  An instance never looks at another one: with the caller's draws its
+ * trajectory does not depend on R or on its index.
+ * out_trace (nullable): [n_generations + 1][R][4 NP dim + 6 NP + 6].  Entry 0 is the start, entry g + 1 generation g: F; a, b,
+ * jrand (NP each); the trial points, the crossover and the repair masks as 0 / 1 (NP x dim each); the trial values and the
+ * accept bits (NP each); then the state AFTER the select: population (NP x dim), values (NP), best index, sum, mean, M2, code
+ * (0 ran, 1 converged here, 2 every trial value NaN here, 3 stopped earlier).  Entry 0 has zeros up to the state; an instance
+ * stopped before generation g has zeros in entry g + 1 except for its trial points, the copies of its best point.
+ * ROBO_BAD_ARGUMENT: a bad acq_kind, a limit above violated, n_generations < 0, not 0 <= f_lo <= f_hi <= 2, cr outside [0, 1],
+ * tol or atol negative or NaN, an entry of u outside [0, 1) (decided on the host before any launch), a Fabolas kernel, a model
+ * handle given twice; ROBO_NOT_FITTED: a model that is not fitted; ROBO_BAD_SHAPE: cand's dim is not the GP's, cand does not
+ * hold R NP rows, or they do not fit the solve workspace.  One synchronisation per call; the state stays with gp (gps[0]).  A
+ * generation is one launch of de_step_kernel plus the posterior's; a caller's u is uploaded up front (robo_acq_cmaes_cand's
+ * remark on pageable memory holds).                                                                                          */
+int32_t robo_acq_de_cand(robo_gp* gp, int32_t acq_kind, double par, double eta, robo_cand* cand, int32_t n_instances,
+                         int32_t popsize, int32_t n_generations, double f_lo, double f_hi, double cr, double tol, double atol,
+                         const double* u, uint64_t seed, double* out_x, double* out_value, int32_t* out_instance,
+                         int32_t* out_generations, uint32_t* out_flags, double* out_trace);
+/* the same for the mean over S fitted GPs (distinct handles; robo_acq_eval_marginal_cand's sweep): the trial rows are scaled
+ * with every sample's length scales and solved against its factor.  S = 1 is robo_acq_de_cand bit for bit.                  */
+int32_t robo_acq_de_marginal_cand(robo_gp* const* gps, int32_t S, int32_t acq_kind, double par, const double* etas,
+                                  robo_cand* cand, int32_t n_instances, int32_t popsize, int32_t n_generations, double f_lo,
+                                  double f_hi, double cr, double tol, double atol, const double* u, uint64_t seed,
+                                  double* out_x, double* out_value, int32_t* out_instance, int32_t* out_generations,
+                                  uint32_t* out_flags, double* out_trace);
+
 /* ---- DIRECT over the acquisition (the reference's robo/maximizers/direct.py drives the DIRECT package from the host, one
  * 1 x dim acquisition call per function value): Jones, Perttunen and Stuckman's DIviding RECTangles in its original form,
  * minimising f = -a over the box [0, 1]^dim of the GP's normalised input space, 1 <= dim <= 64, all on the device.  It takes

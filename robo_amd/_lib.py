@@ -66,6 +66,7 @@ SYMBOLS = [
     "robo_acq_screen_bounds",
     "robo_acq_refine_cand", "robo_acq_refine_marginal_cand",
     "robo_acq_cmaes_cand", "robo_acq_cmaes_marginal_cand",
+    "robo_acq_de_cand", "robo_acq_de_marginal_cand",
     "robo_acq_direct", "robo_acq_direct_marginal",
     "robo_rep_sample", "robo_rep_sample_batch",
     "robo_acq_batch_cand", "robo_acq_batch_marginal_cand", "robo_qei_batch_cand", "robo_qei_batch_marginal_cand",
@@ -256,6 +257,10 @@ def lib():
                                 C.POINTER(C.c_uint32), _dp],
         "robo_acq_cmaes_marginal_cand": [pp, i32, i32, dbl, _dp, vp, i32, i32, i32, dbl, dbl, i32, _dp, C.c_uint64, _dp, _dp,
                                          C.POINTER(i32), C.POINTER(C.c_uint32), _dp],
+        "robo_acq_de_cand": [vp, i32, dbl, dbl, vp, i32, i32, i32, dbl, dbl, dbl, dbl, dbl, _dp, C.c_uint64, _dp, _dp,
+                             C.POINTER(i32), C.POINTER(i32), C.POINTER(C.c_uint32), _dp],
+        "robo_acq_de_marginal_cand": [pp, i32, i32, dbl, _dp, vp, i32, i32, i32, dbl, dbl, dbl, dbl, dbl, _dp, C.c_uint64, _dp,
+                                      _dp, C.POINTER(i32), C.POINTER(i32), C.POINTER(C.c_uint32), _dp],
         "robo_acq_direct": [vp, i32, dbl, dbl, i32, i32, i32, dbl, i32, _dp, _dp, C.POINTER(i32), C.POINTER(i32),
                             C.POINTER(C.c_uint32), _dp],
         "robo_acq_direct_marginal": [pp, i32, i32, dbl, _dp, i32, i32, i32, dbl, i32, _dp, _dp, C.POINTER(i32), C.POINTER(i32),
@@ -1020,6 +1025,11 @@ class DeviceGP(object):
         """sweep over ``cand`` + lock-step CMA-ES instances from its best rows on the device (robo_acq_cmaes_cand)
         -> CMAESResult; see :func:`cmaes_marginal`"""
         return cmaes_marginal([self], kind, par, eta, cand, n_instances, popsize, n_generations, sigma0, marginal=False, **how)
+
+    def de(self, kind, par, eta, cand, n_instances=1, popsize=None, n_generations=20, **how):
+        """lock-step differential-evolution populations on the device, ``cand`` their start (robo_acq_de_cand)
+        -> DEResult; see :func:`de_marginal`"""
+        return de_marginal([self], kind, par, eta, cand, n_instances, popsize, n_generations, marginal=False, **how)
 
     def direct(self, kind, par, eta, max_evals=400, max_iters=200, **how):
         """DIRECT over the box [0, 1]^D on the device (robo_acq_direct) -> DirectResult; see :func:`direct_marginal`"""
@@ -1920,6 +1930,53 @@ def cmaes_marginal(gps, kind, par, eta, cand, n_instances=1, popsize=None, n_gen
              float(sigma_min), int(eig_every), None if z is None else _arr(z), int(seed), _arr(x), C.byref(value),
              C.byref(inst), C.byref(flags), _arr(raw) if want else None))
     return CMAESResult(x, value.value, inst.value, flags.value, cmaes_trace_views(raw, D, L) if want else None)
+
+
+class DEResult(object):
+    """x (D,) in the GP's normalised input space, value, instance (the winning population; -1: every value was NaN),
+    generations (R,) each instance selected, flags; with diagnostics the trace as a dict of views: F (T + 1, R), a, b, jrand,
+    trial_values, accept, values (T + 1, R, NP), trial, cross, repair, pop (T + 1, R, NP, D), best, sum, mean, M2, code
+    (T + 1, R); entry 0 is the start, entry g + 1 generation g with the state after its select (include/robo_hip.h)"""
+
+    def __init__(self, x, value, instance, generations, flags, trace=None):
+        self.x, self.value, self.instance, self.flags, self.trace = x, float(value), int(instance), int(flags), trace
+        self.generations = generations
+
+
+def de_default_popsize(dim):
+    """SciPy's 15 D members, within what one workgroup's LDS holds"""
+    return max(4, min(15 * int(dim), 16384 // int(dim), 1024))
+
+
+def de_marginal(gps, kind, par, eta, cand, n_instances=1, popsize=None, n_generations=20, f_lo=0.5, f_hi=1.0, cr=0.7, tol=0.01,
+                atol=0.0, u=None, seed=0, diagnostics=False, marginal=True):
+    """the differential-evolution maximiser (best1bin, dithered scale, deferred updating) of a closed-form acquisition over
+    device GPs (one: robo_acq_de_cand; the mean over several hyper-parameter samples: robo_acq_de_marginal_cand).  ``cand``
+    holds the n_instances * popsize start members, instance by instance.  eta: one incumbent value, or one per sample.
+    popsize None: min(15 D, 16384 // D, 1024).  u (n_generations, n_instances, 1 + popsize (3 + 2 D)): the uniform draws, or
+    None: Philox under ``seed``."""
+    R, T, D = int(n_instances), int(n_generations), cand.dim
+    NP = de_default_popsize(D) if popsize is None else int(popsize)
+    if u is not None:
+        u = _f64(u, (T, R, 1 + NP * (3 + 2 * D)))
+    x, gens = np.empty(D), np.zeros(max(R, 1), dtype=np.int32)
+    value, inst, flags = C.c_double(0), C.c_int32(0), C.c_uint32(0)
+    want = bool(diagnostics) and 1 <= R <= 64 and 4 <= NP <= 1024 and 1 <= D <= 64 and T >= 0
+    raw = np.empty((T + 1, R, 4 * NP * D + 6 * NP + 6)) if want else None
+    fn = lib().robo_acq_de_marginal_cand if marginal else lib().robo_acq_de_cand
+    check(fn(*_ensemble_head(gps, eta, marginal, ACQ_KINDS[kind], float(par)), cand._h, R, NP, T, float(f_lo), float(f_hi),
+             float(cr), float(tol), float(atol), None if u is None else _arr(u), int(seed), _arr(x), C.byref(value),
+             C.byref(inst), gens.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(flags), _arr(raw) if want else None))
+    trace = None
+    if want:
+        trace, at = {}, 0
+        for name, shape in (("F", ()), ("a", (NP,)), ("b", (NP,)), ("jrand", (NP,)), ("trial", (NP, D)), ("cross", (NP, D)),
+                            ("repair", (NP, D)), ("trial_values", (NP,)), ("accept", (NP,)), ("pop", (NP, D)), ("values", (NP,)),
+                            ("best", ()), ("sum", ()), ("mean", ()), ("M2", ()), ("code", ())):
+            n = int(np.prod(shape, dtype=np.int64))
+            trace[name] = raw[:, :, at:at + n].reshape((T + 1, R) + shape)
+            at += n
+    return DEResult(x, value.value, inst.value, gens[:max(R, 0)], flags.value, trace)
 
 
 DIRECT_LMAX = 24                                 # robo_acq_direct*: trisections per dimension (ROBO_DIRECT_LMAX)

@@ -59,6 +59,12 @@ class BaseAcquisitionFunction(object):
         raise TypeError("%s has no moments-only value for the device's CMA-ES: cmaes() is available for EI, LogEI, PI and LCB "
                         "over a robo_amd GaussianProcess (or MarginalizationGPMCMC over them)" % self.__class__.__name__)
 
+    def de(self, X, n_instances=1, popsize=None, n_generations=20, seed=0):
+        """Differential-evolution maximiser on the device: EI / LogEI / PI / LCB over robo_amd GP models only."""
+        raise TypeError("%s has no moments-only value for the device's differential evolution: de() is available for EI, "
+                        "LogEI, PI and LCB over a robo_amd GaussianProcess (or MarginalizationGPMCMC over them)"
+                        % self.__class__.__name__)
+
     def direct(self, n_func_evals=400, n_iters=200, eps=1e-4, batch=None):
         """DIRECT maximiser on the device: EI / LogEI / PI / LCB over robo_amd GP models only."""
         raise TypeError("%s has no moments-only value for the device's DIRECT: direct() is available for EI, LogEI, PI and LCB "
@@ -379,6 +385,18 @@ class ClosedFormAcquisition(BaseAcquisitionFunction):
             res = model.gp.cmaes(self.kind, self.par, self._eta(eta), cand, n_instances, popsize, n_generations, sigma0,
                                  seed=seed, **how)
             return refine_finish(self, self.kind, model, res, cand, "last_cmaes")
+
+    def de(self, X, n_instances=1, popsize=None, n_generations=20, seed=0, eta=None, **how):
+        """The maximiser found by differential evolution on the device (robo_acq_de_cand): the ``n_instances * popsize``
+        candidates X (as for ``refine``) are the start members of ``n_instances`` independent best1bin populations of
+        ``popsize`` members (None: min(15 D, 16384 // D, 1024)), which run ``n_generations`` generations in lock step
+        -> the best member, in the caller's input space.  ``last_de`` keeps the library's result."""
+        model = self.model
+        refine_model_check(model, self.__class__.__name__, "de")
+        model._materialise()
+        with staged_candidates(model, X) as cand:
+            res = model.gp.de(self.kind, self.par, self._eta(eta), cand, n_instances, popsize, n_generations, seed=seed, **how)
+            return refine_finish(self, self.kind, model, res, cand, "last_de")
 
     def direct(self, n_func_evals=400, n_iters=200, eps=1e-4, batch=None, eta=None, **how):
         """The maximiser found by DIRECT on the device (robo_acq_direct): Jones' DIviding RECTangles over the model's

@@ -515,6 +515,30 @@ class MarginalizationGPMCMC(BaseAcquisitionFunction):
                                       seed=seed, **how)
             return refine_finish(self, est[0].kind, m0, res, cand, "last_cmaes")
 
+    def de(self, X_test, n_instances=1, popsize=None, n_generations=20, seed=0, **how):
+        """Differential-evolution maximiser of the marginalised acquisition on the device (robo_acq_de_marginal_cand): as
+        ClosedFormAcquisition.de, the values averaged over the hyper-parameter samples in sample order."""
+        from robo_amd.acquisition_functions.base_acquisition import refine_finish, refine_model_check
+        if not isinstance(self.acquisition_func, ClosedFormAcquisition) or not self.estimators:
+            raise TypeError("MarginalizationGPMCMC.de is available for EI, LogEI, PI and LCB only (got %s)"
+                            % type(self.acquisition_func).__name__)
+        if getattr(self.model, "devices", None) or self._shard() is not None:
+            raise NotImplementedError("MarginalizationGPMCMC.de runs on one device; multi-device and multi-process "
+                                      "sharding of it is not implemented")
+        for e in self.estimators:
+            refine_model_check(e.model, "MarginalizationGPMCMC", "de")
+            e.model._materialise()
+        est = self.estimators
+        gps = [e.model.gp for e in est]
+        if len({id(g.ctx) for g in gps}) != 1:
+            raise NotImplementedError("MarginalizationGPMCMC.de: the sub-models live on several contexts")
+        eta = np.array([e._eta(None) for e in est])
+        m0 = est[0].model
+        with staged_candidates(m0, X_test) as cand:
+            res = _lib.de_marginal(gps, est[0].kind, est[0].par, eta, cand, n_instances, popsize, n_generations, seed=seed,
+                                   **how)
+            return refine_finish(self, est[0].kind, m0, res, cand, "last_de")
+
     def direct(self, n_func_evals=400, n_iters=200, eps=1e-4, batch=None, **how):
         """DIRECT maximiser of the marginalised acquisition on the device (robo_acq_direct_marginal): as
         ClosedFormAcquisition.direct, the values averaged over the hyper-parameter samples in sample order."""

@@ -66,6 +66,7 @@ int32_t robo_gp_destroy(robo_gp* g) {
     rep_free(g->rep);
     cma_free(g->cma);
     dir_free(g->dir);
+    de_free(g->de);
     hyper_free(g->hyper);
     hipFree(g->d_X);
     hipFree(g->d_Xs);

@@ -553,6 +553,41 @@ int launch_dir_select(robo_ctx* ctx, const DirState& st, int t);
 int launch_dir_divide(robo_ctx* ctx, const DirState& st, int t);
 int launch_dir_result(robo_ctx* ctx, const DirState& st);
 
+// ---- differential evolution over an acquisition (de.hip, api_de.hip) -----------------------------------------------------------
+constexpr int DE_MAX_DIM = 64, DE_MAX_NP = 1024, DE_MAX_R = 64;
+constexpr int DE_MAX_POP = 16384;   // NP D doubles of one instance's population: 128 KB of the 160 KB LDS
+// codes of an instance in a trace row (0: the generation was selected and the instance goes on)
+enum DeCode { DE_RAN = 0, DE_CONVERGED = 1, DE_ALL_NAN = 2, DE_STOPPED = 3 };
+// the state of one call: R instances of NP members in D dimensions; all arrays device memory of one block
+struct DeState {
+    int R, D, NP, T, S, kind;
+    long long m_pad;                // rows of a model's candidate handle (rows beyond R NP replicate row 0)
+    double par, f_lo, f_hi, cr, tol, atol;
+    unsigned long long seed;
+    const double *x0, *f0;          // the candidate handle's points and the sweep's values: the start
+    double *pop, *val;              // [R][NP][D], [R][NP]
+    double* trial;                  // [R][NP][D] the pending generation's trial points, unscaled
+    int *best, *gen, *code;         // [R] best member; generations selected; DeCode the instance stopped with (0: live)
+    unsigned* flags;                // [R] ROBO_FLAG_* of every instance's generations (one writer each: no atomics)
+    double* out;                    // [D + 3]: point, value, instance, flags
+    const double* u;                // [T][R][1 + NP (3 + 2 D)] the caller's draws, or nullptr: Philox
+    const CmaModel* model;          // [S]
+    double* trace;                  // [T + 1][R][de_trace_row(D, NP)], or nullptr
+};
+// one trace row: F, a, b, jrand (NP each), trial, crossover mask, repair mask (NP x D each), trial values, accept bits (NP
+// each), then the state AFTER the select: population (NP x D), values (NP), best, sum, mean, M2, code
+__host__ __device__ inline size_t de_trace_row(int D, int NP) { return (size_t)4 * NP * D + (size_t)6 * NP + 6; }
+__host__ __device__ inline size_t de_draws_row(int D, int NP) { return (size_t)1 + (size_t)NP * (3 + 2 * D); }
+struct DeWork {
+    size_t bytes;                   // of d_block (dev_grow: grows, never shrinks)
+    char* d_block;                  // laid out anew by every call (de_core's BlockLayout)
+    double* d_trace;
+    size_t trace_cap;               // doubles
+};
+void de_free(DeWork* w);
+int launch_de_step(robo_ctx* ctx, const DeState& st, int g);
+int launch_de_result(robo_ctx* ctx, const DeState& st, unsigned* d_cand_flags);
+
 // ---- multi-start MAP optimisation of the hyper-parameters (hyperopt.hip) ------------------------------------------------------
 constexpr int HYPER_MAX_STARTS = 64, HYPER_MAX_HISTORY = 16;
 // everything a start carries between two launches; all arrays [K], [K][P] or [K][hist][P], device memory of one block
@@ -716,6 +751,7 @@ struct robo_gp {
     robo::HyperWork* hyper;         // workspace of robo_gp_grad_loglik_batch / robo_gp_optimize_hypers (hyperopt.hip)
     robo::CmaWork* cma;             // state of robo_acq_cmaes_* (cmaes.hip), kept with gps[0] between calls
     robo::DirWork* dir;             // state of robo_acq_direct* (direct.hip), kept with gps[0] between calls
+    robo::DeWork* de;               // state of robo_acq_de_* (de.hip), kept with gps[0] between calls
     // the acquisition screen (screen.hip), lazy: [scratch (n_pad_max) | alpha = L^-T z (n_pad_max) | sum_j |alpha_j| sqrt(k_jj),
     // then, for the kinds and D the dot-form bounds kernel takes, its per-fit inputs (screen.hip "The dot form")]
     double* d_alpha;

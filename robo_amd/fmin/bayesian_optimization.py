@@ -15,6 +15,7 @@ without george, pybnn and pyrfr: :2,5,8,11), wired to the MI355X GP path:
               | DeviceRandomSampling | DeviceGradientAscent (not in the reference)
               | CMAES (the reference's fabolas / entropy_search front ends take it; here it runs on the device)
               | Direct (the reference's robo/maximizers/direct.py; here Jones' rule runs on the device)
+              | DifferentialEvolution(device=True) ("device_de": best1bin populations resident on the device)
 
 DNGO, BOHAMIANN and the random forest are device models (models/dngo.py, models/bohamiann.py, models/forest.py) but not
 model_types of this front end (rf keeps raising ValueError): build them and drive an acquisition and a maximiser with them
@@ -71,6 +72,11 @@ def bayesian_optimization(objective_function, lower, upper, num_iterations=30, X
     ``maximizer="direct"``: Jones' DIviding RECTangles over the whole box on the device (maximizers/direct.py) with the
     reference's budget of 400 values in at most 200 iterations.  It draws nothing and starts nowhere: ``n_candidates`` is
     unused and the same model gives the same proposal.  ei / log_ei / pi / lcb over ``gp`` or ``gp_mcmc``, one device.
+
+    ``maximizer="device_de"``: differential evolution on the device (maximizers/differential_evolution.py, ``device=True``):
+    one best1bin population of min(15 D, 16384 // D, 1024) members, 20 generations, one synchronisation; ``n_candidates`` is
+    unused.  ``"differential_evolution"`` stays the reference's host form.  ei / log_ei / pi / lcb over ``gp`` or ``gp_mcmc``,
+    one device.
 
     ``fantasy="joint"`` (``acquisition_func="ei"`` only): the proposals of a round are picked by joint Monte-Carlo batch
     EI over ``n_mc`` scenarios drawn from this call's rng (``EI.select_batch``); ``liar`` is ignored.  Any other
@@ -145,13 +151,16 @@ def bayesian_optimization(objective_function, lower, upper, num_iterations=30, X
     elif maximizer == "direct":
         # no candidates and no draws: DIviding RECTangles over the whole box on the device, the reference's budget
         max_func = Direct(acq, lower, upper, verbose=False, rng=rng)
+    elif maximizer == "device_de":
+        # SciPy's best1bin defaults, the populations resident on the device; no candidates beyond the start members
+        max_func = DifferentialEvolution(acq, lower, upper, rng=rng, device=True)
     elif maximizer == "scipy":
         max_func = SciPyOptimizer(acq, lower, upper, rng=rng)
     elif maximizer == "differential_evolution":
         max_func = DifferentialEvolution(acq, lower, upper, rng=rng)
     else:
         raise ValueError("'{}' is not a valid function to maximize the acquisition function (random, device_random, "
-                         "device_gradient, cmaes, direct, scipy, differential_evolution)".format(maximizer))
+                         "device_gradient, cmaes, direct, device_de, scipy, differential_evolution)".format(maximizer))
 
     # batch_size > 1: rounds of batch_size proposals from one model fit (greedy selection with fantasised picks on the
     # device), evaluated one by one or by evaluate_batch(Xq) -> yq; batch_size = 1 is the reference's loop, untouched
