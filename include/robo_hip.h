@@ -1326,6 +1326,50 @@ int32_t robo_rf_predict(robo_rf* rf, const double* rows /* m x dim */, int64_t m
 int32_t robo_rf_acq_eval_cand(robo_rf* rf, int32_t acq_kind, double par, double eta, const double* rows, int64_t m,
                               double* out_acq /* nullable */, double* out_max, int64_t* out_argmax, uint32_t* out_flags);
 
+/* ---- Parzen estimators and their log-density ratio: the Tree-structured Parzen Estimator of Bergstra et al. 2011 (not in the
+ * reference).  TPE models no p(y | x): it fits a mixture l(x) to the good observations and g(x) to the bad ones and proposes
+ * the candidate with the largest l(x) / g(x), which is monotone in EI.
+ *   Mixture.    Over the box [lo, hi] (1 <= dim <= ROBO_KDE_MAX_DIM), n components (mu_j, h_j, w_j), 1 <= n <= 2^20: mu_j
+ *               inside the box; h_j > 0 per component and dimension (n x dim), or one row shared by all (shared_h, dim);
+ *               w_j >= 0, not all 0; w NULL: equal weights.
+ *   Density.    log p(x) = logsumexp_j e_j(x),   e_j(x) = c_j - 0.5 sum_d ((x_d - mu_jd) / h_jd)^2
+ *               c_j  = log w_j - log(sum w) - sum_d [ log h_jd + 0.5 log(2 pi) + log Z_jd ]
+ *               Z_jd = Phi((hi_d - mu_jd) / h_jd) - Phi((lo_d - mu_jd) / h_jd)
+ *               The box indicator is not applied: callers pass candidates inside the box.  mu lies in the box, so the two
+ *               arguments of Z straddle 0 and Z = 1 - 0.5 (erfc(a / sqrt 2) + erfc(b / sqrt 2)) with a = (mu - lo) / h >= 0
+ *               and b = (hi - mu) / h >= 0: no difference of nearly equal values, and Z >= Phi(0) - Phi(-1/2) whenever
+ *               h <= hi - lo.  sum w is the sum in index order.
+ *   Expansion.  With the centre (lo + hi) / 2 (rounded once), t = x - centre and mu' = mu - centre:
+ *                   e_j = c'_j + phi(x) . psi_j,   phi(x) = [t, -0.5 t^2]   (length 2 dim)
+ *                   psi_j = [mu'_j / h_j^2, 1 / h_j^2],   c'_j = c_j - 0.5 sum_d mu'_jd^2 / h_jd^2
+ *               robo_kde_set_mixture computes (c'_j, psi_j) once, a component per lane; robo_kde_get_terms returns them.
+ *   Sweep.      The m x n dot products run on the matrix pipe with the components on the accumulator's rows and the
+ *               candidates on its columns; every lane keeps a running (max, sum) of its candidate's exponents.  A part
+ *               whose exponents are all -inf (weight 0) leaves (max, sum) unchanged.  The order of the components and the
+ *               tree that joins a candidate's partial sums are fixed by n alone: a candidate's bits do not depend on its
+ *               position in the batch, on m, on the other candidates or on the passes the workspace splits the batch into.
+ *   NaN.        A NaN coordinate gives NaN in log l, log g and the ratio of that candidate and ROBO_FLAG_NAN.
+ * robo_kde_ratio_eval_cand: log l (mixture 0), log g (mixture 1) and out_ratio = log l - log g of m candidates (all three
+ * nullable), the ratio's maximum and argmax (np.argmax: first index, NaN maximal) and the flags; one synchronisation.
+ * robo_kde_logpdf: one mixture's log density, the fused call's bits.
+ * dim outside 1 .. 64, lo >= hi or a bound that is not finite, which not 0 or 1, n outside 1 .. 2^20, a mu outside the box, an h
+ * that is not finite or <= 0, a weight that is negative or not finite, all weights 0, m < 1, a NULL required pointer:
+ * ROBO_BAD_ARGUMENT, decided before anything is launched.  A sweep or robo_kde_get_terms before the mixture(s) it needs are
+ * set: ROBO_NOT_FITTED.  Event slots: 30 -> 31 around the sweep kernel under the condition of slots 24..27.
+ * robo_kde_destroy(NULL) is harmless.                                                                                       */
+#define ROBO_KDE_MAX_DIM 64
+typedef struct robo_kde robo_kde;
+int32_t robo_kde_create(robo_ctx* ctx, int32_t dim, const double* lo, const double* hi, robo_kde** out);
+int32_t robo_kde_destroy(robo_kde* kde);
+int32_t robo_kde_set_mixture(robo_kde* kde, int32_t which /* 0 good, 1 bad */, const double* mu /* n x dim */,
+                             const double* h /* n x dim, or dim if shared_h */, int32_t shared_h,
+                             const double* w /* n, nullable */, int64_t n /* 1 .. 2^20 */);
+int32_t robo_kde_get_terms(robo_kde* kde, int32_t which, double* out_c /* n */, double* out_psi /* n x 2 dim */);
+int32_t robo_kde_logpdf(robo_kde* kde, int32_t which, const double* rows /* m x dim */, int64_t m, double* out_logp);
+int32_t robo_kde_ratio_eval_cand(robo_kde* kde, const double* rows /* m x dim */, int64_t m, double* out_ratio /* nullable */,
+                                 double* out_logl /* nullable */, double* out_logg /* nullable */, double* out_max,
+                                 int64_t* out_argmax, uint32_t* out_flags);
+
 /* ---- entropy search: replaces InformationGain.innovations/_dh_fun/compute ---------------
  * (robo/acquisition_functions/information_gain.py:87-125,169-203,253-272), batched over candidates.
  * rep: the Nb <= 64 representer points as a candidate batch (same normalised space).  The EP

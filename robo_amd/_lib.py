@@ -39,6 +39,7 @@ BLR_MAX_FEATURES, BLR_MAX_DIM, BLR_MAX_SAMPLES = 128, 64, 64
 MLP_MAX_DIM, MLP_MAX_WIDTH, MLP_MAX_LAYERS = 64, 64, 3                     # robo_mlp_create
 BNN_MAX_CHAINS, BNN_MAX_BATCH, BNN_MAX_SAMPLES = 64, 64, 512               # robo_bnn_create, robo_bnn_run, the sample table
 RF_MAX_N, RF_MAX_TREES, RF_MAX_DIM = 4096, 128, 64                        # robo_rf_create, robo_rf_fit
+KDE_MAX_DIM, KDE_MAX_N, KDE_CHUNK = 64, 1 << 20, 64     # robo_kde_*; components staged through LDS at a time by the sweep
 RF_STAGE_NODES = 768                          # a tree of at most this many nodes is walked in LDS by the forest's sweep
 BLR_CHUNK, BLR_TILE = 1024, 64                # rows per workgroup of the statistics kernel; candidates per workgroup of the sweep
 PATHS_MAX = 64                                   # robo_paths_*: cap on the sample paths of one object
@@ -83,6 +84,8 @@ SYMBOLS = [
     "robo_bnn_acq_eval_cand",
     "robo_rf_create", "robo_rf_destroy", "robo_rf_fit", "robo_rf_get_trees", "robo_rf_set_trees", "robo_rf_predict",
     "robo_rf_acq_eval_cand",
+    "robo_kde_create", "robo_kde_destroy", "robo_kde_set_mixture", "robo_kde_get_terms", "robo_kde_logpdf",
+    "robo_kde_ratio_eval_cand",
     "robo_paths_create", "robo_paths_eval_cand", "robo_paths_destroy", "robo_paths_descend", "robo_paths_refine_cand",
     "robo_ig_eval_cand", "robo_ig_eval_per_cost_cand", "robo_ig_eval_moments", "robo_gp_cross_cov",
     "robo_ep_joint_min", "robo_pmin_mc", "robo_igmc_eval_cand", "robo_igmc_eval_moments",
@@ -333,6 +336,12 @@ def lib():
         "robo_rf_set_trees": [vp, C.POINTER(i32), i32, vp],
         "robo_rf_predict": [vp, _dp, i64, _dp, _dp, _dp],
         "robo_rf_acq_eval_cand": [vp, i32, dbl, dbl, _dp, i64, _dp, _dp, C.POINTER(i64), C.POINTER(C.c_uint32)],
+        "robo_kde_create": [vp, i32, _dp, _dp, pp],
+        "robo_kde_destroy": [vp],
+        "robo_kde_set_mixture": [vp, i32, _dp, _dp, i32, _dp, i64],
+        "robo_kde_get_terms": [vp, i32, _dp, _dp],
+        "robo_kde_logpdf": [vp, i32, _dp, i64, _dp],
+        "robo_kde_ratio_eval_cand": [vp, _dp, i64, _dp, _dp, _dp, _dp, C.POINTER(i64), C.POINTER(C.c_uint32)],
         "robo_paths_create": [vp, i32, i32, _dp, _dp, _dp, _dp, pp],
         "robo_paths_eval_cand": [vp, vp, _dp, _dp, C.POINTER(i64), C.POINTER(C.c_uint32)],
         "robo_paths_destroy": [vp],
@@ -1693,6 +1702,73 @@ class DeviceForest(object):
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
             self._owner.robo_rf_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DeviceKDE(object):
+    """robo_kde: two truncated Gaussian mixtures over a box, l (``which`` 0, the good observations) and g (1, the bad ones),
+    and the sweep of candidates through both (include/robo_hip.h)."""
+
+    def __init__(self, ctx, lower, upper):
+        self._h = None
+        lower, upper = _f64(np.ravel(lower)), _f64(np.ravel(upper))
+        if lower.shape != upper.shape:
+            raise RoboBadShape("lower %r and upper %r differ in shape" % (lower.shape, upper.shape))
+        self.ctx, self.dim, self.n = ctx, lower.shape[0], [0, 0]
+        self._owner = lib()
+        h = C.c_void_p()
+        check(self._owner.robo_kde_create(ctx._h, self.dim, _arr(lower), _arr(upper), C.byref(h)))
+        self._h = h
+
+    def _rows(self, rows, what="rows"):
+        rows = _f64(rows)
+        if rows.ndim != 2 or rows.shape[1] != self.dim:
+            raise RoboBadShape("%s must be (n, %d), got %r" % (what, self.dim, rows.shape))
+        return rows
+
+    def set_mixture(self, which, mu, h, w=None):
+        """h (n, dim), or (dim,): one row shared by all components; w (n,) or None: equal weights"""
+        mu, h = self._rows(mu, "mu"), _f64(h)
+        shared = h.ndim == 1
+        if h.shape != ((self.dim,) if shared else mu.shape):
+            raise RoboBadShape("h must be %r or (%d,), got %r" % (mu.shape, self.dim, h.shape))
+        w = None if w is None else _f64(w, (mu.shape[0],))
+        check(lib().robo_kde_set_mixture(self._h, int(which), _arr(mu), _arr(h), int(shared), None if w is None else _arr(w),
+                                         mu.shape[0]))
+        self.n[int(which)] = mu.shape[0]
+
+    def terms(self, which):
+        """-> (c' (n,), psi (n, 2 dim)) as the device computed them"""
+        n = max(self.n[int(which)], 1)
+        c, psi = np.empty(n), np.empty((n, 2 * self.dim))
+        check(lib().robo_kde_get_terms(self._h, int(which), _arr(c), _arr(psi)))
+        return c, psi
+
+    def logpdf(self, which, rows):
+        rows = self._rows(rows)
+        out = np.empty(rows.shape[0])
+        check(lib().robo_kde_logpdf(self._h, int(which), _arr(rows), rows.shape[0], _arr(out)))
+        return out
+
+    def ratio(self, rows, want_values=True):
+        """sweep + argmax in one call (robo_kde_ratio_eval_cand) -> (ratio, log l, log g, max, argmax, flags); the three
+        vectors are None unless ``want_values``"""
+        rows = self._rows(rows)
+        out = [np.empty(rows.shape[0]) if want_values else None for _ in range(3)]
+        best = _Best()
+        check(lib().robo_kde_ratio_eval_cand(self._h, _arr(rows), rows.shape[0], *([_arr(o) if want_values else None for o in out]
+                                                                                    + list(best.refs))))
+        return tuple(out) + best.values()
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            self._owner.robo_kde_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -17,6 +17,9 @@ without george, pybnn and pyrfr: :2,5,8,11), wired to the MI355X GP path:
               | Direct (the reference's robo/maximizers/direct.py; here Jones' rule runs on the device)
               | DifferentialEvolution(device=True) ("device_de": best1bin populations resident on the device)
 
+    model    ... | TPE ("tpe": two Parzen estimators and their density ratio; not in the reference), maximised by
+             RandomSampling or ParzenSampling ("parzen": candidates drawn from the good density)
+
 DNGO, BOHAMIANN and the random forest are device models (models/dngo.py, models/bohamiann.py, models/forest.py) but not
 model_types of this front end (rf keeps raising ValueError): build them and drive an acquisition and a maximiser with them
 through robo_amd.solver.BayesianOptimization.
@@ -25,13 +28,13 @@ import logging
 
 import numpy as np
 
-from robo_amd.acquisition_functions import (EI, LCB, MES, PI, KnowledgeGradient, LogEI, MarginalizationGPMCMC,
-                                            ThompsonSampling)
+from robo_amd.acquisition_functions import (EI, LCB, MES, PI, DensityRatio, KnowledgeGradient, LogEI,
+                                            MarginalizationGPMCMC, ThompsonSampling)
 from robo_amd.initial_design import init_latin_hypercube_sampling
 from robo_amd.kernels import Matern52Kernel
 from robo_amd.maximizers import (CMAES, DeviceGradientAscent, DeviceRandomSampling, DifferentialEvolution, Direct,
-                                 RandomSampling, SciPyOptimizer)
-from robo_amd.models import GaussianProcess, GaussianProcessMCMC
+                                 ParzenSampling, RandomSampling, SciPyOptimizer)
+from robo_amd.models import TPE, GaussianProcess, GaussianProcessMCMC
 from robo_amd.models.bayesian_linear_regression import BayesianLinearRegression, quadratic_basis_func
 from robo_amd.priors import DefaultPrior
 from robo_amd.solver import BayesianOptimization
@@ -68,6 +71,11 @@ def bayesian_optimization(objective_function, lower, upper, num_iterations=30, X
     the ensemble sampler (``chain_length``, ``burnin_steps``, 20 walkers).  ``acquisition_func`` is one of ei / log_ei / pi
     / lcb and ``maximizer`` a host one; every maximisation over a candidate batch is one fused device call
     (robo_blr_acq_eval_cand).  One device, ``batch_size=1``.
+
+    ``model_type="tpe"``: the Tree-structured Parzen Estimator (models/tpe.py): no p(y | x); the proposal maximises the
+    density ratio l(x) / g(x), which selects EI's point, so ``acquisition_func`` must be ei or log_ei.  ``maximizer`` is
+    ``"random"`` (the reference's candidate recipe) or ``"parzen"`` (``n_candidates`` draws from l(x), TPE's own rule); every
+    maximisation is one fused device call (robo_kde_ratio_eval_cand).  One device, ``batch_size=1``.
 
     ``maximizer="direct"``: Jones' DIviding RECTangles over the whole box on the device (maximizers/direct.py) with the
     reference's budget of 400 values in at most 200 iterations.  It draws nothing and starts nowhere: ``n_candidates`` is
@@ -121,10 +129,19 @@ def bayesian_optimization(objective_function, lower, upper, num_iterations=30, X
                              "/ differential_evolution), one device and batch_size=1")
         model = BayesianLinearRegression(basis_func=quadratic_basis_func if basis is None else basis, rng=rng,
                                          chain_length=chain_length, burnin_steps=burnin_steps)
+    elif model_type == "tpe":
+        if acquisition_func not in ("ei", "log_ei"):
+            raise ValueError("model_type='tpe' takes acquisition_func 'ei' or 'log_ei' (the density ratio l / g selects EI's "
+                             "point), got '{}'".format(acquisition_func))
+        if maximizer not in ("random", "parzen") or devices or batch_size != 1 or hyper_optimizer != "host":
+            raise ValueError("model_type='tpe' takes maximizer 'random' or 'parzen', one device and batch_size=1")
+        model = TPE(lower, upper, rng=rng)
     else:
-        raise ValueError("'{}' is not a valid model (robo_amd provides 'gp', 'gp_mcmc' and 'blr')".format(model_type))
+        raise ValueError("'{}' is not a valid model (robo_amd provides 'gp', 'gp_mcmc', 'blr' and 'tpe')".format(model_type))
     if basis is not None and model_type != "blr":
         raise ValueError("basis=... applies to model_type='blr'")
+    if maximizer == "parzen" and model_type != "tpe":
+        raise ValueError("maximizer='parzen' draws its candidates from a TPE's good density: it needs model_type='tpe'")
 
     # "mes": max-value entropy search; its draws (discretisation, uniforms) come from this call's rng
     # "kg": knowledge gradient over a discretisation drawn from this call's rng as well
@@ -133,11 +150,15 @@ def bayesian_optimization(objective_function, lower, upper, num_iterations=30, X
                    "thompson": lambda m: ThompsonSampling(m, n_paths=max(int(batch_size), 1), n_features=n_features, rng=rng)}
     if acquisition_func not in acq_classes:
         raise ValueError("'{}' is not a valid acquisition function".format(acquisition_func))
-    a = acq_classes[acquisition_func](model)
+    # (a TPE has no moments: EI's point is selected by the density ratio)
+    a = DensityRatio(model) if model_type == "tpe" else acq_classes[acquisition_func](model)
     # (Thompson sampling draws a hyper-parameter sample per path: that is its marginalisation)
     acq = MarginalizationGPMCMC(a) if model_type == "gp_mcmc" and acquisition_func != "thompson" else a
 
-    if maximizer == "random":
+    if maximizer == "parzen":
+        # TPE's own candidates: draws from its good density, scored by one fused call
+        max_func = ParzenSampling(acq, lower, upper, n_samples=n_candidates, rng=rng)
+    elif maximizer == "random":
         max_func = RandomSampling(acq, lower, upper, n_samples=n_candidates, rng=rng)
     elif maximizer == "device_random":
         # same recipe, candidates generated and scored on the device, only x* comes back
@@ -160,7 +181,7 @@ def bayesian_optimization(objective_function, lower, upper, num_iterations=30, X
         max_func = DifferentialEvolution(acq, lower, upper, rng=rng)
     else:
         raise ValueError("'{}' is not a valid function to maximize the acquisition function (random, device_random, "
-                         "device_gradient, cmaes, direct, device_de, scipy, differential_evolution)".format(maximizer))
+                         "device_gradient, cmaes, direct, device_de, scipy, differential_evolution, parzen)".format(maximizer))
 
     # batch_size > 1: rounds of batch_size proposals from one model fit (greedy selection with fantasised picks on the
     # device), evaluated one by one or by evaluate_batch(Xq) -> yq; batch_size = 1 is the reference's loop, untouched

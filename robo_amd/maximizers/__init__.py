@@ -6,3 +6,4 @@ from robo_amd.maximizers.grid_search import GridSearch  # noqa: F401
 from robo_amd.maximizers.device_gradient import DeviceGradientAscent  # noqa: F401
 from robo_amd.maximizers.cmaes import CMAES  # noqa: F401
 from robo_amd.maximizers.direct import Direct  # noqa: F401
+from robo_amd.maximizers.parzen_sampling import ParzenSampling  # noqa: F401

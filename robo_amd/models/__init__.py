@@ -7,3 +7,4 @@ from robo_amd.models.dngo import DNGO  # noqa: F401
 from robo_amd.models.bohamiann import Bohamiann  # noqa: F401
 from robo_amd.models.wrapper_bohamiann import WrapperBohamiann  # noqa: F401
 from robo_amd.models.forest import RandomForest  # noqa: F401
+from robo_amd.models.tpe import TPE  # noqa: F401
