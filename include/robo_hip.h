@@ -289,11 +289,22 @@ int32_t robo_cand_destroy(robo_cand* cand);
 /* a new batch of the SAME size into an existing handle (H2D only; buffers and solve workspace are kept): what a BO
  * loop does once per iteration with robo/maximizers/random_sampling.py:38-47's fresh candidate matrix            */
 int32_t robo_cand_set_points(robo_cand* cand, const double* Xc, int64_t m);
-/* device-side generation, no H2D: uniform [0,1)^dim, counter-based (Philox-4x32-10)         */
+/* device-side generation, no H2D: uniform [0,1)^dim, counter-based (Philox-4x32-10, Salmon et al. 2011: multipliers
+ * 0xD2511F53 / 0xCD9E8D57, key words k0 = seed & 0xffffffff and k1 = seed >> 32 bumped by 0x9E3779B9 / 0xBB67AE85 after
+ * every round).  The candidates are a row-major m_pad x dim array, m_pad = m rounded up to a multiple of 128, of which
+ * robo_cand_get_points returns the first m rows.  Block p, on the counter (p & 0xffffffff, p >> 32, 0, 0), maps to the words
+ * (w0, w1, w2, w3) and gives two uniforms of 53 bits, u_a = ((w0 << 32 | w1) >> 11) 2^-53 and u_b = ((w2 << 32 | w3) >> 11) 2^-53:
+ * u_a is element 2 p of the array and u_b element 2 p + 1 (an odd m_pad dim leaves the last block's u_b unused).  An
+ * element is a function of (seed, its index) alone, whatever the launch looks like.                                       */
 int32_t robo_cand_create_uniform(robo_ctx* ctx, int64_t m, int32_t dim, uint64_t seed, robo_cand** out);
 /* RandomSampling.maximize's candidate recipe on the device (random_sampling.py:38-47), in the
  * normalised space: rows < n_uniform uniform, the rest N(loc, scale) clipped to [0,1]
- * (loc = normalised incumbent, scale_d = 0.1 / (upper_d - lower_d)).                           */
+ * (loc = normalised incumbent, scale_d = 0.1 / (upper_d - lower_d)).  The same array and the same blocks as
+ * robo_cand_create_uniform on the counter (p & 0xffffffff, p >> 32, 0x52425321, 0): element e = 2 p + h (h = 0, 1) lies in row
+ * e / dim at coordinate d = e % dim.  In a row < n_uniform it is the block's uniform of its half (h = 0: u_a, h = 1: u_b).
+ * In a row >= n_uniform it is clip(loc[d] + scale[d] g, 0, 1) with the Box-Muller pair of the block,
+ * rad = sqrt(-2 log(1 - u_a)), g = rad cos(2 pi u_b) for h = 0 and rad sin(2 pi u_b) for h = 1.  A block may straddle two
+ * rows, the rows n_uniform - 1 | n_uniform among them: each half follows the rule of its own row.  0 <= n_uniform <= m.  */
 int32_t robo_cand_create_random(robo_ctx* ctx, int64_t m, int32_t dim, uint64_t seed, int64_t n_uniform,
                                 const double* loc, const double* scale, robo_cand** out);
 /* points first_index .. first_index + m - 1 of a (scrambled) Sobol' sequence in [0,1)^dim, generated on the device
